@@ -67,6 +67,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-row-step", type=int, default=1, help="the CPU baseline renders every n-th row of each frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the HDR frame the last timed step rendered (what a caller of the path receives; rank 0's assembled "
+                         "frame when tiled) to DIR/frame.npy, float32 (h, w, 4); a frame over 64 MB is written as a fixed, seeded sample of its pixels "
+                         "(DIR/frame.npy (n, 4) and their row-major indices DIR/frame_pixel_index.npy, float64)")
     args = ap.parse_args()
     # stdout carries exactly one line, the result.  Libraries print there too (RCCL announces its version on stdout when the
     # communicator comes up), so file descriptor 1 is pointed at stderr for the run and the result goes to the saved original.
@@ -239,8 +243,14 @@ def main():
         sync_all()
     run_steps(0, args.warmup)
     r.totals(reset=True)
+    first_slot = ex.submitted % ex.batch if tiled else 0
     elapsed = run_steps(args.warmup, args.steps)
     tot = r.totals(reset=True)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame, before the regions below render into the same buffers again
+        last = args.warmup + args.steps - 1
+        out = frames[last % nbuf] if not tiled else ex.frames[(first_slot + args.steps - 1) % ex.batch]
+        dump_outputs(args.dump_outputs, out.view(h, w, 4).cpu().numpy())
     queue_sizes = r.queue_sizes()
     # Second timed region, identical except that a HIP event pair brackets every kernel launch on the stream it runs on:
     # it provides the per-launch durations of the roofline object.  (The event records cost ~10 % of frame time at this
@@ -371,6 +381,25 @@ def main():
     r.close()
     if tiled:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: frame (h, w, 4) float32 -> out_dir/frame.npy, or a seeded sample of its pixels if the whole frame is over the limit"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    flat = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (flat.shape[1] * 4)  # half the limit for the pixels, the indices (8 bytes each) fit in the rest
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
 
 
 def cabi_post_check(r, ex, ops, dist, torch, dev, rank, world, run_steps, args):
