@@ -16,7 +16,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -84,6 +84,8 @@ class HipLib:
         lib.pt_tonemap.argtypes = [vp, vp, u32, vp, vp]
         lib.pt_accumulate.restype = C.c_int
         lib.pt_accumulate.argtypes = [vp, vp, vp, u32, u32]
+        lib.pt_bloom.restype = C.c_int
+        lib.pt_bloom.argtypes = [vp, vp, vp, u32, u32, C.c_float]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -318,6 +320,11 @@ class Renderer:
     def accumulate(self, accum_ptr, radiance_ptr, n_pixels, frames_accumulated):
         """running mean of successive frames (device pointers), asynchronous on the context's stream"""
         self._check(self._lib.pt_accumulate(self._ctx, C.c_void_p(accum_ptr), C.c_void_p(radiance_ptr), n_pixels, frames_accumulated))
+
+    def bloom(self, hdr_ptr, out_ptr, width, height, strength):
+        """bloom (row N5): device float4[height * width] -> device float4[height * width] (out_ptr may equal hdr_ptr),
+        asynchronous on the context's stream"""
+        self._check(self._lib.pt_bloom(self._ctx, C.c_void_p(hdr_ptr), C.c_void_p(out_ptr), width, height, strength))
 
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""

@@ -19,6 +19,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_kernels.h"
+#include "pt_bloom.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
 
@@ -164,6 +165,8 @@ struct PtContext {
     bool empty_scene = false;  // pt_set_scene(n = 0): one internal sphere that no ray can hit stands in (see pt_set_scene)
     float4* d_out = nullptr;
     size_t cap_out = 0;
+    float4* d_bloom = nullptr;  // pt_bloom's blur chain (used on `stream` only), grown on demand
+    uint64_t cap_bloom = 0;     // texels
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
     uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists
 
@@ -1377,6 +1380,7 @@ void pt_destroy(PtContext* c)
     if (c->beam.ev_last_use) (void)hipEventDestroy(c->beam.ev_last_use);
     if (c->beam.stream) (void)hipStreamDestroy(c->beam.stream);
     free_dev(c->d_out);
+    free_dev(c->d_bloom);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
     if (c->gpu_builder) lbvh_gpu_destroy(c->gpu_builder);
     for (auto& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1885,6 +1889,29 @@ PtStatus pt_accumulate(PtContext* c, void* accum, const void* radiance, uint32_t
     if (n_pixels == 0) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, launch_accumulate(static_cast<float4*>(accum), static_cast<const float4*>(radiance), n_pixels, frames_accumulated, c->stream));
+    return PT_OK;
+}
+
+PtStatus pt_bloom(PtContext* c, const void* hdr, void* out, uint32_t width, uint32_t height, float strength)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!hdr || !out) return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: null pointer");
+    // >= 32: every level of the 5-mip half-size chain is at least one texel; <= 16384: the largest D3D12 2-D texture
+    if (width < kBloomMinSize || height < kBloomMinSize || width > 16384u || height > 16384u)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: width and height must be in [32, 16384]");
+    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: strength must be in [0, 1]");
+    PT_HIP(c, hipSetDevice(c->device));
+    const uint64_t need = bloom_chain(width, height).texels;
+    if (need > c->cap_bloom) {
+        // the chain is only used on `stream`: once the bloom calls queued there have finished, the old one is free (the render
+        // lanes never touch it, so their frames in flight go on)
+        PT_HIP(c, hipStreamSynchronize(c->stream));
+        free_dev(c->d_bloom);
+        c->cap_bloom = 0;
+        PT_HIP(c, hipMalloc(&c->d_bloom, need * sizeof(float4)));
+        c->cap_bloom = need;
+    }
+    PT_HIP(c, launch_bloom(static_cast<const float4*>(hdr), static_cast<float4*>(out), c->d_bloom, width, height, strength, c->stream));
     return PT_OK;
 }
 

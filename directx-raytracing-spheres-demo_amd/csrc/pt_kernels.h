@@ -47,5 +47,8 @@ hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams&
                      hipStream_t stream);
 hipError_t launch_tonemap(const float4* hdr, uint32_t* out, uint32_t n, const PtToneMapParams& p, hipStream_t stream);
 hipError_t launch_accumulate(float4* accum, const float4* rad, uint32_t n, uint32_t frames_accumulated, hipStream_t stream);
+// bloom (row N5, pt_bloom.hip): the 9 chain steps and the merge, 10 launches on `stream`.  chain: bloom_chain(width,
+// height).texels float4 of scratch; out may equal in.
+hipError_t launch_bloom(const float4* in, float4* out, float4* chain, uint32_t width, uint32_t height, float strength, hipStream_t stream);
 
 }  // namespace pt

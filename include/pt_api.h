@@ -218,6 +218,13 @@ PtStatus pt_tonemap(PtContext *ctx, const void *hdr_device, uint32_t n_pixels, c
 PtStatus pt_accumulate(PtContext *ctx, void *accum_device, const void *radiance_device, uint32_t n_pixels,
                        uint32_t frames_accumulated);
 
+/* Row N5 -- bloom (Source/Bloom.ixx, Shaders/Bloom.hlsl, Shaders/Merge.hlsl), on the context's stream (asynchronous).
+ * hdr / out = width*height float4, row-major, DEVICE pointers; out == hdr is allowed.  RGB is bloomed, alpha copied:
+ * out = hdr * (1 - strength) + blur * strength.  width and height must be >= 32 and strength in [0, 1] (NaN rejected).
+ * The context holds the blur chain; a call that needs a larger one than it has waits for the context's stream (the
+ * previous bloom calls) before it frees the old chain.  The render lanes' frames in flight never touch it. */
+PtStatus pt_bloom(PtContext *ctx, const void *hdr_device, void *out_device, uint32_t width, uint32_t height, float strength);
+
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in
  * the lanes' private copies and are not seen here): o,d = n*3 floats (d unit length), tmin per call.

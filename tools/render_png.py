@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Render the demo scene on the GPU and write a PNG through the product's own display path: N frames of the path tracer
-with jittered cameras -> pt_accumulate (running mean) -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
+with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom] -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
 R8G8B8A8.  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05]"""
 import argparse
 import os
 import sys
@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--texture-dir", default=None, help="directory of decoded images (<stem>.ptex, e.g. tests/golden/textures = the reference's Assets/Textures): use them instead of the stand-ins")
     ap.add_argument("--operator", choices=["saturate", "reinhard", "aces"], default="aces")
     ap.add_argument("--exposure", type=float, default=0.0, help="stops")
+    ap.add_argument("--bloom", type=float, default=None, metavar="STRENGTH",
+                    help="pt_bloom on the accumulated radiance before tone mapping (the reference's default is 0.05); off by default")
     args = ap.parse_args()
     from PIL import Image
 
@@ -63,7 +65,11 @@ def main():
         r.render_device(frame.data_ptr())
         r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
     op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
-    r.tonemap(accum.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+    hdr = accum
+    if args.bloom is not None:
+        hdr = torch.empty_like(accum)  # the running mean stays as it is
+        r.bloom(accum.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+    r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
     r.synchronize()
     rgba = ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)
     Image.fromarray(rgba[..., :3]).save(args.out)
