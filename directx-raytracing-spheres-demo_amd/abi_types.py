@@ -48,6 +48,19 @@ class PtRect(C.Structure):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
 
 
+# Row N6 (pt_render_gbuffer): the 13 G-buffer channels in PtGBuffer's field order, with their float32 counts per pixel
+GBUFFER_CHANNELS = (("Position", 4), ("FlatNormal", 2), ("GeometricNormal", 2), ("LinearDepth", 1), ("NormalizedDepth", 1),
+                    ("MotionVector", 3), ("BaseColorMetalness", 4), ("DiffuseAlbedo", 3), ("SpecularAlbedo", 3), ("NormalRoughness", 4),
+                    ("IOR", 1), ("Transmission", 1), ("Radiance", 3))
+GBUFFER_WIDTH = dict(GBUFFER_CHANNELS)
+# what a denoiser reads (NRD's inputs): 48 bytes per pixel against the 128 of all 13
+GBUFFER_DENOISER = ("LinearDepth", "NormalRoughness", "MotionVector", "BaseColorMetalness")
+
+
+class PtGBuffer(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in GBUFFER_CHANNELS]
+
+
 class PtTextureMapInfo(C.Structure):
     _fields_ = [("Descriptor", C.c_uint32), ("TextureCoordinateIndex", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 

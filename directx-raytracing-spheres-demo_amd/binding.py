@@ -7,7 +7,8 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, PtAccelInfo, PtCamera, PtConfig, PtGraphicsSettings, PtRect, PtSceneData, PtStats)
+from .abi_types import (BVH_NODE_DTYPE, GBUFFER_CHANNELS, PtAccelInfo, PtCamera, PtConfig, PtGBuffer, PtGraphicsSettings, PtRect, PtSceneData,
+                        PtStats)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -16,7 +17,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -86,6 +87,8 @@ class HipLib:
         lib.pt_accumulate.argtypes = [vp, vp, vp, u32, u32]
         lib.pt_bloom.restype = C.c_int
         lib.pt_bloom.argtypes = [vp, vp, vp, u32, u32, C.c_float]
+        lib.pt_render_gbuffer.restype = C.c_int
+        lib.pt_render_gbuffer.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBuffer), vp, vp]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -325,6 +328,37 @@ class Renderer:
         """bloom (row N5): device float4[height * width] -> device float4[height * width] (out_ptr may equal hdr_ptr),
         asynchronous on the context's stream"""
         self._check(self._lib.pt_bloom(self._ctx, C.c_void_p(hdr_ptr), C.c_void_p(out_ptr), width, height, strength))
+
+    def render_gbuffer_device(self, buffers, rect=None, previous_spheres=None, previous_rotations=None):
+        """G-buffer (row N6) of the frame the next render call renders.  buffers: {channel name: device pointer} (names of
+        GBUFFER_CHANNELS; the others are not requested).  Asynchronous, ordered like the frame the next render call renders (with frames
+        in flight: rotate over one set of buffers per lane); what is queued on the context's stream later sees the result.  previous_spheres (SPHERE_DTYPE[n]) / previous_rotations (float32[n, 4]): the previous
+        pose the motion vectors are measured from, None = the current one."""
+        unknown = set(buffers) - {name for name, _ in GBUFFER_CHANNELS}
+        if unknown:
+            raise ValueError(f"unknown G-buffer channels {sorted(unknown)}")
+        gb = PtGBuffer(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        r = PtRect(*rect) if rect is not None else None
+        ps = np.ascontiguousarray(previous_spheres) if previous_spheres is not None else None
+        pr = np.ascontiguousarray(previous_rotations, dtype=np.float32) if previous_rotations is not None else None
+        self._check(self._lib.pt_render_gbuffer(self._ctx, C.byref(r) if r is not None else None, C.byref(gb),
+                                                ps.ctypes.data if ps is not None else None, pr.ctypes.data if pr is not None else None))
+
+    def render_gbuffer(self, channels="all", rect=None, previous_spheres=None, previous_rotations=None, fill=float("nan"), device=None):
+        """render_gbuffer_device into torch buffers filled with `fill` (what a pixel the pass does not write keeps) -> {channel:
+        numpy float32 (h, w, width)} for the requested channels ("all" or names).  Synchronous."""
+        import torch
+        names = [name for name, _ in GBUFFER_CHANNELS] if channels == "all" else list(channels)
+        width = dict(GBUFFER_CHANNELS)
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        bufs = {name: torch.full((h, w, width[name]), fill, dtype=torch.float32, device=dev) for name in names}
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        self.render_gbuffer_device({name: b.data_ptr() for name, b in bufs.items()}, rect, previous_spheres, previous_rotations)
+        self.synchronize()
+        return {name: b.cpu().numpy() for name, b in bufs.items()}
 
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""

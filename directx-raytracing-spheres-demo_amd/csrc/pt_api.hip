@@ -90,6 +90,14 @@ struct Lane {
     hipEvent_t ev_rot = nullptr;      // the last upload from h_rot_stage has been consumed
     uint64_t rot_gen = 0;
     uint32_t rot_n = 0;
+    // pt_render_gbuffer: the caller's previous poses (spheres, then rotations) as the lane's calls read them, their pinned staging
+    // buffer, and the marker that orders a G-buffer call after what the caller queued on `stream`
+    float4* d_prev_pose = nullptr;
+    float4* h_prev_stage = nullptr;
+    hipEvent_t ev_prev = nullptr;     // the last upload from h_prev_stage has been consumed
+    uint32_t prev_cap = 0;            // spheres the two buffers hold room for
+    hipEvent_t ev_gb_in = nullptr;
+    void* last_gb[13] = {};           // the buffers of the lane's latest G-buffer call (its ordering against the caller's stream)
 };
 constexpr uint32_t kMaxLanes = 8;
 
@@ -165,6 +173,12 @@ struct PtContext {
     bool empty_scene = false;  // pt_set_scene(n = 0): one internal sphere that no ray can hit stands in (see pt_set_scene)
     float4* d_out = nullptr;
     size_t cap_out = 0;
+    // pt_render_gbuffer before the render call that will take lane `gb_lane` as frame number `gb_frame`: whether every lane was idle
+    // when it was made (render_common's one-frame-at-a-time test must not mistake that frame's own G-buffer work for a frame in flight)
+    uint64_t frames = 0;  // render calls that took a lane
+    uint64_t gb_frame = ~0ull;
+    uint32_t gb_lane = 0;
+    bool gb_lanes_idle = false;
     float4* d_bloom = nullptr;  // pt_bloom's blur chain (used on `stream` only), grown on demand
     uint64_t cap_bloom = 0;     // texels
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
@@ -938,6 +952,20 @@ static PtStatus sync_lane_spheres(PtContext* c, Lane& L)
     return refit_lane(c, L);
 }
 
+// the environment map SceneData names must be in the texture table (render_common, pt_render_gbuffer)
+static PtStatus check_environment(PtContext* c)
+{
+    if (const uint32_t env = c->sd.EnvironmentLightTextureDescriptor; env != ~0u) {
+        const size_t n_faces = c->sd.IsEnvironmentLightTextureCubeMap ? 6 : 1;
+        if (!c->has_textures || (size_t)env + n_faces > c->tex_dims.size())
+            return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor names a texture the table of pt_set_textures does not hold (call pt_set_textures after pt_set_scene; a cube map takes six consecutive entries)");
+        for (size_t f = 0; f < n_faces; f++)
+            if (n_faces == 6 && (c->tex_dims[env + f].first != c->tex_dims[env].first || c->tex_dims[env + f].second != c->tex_dims[env].first))
+                return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor: the six faces of a cube map must be square and of one size");
+    }
+    return PT_OK;
+}
+
 // The per-frame launch sequence.  out: device float4 buffer addressed by PixelRef::out_index.
 //
 // Fused schedule (default):  bounce<primary> -> bounce (x S) -> bounce<loop>
@@ -951,14 +979,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
 {
     const RoctxRange range(c, pm.mode == 0 ? "pt_render" : "pt_render_tiles");
     const uint32_t bounces = c->gs.Bounces, spp = c->gs.SamplesPerPixel;
-    if (const uint32_t env = c->sd.EnvironmentLightTextureDescriptor; env != ~0u) {
-        const size_t n_faces = c->sd.IsEnvironmentLightTextureCubeMap ? 6 : 1;
-        if (!c->has_textures || (size_t)env + n_faces > c->tex_dims.size())
-            return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor names a texture the table of pt_set_textures does not hold (call pt_set_textures after pt_set_scene; a cube map takes six consecutive entries)");
-        for (size_t f = 0; f < n_faces; f++)
-            if (n_faces == 6 && (c->tex_dims[env + f].first != c->tex_dims[env].first || c->tex_dims[env + f].second != c->tex_dims[env].first))
-                return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor: the six faces of a cube map must be square and of one size");
-    }
+    if (const PtStatus st = check_environment(c); st != PT_OK) return st;
     const size_t max_iters = (size_t)spp * bounces + 1;  // passes if everything ran as wavefront
     const size_t wf_cap = spp > 1 ? max_iters : std::min<size_t>(max_iters, 64);
     // LDS-resident BVH: fused trace+shade passes (traversal is cheap, the hit stream is pure overhead).  BVH in global
@@ -979,9 +1000,12 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     const bool di = c->gs.IsDIEnabled && c->n_lights > 0;
     // Is the caller waiting for each frame (App::Tick -> Render -> WaitForGPU) or keeping several in flight?  Asked of the streams before this
     // frame queues anything: all lanes drained = one frame at a time, and the frame is scheduled for latency (below: the fused form).
-    bool lanes_idle = true;
+    // (A pt_render_gbuffer call for this very frame has queued work on its lane: that lane counts as idle if every lane was when that call
+    // was made.)
+    const bool gb_before = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
+    bool lanes_idle = !gb_before || c->gb_lanes_idle;
     for (uint32_t i = 0; i < c->n_lanes && lanes_idle; i++)
-        if (hipStreamQuery(c->lanes[i].stream) != hipSuccess) { lanes_idle = false; (void)hipGetLastError(); }
+        if (!(gb_before && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { lanes_idle = false; (void)hipGetLastError(); }
     // Persistent workgroups: with the BVH staged into LDS per workgroup, 2 per CU (= the 4 waves/SIMD the kernel is built
     // for) amortise the 37 KB staging over ~4 batches of rays at 1080p / 1 spp (0.121 -> 0.116 ms per frame), from about
     // 1.5 M slots: below that 8 per CU is 4-10 % faster.  (Since the waves of a workgroup draw their tiles dynamically the
@@ -1004,6 +1028,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;  // pt_update_spheres without pt_refit_accel: the frame refits by itself
     c->last_lane = c->next_lane;
     c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    c->frames++;
     // Primary beams: use cached candidate lists that hold for this frame's view (beam_cache_lookup): exact ones for a view that has rested
     // for two frames, ones with slack for a camera that moves without turning.  PT_BEAMS=0 switches them off, PT_BEAM_REACH=0 the moving
     // kind, for A/B runs.  (Building lists in front of EVERY frame of a changing view was measured, with the tree staged in LDS for the
@@ -1364,6 +1389,10 @@ void pt_destroy(PtContext* c)
         free_dev(L.d_rot);
         if (L.h_rot_stage) (void)hipHostFree(L.h_rot_stage);
         if (L.ev_rot) (void)hipEventDestroy(L.ev_rot);
+        free_dev(L.d_prev_pose);
+        if (L.h_prev_stage) (void)hipHostFree(L.h_prev_stage);
+        if (L.ev_prev) (void)hipEventDestroy(L.ev_prev);
+        if (L.ev_gb_in) (void)hipEventDestroy(L.ev_gb_in);
         if (L.ev_upload) (void)hipEventDestroy(L.ev_upload);
         for (auto& e : L.ev_poll) if (e) (void)hipEventDestroy(e);
         free_dev(L.d_counts); free_dev(L.d_totals); free_dev(L.d_seg_counts);
@@ -1654,17 +1683,13 @@ uint32_t pt_tiles_count_ex(PtContext* c, uint32_t first, uint32_t run, uint32_t 
     return count_tiles(frame_tiles(c), first, run, stride);
 }
 
-PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
+// rect (NULL = the whole RenderSize) -> the slot map of the primary pass (8x8-pixel blocks of the rect, one per wave)
+static PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who, PtRect& r, PixelMap& pm)
 {
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!out) return fail(c, PT_ERR_INVALID_ARG, "pt_render: null output");
-    PtStatus st = validate_frame(c);
-    if (st != PT_OK) return st;
-    PT_HIP(c, hipSetDevice(c->device));
-    PtRect r = rect ? *rect : PtRect{ 0, 0, c->gs.RenderSize[0], c->gs.RenderSize[1] };
+    r = rect ? *rect : PtRect{ 0, 0, c->gs.RenderSize[0], c->gs.RenderSize[1] };
     if (r.w == 0 || r.h == 0 || r.x >= c->gs.RenderSize[0] || r.w > c->gs.RenderSize[0] - r.x || r.y >= c->gs.RenderSize[1] || r.h > c->gs.RenderSize[1] - r.y)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_render: rect is empty or outside RenderSize");
-    PixelMap pm{};
+        return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect is empty or outside RenderSize");
+    pm = PixelMap{};
     pm.mode = 0;
     pm.img_w = c->gs.RenderSize[0]; pm.img_h = c->gs.RenderSize[1];
     pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
@@ -1672,8 +1697,21 @@ PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_devic
     pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
     const uint64_t slots = (uint64_t)pm.blocks_x * ((r.h + 7) / 8) * 64ull;
     pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
-    if (slots > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, "pt_render: rect too large");
+    if (slots > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect too large");
     pm.n_slots = (uint32_t)slots;
+    return PT_OK;
+}
+
+PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!out) return fail(c, PT_ERR_INVALID_ARG, "pt_render: null output");
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    PtRect r;
+    PixelMap pm{};
+    if ((st = rect_pixel_map(c, rect, "pt_render", r, pm)) != PT_OK) return st;
     float4* dev_out = static_cast<float4*>(out);
     const size_t out_px = (size_t)r.w * r.h;
     if (!out_is_device) {
@@ -1692,6 +1730,151 @@ PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_devic
         PT_HIP(c, hipStreamSynchronize(c->stream));
     }
     return PT_OK;
+}
+
+// Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12)
+PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!gb) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: null PtGBuffer");
+    // the requested channels; every buffer must be aligned to its channel's vector width (float4: 16 B, float2: 8 B, else 4 B)
+    void* const ptrs[13] = { gb->Position, gb->FlatNormal, gb->GeometricNormal, gb->LinearDepth, gb->NormalizedDepth, gb->MotionVector,
+                             gb->BaseColorMetalness, gb->DiffuseAlbedo, gb->SpecularAlbedo, gb->NormalRoughness, gb->IOR, gb->Transmission, gb->Radiance };
+    const uint32_t align[13] = { 16, 8, 8, 4, 4, 4, 16, 4, 4, 16, 4, 4, 4 };
+    uint32_t want = 0;
+    for (uint32_t k = 0; k < 13; k++) {
+        if (!ptrs[k]) continue;
+        if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: a buffer is not aligned to its channel's width");
+        want |= 1u << k;
+    }
+    if (!want) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: no output requested (all 13 pointers are NULL)");
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    PtRect r;
+    PixelMap pm{};
+    if ((st = rect_pixel_map(c, rect, "pt_render_gbuffer", r, pm)) != PT_OK) return st;
+    if ((st = check_environment(c)) != PT_OK) return st;
+    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)
+        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    // previous poses (PreviousObjectToWorld): only while the scene is not static; the empty scene has none
+    const uint32_t n = c->empty_scene ? 0u : c->n;
+    const bool use_prev_sph = previous_spheres && !c->sd.IsStatic && n > 0, use_prev_rot = previous_rotations && !c->sd.IsStatic && n > 0;
+    for (uint32_t i = 0; use_prev_sph && i < n; i++) {
+        const PtSphere& p = previous_spheres[i];
+        if (!std::isfinite(p.cx) || !std::isfinite(p.cy) || !std::isfinite(p.cz) || !std::isfinite(p.r) || !(p.r > 0.0f))
+            return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous sphere " + std::to_string(i) + " is not finite or has radius <= 0");
+    }
+    for (uint32_t i = 0; use_prev_rot && i < 4u * n; i++)
+        if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous rotation " + std::to_string(i / 4) + " is not finite");
+    PT_HIP(c, hipSetDevice(c->device));
+
+    // the lane of the next frame, brought up to date as render_common does (its rotation is not advanced: the next pt_render finds it
+    // synchronised)
+    Lane& L = c->lanes[c->next_lane];
+    // asked before anything is queued: are all lanes idle (render_common's one-frame-at-a-time test, made for the frame this G-buffer
+    // belongs to)?  A second call for the same frame finds its own lane busy with the first one.
+    {
+        const bool again = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
+        bool idle = !again || c->gb_lanes_idle;
+        for (uint32_t i = 0; i < c->n_lanes && idle; i++)
+            if (!(again && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { idle = false; (void)hipGetLastError(); }
+        c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
+    }
+    if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
+    if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
+    if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;
+    if (L.stream != c->stream) {
+        // Ordered as the frame it belongs to (render_common): the caller rotates over n_lanes sets of G-buffer buffers as it does over
+        // frame buffers, so the pass waits for the marker recorded on the caller's stream at the start of the render call n_lanes - 1
+        // calls ago (after the consumer of this lane's previous buffers), not for the frames in between.  Before the first render call,
+        // or when a buffer is one that another lane's G-buffer or frame wrote within that window, it waits for everything the caller has
+        // queued so far instead.
+        const uint64_t nl = c->n_lanes;
+        bool shared = c->calls == 0;
+        for (uint32_t i = 0; i < c->n_lanes && !shared; i++) {
+            if (&c->lanes[i] == &L) continue;
+            for (uint32_t k = 0; k < 13 && !shared; k++)
+                if (ptrs[k]) {
+                    shared = ptrs[k] == c->lanes[i].last_out;
+                    for (uint32_t j = 0; j < 13 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_gb[j];
+                }
+        }
+        if (shared) {
+            if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
+            PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
+            PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
+        } else {
+            const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
+            if (hipEventQuery(marker) != hipSuccess) {
+                (void)hipGetLastError();  // hipErrorNotReady is not an error here
+                PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
+            }
+        }
+        for (uint32_t k = 0; k < 13; k++) L.last_gb[k] = ptrs[k];
+    }
+    const SceneView sv = make_scene_view(c, &L);
+    GBufferScene sc{};
+    sc.sph = sv.sph; sc.mats = sv.mats; sc.tex = sv.tex; sc.tex_maps = sv.tex_maps; sc.rot = sv.rot;
+    sc.is_static = c->sd.IsStatic ? 1u : 0u;
+    sc.env_tex = sv.env_tex; sc.env_cube = sv.env_cube;
+    for (int k = 0; k < 4; k++) sc.env[k] = sv.env[k];
+    for (int k = 0; k < 9; k++) sc.env_xf[k] = sv.env_xf[k];
+    if (use_prev_sph || use_prev_rot) {
+        // one set per lane: a call on another lane may still be reading its own
+        if (L.prev_cap < n) {
+            PT_HIP(c, hipStreamSynchronize(L.stream));
+            free_dev(L.d_prev_pose);
+            if (L.h_prev_stage) { (void)hipHostFree(L.h_prev_stage); L.h_prev_stage = nullptr; }
+            L.prev_cap = 0;
+            PT_HIP(c, hipMalloc(&L.d_prev_pose, 2u * (size_t)n * sizeof(float4)));
+            PT_HIP(c, hipHostMalloc(&L.h_prev_stage, 2u * (size_t)n * sizeof(float4)));
+            if (!L.ev_prev) PT_HIP(c, hipEventCreateWithFlags(&L.ev_prev, hipEventDisableTiming));
+            L.prev_cap = n;
+        } else {
+            PT_HIP(c, hipEventSynchronize(L.ev_prev));  // the previous upload from the staging buffer has been consumed
+        }
+        if (use_prev_sph) std::memcpy(L.h_prev_stage, previous_spheres, (size_t)n * sizeof(float4));
+        if (use_prev_rot) std::memcpy(L.h_prev_stage + n, previous_rotations, (size_t)n * sizeof(float4));
+        PT_HIP(c, hipMemcpyAsync(L.d_prev_pose, L.h_prev_stage, 2u * (size_t)n * sizeof(float4), hipMemcpyHostToDevice, L.stream));
+        PT_HIP(c, hipEventRecord(L.ev_prev, L.stream));
+        sc.prev_sph = use_prev_sph ? L.d_prev_pose : nullptr;
+        sc.prev_rot = use_prev_rot ? L.d_prev_pose + n : nullptr;
+    }
+    GBufferFrame fr{};
+    fr.cam = camera_params(c->cam, c->gs.RenderSize[0], c->gs.RenderSize[1]);
+    fr.width = (float)c->gs.RenderSize[0];
+    fr.height = (float)c->gs.RenderSize[1];
+    fr.reversed = c->cam.IsNormalizedDepthReversed ? 1u : 0u;
+    std::memcpy(fr.world_to_projection, c->cam.Matrices[5], sizeof fr.world_to_projection);
+    std::memcpy(fr.prev_world_to_projection, c->cam.Matrices[2], sizeof fr.prev_world_to_projection);
+    std::memcpy(fr.prev_world_to_view, c->cam.Matrices[0], sizeof fr.prev_world_to_view);
+    GBufferOut out{};
+    out.Position = static_cast<float4*>(gb->Position);
+    out.FlatNormal = static_cast<float2*>(gb->FlatNormal);
+    out.GeometricNormal = static_cast<float2*>(gb->GeometricNormal);
+    out.LinearDepth = static_cast<float*>(gb->LinearDepth);
+    out.NormalizedDepth = static_cast<float*>(gb->NormalizedDepth);
+    out.MotionVector = static_cast<f3*>(gb->MotionVector);
+    out.BaseColorMetalness = static_cast<float4*>(gb->BaseColorMetalness);
+    out.DiffuseAlbedo = static_cast<f3*>(gb->DiffuseAlbedo);
+    out.SpecularAlbedo = static_cast<f3*>(gb->SpecularAlbedo);
+    out.NormalRoughness = static_cast<float4*>(gb->NormalRoughness);
+    out.IOR = static_cast<float*>(gb->IOR);
+    out.Transmission = static_cast<float*>(gb->Transmission);
+    out.Radiance = static_cast<f3*>(gb->Radiance);
+    const uint32_t threads = traverse_threads(c->lds_scene);
+    // LDS-resident scenes stage the tree once per workgroup: a few workgroups per CU walk the whole frame
+    const uint32_t grid = std::max(1u, std::min((pm.n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
+    st = PT_OK;
+    if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, grid, L.stream); e != hipSuccess)
+        st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: launch: ") + hipGetErrorString(e));
+    if (L.stream != c->stream) {
+        // whatever the caller queues next on its stream (pt_download, pt_bloom, the next use of the buffers) sees the G-buffer
+        const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
+        if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: completion event: ") + hipGetErrorString(e2));
+    }
+    return st;
 }
 
 PtStatus pt_render_tiles(PtContext* c, void* out_device_packed, PtStats* stats)

@@ -1,0 +1,89 @@
+// pt_gbuffer.hip -- the G-buffer pass (row N6, DESIGN.md spec S12): one lane per pixel, one 8x8 pixel block per wave (the
+// PixelMap of the primary pass, so that traversal stays coherent), the closest hit of the pixel's primary ray through the
+// tree the context has (LDS copy or the wide global walk), then gbuffer_pixel (pt_gbuffer.h) and the requested stores.
+// No beam lists: the pass neither reads nor touches the primary-beam cache.
+#include "pt_trace.h"
+
+namespace pt {
+
+namespace {
+
+// kTex: EvaluateMaterial's texture branches and the environment maps; kAlpha: the per-crossing alpha test of S10 (scenes
+// with alpha-tested spheres, which only textured scenes have)
+template <bool kLds, typename StackT, bool kTex, bool kAlpha>
+__global__ __launch_bounds__(kTraverseThreads) void gbuffer_kernel(SceneView sv, PixelMap pm, GBufferFrame fr, GBufferScene sc, GBufferOut out, uint32_t want)
+{
+    extern __shared__ float4 smem[];
+    const float4* nodes = sv.nodes;
+    const float4* sph = sv.sph_sorted;
+    const uint32_t* ids = sv.sorted_id;
+    StackT* stack;
+    if (kLds) {
+        stage_scene(sv, smem);
+        nodes = smem;
+        sph = smem + sv.n_nodes * 4u;
+        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
+        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
+    } else {
+        stack = reinterpret_cast<StackT*>(smem);
+    }
+    stack += threadIdx.x;
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
+        const PixelRef pr = slot_to_pixel(pm, slot);
+        if (!pr.valid) continue;
+        f3 o, d;
+        float tmin, tmax, t;
+        uint32_t id;
+        primary_ray(fr.cam, pr.px, pr.py, o, d, tmin, tmax);
+        closest_hit_any<kLds, StackT, kAlpha>(sv, nodes, sph, ids, o, d, tmin, tmax, stack, blockDim.x, t, id);
+        const GBufferPixel g = gbuffer_pixel<kTex>(fr, sc, pr.px, pr.py, t, id == kMissId ? kGbNoHit : id, want);
+        const uint32_t i = pr.out_index;
+        // `want` is uniform: each store sits behind a scalar branch, the per-pixel mask only sets the lanes
+        if (want & kGbPosition) if (g.mask & kGbPosition) out.Position[i] = g.Position;
+        if (want & kGbFlatNormal) if (g.mask & kGbFlatNormal) out.FlatNormal[i] = make_float2(g.FlatNormal.x, g.FlatNormal.y);
+        if (want & kGbGeometricNormal) if (g.mask & kGbGeometricNormal) out.GeometricNormal[i] = make_float2(g.GeometricNormal.x, g.GeometricNormal.y);
+        if (want & kGbLinearDepth) if (g.mask & kGbLinearDepth) out.LinearDepth[i] = g.LinearDepth;
+        if (want & kGbNormalizedDepth) if (g.mask & kGbNormalizedDepth) out.NormalizedDepth[i] = g.NormalizedDepth;
+        if (want & kGbMotionVector) if (g.mask & kGbMotionVector) out.MotionVector[i] = g.MotionVector;
+        if (want & kGbBaseColorMetalness) if (g.mask & kGbBaseColorMetalness) out.BaseColorMetalness[i] = g.BaseColorMetalness;
+        if (want & kGbDiffuseAlbedo) if (g.mask & kGbDiffuseAlbedo) out.DiffuseAlbedo[i] = g.DiffuseAlbedo;
+        if (want & kGbSpecularAlbedo) if (g.mask & kGbSpecularAlbedo) out.SpecularAlbedo[i] = g.SpecularAlbedo;
+        if (want & kGbNormalRoughness) if (g.mask & kGbNormalRoughness) out.NormalRoughness[i] = g.NormalRoughness;
+        if (want & kGbIOR) if (g.mask & kGbIOR) out.IOR[i] = g.IOR;
+        if (want & kGbTransmission) if (g.mask & kGbTransmission) out.Transmission[i] = g.Transmission;
+        if (want & kGbRadiance) if (g.mask & kGbRadiance) out.Radiance[i] = g.Radiance;
+    }
+}
+
+template <bool kTex, bool kAlpha>
+hipError_t launch_gbuffer_t(const SceneView& sv, const PixelMap& pm, const GBufferFrame& fr, const GBufferScene& sc, const GBufferOut& out,
+                            uint32_t want, uint32_t grid, hipStream_t stream)
+{
+    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
+    const uint32_t threads = traverse_threads(lds_scene);
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
+    const void* fn = lds_scene ? (small ? (const void*)gbuffer_kernel<true, uint16_t, kTex, kAlpha> : (const void*)gbuffer_kernel<true, uint32_t, kTex, kAlpha>)
+                               : (small ? (const void*)gbuffer_kernel<false, uint16_t, kTex, kAlpha> : (const void*)gbuffer_kernel<false, uint32_t, kTex, kAlpha>);
+    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds_scene) {
+        if (small) hipLaunchKernelGGL((gbuffer_kernel<true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
+        else hipLaunchKernelGGL((gbuffer_kernel<true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
+    } else {
+        if (small) hipLaunchKernelGGL((gbuffer_kernel<false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
+        else hipLaunchKernelGGL((gbuffer_kernel<false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_gbuffer(const SceneView& sv, const PixelMap& pm, const GBufferFrame& fr, const GBufferScene& sc, const GBufferOut& out, uint32_t want,
+                          uint32_t grid, hipStream_t stream)
+{
+    // the textured variants only where textures exist; the alpha-tested walk only where some sphere's hits are tested against a map
+    if (!sv.tex_maps) return launch_gbuffer_t<false, false>(sv, pm, fr, sc, out, want, grid, stream);
+    if (sv.alpha_tested) return launch_gbuffer_t<true, true>(sv, pm, fr, sc, out, want, grid, stream);
+    return launch_gbuffer_t<true, false>(sv, pm, fr, sc, out, want, grid, stream);
+}
+
+}  // namespace pt

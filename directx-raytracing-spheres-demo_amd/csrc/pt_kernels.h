@@ -3,6 +3,7 @@
 
 #include "pt_device.h"
 #include "pt_post.h"
+#include "pt_gbuffer.h"
 
 namespace pt {
 
@@ -50,5 +51,24 @@ hipError_t launch_accumulate(float4* accum, const float4* rad, uint32_t n, uint3
 // bloom (row N5, pt_bloom.hip): the 9 chain steps and the merge, 10 launches on `stream`.  chain: bloom_chain(width,
 // height).texels float4 of scratch; out may equal in.
 hipError_t launch_bloom(const float4* in, float4* out, float4* chain, uint32_t width, uint32_t height, float strength, hipStream_t stream);
+// G-buffer (row N6, pt_gbuffer.hip): the 13 surface buffers of the pixels of pm (mode 0, a rect), row-major inside the rect; a null
+// pointer is a channel not requested (want = the bits of the non-null ones).  One launch on `stream`.
+struct GBufferOut {
+    float4* Position;
+    float2* FlatNormal;
+    float2* GeometricNormal;
+    float* LinearDepth;
+    float* NormalizedDepth;
+    f3* MotionVector;
+    float4* BaseColorMetalness;
+    f3* DiffuseAlbedo;
+    f3* SpecularAlbedo;
+    float4* NormalRoughness;
+    float* IOR;
+    float* Transmission;
+    f3* Radiance;
+};
+hipError_t launch_gbuffer(const SceneView& sv, const PixelMap& pm, const GBufferFrame& fr, const GBufferScene& sc, const GBufferOut& out, uint32_t want,
+                          uint32_t grid, hipStream_t stream);
 
 }  // namespace pt

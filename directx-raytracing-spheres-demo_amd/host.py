@@ -111,6 +111,21 @@ class HostLib:
         self.lib.pth_camera(pos, la, hfov, width, height, 1 if jitter else 0, jitter_index, jitter_count, C.byref(cam))
         return cam
 
+    def camera_matrices(self, width, height, position=(0.0, 0.0, -15.0), look_at=None, hfov=math.pi / 2, jitter=True, jitter_index=0, jitter_count=8,
+                        near_depth=1e-2, far_depth=math.inf, reversed_depth=True, previous=None):
+        """camera() with SetLens(hfov, w/h, near_depth, far_depth) and the eight matrices (CameraController::FillMatrices) that the
+        G-buffer pass reads; previous = the previous frame's camera from this method (None: a first frame, Previous* = current)."""
+        fn = self.lib.pth_camera_matrices
+        fn.restype = None
+        fn.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                       C.c_float, C.c_float, C.c_int, C.POINTER(PtCamera), C.POINTER(PtCamera)]
+        cam = PtCamera()
+        pos = (C.c_float * 3)(*position)
+        la = (C.c_float * 3)(*look_at) if look_at is not None else None
+        fn(pos, la, hfov, width, height, 1 if jitter else 0, jitter_index, jitter_count, near_depth, far_depth, 1 if reversed_depth else 0,
+           C.byref(previous) if previous is not None else None, C.byref(cam))
+        return cam
+
     def halton(self, index, base):
         return float(self.lib.pth_halton(index, base))
 

@@ -99,6 +99,36 @@ void pth_camera(const float position[3], const float* look_at, float hfov, uint3
     *out = ToPt(camera);
 }
 
+// pth_camera with the lens depths and the eight matrices (CameraController::FillMatrices) for the G-buffer pass: SetLens(hfov, w/h,
+// near_depth, far_depth) (far_depth = inf: the infinite projection), reversed = IsNormalizedDepthReversed, previous = the previous
+// frame's camera (an earlier output of this function), NULL = this camera (a first frame: motion vectors of a resting view are 0).
+void pth_camera_matrices(const float position[3], const float* look_at, float hfov, uint32_t width, uint32_t height, int jitter_enabled,
+                         uint32_t jitter_index, uint32_t jitter_count, float near_depth, float far_depth, int reversed, const PtCamera* previous,
+                         PtCamera* out)
+{
+    CameraController controller(reversed != 0);
+    controller.SetPosition({ position[0], position[1], position[2] });
+    if (look_at) controller.LookAt({ look_at[0], look_at[1], look_at[2] }, { 0, 1, 0 }, false);
+    controller.SetLens(hfov, static_cast<float>(width) / static_cast<float>(height), near_depth, far_depth);
+    Float2 jitter{};
+    if (jitter_enabled) {
+        const auto h = HaltonSampler::Get2D(jitter_index % (jitter_count ? jitter_count : 1) + 1);
+        jitter = { h.x - 0.5f, h.y - 0.5f };
+    }
+    Camera camera;
+    if (previous) std::memcpy(&camera, previous, sizeof(PtCamera));  // Fill: PreviousPosition = the previous camera's Position
+    controller.Fill(camera, jitter);
+    if (!previous) camera.PreviousPosition = camera.Position;
+    if (previous) {
+        Camera prev;
+        std::memcpy(&prev, previous, sizeof(PtCamera));
+        controller.FillMatrices(camera, prev);
+    } else {
+        controller.FillMatrices(camera);  // a first frame: Previous* = this frame's
+    }
+    *out = ToPt(camera);
+}
+
 // The demo scene at simulation time `time` seconds (closed-form motion, MyScene::SetTime): spheres only (the materials and
 // the object order are those of pth_scene(0, seed)).
 int pth_scene_at_time(uint32_t seed, double time, PtSphere* spheres, uint32_t capacity, uint32_t* count)

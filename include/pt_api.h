@@ -14,6 +14,7 @@
  *   pt_set_constants         Raytracing::SetConstants(const GraphicsSettings&)    Source/Raytracing.ixx:92-104
  *   pt_render                GBufferGeneration::Render + Raytracing::Render -> Dispatch / DispatchRays(W,H,1)
  *                                                       Source/GBufferGeneration.ixx:80-117, Raytracing.ixx:106-112,228-249
+ *   pt_render_gbuffer        GBufferGeneration::Render with its output textures   Source/GBufferGeneration.ixx:80-117
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -224,6 +225,33 @@ PtStatus pt_accumulate(PtContext *ctx, void *accum_device, const void *radiance_
  * The context holds the blur chain; a call that needs a larger one than it has waits for the context's stream (the
  * previous bloom calls) before it frees the old chain.  The render lanes' frames in flight never touch it. */
 PtStatus pt_bloom(PtContext *ctx, const void *hdr_device, void *out_device, uint32_t width, uint32_t height, float strength);
+
+/* Row N6 -- the G-buffer pass (Source/GBufferGeneration.ixx, Shaders/GBufferGeneration.hlsl; DESIGN.md spec S12): the 13 per-pixel
+ * surface buffers of the frame the next pt_render renders (current camera, constants, scene data and textures), for a host's
+ * denoiser, upscaler or TAA.  All float32, row-major inside the rect, with the reference's channel counts:
+ *   Position float4 (P, PositionOffset) | FlatNormal, GeometricNormal float2 (signed octahedral) | LinearDepth float |
+ *   NormalizedDepth float | MotionVector float3 (pixels, pixels, view depth) | BaseColorMetalness float4 | DiffuseAlbedo,
+ *   SpecularAlbedo float3 | NormalRoughness float4 | IOR float | Transmission float | Radiance float3 (emission, or the
+ *   environment on a miss).
+ * A miss writes Position = inf, LinearDepth = inf, NormalizedDepth = IsNormalizedDepthReversed ? 0 : 1, MotionVector and Radiance,
+ * and leaves the other buffers untouched; Transmission is written only where Metallic < 1.  Camera.Matrices must be filled
+ * (WorldToProjection, and PreviousWorldToProjection / PreviousWorldToView for the motion vectors).
+ * Runs asynchronously on the lane of the next pt_render and is ordered like that frame: with frames in flight the caller rotates over
+ * as many sets of G-buffer buffers as there are lanes (PT_FLAG_TWO_FRAMES_IN_FLIGHT's contract for frame buffers), and the pass waits
+ * for what the caller had queued before the render call N - 1 calls earlier -- or for everything queued so far, before the first render
+ * call or when a buffer is one another lane wrote within that window.  What is queued on the context's stream afterwards sees the result.
+ * It adds nothing to pt_get_totals and does not advance the frame lanes. */
+typedef struct PtGBuffer {          /* DEVICE pointers, NULL = not requested; float4 buffers 16-byte aligned, float2 8-byte */
+    void *Position, *FlatNormal, *GeometricNormal, *LinearDepth, *NormalizedDepth, *MotionVector,
+         *BaseColorMetalness, *DiffuseAlbedo, *SpecularAlbedo, *NormalRoughness, *IOR, *Transmission, *Radiance;
+} PtGBuffer;
+/* rect: NULL = the whole RenderSize (UVs are relative to the whole RenderSize either way).  previous_spheres (n PtSphere) and
+ * previous_rotations (n quaternions x, y, z, w): host arrays of the scene's n spheres, the previous pose (PreviousObjectToWorld of
+ * Scene::Refresh) the motion vectors of hits are measured from; NULL = the same as the current pose; both ignored while
+ * SceneData.IsStatic != 0.  PT_ERR_INVALID_ARG: no buffer requested, a misaligned buffer, a bad rect, a previous sphere that is
+ * not finite or has radius <= 0, a rotation that is not finite.  PT_ERR_STATE: as pt_render. */
+PtStatus pt_render_gbuffer(PtContext *ctx, const PtRect *rect, const PtGBuffer *out,
+                           const PtSphere *previous_spheres, const float *previous_rotations);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

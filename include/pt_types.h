@@ -50,7 +50,8 @@ typedef struct PtMaterial {
 
 /* Source/Camera.ixx:16-36. The bounce loop reads only Position, Right/Up/Forward
  * (un-normalised, lens scaled), NearDepth, FarDepth and Jitter
- * (Shaders/Raytracing.hlsl:114,126,138; Shaders/Camera.hlsli:27-41). */
+ * (Shaders/Raytracing.hlsl:114,126,138; Shaders/Camera.hlsli:27-41).  The G-buffer pass (pt_render_gbuffer)
+ * also reads IsNormalizedDepthReversed and three of the matrices (DirectXMath row-vector layout, 16 floats each). */
 typedef struct PtCamera {
     uint32_t IsNormalizedDepthReversed; /*   0 */
     float PreviousPosition[3];          /*   4 */
@@ -68,7 +69,8 @@ typedef struct PtCamera {
     float Matrices[8][16];              /*  96: PreviousWorldToView, PreviousViewToProjection,
                                                 PreviousWorldToProjection, PreviousProjectionToView,
                                                 PreviousViewToWorld, WorldToProjection, ProjectionToView,
-                                                ViewToWorld -- unused by the bounce loop */
+                                                ViewToWorld -- unused by the bounce loop; pt_render_gbuffer reads
+                                                WorldToProjection, PreviousWorldToProjection, PreviousWorldToView */
 } PtCamera;
 
 /* Source/CommonShaderData.ixx:15-20. EnvironmentLightColor.a < 0 selects the

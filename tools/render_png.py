@@ -4,7 +4,7 @@ with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom]
 R8G8B8A8.  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness]"""
 import argparse
 import os
 import sys
@@ -15,6 +15,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402  (device buffers only)
 import dxrs_amd_loader  # noqa: E402,F401
 import dxrs_amd  # noqa: E402
+
+
+def gbuffer_image(name, a):
+    """a G-buffer channel (h, w, c) as 8-bit RGB: unit vectors and octahedral normals as 0.5 + 0.5 v, motion vectors around grey,
+    colours and scalars scaled by their largest finite value; pixels the pass did not write (NaN) or infinite ones are black"""
+    valid = np.isfinite(a).all(axis=-1)
+    v = np.where(np.isfinite(a), a, 0.0).astype(np.float64)
+    if name in ("FlatNormal", "GeometricNormal", "NormalRoughness"):
+        rgb = 0.5 + 0.5 * np.concatenate([v[..., :3], np.zeros(v.shape[:2] + (max(0, 3 - v.shape[-1]),))], -1)[..., :3]
+    elif name == "MotionVector":
+        m = max(np.abs(v[..., :2]).max(), 1e-6)
+        rgb = np.stack([0.5 + 0.5 * v[..., 0] / m, 0.5 + 0.5 * v[..., 1] / m, np.full(v.shape[:2], 0.5)], -1)
+    else:
+        m = max(np.abs(v[valid]).max() if valid.any() else 1.0, 1e-6)
+        x = np.abs(v) / m
+        rgb = np.repeat(x[..., :1], 3, -1) if v.shape[-1] < 3 else x[..., :3]
+        rgb = rgb ** (1 / 2.2)
+    rgb[~valid] = 0.0
+    return (np.clip(rgb, 0.0, 1.0) * 255 + 0.5).astype(np.uint8)
 
 
 def main():
@@ -33,6 +52,8 @@ def main():
     ap.add_argument("--exposure", type=float, default=0.0, help="stops")
     ap.add_argument("--bloom", type=float, default=None, metavar="STRENGTH",
                     help="pt_bloom on the accumulated radiance before tone mapping (the reference's default is 0.05); off by default")
+    ap.add_argument("--gbuffer", default=None, metavar="CHANNEL", choices=[n for n, _ in dxrs_amd.types.GBUFFER_CHANNELS],
+                    help="write one channel of pt_render_gbuffer (row N6) of the first frame instead of the path-traced image")
     args = ap.parse_args()
     from PIL import Image
 
@@ -55,6 +76,14 @@ def main():
         r.set_textures(ts)
     w, h, n = args.width, args.height, args.width * args.height
     gs = t.graphics_settings(w, h, bounces=args.bounces, spp=args.spp)
+    if args.gbuffer:
+        r.set_camera(host.camera_matrices(w, h, jitter_index=0, jitter_count=max(args.frames, 8)))
+        r.set_constants(gs)
+        img = gbuffer_image(args.gbuffer, r.render_gbuffer([args.gbuffer])[args.gbuffer])
+        Image.fromarray(img).save(args.out)
+        print(f"G-buffer {args.gbuffer} {w}x{h} -> {args.out}")
+        r.close()
+        return
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
