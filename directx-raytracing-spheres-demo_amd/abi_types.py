@@ -61,6 +61,19 @@ class PtGBuffer(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in GBUFFER_CHANNELS]
 
 
+# Row N7 (pt_render_denoiser): GraphicsSettings.Denoiser values (Source/Denoiser.ixx) and the outputs of each mode, with their float32
+# counts per pixel
+DENOISER_NONE, DENOISER_DLSS_RR, DENOISER_NRD_REBLUR, DENOISER_NRD_RELAX = 0, 1, 2, 3
+DENOISER_OUTPUTS = {DENOISER_DLSS_RR: (("SpecularHitDistance", 1),),
+                    DENOISER_NRD_REBLUR: (("Diffuse", 4), ("Specular", 4)),
+                    DENOISER_NRD_RELAX: (("Diffuse", 4), ("Specular", 4))}
+
+
+class PtDenoiserOutputs(C.Structure):
+    _fields_ = [("Denoiser", C.c_uint32), ("_pad", C.c_uint32), ("Diffuse", C.c_void_p), ("Specular", C.c_void_p),
+                ("SpecularHitDistance", C.c_void_p)]
+
+
 class PtTextureMapInfo(C.Structure):
     _fields_ = [("Descriptor", C.c_uint32), ("TextureCoordinateIndex", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 

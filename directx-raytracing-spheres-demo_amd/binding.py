@@ -7,8 +7,8 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, GBUFFER_CHANNELS, PtAccelInfo, PtCamera, PtConfig, PtGBuffer, PtGraphicsSettings, PtRect, PtSceneData,
-                        PtStats)
+from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, PtAccelInfo, PtCamera, PtConfig, PtDenoiserOutputs, PtGBuffer,
+                        PtGraphicsSettings, PtRect, PtSceneData, PtStats)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -17,7 +17,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -89,6 +89,8 @@ class HipLib:
         lib.pt_bloom.argtypes = [vp, vp, vp, u32, u32, C.c_float]
         lib.pt_render_gbuffer.restype = C.c_int
         lib.pt_render_gbuffer.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBuffer), vp, vp]
+        lib.pt_render_denoiser.restype = C.c_int
+        lib.pt_render_denoiser.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtDenoiserOutputs), C.POINTER(PtStats)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -359,6 +361,33 @@ class Renderer:
         self.render_gbuffer_device({name: b.data_ptr() for name, b in bufs.items()}, rect, previous_spheres, previous_rotations)
         self.synchronize()
         return {name: b.cpu().numpy() for name, b in bufs.items()}
+
+    def render_denoiser_device(self, mode, out_ptr, buffers, rect=None, want_stats=False):
+        """A frame with the denoiser outputs of `mode` (row N7; abi_types.DENOISER_*) into device memory.  buffers: {output name: device
+        pointer} (DENOISER_OUTPUTS[mode]; others are ignored, a missing one is the library's PT_ERR_INVALID_ARG).  Asynchronous unless
+        want_stats; with frames in flight rotate over one set of buffers per lane, as for out."""
+        r = PtRect(*rect) if rect is not None else None
+        o = PtDenoiserOutputs(Denoiser=mode, **{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        stats = PtStats()
+        self._check(self._lib.pt_render_denoiser(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr), 1, C.byref(o),
+                                                 C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_denoiser(self, mode, rect=None, fill=float("nan"), device=None):
+        """render_denoiser_device into torch buffers filled with `fill` (what a pixel the frame does not write keeps) -> (out (h, w, 4),
+        {output name: numpy float32 (h, w, width)}).  Synchronous."""
+        import torch
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        # (filled from numpy: the fill's bits reach the buffers exactly, a NaN payload included)
+        out = torch.from_numpy(np.full((h, w, 4), fill, dtype=np.float32)).to(dev)
+        bufs = {name: torch.from_numpy(np.full((h, w, width), fill, dtype=np.float32)).to(dev) for name, width in DENOISER_OUTPUTS.get(mode, ())}
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        self.render_denoiser_device(mode, out.data_ptr(), {name: b.data_ptr() for name, b in bufs.items()}, rect)
+        self.synchronize()
+        return out.cpu().numpy(), {name: b.cpu().numpy() for name, b in bufs.items()}
 
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""

@@ -84,6 +84,7 @@ struct Lane {
     bool needs_refit = false;     // spheres were staged on this lane and its boxes / Morton-ordered copy have not been redone yet
     bool upload_pending = false;  // h_stage holds spheres that have not been copied to d_sph yet (pt_update_spheres of a small scene: pt_refit_accel's kernel reads them)
     const void* last_out = nullptr;   // output buffer of the lane's latest frame (render_common: repeated buffers inside the window)
+    const void* last_dn[3] = {};      // ... and its denoiser buffers (Diffuse, Specular, SpecularHitDistance; null for other frames)
     // object rotations (textured scenes): the lane's own copy, refreshed from PtContext::h_rot when its generation is behind
     float4* d_rot = nullptr;
     float4* h_rot_stage = nullptr;    // pinned
@@ -355,6 +356,7 @@ void free_lane_buffers(Lane& L)
 {
     for (auto& q : L.q) { free_dev(q.q0); free_dev(q.q1); free_dev(q.q2); free_dev(q.hit); }
     free_dev(L.scratch.sample_rad); free_dev(L.scratch.radiance); free_dev(L.scratch.primary_hit); free_dev(L.scratch.di); free_dev(L.scratch.primary_cache);
+    free_dev(L.scratch.dn.rec); free_dev(L.scratch.dn.di_s);
     L.cap_slots = 0;
     L.scratch_spp = false;
 }
@@ -975,9 +977,10 @@ static PtStatus check_environment(PtContext* c)
 //   separate traverse and shade kernels with a hit stream in between.
 // S = PT_TAIL_AFTER for spp == 1; with spp > 1 (sample regeneration keeps the queue full) the host polls the queue
 // size after every pass and switches to the looping kernel when it drops below PT_TAIL_THRESHOLD rays.
-PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, float4* out, PtStats* stats)
+// dn (row N7, pt_render_denoiser): the denoiser outputs of the frame (mode, caller buffers); null = an ordinary frame
+PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, float4* out, PtStats* stats, const DenoiseOut* dn = nullptr)
 {
-    const RoctxRange range(c, pm.mode == 0 ? "pt_render" : "pt_render_tiles");
+    const RoctxRange range(c, dn ? "pt_render_denoiser" : (pm.mode == 0 ? "pt_render" : "pt_render_tiles"));
     const uint32_t bounces = c->gs.Bounces, spp = c->gs.SamplesPerPixel;
     if (const PtStatus st = check_environment(c); st != PT_OK) return st;
     const size_t max_iters = (size_t)spp * bounces + 1;  // passes if everything ran as wavefront
@@ -1023,6 +1026,10 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     const bool seg_possible = !split && max_iters > 1 && primary_grid <= kMaxSegs && knob_or(c->knobs.seg, 1u) != 0 && c->knobs.loop_use_tail < 0;
     PtStatus st = ensure_buffers(c, L, split ? pm.n_slots : std::max<size_t>(pm.n_slots, seg_total), spp > 1, split, wf_cap + 2, di);
     if (st != PT_OK) return st;
+    // denoiser frames: the per-slot record and, in the NRD modes with DI, the specular half of the estimate (DenoiseOut); freed and
+    // reallocated with the lane's other per-slot buffers
+    if (dn && !L.scratch.dn.rec) PT_HIP(c, hipMalloc(&L.scratch.dn.rec, L.cap_slots * sizeof(float4)));
+    if (dn && dn->mode != 1 && di && !L.scratch.dn.di_s) PT_HIP(c, hipMalloc(&L.scratch.dn.di_s, L.cap_slots * sizeof(float4)));
     if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
     if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
     if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;  // pt_update_spheres without pt_refit_accel: the frame refits by itself
@@ -1064,16 +1071,32 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         // other lanes wrote within the window, this frame waits for the marker recorded at the start of THIS call -- i.e. for
         // everything the caller has queued so far, which includes the wait for that earlier frame and whatever consumed it.
         // (Costs the overlap of the frames, never correctness.)
-        for (uint32_t i = 0; i < c->n_lanes; i++)
-            if (&c->lanes[i] != &L && c->lanes[i].last_out == out) {
-                PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_in[c->calls % nl], 0));
-                break;
-            }
+        // (a denoiser frame's Diffuse / Specular / SpecularHitDistance are held to the same rule as `out`)
+        const void* mine[4] = { out, dn ? dn->diffuse : nullptr, dn ? dn->specular : nullptr, dn ? dn->spec_hit_dist : nullptr };
+        bool reused = false;
+        for (uint32_t i = 0; i < c->n_lanes && !reused; i++) {
+            if (&c->lanes[i] == &L) continue;
+            const Lane& o = c->lanes[i];
+            const void* theirs[4] = { o.last_out, o.last_dn[0], o.last_dn[1], o.last_dn[2] };
+            for (int a = 0; a < 4 && !reused; a++)
+                for (int b = 0; b < 4 && !reused; b++) reused = mine[a] && mine[a] == theirs[b];
+        }
+        if (reused) PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_in[c->calls % nl], 0));
         L.last_out = out;
+        for (int a = 0; a < 3; a++) L.last_dn[a] = mine[a + 1];
         c->calls++;
     }
 
     const SceneView sv = make_scene_view(c, &L);
+    // the lane's scratch as this frame's kernels see it: a denoiser frame names its mode and outputs (the kDn kernel instances), an
+    // ordinary one names none
+    Scratch scr = L.scratch;
+    scr.dn = DenoiseOut{};
+    if (dn) {
+        scr.dn = *dn;
+        scr.dn.rec = L.scratch.dn.rec;
+        scr.dn.di_s = L.scratch.dn.di_s;
+    }
     FrameParams fp = make_frame_params(c);
     fp.beam_lists = beam_lists;
     fp.beam_job = beam_job;
@@ -1155,7 +1178,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
             // row N4, split schedule: the direct-illumination estimate of every primary surface, before the shade passes read it
             // (the fused schedule's primary pass makes the estimate itself, at the first shading of the primary surface)
             const uint32_t di_grid = grid_for(pm.n_slots, trav_threads, trav_cap_wide);
-            PT_HIP(c, bracket(1, [&] { return launch_di(sv, pm, fp, L.scratch.di, L.scratch.primary_hit, fc.tail_rays, di_grid, L.stream); }));
+            PT_HIP(c, bracket(1, [&] { return launch_di(sv, pm, fp, L.scratch.di, L.scratch.primary_hit, fc.tail_rays, di_grid, L.stream, scr.dn.mode > 1 ? scr.dn.di_s : nullptr); }));
         }
         if (!split) {
             // The looping pass follows the primary pass directly (1 spp with the in-register second bounce; spp > 1): the hand-over
@@ -1175,7 +1198,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
             if (seg) { fc_seg.seg_counts = L.d_seg_counts; fc_seg.n_segs = primary_grid; fc_seg.seg_cap = seg_cap; fc_seg.fuse_loop = fuse ? 1u : 0u; }
             // spp > 1 with a separate looping pass over an untextured scene: the primary pass leaves each pixel's primary-hit record for the
             // samples the looping pass regenerates, and where it writes the pixel (Scratch::primary_cache)
-            Scratch scratch = L.scratch;
+            Scratch scratch = scr;
             if (sv.tex_maps || fuse || spp == 1) scratch.primary_cache = nullptr;  // (the untextured looping kernel of spp > 1 frames relies on the records)
             // pass 0 generates + traces the primaries and shades them into queue 1; pass k >= 1 consumes queue k
             for (size_t k = 0;; k++) {
@@ -1194,7 +1217,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
                 const uint32_t items = primary ? pm.n_slots : estimate(k);
                 const uint32_t cap = loop ? tail_cap : trav_cap;
                 if (loop && c->knobs.loop_use_tail >= 0) {
-                    PT_HIP(c, launch_tail(sv, pm, fp, qin, L.scratch, out, counts + k, fc.tail_rays, fc.totals, grid_for(items, kTailThreads, tail_cap), L.stream));
+                    PT_HIP(c, launch_tail(sv, pm, fp, qin, scr, out, counts + k, fc.tail_rays, fc.totals, grid_for(items, kTailThreads, tail_cap), L.stream));
                     break;
                 }
                 PT_HIP(c, bracket(loop ? 3 : (primary ? 0 : 1), [&] {
@@ -1205,18 +1228,18 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
             }
         } else {
             const uint32_t trav_grid = grid_for(pm.n_slots, trav_threads, trav_cap);
-            PT_HIP(c, bracket(0, [&] { return launch_primary(sv, pm, fp, L.q[0], L.scratch, out, fc, trav_grid, L.stream); }));
+            PT_HIP(c, bracket(0, [&] { return launch_primary(sv, pm, fp, L.q[0], scr, out, fc, trav_grid, L.stream); }));
             // shade pass k consumes queue k (counts[k]) and appends to queue k+1; queue k+1 is then traversed, or handed to the tail
             for (size_t k = 0;; k++) {
                 const RayQueue& qin = L.q[k & 1];
                 const RayQueue& qout = L.q[(k + 1) & 1];
-                PT_HIP(c, bracket(2, [&] { return launch_shade(sv, pm, fp, qin, qout, L.scratch, out, counts + k, counts + k + 1, grid_for(estimate(k), kShadeThreads, shade_cap), L.stream); }));
+                PT_HIP(c, bracket(2, [&] { return launch_shade(sv, pm, fp, qin, qout, scr, out, counts + k, counts + k + 1, grid_for(estimate(k), kShadeThreads, shade_cap), L.stream); }));
                 if (k + 1 == max_iters) break;  // no path can have another ray
                 bool go_loop = false, empty = false;
                 if ((st = poll(k, empty, go_loop)) != PT_OK) return st;
                 if (empty) break;
                 if (go_loop) {
-                    PT_HIP(c, bracket(3, [&] { return launch_tail(sv, pm, fp, qout, L.scratch, out, counts + k + 1, fc.tail_rays, fc.totals, grid_for(estimate(k + 1), kTailThreads, tail_cap), L.stream); }));
+                    PT_HIP(c, bracket(3, [&] { return launch_tail(sv, pm, fp, qout, scr, out, counts + k + 1, fc.tail_rays, fc.totals, grid_for(estimate(k + 1), kTailThreads, tail_cap), L.stream); }));
                     break;
                 }
                 if (!c->lds_scene && sv.n > 1 && knob_or(c->knobs.ray_replacement, 1)) {
@@ -1702,16 +1725,17 @@ static PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who
     return PT_OK;
 }
 
-PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
+// pt_render and pt_render_denoiser: a frame of the rect into `out` (a host buffer is staged through the context's device buffer and
+// copied back); dn = the denoiser outputs of a pt_render_denoiser frame, null for pt_render
+static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats, const DenoiseOut* dn, const char* who)
 {
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!out) return fail(c, PT_ERR_INVALID_ARG, "pt_render: null output");
+    if (!out) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null output");
     PtStatus st = validate_frame(c);
     if (st != PT_OK) return st;
     PT_HIP(c, hipSetDevice(c->device));
     PtRect r;
     PixelMap pm{};
-    if ((st = rect_pixel_map(c, rect, "pt_render", r, pm)) != PT_OK) return st;
+    if ((st = rect_pixel_map(c, rect, who, r, pm)) != PT_OK) return st;
     float4* dev_out = static_cast<float4*>(out);
     const size_t out_px = (size_t)r.w * r.h;
     if (!out_is_device) {
@@ -1723,13 +1747,42 @@ PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_devic
         }
         dev_out = c->d_out;
     }
-    st = render_common(c, pm, (uint64_t)r.w * r.h, dev_out, stats);
+    st = render_common(c, pm, (uint64_t)r.w * r.h, dev_out, stats, dn);
     if (st != PT_OK) return st;
     if (!out_is_device) {
         PT_HIP(c, hipMemcpyAsync(out, dev_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
         PT_HIP(c, hipStreamSynchronize(c->stream));
     }
     return PT_OK;
+}
+
+PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    return render_rect(c, rect, out, out_is_device, stats, nullptr, "pt_render");
+}
+
+// Row N7 -- a frame that writes the denoiser outputs of its mode (DESIGN.md spec S13): render_common with the kDn kernel instances
+PtStatus pt_render_denoiser(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtDenoiserOutputs* outputs, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!outputs) return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: null outputs");
+    const uint32_t mode = outputs->Denoiser;
+    if (mode < 1 || mode > 3) return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: Denoiser must be 1 (DLSSRayReconstruction), 2 (NRDReBLUR) or 3 (NRDReLAX)");
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
+    DenoiseOut dn{};
+    dn.mode = mode;
+    if (mode == 1) {
+        if (!outputs->SpecularHitDistance || misaligned(outputs->SpecularHitDistance, 4))
+            return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: DLSSRayReconstruction needs a 4-byte aligned SpecularHitDistance");
+        dn.spec_hit_dist = static_cast<float*>(outputs->SpecularHitDistance);
+    } else {
+        if (!outputs->Diffuse || !outputs->Specular || misaligned(outputs->Diffuse, 16) || misaligned(outputs->Specular, 16))
+            return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: the NRD modes need 16-byte aligned Diffuse and Specular");
+        dn.diffuse = static_cast<float4*>(outputs->Diffuse);
+        dn.specular = static_cast<float4*>(outputs->Specular);
+    }
+    return render_rect(c, rect, out, out_is_device, stats, &dn, "pt_render_denoiser");
 }
 
 // Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12)
@@ -1797,6 +1850,7 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
                 if (ptrs[k]) {
                     shared = ptrs[k] == c->lanes[i].last_out;
                     for (uint32_t j = 0; j < 13 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_gb[j];
+                    for (uint32_t j = 0; j < 3 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_dn[j];
                 }
         }
         if (shared) {

@@ -29,6 +29,7 @@ constexpr uint32_t kFlagSampleShift = 8;
 constexpr uint32_t kFlagSampleMask = 0xFFFFu;
 constexpr uint32_t kFlagDirty = 1u << 24;
 constexpr uint32_t kFlagViaTransmission = 1u << 25;  // row N4: this sample left the primary surface through the transmission lobe
+constexpr uint32_t kFlagDnSpecular = 1u << 26;       // row N7 (denoiser frames only): sample 0 left the primary surface through a lobe other than diffuse
 constexpr uint32_t kMissId = 0xFFFFFFFFu;
 
 // Alpha-tested hits (DESIGN.md spec S10; Scene.ixx:242-243, RaytracingHelpers.hlsli:19-43, ShadingHelpers.hlsli:105-115).  A sphere whose
@@ -194,6 +195,21 @@ struct FrameCounters {
 
 constexpr uint32_t kMaxSegs = 2048;
 
+// Row N7 (DESIGN.md spec S13): the outputs of a denoiser frame (pt_render_denoiser); mode 0 = an ordinary frame, and every other field is
+// then unused.  The kernels of such frames are the kDn instances; the None kernels never read this.
+//   rec[slot]  = {primary emission (prim), hit distance of sample 0's bounce-1 ray (hd; +inf by default)}: written by the first shading of
+//                the primary surface (and .w again by sample 0's bounce-1 hit), read when the pixel finishes
+//   di_s[slot] = NRD modes with DI: the specular half of the estimate (Scratch::di then holds the diffuse half)
+// diffuse / specular / spec_hit_dist are the caller's buffers, indexed like `out` (row-major inside the rect).
+struct DenoiseOut {
+    uint32_t mode;  // 1 DLSSRayReconstruction, 2 NRDReBLUR, 3 NRDReLAX
+    float4* rec;
+    float4* di_s;
+    float4* diffuse;
+    float4* specular;
+    float* spec_hit_dist;
+};
+
 // per-slot scratch (only touched when needed, see shade kernel)
 struct Scratch {
     float4* sample_rad;   // sampleRadiance of the sample in flight (valid when kFlagDirty)
@@ -204,6 +220,7 @@ struct Scratch {
     // of that pixel would compute again -- {N.xyz, spawn offset} {lobe weights, sphere id} {primary direction, -} per slot.  Written by
     // the primary pass, read by the looping pass when it regenerates a sample (L2-resident: a lane re-reads its 48 bytes every few steps).
     float4* primary_cache;
+    DenoiseOut dn;  // row N7: denoiser frames only (mode != 0)
 };
 
 }  // namespace pt

@@ -44,8 +44,9 @@ hipError_t launch_material_map_flags(float4* mats, const uint32_t* tex_maps, uin
 // alpha-tested hits: out[k] = sorted_id[k] | alpha_class[sorted_id[k]] << 30 (the leaf ids of SceneView::sorted_id)
 hipError_t launch_leaf_ids(const uint32_t* sorted_id, const uint32_t* alpha_class, uint32_t n, uint32_t* out, hipStream_t stream);
 
+// di_s non-null (row N7, NRD modes): di receives the diffuse half of the estimate and di_s the specular half
 hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, float4* di, uint2* primary_hit, unsigned long long* ray_counter, uint32_t grid,
-                     hipStream_t stream);
+                     hipStream_t stream, float4* di_s = nullptr);
 hipError_t launch_tonemap(const float4* hdr, uint32_t* out, uint32_t n, const PtToneMapParams& p, hipStream_t stream);
 hipError_t launch_accumulate(float4* accum, const float4* rad, uint32_t n, uint32_t frames_accumulated, hipStream_t stream);
 // bloom (row N5, pt_bloom.hip): the 9 chain steps and the merge, 10 launches on `stream`.  chain: bloom_chain(width,

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void traverse_dyn_kernel(SceneView sv, RayQueu
     flush_visit_counters(totals, visits);
 }
 
-template <bool kTex>
+template <bool kTex, bool kDn>
 __global__ __launch_bounds__(kShadeThreads) void shade_kernel(SceneView sv, PixelMap pm, FrameParams fp, RayQueue qin, RayQueue qout,
                                                               Scratch scratch, float4* __restrict__ out,
                                                               const uint32_t* __restrict__ count_in_ptr, uint32_t* __restrict__ count_out_ptr)
@@ -222,9 +222,9 @@ __global__ __launch_bounds__(kShadeThreads) void shade_kernel(SceneView sv, Pixe
         bool emit = false;
         PathState ps;
         if (i < count) {
-            ps = load_path(qin, i);
+            ps = load_path<kDn>(qin, i);
             const uint2 h = qin.hit[i];
-            if (ps.bounce != 0xFFu) emit = shade_step<true, kTex>(sv, pm, fp, scratch, out, ps, as_float(h.x), h.y);
+            if (ps.bounce != 0xFFu) emit = shade_step<true, kTex, false, 0, kDn>(sv, pm, fp, scratch, out, ps, as_float(h.x), h.y);
         }
         // ---- wave64 ballot + prefix compaction into the next queue; one atomic per block
         const unsigned long long mask = __ballot(emit);
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kShadeThreads) void shade_kernel(SceneView sv, Pixe
             s_block_base = total ? atomicAdd(count_out_ptr, total) : 0u;
         }
         __syncthreads();
-        if (emit) store_path(qout, s_block_base + s_wave_count[wave] + prefix, ps);
+        if (emit) store_path<kDn>(qout, s_block_base + s_wave_count[wave] + prefix, ps);
         __syncthreads();
     }
 }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(kShadeThreads) void shade_kernel(SceneView sv, Pixe
 // When the queue has become small, per-launch latency (dispatch + BVH staging + one traversal chain) dominates a
 // wavefront pass.  The tail kernel finishes every queued path in ONE launch: each lane alternates closest_hit and
 // shade_step in registers until its pixel is done (persistent threads; no queue traffic, no compaction).
-template <bool kLds, typename StackT, bool kTex>
+template <bool kLds, typename StackT, bool kTex, bool kDn>
 __global__ __launch_bounds__(kTailThreads) void tail_kernel(SceneView sv, PixelMap pm, FrameParams fp, RayQueue qin, Scratch scratch,
                                                             float4* __restrict__ out, const uint32_t* __restrict__ count_ptr,
                                                             unsigned long long* __restrict__ tail_rays, unsigned long long* __restrict__ totals)
@@ -273,13 +273,13 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(SceneView sv, PixelM
     stack += threadIdx.x;
     uint32_t my_rays = 0;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-        PathState ps = load_path(qin, i);
+        PathState ps = load_path<kDn>(qin, i);
         if (ps.bounce == 0xFFu) continue;
         for (;;) {
             float t;
             uint32_t id;
             closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, 0.0f, kInf, stack, blockDim.x, t, id, kLds ? nullptr : visits);
-            if (!shade_step<true, kTex>(sv, pm, fp, scratch, out, ps, t, id)) break;
+            if (!shade_step<true, kTex, false, 0, kDn>(sv, pm, fp, scratch, out, ps, t, id)) break;
             my_rays++;  // rays spawned inside the tail (the input queue's rays are already in counts[])
         }
     }
@@ -293,9 +293,10 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(SceneView sv, PixelM
 // choice, uniform direction in its cone), trace the shadow ray with the ordinary closest-hit query -- the emitter must be
 // the first thing it meets -- and store  DI = Le * (f_diffuse + f_specular) cos * n_lights / pdf.
 // shade_step drops the emission of first-bounce hits reached through a reflective lobe and adds DI to the final radiance.  Own RNG stream; both rays are counted.
-template <bool kLds, typename StackT, bool kTex>
+// kSplit (row N7, NRD modes of denoiser frames): di holds the diffuse half of the estimate, di_s the specular half (di_estimate).
+template <bool kLds, typename StackT, bool kTex, bool kSplit>
 __global__ __launch_bounds__(kTraverseThreads) void di_kernel(SceneView sv, PixelMap pm, FrameParams fp, float4* __restrict__ di, uint2* __restrict__ primary_hit,
-                                                              unsigned long long* __restrict__ ray_counter)
+                                                              unsigned long long* __restrict__ ray_counter, float4* __restrict__ di_s)
 {
     extern __shared__ float4 smem[];
     const float4* nodes = sv.nodes;
@@ -316,6 +317,7 @@ __global__ __launch_bounds__(kTraverseThreads) void di_kernel(SceneView sv, Pixe
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
         f3 est = make_f3(0.f, 0.f, 0.f);
+        f3 halves[2] = { est, est };  // kSplit
         if (pr.valid) {
             f3 o, d;
             float tmin, tmax, t;
@@ -327,12 +329,17 @@ __global__ __launch_bounds__(kTraverseThreads) void di_kernel(SceneView sv, Pixe
             primary_hit[slot] = make_uint2(as_uint(t), id);
             if (id != kMissId) {
                 const HitMaterial hm = hit_material<kTex>(sv, id, o, d, t, true);
-                est = di_estimate<kTex>(sv, fp, pr.px, pr.py, id, d, hm,
-                                        [&](f3 so, f3 sd, float& t2, uint32_t& id2) { closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, so, sd, 0.0f, kInf, stack, blockDim.x, t2, id2); },
-                                        my_rays);
+                est = di_estimate<kTex, kSplit>(sv, fp, pr.px, pr.py, id, d, hm,
+                                                [&](f3 so, f3 sd, float& t2, uint32_t& id2) { closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, so, sd, 0.0f, kInf, stack, blockDim.x, t2, id2); },
+                                                my_rays, halves);
             }
         }
-        di[slot] = make_float4(est.x, est.y, est.z, 0.0f);
+        if (kSplit) {
+            di[slot] = make_float4(halves[0].x, halves[0].y, halves[0].z, 0.0f);
+            di_s[slot] = make_float4(halves[1].x, halves[1].y, halves[1].z, 0.0f);
+        } else {
+            di[slot] = make_float4(est.x, est.y, est.z, 0.0f);
+        }
     }
     block_atomic_add(ray_counter, my_rays);
 }
@@ -579,16 +586,18 @@ hipError_t launch_tail(const SceneView& sv, const PixelMap& pm, const FrameParam
     const bool small = sv.n_nodes < 32767u;
     const uint32_t elem = small ? 2u : 4u;
     const uint32_t lds = (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + kTailThreads * sv.stack_depth * elem;
-#define PT_TAIL2(L, T, X)                                                                                                  \
+#define PT_TAIL3(L, T, X, N)                                                                                               \
     do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)tail_kernel<L, T, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((tail_kernel<L, T, X>), dim3(grid), dim3(kTailThreads), lds, stream, sv, pm, fp, qin, scratch, out, count_ptr, tail_rays, totals); \
+        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)tail_kernel<L, T, X, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((tail_kernel<L, T, X, N>), dim3(grid), dim3(kTailThreads), lds, stream, sv, pm, fp, qin, scratch, out, count_ptr, tail_rays, totals); \
     } while (0)
+#define PT_TAIL2(L, T, X) do { if (scratch.dn.mode) PT_TAIL3(L, T, X, true); else PT_TAIL3(L, T, X, false); } while (0)
 #define PT_TAIL(L, T) do { if (sv.tex_maps) PT_TAIL2(L, T, true); else PT_TAIL2(L, T, false); } while (0)
     if (sv.lds_scene) { if (small) PT_TAIL(true, uint16_t); else PT_TAIL(true, uint32_t); }
     else { if (small) PT_TAIL(false, uint16_t); else PT_TAIL(false, uint32_t); }
 #undef PT_TAIL
 #undef PT_TAIL2
+#undef PT_TAIL3
     return hipGetLastError();
 }
 
@@ -608,8 +617,10 @@ hipError_t launch_bounce(const SceneView& sv, const PixelMap& pm, const FramePar
 hipError_t launch_shade(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const RayQueue& qin, const RayQueue& qout,
                         const Scratch& scratch, float4* out, const uint32_t* count_in, uint32_t* count_out, uint32_t grid, hipStream_t stream)
 {
-    if (sv.tex_maps) hipLaunchKernelGGL(shade_kernel<true>, dim3(grid), dim3(kShadeThreads), 0, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out);
-    else hipLaunchKernelGGL(shade_kernel<false>, dim3(grid), dim3(kShadeThreads), 0, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out);
+#define PT_SHADE(X, N) hipLaunchKernelGGL((shade_kernel<X, N>), dim3(grid), dim3(kShadeThreads), 0, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out)
+    if (scratch.dn.mode) { if (sv.tex_maps) PT_SHADE(true, true); else PT_SHADE(false, true); }  // row N7: denoiser frames
+    else { if (sv.tex_maps) PT_SHADE(true, false); else PT_SHADE(false, false); }
+#undef PT_SHADE
     return hipGetLastError();
 }
 
@@ -646,21 +657,23 @@ hipError_t launch_unpack_tiles(const float4* packed, float4* frame, uint32_t w, 
 }
 
 hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, float4* di, uint2* primary_hit, unsigned long long* ray_counter, uint32_t grid,
-                     hipStream_t stream)
+                     hipStream_t stream, float4* di_s)
 {
     const bool small = sv.n_nodes < 32767u;
     const uint32_t threads = traverse_threads(sv.lds_scene != 0);
     const uint32_t lds = traverse_lds_bytes(sv, small ? 2u : 4u);
-#define PT_DI2(L, T, X)                                                                                                     \
+#define PT_DI3(L, T, X, S)                                                                                                  \
     do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)di_kernel<L, T, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((di_kernel<L, T, X>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, di, primary_hit, ray_counter);       \
+        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)di_kernel<L, T, X, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((di_kernel<L, T, X, S>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, di, primary_hit, ray_counter, di_s); \
     } while (0)
+#define PT_DI2(L, T, X) do { if (di_s) PT_DI3(L, T, X, true); else PT_DI3(L, T, X, false); } while (0)
 #define PT_DI(L, T) do { if (sv.tex_maps) PT_DI2(L, T, true); else PT_DI2(L, T, false); } while (0)
     if (sv.lds_scene) { if (small) PT_DI(true, uint16_t); else PT_DI(true, uint32_t); }
     else { if (small) PT_DI(false, uint16_t); else PT_DI(false, uint32_t); }
 #undef PT_DI
 #undef PT_DI2
+#undef PT_DI3
     return hipGetLastError();
 }
 

@@ -54,6 +54,14 @@ PT_HD f3 bsdf_eval_reflective(const Bsdf& b, const Surf& s, f3 L, f3 V, const fl
     return bsdf_eval(b, s, L, V, w, kLobeDiffuse) + bsdf_eval(b, s, L, V, w, kLobeSpecular);
 }
 
+// Row N7 (spec S13): the two lobes of bsdf_eval_reflective apart, for the NRD modes' diffuse / specular split of the estimate;
+// f_d + f_s is bsdf_eval_reflective bit for bit
+PT_HD void bsdf_eval_reflective_lobes(const Bsdf& b, const Surf& s, f3 L, f3 V, const float w[3], f3& f_d, f3& f_s)
+{
+    f_d = bsdf_eval(b, s, L, V, w, kLobeDiffuse);
+    f_s = bsdf_eval(b, s, L, V, w, kLobeSpecular);
+}
+
 constexpr float kDiNegligible = 1e-7f;  // upper bound of an estimate below which no shadow ray is cast (di_estimate)
 constexpr uint32_t kDiRngSalt = 0x44495F31u;  // the DI pass has its own per-pixel stream: rng_init(px, py, FrameIndex ^ salt)
 

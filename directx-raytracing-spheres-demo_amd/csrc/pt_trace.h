@@ -503,6 +503,7 @@ struct PathState {
     uint32_t slot, rng, bounce, sample;
     bool dirty;  // scratch.sample_rad[slot] holds this sample's radiance so far
     bool via_t;  // the sample left the primary surface through the transmission lobe (direct illumination does not cover it)
+    bool dn_spec;  // denoiser frames (kDn): sample 0 left the primary surface through a lobe other than diffuse (kFlagDnSpecular)
 };
 
 // One iteration of the bounce-loop body (Raytracing.hlsl:213-364) for a path whose ray (ps.o, ps.d) has been traced to
@@ -524,11 +525,14 @@ __device__ __forceinline__ HitMaterial hit_material(const SceneView& sv, uint32_
 // uniformly, a direction uniformly inside the cone it subtends, a shadow ray through `trace` (the ordinary closest-hit query:
 // the emitter must be the first thing it meets), DI = Le * (f_diffuse + f_specular) cos * n_lights / pdf with Le evaluated at the
 // point the shadow ray reaches (EvaluateMaterial: an emissive map modulates it).  Own per-pixel RNG stream.
-template <bool kTex, typename TraceFn>
+// kSplit (row N7, the NRD modes of denoiser frames): also the estimate's diffuse and specular halves, (Le * f_d) * k and (Le * f_s) * k,
+// zeroed wherever the sum is (halves[0], halves[1]); the sum is formed exactly as without the split.
+template <bool kTex, bool kSplit = false, typename TraceFn>
 __device__ __forceinline__ f3 di_estimate(const SceneView& sv, const FrameParams& fp, uint32_t px, uint32_t py, uint32_t id, f3 d, const HitMaterial& hm,
-                                          TraceFn&& trace, uint32_t& rays)
+                                          TraceFn&& trace, uint32_t& rays, f3* halves = nullptr)
 {
     f3 est = make_f3(0.f, 0.f, 0.f);
+    f3 est_d = est, est_s = est;  // kSplit only
     uint32_t rng = rng_init(px, py, fp.frame_index ^ kDiRngSalt);
     const float u0 = rng_float(rng), u1 = rng_float(rng), u2 = rng_float(rng);
     const uint32_t light = sv.lights[pick_light(u0, sv.n_lights)];
@@ -539,7 +543,9 @@ __device__ __forceinline__ f3 di_estimate(const SceneView& sv, const FrameParams
         const f3 V = -d;
         float w[3];
         lobe_weights(hm.bsdf, surf, V, w);
-        const f3 f = bsdf_eval_reflective(hm.bsdf, surf, s.L, V, w);
+        f3 f, f_d, f_s;
+        if (kSplit) { bsdf_eval_reflective_lobes(hm.bsdf, surf, s.L, V, w, f_d, f_s); f = f_d + f_s; }
+        else f = bsdf_eval_reflective(hm.bsdf, surf, s.L, V, w);
         // No shadow ray for a contribution that cannot matter: the estimate's upper bound with the emitter's untextured radiance
         // (maps modulate it downwards) is below kDiNegligible -- a mirror-like primary surface seen off its specular direction,
         // i.e. most of the demo's ground.  (Bias below 1e-7 of unit radiance per pixel; spec of this row, not of the reference.)
@@ -555,11 +561,15 @@ __device__ __forceinline__ f3 di_estimate(const SceneView& sv, const FrameParams
             if (id2 == light) {
                 const f3 le = hit_material<kTex>(sv, light, so, s.L, t2, false).emission;
                 est = (le * f) * k;
+                if (kSplit) { est_d = (le * f_d) * k; est_s = (le * f_s) * k; }
             }
         }
     }
-    if (!(est.x > 0.0f || est.y > 0.0f || est.z > 0.0f) || !is_finite(est.x) || !is_finite(est.y) || !is_finite(est.z))
+    if (!(est.x > 0.0f || est.y > 0.0f || est.z > 0.0f) || !is_finite(est.x) || !is_finite(est.y) || !is_finite(est.z)) {
         est = make_f3(0.f, 0.f, 0.f);  // NaN / inf / negative estimates count as no light
+        est_d = est; est_s = est;
+    }
+    if (kSplit) { halves[0] = est_d; halves[1] = est_s; }
     return est;
 }
 
@@ -580,9 +590,12 @@ struct NoTrace {
 // Merged, a lane whose ray missed finishes its sample first and then shades its regenerated primary hit TOGETHER with the lanes that
 // hit; a lane whose sample ends in the surface code returns kShadePending and starts its next call there (no ray to trace in between).
 // Per-lane order of operations, RNG draws and arithmetic are unchanged.  `pending` in: the previous call returned kShadePending.
+// kDn (row N7, DESIGN.md spec S13; frames of pt_render_denoiser, scratch.dn.mode != 0): the pixel's finish writes the denoiser outputs.  The
+// first shading of sample 0's primary surface leaves {prim, hd = +inf} in scratch.dn.rec, sample 0's lobe at bounce 0 rides in the path's
+// flags (ps.dn_spec), its bounce-1 hit replaces hd; with kDI the estimate goes straight to scratch (split by lobe in the NRD modes).
 enum : int { kShadeDone = 0, kShadeRay = 1, kShadePending = 2 };
 
-template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kMerge = false, typename TraceFn = NoTrace>
+template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kMerge = false, bool kDn = false, typename TraceFn = NoTrace>
 __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const Scratch& scratch,
                                              float4* __restrict__ out, PathState& ps, float t, uint32_t id, bool pending, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr)
 {
@@ -636,6 +649,10 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
             hm = hit_material<kTex>(sv, id, ps.o, ps.d, t, ps.bounce == 0);
         }
         hf = hm.hf;
+        if (kDn && (!kMulti || ps.sample == 0)) {
+            if (ps.bounce == 0) scratch.dn.rec[slot] = make_float4(hm.emission.x, hm.emission.y, hm.emission.z, kInf);  // prim (= G-buffer Radiance), hd default
+            else if (ps.bounce == 1) reinterpret_cast<float*>(scratch.dn.rec + slot)[3] = t;  // sample 0's bounce-1 ray hit at t (a miss keeps +inf)
+        }
         f3 emission = hm.emission;
         const f3 Ns = hm.Ns;
         const Bsdf& bsdf = hm.bsdf;
@@ -647,8 +664,19 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
         if (fp.di_enabled && ps.bounce == 1 && !ps.via_t) emission = make_f3(0.f, 0.f, 0.f);
         if (kDI && fp.di_enabled && ps.bounce == 0 && (!kMulti || ps.sample == 0) && !di_have) {
             const PixelRef dpr = slot_to_pixel(pm, slot);
-            di_val = di_estimate<kTex>(sv, fp, dpr.px, dpr.py, id, ps.d, hm, trace, *di_rays);
-            di_have = true;
+            if (kDn) {  // stored at once (the finish reads it back): no estimate lives across the bounce in registers
+                f3 halves[2];
+                const f3 est = di_estimate<kTex, true>(sv, fp, dpr.px, dpr.py, id, ps.d, hm, trace, *di_rays, halves);
+                if (scratch.dn.mode == 1) {
+                    scratch.di[slot] = make_float4(est.x, est.y, est.z, 0.f);
+                } else {
+                    scratch.di[slot] = make_float4(halves[0].x, halves[0].y, halves[0].z, 0.f);
+                    scratch.dn.di_s[slot] = make_float4(halves[1].x, halves[1].y, halves[1].z, 0.f);
+                }
+            } else {
+                di_val = di_estimate<kTex>(sv, fp, dpr.px, dpr.py, id, ps.d, hm, trace, *di_rays);
+                di_have = true;
+            }
         }
         const bool t_finite = is_finite(ps.T.x) && is_finite(ps.T.y) && is_finite(ps.T.z);
         if (emission.x != 0.0f || emission.y != 0.0f || emission.z != 0.0f || !t_finite) {
@@ -693,6 +721,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
         }
         if (!end_sample && luminance(ps.T) <= fp.throughput_threshold) end_sample = true;  // :361
         if (last) end_sample = true;
+        if (kDn && !end_sample && ps.bounce == 0 && (!kMulti || ps.sample == 0)) ps.dn_spec = lobe != kLobeDiffuse;  // (transmission counts as specular)
     };
 
     // spawn the next ray (Raytracing.hlsl:219-224)
@@ -717,6 +746,27 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
             f3 res = make_f3(0.f, 0.f, 0.f);
             if (is_finite(total.x) && is_finite(total.y) && is_finite(total.z)) {
                 res = total * fp.inv_spp;
+            }
+            if (kDn) {  // spec S13, by mode (Raytracing.hlsl:377-414)
+                const uint32_t out_index = kCacheMode == 2 ? as_uint(scratch.primary_cache[(size_t)slot * 3u + 2u].w) : slot_to_pixel(pm, slot).out_index;
+                const float4 rec = scratch.dn.rec[slot];
+                const bool diffuse = !ps.dn_spec;
+                if (scratch.dn.mode == 1) {  // DLSS-RR: the radiance of pt_render, and the hit distance of a specular first bounce
+                    if (fp.di_enabled) { const float4 di = scratch.di[slot]; res = res + load3(di); }
+                    out[out_index] = make_float4(res.x, res.y, res.z, 1.0f);
+                    if (!diffuse && is_finite(rec.w)) scratch.dn.spec_hit_dist[out_index] = rec.w;
+                } else {  // NRD: the primary emission; the rest by the lobe of the first bounce, with the DI halves
+                    const f3 prim = load3(rec);
+                    const f3 ind = make_f3(pt_max(res.x - prim.x, 0.0f), pt_max(res.y - prim.y, 0.0f), pt_max(res.z - prim.z, 0.0f));
+                    f3 di_d = make_f3(0.f, 0.f, 0.f), di_s = di_d;
+                    if (fp.di_enabled) { const float4 a = scratch.di[slot], b = scratch.dn.di_s[slot]; di_d = load3(a); di_s = load3(b); }
+                    const f3 zero = make_f3(0.f, 0.f, 0.f);
+                    const f3 dif = di_d + (diffuse ? ind : zero), spe = di_s + (diffuse ? zero : ind);
+                    scratch.dn.diffuse[out_index] = make_float4(dif.x, dif.y, dif.z, diffuse ? rec.w : 0.0f);
+                    scratch.dn.specular[out_index] = make_float4(spe.x, spe.y, spe.z, diffuse ? 0.0f : rec.w);
+                    out[out_index] = make_float4(prim.x, prim.y, prim.z, 1.0f);
+                }
+                return true;
             }
             if (fp.di_enabled) {  // radiance += DI (:381)
                 if (kDI && di_have) res = res + di_val;
@@ -780,13 +830,15 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
 
 // One iteration of the bounce-loop body for a path whose ray (ps.o, ps.d) has been traced to (t, id), as the kernels outside the merged
 // looping pass use it: true = ps holds a new ray that must be traced, false = the pixel is finished.
-template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, typename TraceFn = NoTrace>
+template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kDn = false, typename TraceFn = NoTrace>
 __device__ __forceinline__ bool shade_step(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const Scratch& scratch,
                                            float4* __restrict__ out, PathState& ps, float t, uint32_t id, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr)
 {
-    return shade_step_ex<kMulti, kTex, kDI, kCacheMode, false>(sv, pm, fp, scratch, out, ps, t, id, false, trace, di_rays) == kShadeRay;
+    return shade_step_ex<kMulti, kTex, kDI, kCacheMode, false, kDn>(sv, pm, fp, scratch, out, ps, t, id, false, trace, di_rays) == kShadeRay;
 }
 
+// kDn: the queue record also carries PathState::dn_spec (kFlagDnSpecular; denoiser frames)
+template <bool kDn = false>
 __device__ __forceinline__ PathState load_path(const RayQueue& q, uint32_t i)
 {
     const float4 a = q.q0[i], b = q.q1[i], c = q.q2[i];
@@ -798,13 +850,15 @@ __device__ __forceinline__ PathState load_path(const RayQueue& q, uint32_t i)
     ps.sample = (flags >> kFlagSampleShift) & kFlagSampleMask;
     ps.dirty = (flags & kFlagDirty) != 0;
     ps.via_t = (flags & kFlagViaTransmission) != 0;
+    ps.dn_spec = kDn && (flags & kFlagDnSpecular) != 0;
     return ps;
 }
 
+template <bool kDn = false>
 __device__ __forceinline__ void store_path(const RayQueue& q, uint32_t j, const PathState& ps)
 {
     const uint32_t flags = (ps.bounce & kFlagBounceMask) | ((ps.sample & kFlagSampleMask) << kFlagSampleShift) | (ps.dirty ? kFlagDirty : 0u)
-                           | (ps.via_t ? kFlagViaTransmission : 0u);
+                           | (ps.via_t ? kFlagViaTransmission : 0u) | (kDn && ps.dn_spec ? kFlagDnSpecular : 0u);
     q.q0[j] = make_float4(ps.o.x, ps.o.y, ps.o.z, as_float(ps.slot));
     q.q1[j] = make_float4(ps.d.x, ps.d.y, ps.d.z, as_float(ps.rng));
     q.q2[j] = make_float4(ps.T.x, ps.T.y, ps.T.z, as_float(flags));
@@ -835,8 +889,8 @@ __device__ __forceinline__ T cold_arg(uint32_t offset)
 // from the input queue), traces it, and runs one shade_step.  kLoop = false: survivors are compacted into the output
 // queue (wave64 ballot + prefix, one atomic per workgroup) -- one wavefront bounce per launch, 96 B of queue traffic
 // per ray and no hit stream.  kLoop = true: the lane keeps alternating trace and shade_step until its pixel is done
-// (the persistent "tail" form for small queues).
-template <bool kLds, typename StackT, bool kPrimary, bool kLoop, bool kMulti, bool kTex, bool kInline2, bool kFuse, bool kDI>
+// (the persistent "tail" form for small queues).  kDn: the instance of a denoiser frame (shade_step_ex; row N7).
+template <bool kLds, typename StackT, bool kPrimary, bool kLoop, bool kMulti, bool kTex, bool kInline2, bool kFuse, bool kDI, bool kDn>
 // 4 waves/SIMD (<= 128 VGPRs): two 512-thread workgroups per CU with the BVH in LDS (the unconstrained build takes 134
 // VGPRs for the primary variant and drops to 3 waves/SIMD: measured 171 -> 149 us for the two compacting passes at C2)
 __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void bounce_kernel(SceneView sv, PixelMap pm, FrameParams fp, RayQueue qin, RayQueue qout,
@@ -985,7 +1039,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 const PixelMap pm_c = cold_arg<PixelMap>(offsetof(BounceArgHead, pm));
                 const PixelRef pr = slot_to_pixel(pm_c, i);
                 live = pr.valid;
-                ps.slot = i; ps.bounce = 0; ps.sample = 0; ps.dirty = false; ps.via_t = false; ps.rng = 0;
+                ps.slot = i; ps.bounce = 0; ps.sample = 0; ps.dirty = false; ps.via_t = false; ps.dn_spec = false; ps.rng = 0;
                 ps.T = make_f3(1.f, 1.f, 1.f);
                 ps.o = make_f3(0.f, 0.f, 0.f); ps.d = make_f3(0.f, 0.f, 1.f);
                 if (live) {
@@ -999,9 +1053,9 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 // dense index -> (segment, offset): the last segment whose prefix is <= i
                 uint32_t lo = 0, hi = fc.n_segs;
                 while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (s_seg_prefix[mid] <= i) lo = mid; else hi = mid; }
-                ps = load_path(qin, lo * fc.seg_cap + (i - s_seg_prefix[lo]));
+                ps = load_path<kDn>(qin, lo * fc.seg_cap + (i - s_seg_prefix[lo]));
             } else {
-                ps = load_path(qin, i);
+                ps = load_path<kDn>(qin, i);
             }
             constexpr bool kMerged = kLoop && kMulti && !kPrimary;  // (shade_step_ex: one pass through the surface code per iteration)
             if (kMerged) {
@@ -1011,7 +1065,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                     float t = 0.0f;
                     uint32_t id = kMissId;
                     if (!pending) closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, 0.0f, kInf, stack, blockDim.x, t, id);
-                    const int r = shade_step_ex<true, kTex, false, kCacheMode, true>(sv, pm, fp, scratch, out, ps, t, id, pending);
+                    const int r = shade_step_ex<true, kTex, false, kCacheMode, true, kDn>(sv, pm, fp, scratch, out, ps, t, id, pending);
                     if (r == kShadeDone) break;
                     pending = r == kShadePending;
                     if (!pending) my_rays++;  // a ray spawned and traced inside this kernel
@@ -1033,11 +1087,11 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                     // Scratch::primary_cache: the compacting primary pass of an spp > 1 frame writes the records, the looping pass restarts samples from them
                     constexpr int kCacheMode = (kMulti && !kTex) ? ((kPrimary && !kLoop) ? 1 : ((kLoop && !kPrimary) ? 2 : 0)) : 0;
                     if (kDI)  // row N4: the first shading of the primary surface also makes its direct-illumination estimate
-                        emit = shade_step<kMulti, kTex, true, kCacheMode>(sv, pm, fp, scratch, out, ps, t, id,
+                        emit = shade_step<kMulti, kTex, true, kCacheMode, kDn>(sv, pm, fp, scratch, out, ps, t, id,
                                                               [&](f3 so, f3 sd, float& t2, uint32_t& id2) { closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, so, sd, 0.0f, kInf, stack, blockDim.x, t2, id2); },
                                                               &my_rays);
                     else
-                        emit = shade_step<kMulti, kTex, false, kCacheMode>(sv, pm, fp, scratch, out, ps, t, id);
+                        emit = shade_step<kMulti, kTex, false, kCacheMode, kDn>(sv, pm, fp, scratch, out, ps, t, id);
                     if (!emit) break;
                     if (!kLoop && ++iter >= kIters) break;
                     my_rays++;  // a ray spawned and traced inside this kernel (queued rays are counted by counts[])
@@ -1054,7 +1108,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             uint32_t base = 0;
             if (lane == 0 && wave_n) base = atomicAdd(&s_seg_count, wave_n);
             base = __shfl(base, 0, 64);
-            if (emit) store_path(qout, blockIdx.x * fc.seg_cap + base + __popcll(mask & ((1ull << lane) - 1ull)), ps);
+            if (emit) store_path<kDn>(qout, blockIdx.x * fc.seg_cap + base + __popcll(mask & ((1ull << lane) - 1ull)), ps);
         } else if (!kLoop) {
             // One atomic per WORKGROUP.  (One per wave -- no barriers, waves never wait for each other -- was measured and is
             // far worse: 0.116 -> 0.201 ms per C2 frame; 8x as many same-address device-scope atomics from 8 XCDs serialise.)
@@ -1070,7 +1124,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 s_block_base = total ? atomicAdd(count_out_ptr, total) : 0u;
             }
             __syncthreads();
-            if (emit) store_path(qout, s_block_base + s_wave_count[wave] + prefix, ps);
+            if (emit) store_path<kDn>(qout, s_block_base + s_wave_count[wave] + prefix, ps);
             __syncthreads();
         }
     }
@@ -1093,12 +1147,12 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 if (w >= n_own) break;
                 const uint32_t i = w + lane;
                 if (i < n_own) {
-                    PathState ps = load_path(qout, blockIdx.x * fc.seg_cap + i);
+                    PathState ps = load_path<kDn>(qout, blockIdx.x * fc.seg_cap + i);
                     for (;;) {
                         float t;
                         uint32_t id;
                         closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, 0.0f, kInf, stack, blockDim.x, t, id);
-                        if (!shade_step<kMulti, kTex>(sv, pm, fp, scratch, out, ps, t, id)) break;
+                        if (!shade_step<kMulti, kTex, false, 0, kDn>(sv, pm, fp, scratch, out, ps, t, id)) break;
                         my_loop_rays++;
                     }
                 }
@@ -1135,11 +1189,14 @@ hipError_t launch_bounce_for(const SceneView& sv, const PixelMap& pm, const Fram
                              bool primary, bool loop, bool inline2, uint32_t threads, uint32_t grid, hipStream_t stream)
 {
     const uint32_t lds = (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + threads * sv.stack_depth * (uint32_t)sizeof(StackT);
-#define PT_BOUNCE8(P, LP, M, X, I, F, D)                                                                                   \
+#define PT_BOUNCE9(P, LP, M, X, I, F, D, N)                                                                                \
     do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out, fc); \
+        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D, N>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out, fc); \
     } while (0)
+/* row N7: a denoiser frame (scratch.dn.mode != 0) runs the kDn instance of the same schedule */
+#define PT_BOUNCE8(P, LP, M, X, I, F, D)                                                                                   \
+    do { if (scratch.dn.mode) PT_BOUNCE9(P, LP, M, X, I, F, D, true); else PT_BOUNCE9(P, LP, M, X, I, F, D, false); } while (0)
 /* the direct-illumination estimate (row N4) is made by the compacting primary pass */
 #define PT_BOUNCE7(P, LP, M, X, I, F)                                                                                      \
     do { if (fp.di_enabled && P && !LP) PT_BOUNCE8(P, LP, M, X, I, F, (P && !LP)); else PT_BOUNCE8(P, LP, M, X, I, F, false); } while (0)
@@ -1161,6 +1218,7 @@ hipError_t launch_bounce_for(const SceneView& sv, const PixelMap& pm, const Fram
 #undef PT_BOUNCE6
 #undef PT_BOUNCE7
 #undef PT_BOUNCE8
+#undef PT_BOUNCE9
     return hipGetLastError();
 }
 

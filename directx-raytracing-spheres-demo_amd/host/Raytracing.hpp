@@ -115,6 +115,35 @@ struct Raytracing {
         return stats;
     }
 
+    // The outputs Raytracing.hlsl writes besides the radiance when GraphicsSettings.Denoiser != None (App.cpp:1140-1146, 1230-1263):
+    // DEVICE buffers of W*H texels, cleared by the caller as the reference's host clears its textures.  DLSSRayReconstruction writes
+    // SpecularHitDistance (float); NRDReBLUR / NRDReLAX write Diffuse and Specular (float4, 16-byte aligned).
+    struct DenoiserBuffers {
+        void* Diffuse = nullptr;
+        void* Specular = nullptr;
+        void* SpecularHitDistance = nullptr;
+    };
+
+    // Raytracing::Render of a frame for the denoiser GraphicsSettings.Denoiser names (row N7, pt_render_denoiser).  The library takes the
+    // mode per frame, not in the constants: they go up with Denoiser = None.  Render(radiance) keeps refusing a denoiser, as
+    // pt_set_constants does.
+    PtStats Render(std::vector<Float4>& radiance, DenoiserBuffers& buffers)
+    {
+        if (m_graphicsSettings.Denoiser == 0) throw std::invalid_argument("Raytracing::Render: GraphicsSettings.Denoiser is None (use Render(radiance))");
+        PtGraphicsSettings constants = m_graphicsSettings;
+        constants.Denoiser = 0;
+        ThrowIfFailed(pt_set_constants(m_ctx, &constants), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtDenoiserOutputs outputs{};
+        outputs.Denoiser = m_graphicsSettings.Denoiser;
+        outputs.Diffuse = buffers.Diffuse;
+        outputs.Specular = buffers.Specular;
+        outputs.SpecularHitDistance = buffers.SpecularHitDistance;
+        PtStats stats{};
+        ThrowIfFailed(pt_render_denoiser(m_ctx, nullptr, radiance.data(), 0, &outputs, &stats), m_ctx, "pt_render_denoiser");
+        return stats;
+    }
+
 private:
     PtContext* m_ctx;
     PtGraphicsSettings m_graphicsSettings{};

@@ -15,6 +15,7 @@
  *   pt_render                GBufferGeneration::Render + Raytracing::Render -> Dispatch / DispatchRays(W,H,1)
  *                                                       Source/GBufferGeneration.ixx:80-117, Raytracing.ixx:106-112,228-249
  *   pt_render_gbuffer        GBufferGeneration::Render with its output textures   Source/GBufferGeneration.ixx:80-117
+ *   pt_render_denoiser       Raytracing::Render with GraphicsSettings.Denoiser != None   Shaders/Raytracing.hlsl:377-414, Source/App.cpp:1140-1146
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -144,7 +145,9 @@ PtStatus pt_build_accel(PtContext *ctx, PtAccelInfo *info);
 PtStatus pt_update_spheres(PtContext *ctx, const PtSphere *spheres, uint32_t n);
 PtStatus pt_refit_accel(PtContext *ctx);
 PtStatus pt_set_camera(PtContext *ctx, const PtCamera *camera);
-/* Raytracing::SetConstants.  Denoiser must be 0 (Denoiser::None) and IsShaderExecutionReorderingEnabled is ignored.
+/* Raytracing::SetConstants.  Denoiser must be 0 (Denoiser::None) and IsShaderExecutionReorderingEnabled is ignored: the denoiser
+ * outputs are requested per frame, by calling pt_render_denoiser with the mode instead of pt_render (a mode held in the constants
+ * would change what every later pt_render writes, and those need buffers pt_render does not take).
  * IsDIEnabled = 1 (row N4) adds the sphere-light direct-illumination pass, the build's stand-in for the RTXDI passes
  * whose DI texture Raytracing.hlsl:150-163 reads: one emitter / one cone direction per pixel before the bounce passes,
  * the emission of first-bounce hits reached through a reflective lobe dropped (:302), DI added to the radiance (:381). */
@@ -252,6 +255,27 @@ typedef struct PtGBuffer {          /* DEVICE pointers, NULL = not requested; fl
  * not finite or has radius <= 0, a rotation that is not finite.  PT_ERR_STATE: as pt_render. */
 PtStatus pt_render_gbuffer(PtContext *ctx, const PtRect *rect, const PtGBuffer *out,
                            const PtSphere *previous_spheres, const float *previous_rotations);
+
+/* Row N7 -- the bounce loop's denoiser outputs (DESIGN.md spec S13; Raytracing.hlsl:377-414).  An ordinary frame in every respect (the
+ * contract of pt_render: lanes, frames in flight, totals, beam lists, refit, textures, alpha) that writes, per pixel of the rect:
+ *   Denoiser 1 (DLSSRayReconstruction): out = the radiance pt_render writes; SpecularHitDistance (float) = the hit distance of sample 0's
+ *     first bounce where the primary ray hit, that bounce left through a lobe other than diffuse and its ray hit something; else untouched.
+ *   Denoiser 2 (NRDReBLUR), 3 (NRDReLAX): out = the primary surface's emission (the environment on a miss); on hits, Diffuse (float4) =
+ *     (DI_diffuse + (diffuse ? indirect : 0), diffuse ? hit distance : 0) and Specular (float4) = (DI_specular + (diffuse ? 0 : indirect),
+ *     diffuse ? 0 : hit distance), indirect = max(radiance without DI - emission, 0); misses leave both untouched.
+ * "diffuse" is the lobe sample 0 took at the primary surface (true when sample 0 ended there; the hit distance is then +inf).  The caller
+ * clears the buffers first, as the reference's host does.  Buffers are rect.w * rect.h, row-major inside the rect; with frames in flight
+ * the caller rotates one set per lane, as for out, and as for out the rule is enforced: a frame whose buffer (out or a denoiser
+ * buffer) is one another lane's frame wrote within that window waits for everything queued before it (correct, at the cost of overlap).  PT_ERR_INVALID_ARG: an unknown mode (0 included), a required buffer missing or
+ * misaligned, a bad rect.  PT_ERR_STATE: as pt_render.  The tile entry points render Denoiser::None only. */
+typedef struct PtDenoiserOutputs {   /* DEVICE pointers, float4 ones 16-byte aligned */
+    uint32_t Denoiser;               /* 1 DLSSRayReconstruction, 2 NRDReBLUR, 3 NRDReLAX (Source/Denoiser.ixx) */
+    uint32_t _pad;
+    void *Diffuse, *Specular;        /* NRD modes: both required */
+    void *SpecularHitDistance;       /* DLSS-RR: required */
+} PtDenoiserOutputs;
+PtStatus pt_render_denoiser(PtContext *ctx, const PtRect *rect, void *out, int out_is_device,
+                            const PtDenoiserOutputs *outputs, PtStats *stats);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

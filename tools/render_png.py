@@ -4,7 +4,7 @@ with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom]
 R8G8B8A8.  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse]"""
 import argparse
 import os
 import sys
@@ -54,6 +54,9 @@ def main():
                     help="pt_bloom on the accumulated radiance before tone mapping (the reference's default is 0.05); off by default")
     ap.add_argument("--gbuffer", default=None, metavar="CHANNEL", choices=[n for n, _ in dxrs_amd.types.GBUFFER_CHANNELS],
                     help="write one channel of pt_render_gbuffer (row N6) of the first frame instead of the path-traced image")
+    ap.add_argument("--denoiser-output", default=None, choices=["Diffuse", "Specular", "SpecularHitDistance"],
+                    help="write one output of pt_render_denoiser (row N7) of the first frame instead of the path-traced image: Diffuse / "
+                         "Specular from NRDReBLUR (radiance; their hit distance is not shown), SpecularHitDistance from DLSSRayReconstruction")
     args = ap.parse_args()
     from PIL import Image
 
@@ -82,6 +85,16 @@ def main():
         img = gbuffer_image(args.gbuffer, r.render_gbuffer([args.gbuffer])[args.gbuffer])
         Image.fromarray(img).save(args.out)
         print(f"G-buffer {args.gbuffer} {w}x{h} -> {args.out}")
+        r.close()
+        return
+    if args.denoiser_output:
+        mode = t.DENOISER_DLSS_RR if args.denoiser_output == "SpecularHitDistance" else t.DENOISER_NRD_REBLUR
+        r.set_camera(host.camera(w, h, jitter_index=0, jitter_count=max(args.frames, 8)))
+        r.set_constants(gs)
+        a = r.render_denoiser(mode)[1][args.denoiser_output]  # (NaN where the frame wrote nothing: black)
+        img = gbuffer_image("Radiance", a[..., :3] if a.shape[-1] == 4 else a)
+        Image.fromarray(img).save(args.out)
+        print(f"denoiser output {args.denoiser_output} {w}x{h} -> {args.out}")
         r.close()
         return
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
