@@ -18,7 +18,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
     "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
-    "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_synchronize", "pt_last_error", "pt_version",
+    "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
 
@@ -109,6 +109,8 @@ class HipLib:
         lib.pt_get_profile.argtypes = [vp, C.POINTER(PtStats), C.c_int]
         lib.pt_get_totals.restype = C.c_int
         lib.pt_get_totals.argtypes = [vp, C.POINTER(PtStats), C.c_int]
+        lib.pt_get_refl_stats.restype = C.c_int
+        lib.pt_get_refl_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
         lib.pt_get_queue_sizes.restype = C.c_int
         lib.pt_get_queue_sizes.argtypes = [vp, vp, u32, C.POINTER(u32)]
         lib.pt_synchronize.restype = C.c_int
@@ -247,6 +249,12 @@ class Renderer:
         stats = PtStats()
         self._check(self._lib.pt_get_totals(self._ctx, C.byref(stats), 1 if reset else 0))
         return stats
+
+    def refl_stats(self, reset=False):
+        """Reflection beams: (waves that traced in-register bounce-1 rays, ... of them served by a region list) since the last reset."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.pt_get_refl_stats(self._ctx, C.byref(a), C.byref(b), 1 if reset else 0))
+        return a.value, b.value
 
     def queue_sizes(self):
         """Ray-queue sizes of the last spp == 1 frame: [slots, rays at bounce 1, rays at bounce 2, ...]."""

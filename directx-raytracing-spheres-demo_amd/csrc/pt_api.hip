@@ -43,7 +43,7 @@ struct EventPair {
 struct Knobs {
     int split = -1, traverse_blocks_per_cu = -1, fused_threads = -1, no_adaptive_grid = -1, shade_blocks_per_cu = -1, tail_threshold = -1,
         tail_blocks_per_cu = -1, loop_threads = -1, inline2_min_slots = -1, tail_after = -1, seg = -1, loop_use_tail = -1, fuse_loop = -1,
-        ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1;
+        ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1, refl_beams = -1;
 };
 
 // Per-frame-in-flight state (see PtContext::lanes).
@@ -64,9 +64,12 @@ struct Lane {
     uint32_t* d_prev_counts = nullptr;   // device address of h_prev_counts
     uint64_t prev_signature = 0;
     uint32_t* d_seg_counts = nullptr;        // kMaxSegs segment sizes of the primary pass -> looping pass hand-over
+    static constexpr uint32_t kTotals = 10;
     unsigned long long* d_totals = nullptr;  // [0] running secondary-ray total, [1] last folded frame, [2],[3] tail counters,
                                              // [4] running count of in-register secondary rays of primary passes, [5] unused,
-                                             // [6] node visits, [7] sphere tests of the global-memory traversal kernels
+                                             // [6] node visits, [7] sphere tests of the global-memory traversal kernels,
+                                             // [8] waves of primary passes that traced in-register bounce-1 rays, [9] ... of them from a
+                                             // reflection-beam list (pt_get_refl_stats)
     // private copy of the moving part of the scene (pt_update_spheres / pt_refit_accel): spheres, Morton-ordered spheres
     // and node boxes; null = this lane renders the context's master scene
     float4* d_sph = nullptr;
@@ -196,6 +199,9 @@ struct PtContext {
     struct BeamLists {
         uint32_t* d_lists = nullptr;   // n_blocks records of 16 dwords
         size_t cap_blocks = 0;
+        uint32_t* d_regions = nullptr; // reflection beams: n_blocks region records of kReflRecord dwords (pt_region.h) ...
+        size_t cap_regions = 0;
+        bool regions = false;          // ... that d_regions holds for these lists (resting views' builds only)
         std::vector<uint32_t> key;     // orientation, frame geometry, scene generation of the lists in d_lists; empty = none
         float pos[3] = { 0, 0, 0 };    // the camera position they were built around ...
         float slack = 0.0f;            // ... and how far from it they hold
@@ -554,7 +560,7 @@ Knobs read_knobs()
     k.inline2_min_slots = env_knob("PT_INLINE2_MIN_SLOTS"); k.tail_after = env_knob("PT_TAIL_AFTER"); k.seg = env_knob("PT_SEG");
     k.loop_use_tail = std::getenv("PT_LOOP_USE_TAIL") ? 1 : -1; k.fuse_loop = env_knob("PT_FUSE_LOOP"); k.beam_reach = env_knob("PT_BEAM_REACH"); k.beam_max_slack_pct = env_knob("PT_BEAM_MAX_SLACK_PCT"); k.beam_max_margin = env_knob("PT_BEAM_MAX_MARGIN"); k.beam_share_wgs = env_knob("PT_BEAM_SHARE_WGS"); k.lane_priority = env_knob("PT_LANE_PRIORITY"); k.fused_refit = env_knob("PT_FUSED_REFIT"); k.ray_replacement = env_knob("PT_RAY_REPLACEMENT");
     k.dyn_blocks_per_cu = env_knob("PT_DYN_BLOCKS_PER_CU"); k.debug_counts = std::getenv("PT_DEBUG_COUNTS") ? 1 : -1; k.sah = env_knob("PT_SAH");
-    k.sah_max_spheres = env_knob("PT_SAH_MAX_SPHERES"); k.beams = env_knob("PT_BEAMS"); k.wide = env_knob("PT_WIDE"); k.descent = env_knob("PT_DESCENT"); k.roctx = env_knob("PT_ROCTX");
+    k.sah_max_spheres = env_knob("PT_SAH_MAX_SPHERES"); k.beams = env_knob("PT_BEAMS"); k.refl_beams = env_knob("PT_REFL_BEAMS"); k.wide = env_knob("PT_WIDE"); k.descent = env_knob("PT_DESCENT"); k.roctx = env_knob("PT_ROCTX");
     return k;
 }
 
@@ -623,7 +629,8 @@ void sum_events(PtContext* c, size_t begin, size_t end, PtStats* stats)
 }
 
 // Launches the build of primary-beam lists into `dst` (centre, slack: Beam), on stream `on` or, if null, on the cache's side stream.
-static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamLists* dst, const float centre[3], float slack, std::vector<uint32_t> key, hipStream_t on)
+// regions: also the blocks' reflection-beam records (exact lists of a resting view only: slack 0).
+static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamLists* dst, const float centre[3], float slack, std::vector<uint32_t> key, hipStream_t on, bool regions)
 {
     auto& B = c->beam;
     if (!B.ev_last_use) PT_HIP(c, hipEventCreateWithFlags(&B.ev_last_use, hipEventDisableTiming));
@@ -642,6 +649,15 @@ static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamList
         dst->cap_blocks = n_blocks;
         dst->used = false;
     }
+    if (regions && n_blocks > dst->cap_regions) {
+        PT_HIP(c, sync_all(c));
+        if (B.stream) PT_HIP(c, hipStreamSynchronize(B.stream));
+        free_dev(dst->d_regions);
+        dst->cap_regions = 0;
+        PT_HIP(c, hipMalloc(&dst->d_regions, n_blocks * kReflRecord * sizeof(uint32_t)));
+        dst->cap_regions = n_blocks;
+        dst->used = false;
+    }
     // an earlier build into this buffer may still run (on another lane's stream), and the frames in flight may still read the buffer's
     // previous lists: the build waits for both (device-side waits only)
     if (dst->building) PT_HIP(c, hipStreamWaitEvent(on, dst->ev_ready, 0));
@@ -653,21 +669,23 @@ static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamList
         }
     FrameParams fp = make_frame_params(c);
     fp.cam.Position = make_f3(centre[0], centre[1], centre[2]);
-    PT_HIP(c, launch_beams(make_scene_view(c), pm, fp, slack, dst->d_lists, on));
+    PT_HIP(c, launch_beams(make_scene_view(c), pm, fp, slack, dst->d_lists, regions ? dst->d_regions : nullptr, on));
     PT_HIP(c, hipEventRecord(dst->ev_ready, on));
     dst->key = std::move(key);
     std::memcpy(dst->pos, centre, 12);
     dst->slack = slack;
+    dst->regions = regions;
     dst->building = true;
     dst->used = false;
     return PT_OK;  // this frame still traverses (or uses the lists it has); later ones find the new lists
 }
 
 // Primary-beam cache (PtContext::BeamCache).  *lists = lists that hold for this frame's view, else null; *wait = an event the frame must
-// wait for before it reads them (the first frames of a resting view), or null.
-PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_blocks, const uint32_t** lists, hipEvent_t* wait, BeamJob* job)
+// wait for before it reads them (the first frames of a resting view), or null.  *regions = the reflection-beam records built with *lists, or null.
+PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_blocks, const uint32_t** lists, const uint32_t** regions, hipEvent_t* wait, BeamJob* job)
 {
     *lists = nullptr;
+    *regions = nullptr;
     *wait = nullptr;
     *job = BeamJob{};
     auto& B = c->beam;
@@ -753,6 +771,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
     }
     if (holds(*cur)) {
         *lists = cur->d_lists;
+        if (cur->regions) *regions = cur->d_regions;
         cur->used = true;
         cur->last_use_call = call;
         if (cur->building) *wait = cur->ev_ready;
@@ -787,6 +806,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
         std::memcpy(d->basis, I.basis, 36);
         d->slack = I.slack;
         d->margin_px = I.margin_px;
+        d->regions = false;  // (the shares build primary-beam lists only)
         d->first_call = call + c->n_lanes;
         d->building = false;
         d->built_call = call;
@@ -814,7 +834,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
         dst->built_call = call;
         std::memcpy(dst->basis, basis, 36);
         dst->margin_px = 0.0f;
-        return beam_build(c, pm, dst, pos, 0.0f, std::move(key), nullptr);  // a resting view's: one launch on the side stream; the next frame waits for it, once
+        return beam_build(c, pm, dst, pos, 0.0f, std::move(key), nullptr, knob_or(c->knobs.refl_beams, 1u) != 0);  // a resting view's: one launch on the side stream; the next frame waits for it, once
     }
     // Moving.  The lists are built in shares of max_job_blocks blocks inside the primary passes of the next n_build frames (a build as a launch
     // of its own, behind a frame on its lane, cost that lane 60 us and the three lanes their even spacing for several frames: 0.083 ms per frame
@@ -876,6 +896,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
         dst->cap_blocks = n_blocks;
     }
     dst->key.clear();  // (nothing may take the buffer's old lists from here on)
+    dst->regions = false;
     dst->used = true;   // (written by frames in flight from now on)
     dst->last_use_call = call;
     auto& I = B.inc;
@@ -1042,16 +1063,18 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     // build: the animated C2 frame went from 0.099 to 0.117 ms -- the build lengthens the frame's dependent chain by more than the
     // primary pass gains.  Animated scenes get none.)
     const uint32_t* beam_lists = nullptr;
+    const uint32_t* refl_lists = nullptr;  // reflection beams: region records built with the resting view's lists; PT_REFL_BEAMS=0 builds none
     BeamJob beam_job{};
     if (!split && !L.scene_private && c->n_nodes > 0 && knob_or(c->knobs.beams, 1u) != 0 && std::fabs(c->cam.Jitter[0]) <= 0.5f && std::fabs(c->cam.Jitter[1]) <= 0.5f) {
         hipEvent_t beam_wait = nullptr;
         // (a share of a build rides on the first wave of up to PT_BEAM_SHARE_WGS = 128 workgroups of the primary pass, 64 blocks each: four frames'
         // shares make a 1080p build -- 32 left a camera that travels AND turns without lists for a sixth of its frames, the whole build in one
         // frame costs that frame 1 %)
-        if ((st = beam_cache_lookup(c, pm, std::min(primary_grid, knob_or(c->knobs.beam_share_wgs, 128u)) * 64u, &beam_lists, &beam_wait, &beam_job)) != PT_OK) return st;
+        if ((st = beam_cache_lookup(c, pm, std::min(primary_grid, knob_or(c->knobs.beam_share_wgs, 128u)) * 64u, &beam_lists, &refl_lists, &beam_wait, &beam_job)) != PT_OK) return st;
         if (beam_wait) PT_HIP(c, hipStreamWaitEvent(L.stream, beam_wait, 0));
     } else {
         c->beam.last_key.clear();
+        c->beam.inc.active = false;  // (a share build in progress was planned for a view this frame does not continue)
     }
     if (L.stream != c->stream) {
         // N frames in flight.  The caller rotates over N output buffers, so this frame may start as soon as the consumer of
@@ -1100,6 +1123,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     FrameParams fp = make_frame_params(c);
     fp.beam_lists = beam_lists;
     fp.beam_job = beam_job;
+    fp.refl_lists = refl_lists;
     L.parity ^= 1u;
     const FrameCounters fc = make_counters(L, L.parity);
     uint32_t* counts = fc.counts;
@@ -1391,9 +1415,9 @@ PtStatus pt_create(const PtConfig* config, PtContext** out_ctx)
         bool ok = true;
         for (auto& e : L.ev_poll) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
         if (!ok || hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming) != hipSuccess
-            || hipMalloc(&L.d_totals, 8 * sizeof(unsigned long long)) != hipSuccess
+            || hipMalloc(&L.d_totals, Lane::kTotals * sizeof(unsigned long long)) != hipSuccess
             || hipMalloc(&L.d_seg_counts, kMaxSegs * sizeof(uint32_t)) != hipSuccess
-            || hipMemsetAsync(L.d_totals, 0, 8 * sizeof(unsigned long long), L.stream) != hipSuccess) { pt_destroy(c); return PT_ERR_HIP; }
+            || hipMemsetAsync(L.d_totals, 0, Lane::kTotals * sizeof(unsigned long long), L.stream) != hipSuccess) { pt_destroy(c); return PT_ERR_HIP; }
     }
     *out_ctx = c;
     return PT_OK;
@@ -1427,6 +1451,7 @@ void pt_destroy(PtContext* c)
     free_dev(c->d_sph); free_dev(c->d_mats); free_dev(c->d_nodes); free_dev(c->d_wide); free_dev(c->d_sph_sorted); free_dev(c->d_sorted_id); free_dev(c->d_lights); free_dev(c->d_alpha_class); free_dev(c->d_leaf_ids);
     for (auto& b : c->beam.buf) {
         free_dev(b.d_lists);
+        free_dev(b.d_regions);
         if (b.ev_ready) (void)hipEventDestroy(b.ev_ready);
     }
     if (c->beam.ev_last_use) (void)hipEventDestroy(c->beam.ev_last_use);
@@ -2260,7 +2285,7 @@ PtStatus pt_get_totals(PtContext* c, PtStats* totals, int reset)
         sphere_tests += s[7];
         if (reset) {
             PT_HIP(c, hipMemsetAsync(L.d_totals, 0, 2 * sizeof(unsigned long long), L.stream));
-            PT_HIP(c, hipMemsetAsync(L.d_totals + 4, 0, 4 * sizeof(unsigned long long), L.stream));
+            PT_HIP(c, hipMemsetAsync(L.d_totals + 4, 0, (Lane::kTotals - 4) * sizeof(unsigned long long), L.stream));
         }
     }
     std::memset(totals, 0, sizeof *totals);
@@ -2273,6 +2298,25 @@ PtStatus pt_get_totals(PtContext* c, PtStats* totals, int reset)
     totals->bytes_algorithmic = c->tot_sec_coeff * secondary + c->tot_fixed_bytes;
     totals->beams_used = c->tot_beam_frames;
     if (reset) { c->tot_pixels = c->tot_paths = c->tot_fixed_bytes = 0; c->tot_beam_frames = 0; }
+    return PT_OK;
+}
+
+PtStatus pt_get_refl_stats(PtContext* c, uint64_t* bounce1_waves, uint64_t* listed_waves, int reset)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!bounce1_waves || !listed_waves) return fail(c, PT_ERR_INVALID_ARG, "pt_get_refl_stats: null output");
+    PT_HIP(c, hipSetDevice(c->device));
+    *bounce1_waves = *listed_waves = 0;
+    for (uint32_t i = 0; i < c->n_lanes; i++) {
+        Lane& L = c->lanes[i];
+        unsigned long long s[2] = {};
+        PT_HIP(c, hipStreamSynchronize(L.stream));
+        PT_HIP(c, hipMemcpyAsync(s, L.d_totals + 8, sizeof s, hipMemcpyDeviceToHost, L.stream));
+        PT_HIP(c, hipStreamSynchronize(L.stream));
+        *bounce1_waves += s[0];
+        *listed_waves += s[1];
+        if (reset) PT_HIP(c, hipMemsetAsync(L.d_totals + 8, 0, sizeof s, L.stream));
+    }
     return PT_OK;
 }
 

@@ -165,6 +165,7 @@ struct FrameParams {
     uint32_t di_enabled;  // IsDIEnabled and the scene has emitters: Scratch::di holds this frame's estimate
     const uint32_t* beam_lists;  // primary beams: one 16-dword record per 64 slots {count, sphere ids}; null = every primary ray traverses
     BeamJob beam_job;
+    const uint32_t* refl_lists;  // reflection beams: one kReflRecord-dword region record per 64 slots (pt_region.h); null = every bounce-1 ray traverses
 };
 
 // Per-frame device counters, double buffered by frame parity so that the first kernel of a frame can append to this

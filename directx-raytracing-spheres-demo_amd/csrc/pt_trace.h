@@ -355,7 +355,8 @@ __device__ __forceinline__ f3 beam_plane(f3 a, f3 b, f3 inside)
     return n * __builtin_amdgcn_rsqf(l2);
 }
 
-__device__ __forceinline__ Beam make_beam(const CameraParams& cam, uint32_t px, uint32_t py, float slack, float margin_px = 0.0f)
+// The directions (not normalised) of the four corner rays of the block at (px, py): c[0..3] = c00, c10, c11, c01 of make_beam.
+__device__ __forceinline__ void beam_corners(const CameraParams& cam, uint32_t px, uint32_t py, float margin_px, f3 c[4])
 {
     // NDC of the block's outline: its pixel centres lie in [px, px + 8] for every jitter in [-0.5, 0.5] (the host checks the
     // jitter), widened by half a pixel each way -- the lists serve every frame of a resting view
@@ -366,6 +367,14 @@ __device__ __forceinline__ Beam make_beam(const CameraParams& cam, uint32_t px, 
     const float nxa = pt_fma(xa, 2.0f, -1.0f), nxb = pt_fma(xb, 2.0f, -1.0f), nya = pt_fma(ya, -2.0f, 1.0f), nyb = pt_fma(yb, -2.0f, 1.0f);
     const f3 c00 = mad(nya, cam.Up, cam.Right * nxa) + cam.Forward, c10 = mad(nya, cam.Up, cam.Right * nxb) + cam.Forward;
     const f3 c11 = mad(nyb, cam.Up, cam.Right * nxb) + cam.Forward, c01 = mad(nyb, cam.Up, cam.Right * nxa) + cam.Forward;
+    c[0] = c00; c[1] = c10; c[2] = c11; c[3] = c01;
+}
+
+__device__ __forceinline__ Beam make_beam(const CameraParams& cam, uint32_t px, uint32_t py, float slack, float margin_px = 0.0f)
+{
+    f3 c[4];
+    beam_corners(cam, px, py, margin_px, c);
+    const f3 c00 = c[0], c10 = c[1], c11 = c[2], c01 = c[3];
     const f3 mid = (c00 + c11) + (c10 + c01);
     Beam b;
     b.o = cam.Position;
@@ -448,12 +457,111 @@ __device__ __forceinline__ void beam_walk_block(const SceneView& sv, const float
     rec[0] = count;
 }
 
+// ------------------------------------------------------------------------------------------------ reflection beams
+// The first bounce off a mirror-like sphere (DESIGN.md "Reflection beams", pt_region.h): when the five rays of a block's pyramid (its four
+// corners and its centre) all land on one sphere S whose material samples the specular lobe only, with a roughness of at most
+// kReflMaxRoughness, the block's bounce-1 rays leave a small box around the footprint in a thin cone around the mirrored centre ray.  The
+// block's region record lists every sphere whose padded leaf box meets that swept region; the primary pass serves a wave's bounce-1 rays
+// from it when every active lane's spawned ray passes region_contains, and traverses otherwise.
+// Fills g for the block at (px, py) from its primary-beam list (beam[1..count]: a superset of what the pyramid's rays can hit); false = no region.
+__device__ __forceinline__ bool refl_region(const SceneView& sv, const CameraParams& cam, uint32_t px, uint32_t py, const uint32_t* __restrict__ beam, uint32_t count,
+                                            ReflRegion& g)
+{
+    f3 c[4];
+    beam_corners(cam, px, py, 0.0f, c);
+    f3 dir[5];
+    float t[5];
+    for (int k = 0; k < 4; k++) dir[k] = normalize(c[k]);
+    dir[4] = normalize((c[0] + c[2]) + (c[1] + c[3]));
+    uint32_t s_id = kMissId;
+    for (int k = 0; k < 5; k++) {
+        float best = kInf;
+        uint32_t best_idf = kMissId;
+        for (uint32_t j = 0; j < count; j++) {
+            const uint32_t idf = beam[1 + j];
+            if ((idf >> kIdClassShift) == kAlphaInvisible) continue;
+            const float4 s = sv.sph[idf & kIdMask];
+            float tk;
+            if (intersect_sphere(cam.Position, dir[k], 0.0f, kInf, make_f3(s.x, s.y, s.z), s.w, tk))
+                if (tk < best || (tk == best && best_idf != kMissId && (idf & kIdMask) < (best_idf & kIdMask))) { best = tk; best_idf = idf; }
+        }
+        if (best_idf == kMissId || (best_idf >> kIdClassShift) != 0u) return false;  // a miss, or a sphere whose crossings an alpha test decides
+        if (k > 0 && best_idf != s_id) return false;
+        s_id = best_idf;
+        t[k] = best;
+    }
+    const float4 sp = sv.sph[s_id];
+    const float4 m0 = sv.mats[s_id * 4 + 0], m2 = sv.mats[s_id * 4 + 2], m3 = sv.mats[s_id * 4 + 3];
+    if (sv.tex_maps && (as_uint(m3.x) & kMaterialHasMaps) != 0u) return false;  // textured: maps may change the material and the normal
+    const HitFrame hc = hit_frame(cam.Position, dir[4], t[4], load3(sp), sp.w);
+    // the material as hit_material forms it for a primary hit, and its lobe weights for the centre ray
+    const Bsdf b = bsdf_init_pre(load3(m0), m2.x, m2.y, m2.z, m3.w, m3.z, !(m2.x < 1.0f) ? 0.0f : m2.w, hc.front);
+    float w[3];
+    lobe_weights(b, surf_init(hc.front, hc.N, hc.front ? hc.N : -hc.N), -dir[4], w);
+    if (!(w[kLobeDiffuse] == 0.0f && w[kLobeTransmission] == 0.0f && b.Roughness <= kReflMaxRoughness)) return false;
+    return region_from_hits(cam.Position, dir, t, load3(sp), sp.w, g);
+}
+
+// One lane's work for one 8x8 block after its primary-beam record (lists) is written: the block's region record.
+template <typename StackT>
+__device__ __forceinline__ void refl_walk_block(const SceneView& sv, const float4* nodes, const uint32_t* ids, StackT* stack, uint32_t stride, const PixelMap& pm,
+                                                const CameraParams& cam, uint32_t tile, const uint32_t* __restrict__ lists, uint32_t* __restrict__ regions)
+{
+    uint32_t* rec = regions + (size_t)tile * kReflRecord;
+    const uint32_t* beam = lists + (size_t)tile * kBeamRecord;
+    const PixelRef pr = slot_to_pixel(pm, tile << 6);
+    const uint32_t beam_count = beam[0];
+    uint32_t count = 0;
+    ReflRegion g;
+    if (pr.valid && beam_count >= 1u && beam_count <= kBeamListCap && refl_region(sv, cam, pr.px, pr.py, beam, beam_count, g)) {
+        region_store(g, rec);
+        if (sv.n == 1) {
+            rec[kReflIds] = ids[0];
+            count = 1;
+        } else {
+            int node = 0;
+            uint32_t sp = 0;
+            for (;;) {
+                if (node >= 0) {
+                    const float4 n0 = nodes[node * 4 + 0], n1 = nodes[node * 4 + 1], n2 = nodes[node * 4 + 2], n3 = nodes[node * 4 + 3];
+                    const int c0 = __builtin_bit_cast(int, n3.x), c1 = __builtin_bit_cast(int, n3.y);
+                    const bool h0 = region_meets_box(g, make_f3(n0.x, n0.y, n0.z), make_f3(n0.w, n1.x, n1.y));
+                    const bool h1 = region_meets_box(g, make_f3(n1.z, n1.w, n2.x), make_f3(n2.y, n2.z, n2.w));
+                    if (h0 && h1) { stack[sp] = stack_encode<StackT>(c1); sp += stride; node = c0; continue; }
+                    if (h0) { node = c0; continue; }
+                    if (h1) { node = c1; continue; }
+                } else {
+                    if (count < kReflListCap) rec[kReflIds + count] = ids[~(uint32_t)node];
+                    if (++count > kReflListCap) { count = 0; break; }  // overflow: no region
+                }
+                if (sp == 0) break;
+                sp -= stride;
+                node = stack_decode(stack[sp]);
+            }
+        }
+    }
+    rec[0] = count;
+}
+
+// The run-time test of a lane's bounce-1 ray against its block's region record (scalar loads: the record is the wave's)
+__device__ __forceinline__ bool refl_contains(const uint32_t* rec, f3 o, f3 d)
+{
+    ReflRegion g;
+    g.lo = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[1])), as_float(__builtin_amdgcn_readfirstlane(rec[2])), as_float(__builtin_amdgcn_readfirstlane(rec[3])));
+    g.hi = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[4])), as_float(__builtin_amdgcn_readfirstlane(rec[5])), as_float(__builtin_amdgcn_readfirstlane(rec[6])));
+    g.axis = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[7])), as_float(__builtin_amdgcn_readfirstlane(rec[8])), as_float(__builtin_amdgcn_readfirstlane(rec[9])));
+    g.cos_run = as_float(__builtin_amdgcn_readfirstlane(rec[10]));
+    g.theta = 0.0f;
+    return region_contains(g, o, d);
+}
+
 // kLds: the workgroup stages the tree into LDS first (LDS-resident scenes).  (Measured: 55 vs 58 us at 1080p -- a lane's walk is ~80 visits
 // of ~150 instructions, bound by instruction issue of lone waves rather than by where the nodes live; the build stays off the frames'
 // critical path: on a side stream for a resting view, behind a frame on its lane for a moving camera.  Sixteen lanes per block, each walking
 // one subtree four levels down, were measured: the same 56 us beside the frames -- the build's time is its share of a busy chip, not its chain.)
+// regions (resting views; null = none): the blocks' reflection-beam records, made after their primary-beam records.
 template <bool kLds, typename StackT>
-__global__ __launch_bounds__(256) void beam_kernel(SceneView sv, PixelMap pm, FrameParams fp, float slack, uint32_t* __restrict__ lists)
+__global__ __launch_bounds__(256) void beam_kernel(SceneView sv, PixelMap pm, FrameParams fp, float slack, uint32_t* __restrict__ lists, uint32_t* __restrict__ regions)
 {
     extern __shared__ float4 smem[];
     const uint32_t stride = blockDim.x;
@@ -471,7 +579,10 @@ __global__ __launch_bounds__(256) void beam_kernel(SceneView sv, PixelMap pm, Fr
     }
     stack += threadIdx.x;
     for (uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x; tile < n_blocks; tile += gridDim.x * blockDim.x)
+    {
         beam_walk_block<StackT>(sv, nodes, ids, stack, stride, pm, fp.cam, slack, 0.0f, tile, lists);
+        if (regions) refl_walk_block<StackT>(sv, nodes, ids, stack, stride, pm, fp.cam, tile, lists, regions);
+    }
 }
 
 // Closest hit of a primary ray over its block's candidate list (wave-uniform loop; sphere records come through the scalar
@@ -916,6 +1027,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
     __shared__ uint32_t s_seg_next;                   // ... and the next 64-slot tile of this workgroup's batches to hand to a wave
     __shared__ uint32_t s_loop_next;                  // fused form: the next 64 entries of the workgroup's own segment
     __shared__ uint32_t s_seg_prefix[kMaxSegs + 1];   // consumer side: s_seg_prefix[b] = entries in segments < b
+    __shared__ uint32_t s_refl[2];                    // kIters == 2: waves that traced bounce-1 rays, ... of them served by a region list
     if (kPrimary && blockIdx.x == 0) frame_counters_begin(fc, pm.n_slots);
     const bool seg_out = kPrimary && !kLoop && fc.seg_counts != nullptr;
     const bool seg_in = !kPrimary && kLoop && fc.seg_counts != nullptr;
@@ -945,11 +1057,12 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         count = kPrimary ? pm.n_slots : *count_in_ptr;
     }
     if (seg_out && threadIdx.x == 0) { s_seg_count = 0; s_seg_next = 0; s_loop_next = 0; }
+    if (kIters > 1u && threadIdx.x == 0) { s_refl[0] = 0; s_refl[1] = 0; }
     if (blockIdx.x * blockDim.x >= count) {
         if (seg_out && threadIdx.x == 0) fc.seg_counts[blockIdx.x] = 0;
         return;
     }
-    if (seg_out && !kLds) __syncthreads();  // (with kLds the barrier of stage_scene orders the reset)
+    if ((seg_out || kIters > 1u) && !kLds) __syncthreads();  // (with kLds the barrier of stage_scene orders the reset)
     const float4* nodes = sv.nodes;
     const float4* sph = sv.sph_sorted;
     const uint32_t* ids = sv.sorted_id;
@@ -1080,7 +1193,19 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                         closest_hit_list<kTex>(sv, beam_rec, beam_count, ps.o, ps.d, tmin, tmax, t, id);
                         if (kMulti) scratch.primary_hit[i] = make_uint2(as_uint(t), id);
                     } else {
-                        closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, tmin, tmax, stack, blockDim.x, t, id);
+                        // reflection beams: the in-register first bounce of a block with a region record, when every active lane's ray lies in the region
+                        // (the counts of pt_get_refl_stats are kept only while the records are in use: a frame without them runs nothing but the pointer test)
+                        bool listed = false;
+                        const uint32_t* rrec = nullptr;
+                        uint32_t rcount = 0;
+                        if (kIters > 1u && !primary_trace && fp.refl_lists) {
+                            rrec = fp.refl_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kReflRecord;
+                            rcount = __builtin_amdgcn_readfirstlane(rrec[0]);
+                            listed = rcount != 0u && __ballot(!refl_contains(rrec, ps.o, ps.d)) == 0ull;
+                            if (lane == (uint32_t)__builtin_amdgcn_readfirstlane(lane)) { atomicAdd(&s_refl[0], 1u); if (listed) atomicAdd(&s_refl[1], 1u); }
+                        }
+                        if (listed) closest_hit_list<kTex>(sv, rrec + (kReflIds - 1u), rcount, ps.o, ps.d, tmin, tmax, t, id);
+                        else closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, tmin, tmax, stack, blockDim.x, t, id);
                         if (kMulti && kPrimary && primary_trace) scratch.primary_hit[i] = make_uint2(as_uint(t), id);
                     }
                     primary_trace = false;
@@ -1177,6 +1302,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             for (uint32_t w = 0; w < (blockDim.x >> 6); w++) { sum += s_wave_count[w]; if (kFuse) sum2 += s_wave_count2[w]; }
             if (sum + sum2) atomicAdd(fc.tail_rays, sum + sum2);
             if (sum && !kLoop && !kDI) atomicAdd(fc.totals + 4, sum);  // running count of the rays a primary pass traced in registers (statistics)
+            if (kIters > 1u && s_refl[0]) { atomicAdd(fc.totals + 8, (unsigned long long)s_refl[0]); if (s_refl[1]) atomicAdd(fc.totals + 9, (unsigned long long)s_refl[1]); }
         }
     }
 }

@@ -308,6 +308,10 @@ PtStatus pt_get_totals(PtContext *ctx, PtStats *totals, int reset);
 /* Queue sizes of the last spp == 1 frame: sizes[k] = rays in queue k (sizes[0] = path slots).  Returns the number of
  * valid entries through *n (0 if none).  Synchronises the stream. */
 PtStatus pt_get_queue_sizes(PtContext *ctx, uint32_t *sizes, uint32_t capacity, uint32_t *n);
+/* Reflection beams: running counts, since the last reset (this call's or pt_get_totals'), of the wave64s of 1-spp primary
+ * passes that traced in-register bounce-1 rays (*bounce1_waves) and of those whose rays were all served by their block's region list
+ * (*listed_waves).  Synchronises the lanes. */
+PtStatus pt_get_refl_stats(PtContext *ctx, uint64_t *bounce1_waves, uint64_t *listed_waves, int reset);
 /* Device buffers for callers that do not link a GPU runtime themselves (a C++ host written against this header only): the
  * packed tile buffers of pt_render_tiles / pt_gather and the assembled frames of pt_unpack_tiles live in such memory.  The
  * reference's counterpart is the app-owned GPUBuffer / Texture objects handed to the passes (Source/App.cpp:366-368).
