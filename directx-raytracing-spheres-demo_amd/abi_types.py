@@ -74,6 +74,20 @@ class PtDenoiserOutputs(C.Structure):
                 ("SpecularHitDistance", C.c_void_p)]
 
 
+# Row N8 (pt_nrd_composition): NRDComposition::Constants / ::Textures, and nrd::ReblurSettings().hitDistanceParameters
+NRD_REBLUR_HIT_DISTANCE = (3.0, 0.1, 20.0, -25.0)
+NRD_TEXTURES = ("LinearDepth", "DiffuseAlbedo", "SpecularAlbedo", "NormalRoughness", "NoisyDiffuse", "NoisySpecular", "DenoisedDiffuse",
+                "DenoisedSpecular", "Radiance")
+
+
+class PtNrdCompositionConstants(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("Pack", C.c_uint32), ("Denoiser", C.c_uint32), ("ReBLURHitDistance", C.c_float * 4)]
+
+
+class PtNrdCompositionTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in NRD_TEXTURES]
+
+
 class PtTextureMapInfo(C.Structure):
     _fields_ = [("Descriptor", C.c_uint32), ("TextureCoordinateIndex", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 

@@ -7,8 +7,9 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, PtAccelInfo, PtCamera, PtConfig, PtDenoiserOutputs, PtGBuffer,
-                        PtGraphicsSettings, PtRect, PtSceneData, PtStats)
+from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo, PtCamera, PtConfig,
+                        PtDenoiserOutputs, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures, PtRect,
+                        PtSceneData, PtStats)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -17,7 +18,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_nrd_composition", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -91,6 +92,8 @@ class HipLib:
         lib.pt_render_gbuffer.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBuffer), vp, vp]
         lib.pt_render_denoiser.restype = C.c_int
         lib.pt_render_denoiser.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtDenoiserOutputs), C.POINTER(PtStats)]
+        lib.pt_nrd_composition.restype = C.c_int
+        lib.pt_nrd_composition.argtypes = [vp, C.POINTER(PtNrdCompositionConstants), C.POINTER(PtNrdCompositionTextures)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -396,6 +399,51 @@ class Renderer:
         self.render_denoiser_device(mode, out.data_ptr(), {name: b.data_ptr() for name, b in bufs.items()}, rect)
         self.synchronize()
         return out.cpu().numpy(), {name: b.cpu().numpy() for name, b in bufs.items()}
+
+    def nrd_composition_device(self, mode, pack, width, height, buffers, hit_distance=NRD_REBLUR_HIT_DISTANCE):
+        """NRD composition (row N8; mode abi_types.DENOISER_NRD_*): pack (before NRD, in place on NoisyDiffuse / NoisySpecular) or
+        compose (after NRD, into Radiance) over width x height pixels.  buffers: {NRD_TEXTURES name: device pointer}; the ones the
+        direction does not use may be left out.  hit_distance: ReBLUR's hit distance parameters.  Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(NRD_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown NRD composition buffers {sorted(unknown)}")
+        k = PtNrdCompositionConstants(RenderSize=(C.c_uint32 * 2)(width, height), Pack=1 if pack else 0, Denoiser=mode,
+                                      ReBLURHitDistance=(C.c_float * 4)(*hit_distance))
+        t = PtNrdCompositionTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_nrd_composition(self._ctx, C.byref(k), C.byref(t)))
+
+    def nrd_chain(self, mode, rect=None, denoise=None, hit_distance=NRD_REBLUR_HIT_DISTANCE, device=None):
+        """The reference's NRD path for one frame (App.cpp:1140-1146, 1549-1642) with a stand-in for NRD: pt_render_gbuffer ->
+        pt_render_denoiser (its buffers cleared to 0, as the reference's host clears them) -> pack -> denoise -> compose.  denoise(diffuse,
+        specular) takes the packed torch buffers (h, w, 4) and returns the denoised pair; None = an identity copy.  Synchronous -> {name:
+        numpy float32 (h, w, channels)}: the G-buffer inputs, Emission (pt_render_denoiser's out), NoisyDiffuse / NoisySpecular (as
+        rendered), PackedDiffuse / PackedSpecular, DenoisedDiffuse / DenoisedSpecular and Radiance (the composed frame)."""
+        import torch
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        width = dict(GBUFFER_CHANNELS)
+        gb = {name: torch.zeros((h, w, width[name]), dtype=torch.float32, device=dev) for name in NRD_TEXTURES[:4]}
+        rad, nd, ns = (torch.zeros((h, w, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        torch.cuda.synchronize(dev)  # (cleared on torch's stream, which the context's stream knows nothing of)
+        self.render_gbuffer_device({name: b.data_ptr() for name, b in gb.items()}, rect)
+        self.render_denoiser_device(mode, rad.data_ptr(), {"Diffuse": nd.data_ptr(), "Specular": ns.data_ptr()}, rect)
+        self.synchronize()
+        res = {name: b.cpu().numpy() for name, b in gb.items()}
+        res.update(Emission=rad.cpu().numpy(), NoisyDiffuse=nd.cpu().numpy(), NoisySpecular=ns.cpu().numpy())
+        inputs = {name: b.data_ptr() for name, b in gb.items()}
+        self.nrd_composition_device(mode, True, w, h, dict(inputs, NoisyDiffuse=nd.data_ptr(), NoisySpecular=ns.data_ptr()), hit_distance)
+        self.synchronize()
+        res.update(PackedDiffuse=nd.cpu().numpy(), PackedSpecular=ns.cpu().numpy())
+        dd, ds = denoise(nd, ns) if denoise is not None else (nd.clone(), ns.clone())
+        dd, ds = dd.contiguous(), ds.contiguous()
+        torch.cuda.synchronize(dev)
+        self.nrd_composition_device(mode, False, w, h, dict(inputs, DenoisedDiffuse=dd.data_ptr(), DenoisedSpecular=ds.data_ptr(), Radiance=rad.data_ptr()),
+                                    hit_distance)
+        self.synchronize()
+        res.update(DenoisedDiffuse=dd.cpu().numpy(), DenoisedSpecular=ds.cpu().numpy(), Radiance=rad.cpu().numpy())
+        return res
 
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""

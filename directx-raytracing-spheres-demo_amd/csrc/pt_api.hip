@@ -20,6 +20,7 @@
 #include "../../include/pt_api.h"
 #include "pt_kernels.h"
 #include "pt_bloom.h"
+#include "pt_nrd.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
 
@@ -2174,6 +2175,66 @@ PtStatus pt_bloom(PtContext* c, const void* hdr, void* out, uint32_t width, uint
         c->cap_bloom = need;
     }
     PT_HIP(c, launch_bloom(static_cast<const float4*>(hdr), static_cast<float4*>(out), c->d_bloom, width, height, strength, c->stream));
+    return PT_OK;
+}
+
+// Row N8 -- the NRD composition pass (DESIGN.md spec S14): one launch of pack or compose on the context's stream
+PtStatus pt_nrd_composition(PtContext* c, const PtNrdCompositionConstants* k, const PtNrdCompositionTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!k || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: null pointer");
+    if (k->Denoiser != kNrdReblur && k->Denoiser != kNrdRelax)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: Denoiser must be 2 (NRDReBLUR) or 3 (NRDReLAX)");
+    const uint32_t w = k->RenderSize[0], h = k->RenderSize[1];
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: RenderSize must be in [1, 16384]");
+    const bool pack = k->Pack != 0, reblur = k->Denoiser == kNrdReblur;
+    const uint64_t n = (uint64_t)w * h;
+    // the buffers this direction uses: (pointer, bytes per pixel, alignment, written)
+    struct Use { const void* p; uint32_t bpp, align; bool written; const char* name; };
+    Use use[7];
+    uint32_t nu = 0;
+    use[nu++] = {t->LinearDepth, 4, 4, false, "LinearDepth"};
+    use[nu++] = {t->DiffuseAlbedo, 12, 4, false, "DiffuseAlbedo"};
+    use[nu++] = {t->SpecularAlbedo, 12, 4, false, "SpecularAlbedo"};
+    if (pack) {
+        if (reblur) use[nu++] = {t->NormalRoughness, 16, 16, false, "NormalRoughness"};
+        use[nu++] = {t->NoisyDiffuse, 16, 16, true, "NoisyDiffuse"};
+        use[nu++] = {t->NoisySpecular, 16, 16, true, "NoisySpecular"};
+    } else {
+        use[nu++] = {t->DenoisedDiffuse, 16, 16, false, "DenoisedDiffuse"};
+        use[nu++] = {t->DenoisedSpecular, 16, 16, false, "DenoisedSpecular"};
+        use[nu++] = {t->Radiance, 16, 16, true, "Radiance"};
+    }
+    for (uint32_t i = 0; i < nu; i++) {
+        if (!use[i].p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " is required");
+        if (reinterpret_cast<uintptr_t>(use[i].p) % use[i].align)
+            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " is not " + std::to_string(use[i].align) + "-byte aligned");
+    }
+    // a buffer the pass writes must not share a byte with any other buffer it uses (each lane reads its pixel of a written buffer
+    // before it writes it, so a written buffer may only overlap itself)
+    for (uint32_t i = 0; i < nu; i++)
+        for (uint32_t j = 0; j < nu; j++) {
+            if (i == j || !use[i].written) continue;
+            const uintptr_t a = reinterpret_cast<uintptr_t>(use[i].p), b = reinterpret_cast<uintptr_t>(use[j].p);
+            if (a < b + n * use[j].bpp && b < a + n * use[i].bpp)
+                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " overlaps " + use[j].name);
+        }
+    NrdBuffers b{};
+    b.linear_depth = static_cast<const float*>(t->LinearDepth);
+    b.diffuse_albedo = static_cast<const float*>(t->DiffuseAlbedo);
+    b.specular_albedo = static_cast<const float*>(t->SpecularAlbedo);
+    if (pack) {
+        b.normal_roughness = reblur ? static_cast<const float4*>(t->NormalRoughness) : nullptr;
+        b.noisy_diffuse = static_cast<float4*>(t->NoisyDiffuse);
+        b.noisy_specular = static_cast<float4*>(t->NoisySpecular);
+    } else {
+        b.denoised_diffuse = static_cast<const float4*>(t->DenoisedDiffuse);
+        b.denoised_specular = static_cast<const float4*>(t->DenoisedSpecular);
+        b.radiance = static_cast<float4*>(t->Radiance);
+    }
+    const NrdHitDistParams P{k->ReBLURHitDistance[0], k->ReBLURHitDistance[1], k->ReBLURHitDistance[2], k->ReBLURHitDistance[3]};
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, launch_nrd_composition(b, (uint32_t)n, pack, k->Denoiser, P, c->stream));
     return PT_OK;
 }
 

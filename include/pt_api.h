@@ -16,6 +16,8 @@
  *                                                       Source/GBufferGeneration.ixx:80-117, Raytracing.ixx:106-112,228-249
  *   pt_render_gbuffer        GBufferGeneration::Render with its output textures   Source/GBufferGeneration.ixx:80-117
  *   pt_render_denoiser       Raytracing::Render with GraphicsSettings.Denoiser != None   Shaders/Raytracing.hlsl:377-414, Source/App.cpp:1140-1146
+ *   pt_nrd_composition       PostProcessing::NRDComposition::Process (pack and compose around NRD)   Source/NRDComposition.ixx,
+ *                            Shaders/NRDComposition.hlsl, driven by App::ProcessNRD  Source/App.cpp:1549-1642
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -276,6 +278,31 @@ typedef struct PtDenoiserOutputs {   /* DEVICE pointers, float4 ones 16-byte ali
 } PtDenoiserOutputs;
 PtStatus pt_render_denoiser(PtContext *ctx, const PtRect *rect, void *out, int out_is_device,
                             const PtDenoiserOutputs *outputs, PtStats *stats);
+
+/* Row N8 -- the NRD composition pass (PostProcessing::NRDComposition, Shaders/NRDComposition.hlsl; DESIGN.md spec S14), on the
+ * context's stream (asynchronous): ordered after the G-buffer and the denoiser frames already queued, before whatever the caller
+ * queues there next; it adds nothing to pt_get_totals.  One pass over the RenderSize[0] x RenderSize[1] pixels (row-major, the
+ * rect of the pt_render_gbuffer / pt_render_denoiser calls that made the inputs); a pixel whose LinearDepth is not finite (a miss)
+ * is left untouched.
+ *   Pack != 0 (before NRD): NoisyDiffuse / NoisySpecular in place: rgb /= the lobe's albedo, then the NRD front-end of the mode
+ *     (ReBLUR: hit distance normalised by ReBLURHitDistance and NormalRoughness.w, rgb to YCoCg; ReLAX: sanitised).
+ *   Pack == 0 (after NRD): Radiance.rgb += unpack(DenoisedDiffuse).rgb * DiffuseAlbedo + unpack(DenoisedSpecular).rgb * SpecularAlbedo;
+ *     alpha unchanged.  In the NRD modes pt_render_denoiser's out holds the primary emission, the radiance this adds to.
+ * PT_ERR_INVALID_ARG: a null argument; Denoiser not 2 or 3; a RenderSize of 0 or > 16384; a buffer the direction needs missing
+ * (LinearDepth, both albedos, and: pack both noisy buffers, plus NormalRoughness for ReBLUR; compose both denoised buffers and
+ * Radiance); a float4 buffer not 16-byte aligned or a float / float3 one not 4-byte aligned; a buffer the call writes overlapping
+ * another buffer it uses (Radiance aliasing an input; the two noisy buffers, or one of them and an input). */
+typedef struct PtNrdCompositionTextures {   /* DEVICE pointers (NRDComposition::Textures); NULL where the direction does not use it */
+    const void *LinearDepth;                /* float   (G-buffer LinearDepth) */
+    const void *DiffuseAlbedo;              /* float3  (G-buffer DiffuseAlbedo) */
+    const void *SpecularAlbedo;             /* float3  (G-buffer SpecularAlbedo) */
+    const void *NormalRoughness;            /* float4  (G-buffer NormalRoughness; ReBLUR pack reads .w) */
+    void *NoisyDiffuse, *NoisySpecular;     /* float4  (pt_render_denoiser Diffuse / Specular): pack */
+    const void *DenoisedDiffuse;            /* float4  (NRD's OUT_DIFF_RADIANCE_HITDIST): compose */
+    const void *DenoisedSpecular;           /* float4  (NRD's OUT_SPEC_RADIANCE_HITDIST): compose */
+    void *Radiance;                         /* float4  (pt_render_denoiser out): compose */
+} PtNrdCompositionTextures;
+PtStatus pt_nrd_composition(PtContext *ctx, const PtNrdCompositionConstants *constants, const PtNrdCompositionTextures *textures);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

@@ -7,6 +7,7 @@
  *   PtCamera           == Camera              Source/Camera.ixx:16-36    (== Shaders/Camera.hlsli:5-25), 608 B payload
  *   PtSceneData        == SceneData           Source/CommonShaderData.ixx:15-20 (== Shaders/Common.hlsli:7-13), 80 B payload
  *   PtGraphicsSettings == _GraphicsSettings   Source/Raytracing.ixx:151-166 (== Shaders/Raytracing.hlsl:21-39), 80 B
+ *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
  * geosphere mesh (Source/Scene.ixx:188-203: scale = 2*radius, z flipped): the
@@ -18,6 +19,7 @@
 #ifndef PT_TYPES_H
 #define PT_TYPES_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -148,6 +150,15 @@ typedef struct PtToneMapParams {
     uint32_t _pad[3];
 } PtToneMapParams;
 
+/* Row N8 (pt_nrd_composition): NRDComposition::Constants, uploaded as 8 root constants (Shaders/NRDComposition.hlsl:3-9).
+ * App::ProcessNRD passes nrd::ReblurSettings().hitDistanceParameters = {3, 0.1, 20, -25} in ReBLURHitDistance (DESIGN.md spec S14). */
+typedef struct PtNrdCompositionConstants {
+    uint32_t RenderSize[2];       /*  0 */
+    uint32_t Pack;                /*  8: nonzero = pack (before NRD), 0 = compose (after NRD) */
+    uint32_t Denoiser;            /* 12: 2 NRDReBLUR, 3 NRDReLAX (Source/Denoiser.ixx) */
+    float ReBLURHitDistance[4];   /* 16: hit distance normalisation {A, B, C, D}, read by ReBLUR pack only */
+} PtNrdCompositionConstants;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -165,12 +176,18 @@ static_assert(sizeof(PtSceneData) == 80, "PtSceneData layout");
 static_assert(sizeof(PtGraphicsSettings) == 80, "PtGraphicsSettings layout");
 static_assert(sizeof(PtToneMapParams) == 32, "PtToneMapParams layout");
 static_assert(sizeof(PtTextureMapInfo) == 16 && sizeof(PtObjectTextures) == 112, "TextureMapInfoArray layout");
+static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositionConstants, Pack) == 8
+              && offsetof(PtNrdCompositionConstants, Denoiser) == 12 && offsetof(PtNrdCompositionConstants, ReBLURHitDistance) == 16,
+              "NRDComposition::Constants layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
 _Static_assert(sizeof(PtCamera) == 608, "PtCamera layout");
 _Static_assert(sizeof(PtSceneData) == 80, "PtSceneData layout");
 _Static_assert(sizeof(PtGraphicsSettings) == 80, "PtGraphicsSettings layout");
+_Static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositionConstants, Pack) == 8
+               && offsetof(PtNrdCompositionConstants, Denoiser) == 12 && offsetof(PtNrdCompositionConstants, ReBLURHitDistance) == 16,
+               "NRDComposition::Constants layout");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Render the demo scene on the GPU and write a PNG through the product's own display path: N frames of the path tracer
 with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom] -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
-R8G8B8A8.  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR]"""
 import argparse
 import os
 import sys
@@ -57,6 +57,9 @@ def main():
     ap.add_argument("--denoiser-output", default=None, choices=["Diffuse", "Specular", "SpecularHitDistance"],
                     help="write one output of pt_render_denoiser (row N7) of the first frame instead of the path-traced image: Diffuse / "
                          "Specular from NRDReBLUR (radiance; their hit distance is not shown), SpecularHitDistance from DLSSRayReconstruction")
+    ap.add_argument("--nrd", default=None, choices=["ReBLUR", "ReLAX"],
+                    help="one frame through the reference's NRD path with the identity for NRD (row N8): pt_render_gbuffer -> "
+                         "pt_render_denoiser -> pack -> copy -> compose, then the tone map (no accumulation)")
     args = ap.parse_args()
     from PIL import Image
 
@@ -100,6 +103,19 @@ def main():
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
+    if args.nrd:
+        mode = t.DENOISER_NRD_REBLUR if args.nrd == "ReBLUR" else t.DENOISER_NRD_RELAX
+        r.set_camera(host.camera(w, h, jitter_index=0, jitter_count=max(args.frames, 8)))
+        r.set_constants(gs)
+        composed = torch.from_numpy(r.nrd_chain(mode)["Radiance"].reshape(n, 4)).cuda()
+        torch.cuda.synchronize()
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(composed.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"NRD {args.nrd} (identity denoiser) {w}x{h} -> {args.out}")
+        r.close()
+        return
     for k in range(args.frames):
         gs.FrameIndex = k
         r.set_camera(host.camera(w, h, jitter_index=k, jitter_count=max(args.frames, 8)))
