@@ -83,6 +83,8 @@ class Oracle:
         lib.oracle_render.argtypes = [vp, vp, u32, vp, vp, vp, C.POINTER(_Rect), u32, vp, C.POINTER(OracleStats), C.c_int]
         lib.oracle_trace_pixel.restype = C.c_int
         lib.oracle_trace_pixel.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, vp, u32, C.POINTER(u32)]
+        lib.oracle_trace_pixel_ex.restype = C.c_int
+        lib.oracle_trace_pixel_ex.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, vp, vp, u32, C.POINTER(u32), vp, vp]
         lib.oracle_halton.restype = C.c_float
         lib.oracle_halton.argtypes = [u32, u32]
         lib.oracle_render_textured.restype = C.c_int
@@ -186,6 +188,23 @@ class Oracle:
         if rc:
             raise RuntimeError(f"oracle_trace_pixel failed ({rc})")
         return ev[: n.value]
+
+    def trace_pixel_ex(self, spheres, materials, scene_data, camera, gs, px, py, textures=None, max_events=4096):
+        """the trace of one pixel rendered as render(..., textures=textures) renders it (texture maps, environment maps, DI):
+        (events float32 (n, 16), DI record float32 (10,), rgba float32 (4,)) -- see oracle_trace_pixel_ex in pt_oracle.h"""
+        spheres = np.ascontiguousarray(spheres)
+        materials = np.ascontiguousarray(materials)
+        ev = np.zeros((max_events, 16), dtype=np.float32)
+        di = np.zeros(10, dtype=np.float32)
+        rgba = np.zeros(4, dtype=np.float32)
+        n = C.c_uint32(0)
+        t, keep = self._textures_struct(textures) if textures is not None else (None, None)
+        rc = self.lib.oracle_trace_pixel_ex(spheres.ctypes.data, materials.ctypes.data, len(spheres), C.addressof(scene_data), C.addressof(camera),
+                                            C.addressof(gs), px, py, C.addressof(t) if t is not None else None, ev.ctypes.data, max_events,
+                                            C.byref(n), di.ctypes.data, rgba.ctypes.data)
+        if rc:
+            raise RuntimeError(f"oracle_trace_pixel_ex failed ({rc})")
+        return ev[: n.value], di, rgba
 
 
 _oracle = None

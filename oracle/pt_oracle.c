@@ -827,6 +827,7 @@ void oracle_bsdf_step(const PtMaterial *m, int front, const float Ng_[3], const 
 /* ------------------------------------------------------------------ the per-pixel loop */
 typedef struct {
     float *events; uint32_t max_events, n_events;
+    float *di; /* NULL, or the pixel's DI record (oracle_trace_pixel_ex) */
 } trace_t;
 
 static void trace_event(trace_t *tr, uint32_t s, uint32_t bnc, const hit_t *h, int is_hit, v3 L, v3 T, uint32_t rng, int lobe, int flags)
@@ -1138,6 +1139,8 @@ static material_eval evaluate_material(const tex_ctx *tc, const PtMaterial *m, c
  * ---------------------------------------------------------------------------------------------------------------- */
 #define DI_NEGLIGIBLE 1e-7f
 #define DI_RNG_SALT 0x44495F31u
+/* outcome of a pixel's DI sample in its oracle_trace_pixel_ex record */
+enum { DI_REC_SHADOW = 0, DI_REC_CULLED = 1, DI_REC_NO_CANDIDATE = 2, DI_REC_NONE = 3 };
 
 typedef struct { const uint32_t *ids; uint32_t n; } light_list;
 
@@ -1214,6 +1217,7 @@ static uint64_t render_pixel(const PtSphere *sph, const PtMaterial *mat, uint32_
         v3 L = V3(Ll[0], Ll[1], Ll[2]);
         surf_t sv;
         surf_init(&sv, primary.front, primary.N, primary.shadingN);
+        uint32_t di_shadow_id = 0xFFFFFFFFu, di_outcome = DI_REC_NO_CANDIDATE;
         if (light != primary.id && ok && v_dot(sv.FrontNg, L) > 0.0f) {
             v3 V = v_neg(d);
             float w[3];
@@ -1225,9 +1229,12 @@ static uint64_t render_pixel(const PtSphere *sph, const PtMaterial *mat, uint32_
             const float bound = f_max(f.x * lmc->EmissiveColor[0], f_max(f.y * lmc->EmissiveColor[1], f.z * lmc->EmissiveColor[2])) * (lmc->EmissiveStrength * kk);
             hit_t sh;
             sh.hit = 0;
+            di_outcome = DI_REC_CULLED;
             if (bound > DI_NEGLIGIBLE) {
                 cast_ray(accel, sph, n, spawn_origin(primary.P, primary.N, primary.offset, L), L, 0.0f, INFINITY, &sh, alpha);
                 rays++;
+                di_outcome = DI_REC_SHADOW;
+                if (sh.hit) di_shadow_id = sh.id;
             }
             if (sh.hit && sh.id == light) {
                 /* the emitter's radiance at the point the shadow ray reaches: Material::GetEmission after EvaluateMaterial (an
@@ -1241,6 +1248,11 @@ static uint64_t render_pixel(const PtSphere *sph, const PtMaterial *mat, uint32_
          * estimator DI = 0 is an ordinary sample value, so the gate is "the pixel has a primary surface" (keeps it unbiased) */
         if (!(DI.x > 0.0f || DI.y > 0.0f || DI.z > 0.0f) || !f_finite(DI.x) || !f_finite(DI.y) || !f_finite(DI.z)) DI = V3(0, 0, 0);
         di_valid = 1;
+        if (tr && tr->di) {
+            float *r = tr->di;
+            r[0] = as_float(light); r[1] = L.x; r[2] = L.y; r[3] = L.z; r[4] = inv_pdf; r[5] = as_float(di_shadow_id);
+            r[6] = (float)di_outcome; r[7] = DI.x; r[8] = DI.y; r[9] = DI.z;
+        }
     }
 
     v3 radiance = V3(0, 0, 0);
@@ -1527,11 +1539,47 @@ int oracle_trace_pixel(const PtSphere *spheres, const PtMaterial *materials, uin
 {
     int err = validate(scene, gs, n);
     if (err) return err;
-    trace_t tr = { events, max_events, 0 };
+    trace_t tr = { events, max_events, 0, NULL };
     float rgba[4]; uint64_t paths = 0;
     int has_alpha = 0;
     for (uint32_t i = 0; i < n && !has_alpha; i++) has_alpha = materials[i].AlphaMode != PT_ALPHA_OPAQUE;
     render_pixel(spheres, materials, n, scene, camera, gs, px, py, rgba, &paths, &tr, NULL, NULL, NULL, has_alpha);
     *n_events = tr.n_events;
+    return 0;
+}
+
+int oracle_trace_pixel_ex(const PtSphere *spheres, const PtMaterial *materials, uint32_t n,
+                          const PtSceneData *scene, const PtCamera *camera,
+                          const PtGraphicsSettings *gs, uint32_t px, uint32_t py, const OracleTextures *textures,
+                          float *events, uint32_t max_events, uint32_t *n_events, float di_record[10], float rgba[4])
+{
+    /* the checks and the light list of oracle_render_textured (the pixel is rendered exactly as that renders it, brute force) */
+    int err = validate(scene, gs, n);
+    if (err) return err;
+    if ((err = validate_textures(textures, n)) != 0) return err;
+    if (px >= gs->RenderSize[0] || py >= gs->RenderSize[1]) return 5;
+    if (scene->EnvironmentLightTextureDescriptor != 0xFFFFFFFFu) {
+        const uint32_t e = scene->EnvironmentLightTextureDescriptor, nf = scene->IsEnvironmentLightTextureCubeMap ? 6u : 1u;
+        if (!textures || (uint64_t)e + nf > textures->n_textures) return 4;
+    }
+    tex_ctx tc;
+    const int textured = textures && textures->n_textures > 0;
+    if (textured) tex_ctx_init(&tc, textures);
+    uint32_t *light_ids = (uint32_t *)malloc((size_t)(n ? n : 1) * sizeof(uint32_t));
+    light_list ll = { light_ids, 0 };
+    for (uint32_t i = 0; i < n; i++) {
+        const PtMaterial *m = &materials[i];
+        if (m->EmissiveStrength * m->EmissiveColor[0] > 0.0f || m->EmissiveStrength * m->EmissiveColor[1] > 0.0f || m->EmissiveStrength * m->EmissiveColor[2] > 0.0f)
+            light_ids[ll.n++] = i;
+    }
+    int has_alpha = 0;
+    for (uint32_t i = 0; i < n && !has_alpha; i++) has_alpha = materials[i].AlphaMode != PT_ALPHA_OPAQUE;
+    const float none[10] = { as_float(0xFFFFFFFFu), 0, 0, 0, 0, as_float(0xFFFFFFFFu), (float)DI_REC_NONE, 0, 0, 0 };
+    memcpy(di_record, none, sizeof none);
+    trace_t tr = { events, max_events, 0, di_record };
+    uint64_t paths = 0;
+    render_pixel(spheres, materials, n, scene, camera, gs, px, py, rgba, &paths, &tr, textured ? &tc : NULL, &ll, NULL, has_alpha);
+    *n_events = tr.n_events;
+    free(light_ids);
     return 0;
 }

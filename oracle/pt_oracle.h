@@ -74,6 +74,16 @@ int oracle_trace_pixel(const PtSphere *spheres, const PtMaterial *materials, uin
                        const PtGraphicsSettings *gs, uint32_t px, uint32_t py,
                        float *events, uint32_t max_events, uint32_t *n_events);
 
+/* The same trace with texture maps, environment maps and direct illumination, as oracle_render_textured renders the pixel
+ * (brute-force closest hit).  textures may be NULL.  di_record (10 floats): {emitter id (bits), L (3), inv_pdf, shadow-hit id
+ * (bits; 0xFFFFFFFF = none or miss), outcome (0 shadow ray cast, 1 culled by the negligible-contribution bound, 2 no candidate:
+ * the emitter is the primary object, contains the primary point or lies below its horizon, 3 no DI), estimate (3)};
+ * rgba: the pixel's rendered value. */
+int oracle_trace_pixel_ex(const PtSphere *spheres, const PtMaterial *materials, uint32_t n,
+                          const PtSceneData *scene, const PtCamera *camera,
+                          const PtGraphicsSettings *gs, uint32_t px, uint32_t py, const OracleTextures *textures,
+                          float *events, uint32_t max_events, uint32_t *n_events, float di_record[10], float rgba[4]);
+
 /* ---- leaf functions exported for known-answer tests ---- */
 uint32_t oracle_hash(uint32_t x);
 uint32_t oracle_rng_init(uint32_t px, uint32_t py, uint32_t frame);

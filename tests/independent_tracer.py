@@ -2,8 +2,10 @@
 and the device headers are siblings, so a shared misreading of the shaders would pass every GPU-vs-oracle test).
 
 Written from the reference's shader text alone -- Shaders/Raytracing.hlsl:103-415 (DEFAULT permutation), Shaders/BxDF.hlsli:21-315,
-SurfaceVectors.hlsli, HitInfo.hlsli:60-64,96-99, Camera.hlsli:27-41, Math.hlsli:7-15, ShadingHelpers.hlsli:11-30 -- plus SURVEY.md
-Appendix A for the un-vendored MathLib bodies and DESIGN.md S3 for the build-defined ray-sphere hit.  It shares NO code with the
+SurfaceVectors.hlsli, HitInfo.hlsli:60-64,91-99, Camera.hlsli:27-41, Math.hlsli:7-33, ShadingHelpers.hlsli:11-235,
+RaytracingHelpers.hlsli:19-43, Source/Scene.ixx:197-199 -- plus SURVEY.md Appendix A for the un-vendored MathLib bodies, DESIGN.md S3
+for the build-defined ray-sphere hit, and where the reference has no text for analytic spheres (texture coordinates, sampler, cube
+faces, alpha-tested crossings, the direct-illumination stand-in) the DESIGN.md spec items S6-S10 and section 10 N4.  It shares NO code with the
 oracle or the kernels and deliberately differs from them in everything that is not the estimator itself:
 
   * double precision throughout, libm transcendentals (no fma placement, no polynomial sincos / pow / sky fits),
@@ -11,7 +13,7 @@ oracle or the kernels and deliberately differs from them in everything that is n
   * brute-force closest hit, a flat procedural style (dicts and tuples) instead of the oracle's structs.
 
 What has to agree with the oracle EXACTLY: the integer RNG stream (state after every bounce), every hit id, every lobe choice and
-every termination reason; throughput, hit distance and radiance agree to rounding (1e-3 relative is asserted; typical 1e-6).
+every termination reason, and with direct illumination the emitter, the shadow ray's hit and the cull; throughput, hit distance and radiance agree to rounding (1e-3 relative is asserted; typical 1e-6).
 tests/test_independent_tracer.py compares per event against oracle_trace_pixel and keeps the traces as fixtures."""
 import math
 
@@ -174,6 +176,153 @@ def refract(i, n, eta):
     return sub(scale(i, eta), scale(n, eta * ni + math.sqrt(k)))
 
 
+# ---------------------------------------------------------------- texture maps (row N1: DESIGN.md section 10, specs S6, S7, S9)
+# tex = {"images": [(texels, kind)], "maps": [[descriptor] * 7 per sphere], "rotations": [(x, y, z, w) per sphere]}: the raw data
+# of a TextureSet.  kind "unorm" / "srgb": uint8 texels, "float": float32 texels.  Descriptor 0xFFFFFFFF = no map.
+MAP_BASE_COLOR, MAP_EMISSIVE_COLOR, MAP_METALLIC, MAP_ROUGHNESS, MAP_METALLIC_ROUGHNESS, MAP_TRANSMISSION, MAP_NORMAL = range(7)  # Material.hlsli:24-34
+
+
+def map_of(tex, sphere_id, kind):
+    if tex is None or sphere_id is None:
+        return None
+    desc = int(tex["maps"][sphere_id][kind])
+    return None if desc == MISS else desc
+
+
+def texel(img, x, y):
+    """one texel as linear RGBA, decoded where the upload decodes it (S7): x/255, colour channels of an sRGB image through the
+    sRGB curve (alpha stays x/255), float texels as they are"""
+    texels, kind = img
+    v = [float(c) for c in texels[y][x]]
+    if kind == "float":
+        return v
+    v = [c / 255.0 for c in v]
+    if kind == "srgb":
+        v = [from_srgb(v[0]), from_srgb(v[1]), from_srgb(v[2]), v[3]]
+    return v
+
+
+def bilinear(img, uv, wrap):
+    """SampleLevel(sampler, uv, 0) (S7): level-0 bilinear filter between the four texel centres around uv, wrap addressing on a
+    2D map, clamp addressing inside a cube face (S9); HLSL lerp"""
+    texels = img[0]
+    h, w = len(texels), len(texels[0])
+    u, v = (c if math.isfinite(c) else 0.0 for c in uv)
+    x, y = u * w - 0.5, v * h - 0.5
+    x0, y0 = math.floor(x), math.floor(y)
+    fx, fy = x - x0, y - y0
+    if wrap:
+        ix, iy = (x0 % w, (x0 + 1) % w), (y0 % h, (y0 + 1) % h)
+    else:
+        ix = (min(max(x0, 0), w - 1), min(max(x0 + 1, 0), w - 1))
+        iy = (min(max(y0, 0), h - 1), min(max(y0 + 1, 0), h - 1))
+    c00, c10, c01, c11 = texel(img, ix[0], iy[0]), texel(img, ix[1], iy[0]), texel(img, ix[0], iy[1]), texel(img, ix[1], iy[1])
+    lerp = lambda a, b, t: a + (b - a) * t
+    return [lerp(lerp(c00[k], c10[k], fx), lerp(c01[k], c11[k], fx), fy) for k in range(4)]
+
+
+def sample_map(tex, desc, uv):
+    return bilinear(tex["images"][desc], uv, True)
+
+
+def object_to_world(tex, sphere_id):
+    """the rotation part of ObjectToWorld (Scene.ixx:197-199: diag(1, 1, -1) * pose): R(q) * Z, where q is the object's rotation
+    as the host hands it over -- the pose conjugated with the mirror Z = diag(1, 1, -1), so Z * pose = R(q) * Z -- and R(q) the
+    rotation matrix of the quaternion (x, y, z, w)"""
+    x, y, z, w = (float(c) for c in tex["rotations"][sphere_id])
+    R = ((1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)),
+         (2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)),
+         (2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)))
+    return tuple((row[0], row[1], -row[2]) for row in R)
+
+
+def mat_vec(M, v): return (dot(M[0], v), dot(M[1], v), dot(M[2], v))
+def mat_t_vec(M, v): return (M[0][0] * v[0] + M[1][0] * v[1] + M[2][0] * v[2], M[0][1] * v[0] + M[1][1] * v[1] + M[2][1] * v[2],
+                             M[0][2] * v[0] + M[1][2] * v[1] + M[2][2] * v[2])
+
+
+def mesh_normal(tex, sphere_id, n_world):
+    """the GeoSphere vertex normal at the point whose outward world normal is n_world: ObjectToWorld is orthogonal, so its
+    inverse is its transpose"""
+    return mat_t_vec(object_to_world(tex, sphere_id), n_world)
+
+
+def uv_of_mesh_normal(nm):
+    """S6: u = 1 - (atan2(n.x, -n.z) / 2pi + 1/2), v = acos(n.y) / pi"""
+    return (1.0 - (math.atan2(nm[0], -nm[2]) / (2.0 * PI) + 0.5), math.acos(max(-1.0, min(1.0, nm[1]))) / PI)
+
+
+def sphere_uv(tex, sphere_id, n_world):
+    return uv_of_mesh_normal(mesh_normal(tex, sphere_id, n_world))
+
+
+def sphere_tangent_world(tex, sphere_id, n_world):
+    """S6: the tangent is the direction in which u increases.  d atan2(x, -z) = (x dz - z dx) / (x^2 + z^2), so grad u is along
+    (z, 0, -x) of the mesh normal; zero at the poles.  Carried to world space by ObjectToWorld."""
+    nm = mesh_normal(tex, sphere_id, n_world)
+    l = math.hypot(nm[2], nm[0])
+    if not l > 0.0:
+        return (0.0, 0.0, 0.0)
+    return mat_vec(object_to_world(tex, sphere_id), (nm[2] / l, 0.0, -nm[0] / l))
+
+
+def cross(a, b): return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def perturb_normal(N, T, s):
+    """PerturbNormal (ShadingHelpers.hlsli:89-103): Geometry::UnpackLocalNormal of the map's RG -- the encoding the normal maps
+    are made with, n.xy = s * 255/127 - 1, z = sqrt(saturate(1 - x^2 - y^2)) -- then Math::CalculateTBN (Math.hlsli:17-21:
+    T = normalize(T - N dot(N, T)), rows T, cross(N, T), N) and normalize(RotateVectorInverse(TBN, n))"""
+    x, y = s[0] * 255.0 / 127.0 - 1.0, s[1] * 255.0 / 127.0 - 1.0
+    z = math.sqrt(saturate(1.0 - x * x - y * y))
+    Tn = unit(sub(T, scale(N, dot(N, T))))
+    B = cross(N, Tn)
+    return unit(add(add(scale(Tn, x), scale(B, y)), scale(N, z)))
+
+
+def evaluate_material(mat, hit, tex):
+    """EvaluateMaterial (ShadingHelpers.hlsli:161-235) at a hit: the material with every map applied under the shader's guards,
+    and the shading normal (the hit's front-facing normal, perturbed by the normal map).  The geometric normal is untouched."""
+    e = dict(mat)
+    e["Ns"] = hit["Ns"]
+    sid = hit["id"]
+    if tex is None or all(map_of(tex, sid, k) is None for k in range(7)):
+        return e
+    uv = sphere_uv(tex, sid, hit["N"])
+    T = sphere_tangent_world(tex, sid, hit["N"])
+    if not hit["front"]:                                          # HitInfo::GetFrontTangent, HitInfo.hlsli:91-94
+        T = neg(T)
+    base = list(e["BaseColor"])
+    desc = map_of(tex, sid, MAP_BASE_COLOR)
+    if any(c > 0.0 for c in base) and desc is not None:           # EvaluateBaseColor :61-72 (any over the float4)
+        m = sample_map(tex, desc, uv)
+        base = [base[k] * m[k] for k in range(4)]
+    e["BaseColor"] = base
+    desc = map_of(tex, sid, MAP_EMISSIVE_COLOR)
+    if any(c * e["EmissiveStrength"] > 0.0 for c in e["EmissiveColor"]) and desc is not None:   # :178-184
+        m = sample_map(tex, desc, uv)
+        e["EmissiveColor"] = [e["EmissiveColor"][k] * m[k] for k in range(3)]
+    desc = map_of(tex, sid, MAP_METALLIC_ROUGHNESS)
+    if desc is not None:                                          # :186-196: metallic from B, roughness from G
+        if e["Metallic"] > 0.0 or e["Roughness"] > 0.0:
+            m = sample_map(tex, desc, uv)
+            e["Metallic"], e["Roughness"] = e["Metallic"] * m[2], e["Roughness"] * m[1]
+    else:                                                         # :197-213: the separate maps, red channel
+        desc = map_of(tex, sid, MAP_METALLIC)
+        if e["Metallic"] > 0.0 and desc is not None:
+            e["Metallic"] = e["Metallic"] * sample_map(tex, desc, uv)[0]
+        desc = map_of(tex, sid, MAP_ROUGHNESS)
+        if e["Roughness"] > 0.0 and desc is not None:
+            e["Roughness"] = e["Roughness"] * sample_map(tex, desc, uv)[0]
+    desc = map_of(tex, sid, MAP_TRANSMISSION)
+    if e["Metallic"] < 1.0 and e["Transmission"] > 0.0 and desc is not None:   # :215-222 with EvaluateTransmission :75-87
+        e["Transmission"] = e["Transmission"] * sample_map(tex, desc, uv)[0]
+    desc = map_of(tex, sid, MAP_NORMAL)
+    if any(c != 0.0 for c in T) and desc is not None:            # :224-232
+        e["Ns"] = perturb_normal(hit["Ns"], T, sample_map(tex, desc, uv))
+    return e
+
+
 # ---------------------------------------------------------------- geometry: analytic spheres, brute force (DESIGN.md S3)
 def hit_sphere(o, d, tmin, tmax, c, r):
     f = sub(o, c)
@@ -204,27 +353,50 @@ def surface_crossings(o, d, c, r):
     return (-b - sq, -b + sq)
 
 
-def is_opaque(mat):
-    """IsOpaque (ShadingHelpers.hlsli:105-115) without a base-colour map: BaseColor.a >= AlphaCutoff"""
-    return mat["BaseColor"][3] >= mat["AlphaCutoff"]
+def is_opaque(mat, tex=None, sphere_id=None, n=None, margins=None):
+    """IsOpaque (ShadingHelpers.hlsli:105-115): EvaluateBaseColor (:61-72) multiplies the float4 BaseColor by the base-colour map
+    when any of its four components is positive and the object has that map -- here at the texture coordinates of the crossing
+    whose outward normal is n (DESIGN S10) -- and the crossing is accepted iff the resulting alpha >= AlphaCutoff"""
+    alpha = mat["BaseColor"][3]
+    desc = map_of(tex, sphere_id, MAP_BASE_COLOR)
+    if desc is not None and any(c > 0.0 for c in mat["BaseColor"]):
+        alpha *= sample_map(tex, desc, sphere_uv(tex, sphere_id, n))[3]
+    if margins is not None:
+        margins.append(abs(alpha - mat["AlphaCutoff"]) / max(abs(mat["AlphaCutoff"]), 1e-30))
+    return alpha >= mat["AlphaCutoff"]
 
 
-def cast_ray(spheres, o, d, tmin, tmax, materials=None):
+def cast_ray(spheres, o, d, tmin, tmax, materials=None, tex=None, margins=None):
     """closest hit, ties to the lowest id (ascending scan, strict <); returns the HitInfo the loop needs or None.
     An object whose AlphaMode is not Opaque is non-opaque geometry (Scene.ixx:242-243): each of its candidates is committed only
-    if IsOpaque accepts it (RaytracingHelpers.hlsli:19-43)."""
+    if IsOpaque accepts it (RaytracingHelpers.hlsli:19-43).  margins: the relative margin of every alpha test is appended, and the
+    geometric one of the query: the smallest angle by which the ray would have to turn to graze a sphere's silhouette (spheres
+    ahead that do not contain the origin), and the relative gap between the two nearest hits."""
     best, best_id = tmax, MISS
+    graze, ts = math.inf, []
     for i, (cx, cy, cz, r) in enumerate(spheres):
+        if margins is not None:
+            f = sub((cx, cy, cz), o)
+            dist, along = math.sqrt(dot(f, f)), dot(f, d)
+            if dist > r and along > 0.0:
+                graze = min(graze, abs(math.sqrt(max(dist * dist - along * along, 0.0)) - r) / dist)
         if materials is not None and materials[i].get("AlphaMode", 0) != 0:
             t = None
             for candidate in surface_crossings(o, d, (cx, cy, cz), r):   # the nearer candidate first
-                if candidate > tmin and is_opaque(materials[i]):
-                    t = candidate
-                    break
+                if candidate > tmin and candidate < best:
+                    n = unit(sub(add(o, scale(d, candidate)), (cx, cy, cz)))
+                    if is_opaque(materials[i], tex, i, n, margins):
+                        t = candidate
+                        break
         else:
             t = hit_sphere(o, d, tmin, math.inf, (cx, cy, cz), r)
+        if t is not None and margins is not None:
+            ts.append(t)
         if t is not None and t < best:
             best, best_id = t, i
+    if margins is not None:
+        ts.sort()
+        margins.append(min(graze, (ts[1] - ts[0]) / ts[1] if len(ts) > 1 else math.inf))
     if best_id == MISS:
         return None
     cx, cy, cz, r = spheres[best_id]
@@ -279,7 +451,7 @@ def find_lobe(w, r):                                              # :198-212
     return lobe
 
 
-def sample(b, sv, V, w, rnd):                                     # :214-226
+def sample(b, sv, V, w, rnd, margins=None):                       # :214-226
     lobe = find_lobe(w, rnd[0])
     basis = sv["basis"]
     if lobe == 0:                                                 # :81-86
@@ -290,6 +462,8 @@ def sample(b, sv, V, w, rnd):                                     # :214-226
         L = reflect(neg(V), H)
         return dot(sv["FrontNg"], L) > 0.0, L, lobe
     voh, eta = abs(dot(V, H)), b["iori"] / b["ioro"]              # :148-170
+    if margins is not None:
+        margins.append(min(abs(eta * eta * (1.0 - voh * voh) - 1.0), abs(rnd[3] - fresnel_dielectric(eta, voh))))
     if eta * eta * (1.0 - voh * voh) > 1.0 or rnd[3] < fresnel_dielectric(eta, voh):
         L = reflect(neg(V), H)
     else:
@@ -335,19 +509,110 @@ def eval_of(b, sv, L, V, w, lobe):                                # :301-315
     return scale(schlick(b["f0"], voh), k * wr)
 
 
-# ---------------------------------------------------------------- environment (ShadingHelpers.hlsli:11-30, no texture)
-def environment(env_color, d):
+# ---------------------------------------------------------------- environment (ShadingHelpers.hlsli:11-30)
+def cube_face(d):
+    """TextureCube addressing (S9): the face of the axis of largest magnitude (ties: z over y over x), D3D face order
+    +X -X +Y -Y +Z -Z, and the face coordinates of the D3D cube-map table: (sc, tc, ma) =
+    +X (-z, -y, x), -X (z, -y, x), +Y (x, z, y), -Y (x, -z, y), +Z (x, -y, z), -Z (-x, -y, z); u = (sc/|ma| + 1)/2, v = (tc/|ma| + 1)/2"""
+    x, y, z = d
+    ax, ay, az = abs(x), abs(y), abs(z)
+    if az >= ax and az >= ay:
+        face, sc, tc, ma = (4, x, -y, az) if z >= 0.0 else (5, -x, -y, az)
+    elif ay >= ax:
+        face, sc, tc, ma = (2, x, z, ay) if y >= 0.0 else (3, x, -z, ay)
+    else:
+        face, sc, tc, ma = (0, -z, -y, ax) if x >= 0.0 else (1, z, -y, ax)
+    return face, ((sc / ma + 1.0) * 0.5, (tc / ma + 1.0) * 0.5)
+
+
+def environment(env_color, d, env_map=None):
+    """GetEnvironmentLightColor.  env_map = {"M": 3x3 rows of EnvironmentLightTransform, "cube": bool, "images": the lat-long image
+    or the six faces}: d' = normalize(RotateVector((float3x3)M, d)) (:16), then the cube (:17-21) or the lat-long lookup (:22-23,
+    Math::ToLatLongCoordinate, Math.hlsli:29-33: ((1 + atan2(x, z) / pi) / 2, acos(y) / pi))"""
+    if env_map is not None:
+        r = unit(mat_vec(env_map["M"], d))
+        if env_map["cube"]:
+            face, uv = cube_face(r)
+            return tuple(bilinear(env_map["images"][face], uv, False)[:3])
+        uv = ((1.0 + math.atan2(r[0], r[2]) / PI) / 2.0, math.acos(max(-1.0, min(1.0, r[1]))) / PI)
+        return tuple(bilinear(env_map["images"][0], uv, True)[:3])
     if env_color[3] >= 0.0:
         return tuple(env_color[:3])
     t = (d[1] + 1.0) * 0.5
     return tuple(from_srgb(1.0 + (c - 1.0) * t) for c in (0.5, 0.7, 1.0))
 
 
+# ---------------------------------------------------------------- direct illumination (row N4: DESIGN.md section 10 N4)
+DI_SALT = 0x44495F31
+DI_NEGLIGIBLE = 1e-7
+DI_SHADOW, DI_CULLED, DI_NO_CANDIDATE, DI_NONE = 0, 1, 2, 3   # what became of the pixel's one DI sample
+
+
+def emitters(materials):
+    """the emissive objects in id order (LightPreparation.ixx:52-70): any component of EmissiveStrength * EmissiveColor > 0"""
+    return [i for i, m in enumerate(materials) if any(m["EmissiveStrength"] * c > 0.0 for c in m["EmissiveColor"])]
+
+
+def sphere_cone(P, C, r, u1, u2):
+    """a direction uniform in the cone the sphere (C, r) subtends from P and 1 / its pdf, or None when P is inside.  The cone's
+    solid angle is 2 pi (1 - cos theta_max), 1 - cos formed as sin^2 / (1 + cos); cos theta = 1 - u1 (1 - cos theta_max),
+    phi = 2 pi u2, about the axis in the frame of Geometry::GetBasis (the samplers' frame, SURVEY Appendix A)"""
+    w = sub(C, P)
+    d2 = dot(w, w)
+    if not d2 > r * r:
+        return None
+    sin2 = r * r / d2
+    omc = sin2 / (1.0 + math.sqrt(saturate(1.0 - sin2)))
+    k = u1 * omc
+    cos_t = 1.0 - k
+    sin_t = math.sqrt(saturate(k * (1.0 + cos_t)))
+    phi = 2.0 * PI * u2
+    L = to_world(get_basis(unit(w)), (sin_t * math.cos(phi), sin_t * math.sin(phi), cos_t))
+    return L, 2.0 * PI * omc
+
+
+def direct_illumination(spheres, materials, tex, px, py, frame, primary, b, sv, V, lights, margins):
+    """one emitter uniformly, one direction in its cone, the shadow ray must reach it first; DI = Le (f_d + f_s) cos n / pdf with
+    Le = the emission EvaluateMaterial gives at the point the shadow ray reaches; no shadow ray when the bound with the emitter's
+    untextured radiance is <= kDiNegligible.  Returns (DI, record) -- record = (emitter, L, inv_pdf, shadow hit id, outcome)."""
+    rng = Stream(rng_seed(px, py, (frame ^ DI_SALT) & 0xFFFFFFFF))
+    u0, u1, u2 = rng.unit(), rng.unit(), rng.unit()
+    light = lights[min(int(u0 * len(lights)), len(lights) - 1)]
+    cx, cy, cz, r = spheres[light]
+    cone = sphere_cone(primary["P"], (cx, cy, cz), r, u1, u2)
+    L, inv_pdf = cone if cone is not None else ((0.0, 0.0, 1.0), 0.0)
+    zero = (0.0, 0.0, 0.0)
+    if light == primary["id"] or cone is None or not dot(sv["FrontNg"], L) > 0.0:
+        return zero, (light, L, inv_pdf, MISS, DI_NO_CANDIDATE)
+    w = lobe_weights(b, sv, V)
+    f = add(eval_of(b, sv, L, V, w, 0), eval_of(b, sv, L, V, w, 1))
+    lm = materials[light]
+    k = inv_pdf * len(lights)
+    bound = max(f[c] * lm["EmissiveColor"][c] for c in range(3)) * lm["EmissiveStrength"] * k
+    margins.append(abs(bound - DI_NEGLIGIBLE) / DI_NEGLIGIBLE)
+    if not bound > DI_NEGLIGIBLE:
+        return zero, (light, L, inv_pdf, MISS, DI_CULLED)
+    sh = cast_ray(spheres, safe_origin(primary, L), L, 0.0, math.inf, materials, tex, margins)
+    sid = MISS if sh is None else sh["id"]
+    DI = zero
+    if sid == light:
+        e = evaluate_material(lm, sh, tex)
+        DI = scale(mul(scale(tuple(e["EmissiveColor"]), e["EmissiveStrength"]), f), k)
+    if not any(c > 0.0 for c in DI) or not finite3(DI):
+        DI = zero
+    return DI, (light, L, inv_pdf, sid, DI_SHADOW)
+
+
 # ---------------------------------------------------------------- the pixel (Raytracing.hlsl:103-415, GBufferGeneration.hlsl:117-232)
-def trace_pixel(spheres, materials, env_color, cam, w, h, frame, bounces, spp, rr, threshold, px, py):
-    """spheres: [(cx, cy, cz, r)], materials: [dict], cam: dict(Position, Right, Up, Forward, Near, Far, Jitter).
+def trace_pixel(spheres, materials, env_color, cam, w, h, frame, bounces, spp, rr, threshold, px, py, tex=None, env_map=None, di=False,
+                record=None):
+    """spheres: [(cx, cy, cz, r)], materials: [dict], cam: dict(Position, Right, Up, Forward, Near, Far, Jitter); tex: texture maps
+    (see map_of), env_map: see environment, di: IsDIEnabled.
     Returns (rgb, events); event = dict(sample, bounce, id, t, L, T, rng, lobe, flag) -- flag as oracle_trace_pixel:
-    0 continues, 1 primary miss, 2 bounce miss, 3 sample failed, 4 pdf 0, 5 f 0, 6 roulette, 7 throughput cut-off."""
+    0 continues, 1 primary miss, 2 bounce miss, 3 sample failed, 4 pdf 0, 5 f 0, 6 roulette, 7 throughput cut-off.
+    record (a dict, optional) receives "margins" (per event: the smallest relative margin of the discrete decisions taken for it --
+    alpha tests of the ray that found its hit, lobe choice, sidedness, Fresnel choice, roulette, cut-off) and "di" (the pixel's DI
+    record: emitter, L, inv_pdf, shadow hit id, outcome, estimate; outcome DI_NONE without DI) with "di_margin"."""
     rng = Stream(rng_seed(px, py, frame))                         # :108
     u = (px + 0.5 + cam["Jitter"][0]) / w                          # Math.hlsli:7-10
     v = (py + 0.5 + cam["Jitter"][1]) / h
@@ -355,51 +620,90 @@ def trace_pixel(spheres, materials, env_color, cam, w, h, frame, bounces, spp, r
     d0 = unit(add(add(scale(cam["Right"], ndc[0]), scale(cam["Up"], ndc[1])), cam["Forward"]))  # Camera.hlsli:27-41
     inv_cos = 1.0 / dot(unit(cam["Forward"]), d0)
     o0 = tuple(cam["Position"])
-    events = []
-    primary = cast_ray(spheres, o0, d0, cam["Near"] * inv_cos, cam["Far"] * inv_cos, materials)
+    events, margins = [], []
+    if record is None:
+        record = {}
+    record["margins"] = margins
+    record["di"] = (MISS, (0.0, 0.0, 0.0), 0.0, MISS, DI_NONE, (0.0, 0.0, 0.0))
+    record["di_margin"] = math.inf
+    pm = []
+    primary = cast_ray(spheres, o0, d0, cam["Near"] * inv_cos, cam["Far"] * inv_cos, materials, tex, pm)
+    primary_margin = min(pm, default=math.inf)
     if primary is None:                                           # GBufferGeneration.hlsl:223-227; Raytracing.hlsl:249-252
         events.append({"sample": 0, "bounce": 0, "id": MISS, "t": math.inf, "L": (0, 0, 0), "T": (1, 1, 1), "rng": rng.state, "lobe": -1, "flag": 1})
-        return environment(env_color, d0), events
+        margins.append(primary_margin)
+        return environment(env_color, d0, env_map), events
+    # GBufferGeneration.hlsl:152-166: EvaluateMaterial at the primary hit; the shading normal it returns is the hit's
+    pmat = evaluate_material(materials[primary["id"]], primary, tex)
+    primary = {**primary, "Ns": pmat["Ns"]}
+    lights = emitters(materials) if di else []
+    DI, di_valid = (0.0, 0.0, 0.0), False
+    if lights:
+        b = bsdf_of(pmat, primary["front"], True)
+        sv = {"FrontNg": primary["N"] if primary["front"] else neg(primary["N"]), "Ns": primary["Ns"], "basis": get_basis(primary["Ns"])}
+        dm = []
+        DI, rec = direct_illumination(spheres, materials, tex, px, py, frame, primary, b, sv, neg(d0), lights, dm)
+        record["di"], record["di_margin"] = (*rec, DI), min(dm, default=math.inf)
+        di_valid = True                                           # N4: the gate is "the pixel has a primary surface"
     radiance = (0.0, 0.0, 0.0)
     for s in range(spp):                                          # :191
         o, d, hit = o0, d0, primary
         T, sample_radiance, L, lobe = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), -1
+        via_transmission = False
         for bounce in range(bounces + 1):                         # :213
+            em = [primary_margin] if bounce == 0 else []
             if bounce:
                 o, d = safe_origin(hit, L), L                     # :219-224
-                hit = cast_ray(spheres, o, d, 0.0, math.inf, materials)
+                hit = cast_ray(spheres, o, d, 0.0, math.inf, materials, tex, em)
             ev = {"sample": s, "bounce": bounce, "id": MISS if hit is None else hit["id"], "t": math.inf if hit is None else hit["t"], "lobe": lobe}
+
+            def close(flag):
+                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": flag})
+                margins.append(min(em, default=math.inf))
             if hit is None:                                       # :242-259
-                sample_radiance = add(sample_radiance, mul(T, environment(env_color, d)))
-                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 2})
+                sample_radiance = add(sample_radiance, mul(T, environment(env_color, d, env_map)))
+                close(2)
                 break
-            mat = materials[hit["id"]]
+            mat = pmat if bounce == 0 else evaluate_material(materials[hit["id"]], hit, tex)   # :293-301
+            hit = {**hit, "Ns": mat["Ns"]}
             b = bsdf_of(mat, hit["front"], bounce == 0)
             emission = scale(tuple(mat["EmissiveColor"]), mat["EmissiveStrength"])
+            if di_valid and bounce == 1 and not via_transmission:  # :302 with the N4 departures
+                emission = (0.0, 0.0, 0.0)
             sample_radiance = add(sample_radiance, mul(T, emission))  # :320
             sv = {"FrontNg": hit["N"] if hit["front"] else neg(hit["N"]), "Ns": hit["Ns"], "basis": get_basis(hit["Ns"])}  # SurfaceVectors.hlsli
             V = neg(d)
             w = lobe_weights(b, sv, V)
             rnd = (rng.unit(), rng.unit(), rng.unit(), rng.unit())   # :330
-            ok, L, lobe = sample(b, sv, V, w, rnd)
+            ok, L, lobe = sample(b, sv, V, w, rnd, em)
+            em.append(min(abs(rnd[0] - w[2]), abs(rnd[0] - (w[2] + w[1]))))   # FindLobe's comparisons
+            if lobe != 2:
+                em.append(abs(dot(sv["FrontNg"], L)))                # the sample's sidedness test
             ev["lobe"] = lobe
             if not ok:
-                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 3}); break
+                close(3); break
             pdf = pdf_of(b, sv, L, V, w, lobe)
             if pdf == 0.0:
-                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 4}); break
+                close(4); break
             f = eval_of(b, sv, L, V, w, lobe)
             if f == (0.0, 0.0, 0.0):
-                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 5}); break
+                close(5); break
             T = mul(T, scale(f, 1.0 / pdf))                        # :346
+            if bounce == 0:
+                via_transmission = lobe == 2
             if rr and bounce > 3:                                  # :348-356
                 p = max(T)
-                if rng.unit() >= p:
-                    events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 6}); break
+                r = rng.unit()
+                em.append(abs(r - p) / max(abs(p), 1e-30))
+                if r >= p:
+                    close(6); break
                 T = scale(T, 1.0 / p)
+            em.append(abs(lum(T) - threshold) / threshold)
             if lum(T) <= threshold:                                # :361
-                events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 7}); break
-            events.append({**ev, "L": L, "T": T, "rng": rng.state, "flag": 0})
+                close(7); break
+            close(0)
         radiance = add(radiance, sample_radiance)                 # :373
     radiance = scale(radiance, 1.0 / spp) if finite3(radiance) else (0.0, 0.0, 0.0)   # :378
+    if di:
+        radiance = add(radiance, DI)                              # :381
     return radiance, events
