@@ -88,6 +88,20 @@ class PtNrdCompositionTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NRD_TEXTURES]
 
 
+# Row N9 (pt_nrd_denoise, the NRD stand-in): the settings and the nrd::ResourceType tags it reads and writes
+NRD_DENOISE_TEXTURES = ("ViewZ", "MotionVector", "NormalRoughness", "BaseColorMetalness", "InDiffuse", "InSpecular", "OutDiffuse", "OutSpecular")
+NRD_ACCUMULATION_CONTINUE, NRD_ACCUMULATION_RESTART, NRD_ACCUMULATION_CLEAR_AND_RESTART = 0, 1, 2
+
+
+class PtNrdDenoiseSettings(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("Denoiser", C.c_uint32), ("AccumulationMode", C.c_uint32), ("FrameIndex", C.c_uint32),
+                ("MaxDiffuseFrames", C.c_uint32), ("MaxSpecularFrames", C.c_uint32), ("AtrousIterations", C.c_uint32)]
+
+
+class PtNrdDenoiseTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in NRD_DENOISE_TEXTURES]
+
+
 class PtTextureMapInfo(C.Structure):
     _fields_ = [("Descriptor", C.c_uint32), ("TextureCoordinateIndex", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 

@@ -7,9 +7,9 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo, PtCamera, PtConfig,
-                        PtDenoiserOutputs, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures, PtRect,
-                        PtSceneData, PtStats)
+from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
+                        PtCamera, PtConfig, PtDenoiserOutputs, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures,
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtSceneData, PtStats)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -18,7 +18,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_nrd_composition", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_nrd_composition", "pt_nrd_denoise", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -94,6 +94,8 @@ class HipLib:
         lib.pt_render_denoiser.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtDenoiserOutputs), C.POINTER(PtStats)]
         lib.pt_nrd_composition.restype = C.c_int
         lib.pt_nrd_composition.argtypes = [vp, C.POINTER(PtNrdCompositionConstants), C.POINTER(PtNrdCompositionTextures)]
+        lib.pt_nrd_denoise.restype = C.c_int
+        lib.pt_nrd_denoise.argtypes = [vp, C.POINTER(PtNrdDenoiseSettings), C.POINTER(PtNrdDenoiseTextures)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -425,9 +427,11 @@ class Renderer:
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         width = dict(GBUFFER_CHANNELS)
         gb = {name: torch.zeros((h, w, width[name]), dtype=torch.float32, device=dev) for name in NRD_TEXTURES[:4]}
+        guides = getattr(denoise, "gbuffer", {})  # G-buffer channels the denoiser reads besides these (NrdDenoiser: MotionVector)
         rad, nd, ns = (torch.zeros((h, w, 4), dtype=torch.float32, device=dev) for _ in range(3))
         torch.cuda.synchronize(dev)  # (cleared on torch's stream, which the context's stream knows nothing of)
-        self.render_gbuffer_device({name: b.data_ptr() for name, b in gb.items()}, rect)
+        self.render_gbuffer_device(dict({name: b.data_ptr() for name, b in gb.items()}, **{name: b.data_ptr() for name, b in guides.items()}), rect,
+                                   *getattr(denoise, "previous_pose", ()))
         self.render_denoiser_device(mode, rad.data_ptr(), {"Diffuse": nd.data_ptr(), "Specular": ns.data_ptr()}, rect)
         self.synchronize()
         res = {name: b.cpu().numpy() for name, b in gb.items()}
@@ -436,6 +440,9 @@ class Renderer:
         self.nrd_composition_device(mode, True, w, h, dict(inputs, NoisyDiffuse=nd.data_ptr(), NoisySpecular=ns.data_ptr()), hit_distance)
         self.synchronize()
         res.update(PackedDiffuse=nd.cpu().numpy(), PackedSpecular=ns.cpu().numpy())
+        if hasattr(denoise, "gbuffer"):
+            denoise.guides = gb
+            res.update({name: b.cpu().numpy() for name, b in guides.items()})
         dd, ds = denoise(nd, ns) if denoise is not None else (nd.clone(), ns.clone())
         dd, ds = dd.contiguous(), ds.contiguous()
         torch.cuda.synchronize(dev)
@@ -444,6 +451,26 @@ class Renderer:
         self.synchronize()
         res.update(DenoisedDiffuse=dd.cpu().numpy(), DenoisedSpecular=ds.cpu().numpy(), Radiance=rad.cpu().numpy())
         return res
+
+    def nrd_denoise_device(self, mode, width, height, buffers, accumulation_mode=0, frame_index=0, max_diffuse_frames=0, max_specular_frames=0,
+                           atrous_iterations=0):
+        """The NRD stand-in (row N9, DESIGN.md spec S15; mode abi_types.DENOISER_NRD_*) over width x height pixels: the packed In buffers
+        -> the Out buffers compose reads, with the history the context keeps.  buffers: {NRD_DENOISE_TEXTURES name: device pointer}
+        (BaseColorMetalness may be left out).  accumulation_mode: abi_types.NRD_ACCUMULATION_*.  Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(NRD_DENOISE_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown NRD denoise buffers {sorted(unknown)}")
+        s = PtNrdDenoiseSettings(RenderSize=(C.c_uint32 * 2)(width, height), Denoiser=mode, AccumulationMode=accumulation_mode, FrameIndex=frame_index,
+                                 MaxDiffuseFrames=max_diffuse_frames, MaxSpecularFrames=max_specular_frames, AtrousIterations=atrous_iterations)
+        t = PtNrdDenoiseTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_nrd_denoise(self._ctx, C.byref(s), C.byref(t)))
+
+    def nrd_denoiser(self, mode, rect=None, device=None, **settings):
+        """A `denoise(diffuse, specular)` for nrd_chain that runs pt_nrd_denoise (row N9) in place of the identity copy: it carries the
+        MotionVector buffer nrd_chain fills (its `gbuffer` attribute) and the G-buffer's LinearDepth / NormalRoughness it is handed
+        there.  Successive frames of one denoiser continue the context's history; `restart()` makes the next frame CLEAR_AND_RESTART.
+        settings: nrd_denoise_device's keywords.  `previous_pose` = (previous_spheres, previous_rotations) for the next G-buffer."""
+        return NrdDenoiser(self, mode, rect, device, settings)
 
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""
@@ -479,3 +506,39 @@ class Renderer:
         order = np.zeros(self.accel.leaf_count, dtype=np.uint32)
         self._check(self._lib.pt_accel_download_order(self._ctx, order.ctypes.data, len(order)))
         return nodes, order
+
+
+class NrdDenoiser:
+    """Renderer.nrd_denoiser: the `denoise` callable nrd_chain takes, backed by pt_nrd_denoise."""
+
+    def __init__(self, renderer, mode, rect, device, settings):
+        import torch
+        self._r, self.mode, self.settings = renderer, mode, dict(settings)
+        if rect is None:
+            rect = (0, 0, renderer._gs.RenderSize[0], renderer._gs.RenderSize[1])
+        self.w, self.h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.gbuffer = {"MotionVector": torch.zeros((self.h, self.w, 3), dtype=torch.float32, device=dev)}
+        self.guides = None
+        self.previous_pose = ()
+        self._restart = True
+
+    def restart(self):
+        self._restart = True
+
+    def __call__(self, diffuse, specular):
+        import torch
+        od, os_ = torch.empty_like(diffuse), torch.empty_like(specular)
+        od.copy_(diffuse)  # (misses are never written: they keep the packed value, as the identity chain does)
+        os_.copy_(specular)
+        torch.cuda.synchronize(diffuse.device)
+        mode = 2 if self._restart else self.settings.get("accumulation_mode", 0)
+        settings = dict(self.settings, accumulation_mode=mode)
+        self._r.nrd_denoise_device(self.mode, self.w, self.h, dict(ViewZ=self.guides["LinearDepth"].data_ptr(),
+                                                                   MotionVector=self.gbuffer["MotionVector"].data_ptr(),
+                                                                   NormalRoughness=self.guides["NormalRoughness"].data_ptr(),
+                                                                   InDiffuse=diffuse.data_ptr(), InSpecular=specular.data_ptr(),
+                                                                   OutDiffuse=od.data_ptr(), OutSpecular=os_.data_ptr()), **settings)
+        self._r.synchronize()
+        self._restart = False
+        return od, os_

@@ -21,6 +21,7 @@
 #include "pt_kernels.h"
 #include "pt_bloom.h"
 #include "pt_nrd.h"
+#include "pt_denoise.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
 
@@ -186,6 +187,11 @@ struct PtContext {
     bool gb_lanes_idle = false;
     float4* d_bloom = nullptr;  // pt_bloom's blur chain (used on `stream` only), grown on demand
     uint64_t cap_bloom = 0;     // texels
+    // pt_nrd_denoise's history and work buffers (used on `stream` only): one allocation of kDnBytesPerPixel per pixel, made on first
+    // use and again when RenderSize changes; `slot` = the history slot the last call wrote
+    float* d_dn = nullptr;
+    uint32_t dn_w = 0, dn_h = 0, dn_mode = 0, dn_slot = 0;
+    bool dn_valid = false;
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
     uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists
 
@@ -1459,6 +1465,7 @@ void pt_destroy(PtContext* c)
     if (c->beam.stream) (void)hipStreamDestroy(c->beam.stream);
     free_dev(c->d_out);
     free_dev(c->d_bloom);
+    free_dev(c->d_dn);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
     if (c->gpu_builder) lbvh_gpu_destroy(c->gpu_builder);
     for (auto& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2235,6 +2242,91 @@ PtStatus pt_nrd_composition(PtContext* c, const PtNrdCompositionConstants* k, co
     const NrdHitDistParams P{k->ReBLURHitDistance[0], k->ReBLURHitDistance[1], k->ReBLURHitDistance[2], k->ReBLURHitDistance[3]};
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, launch_nrd_composition(b, (uint32_t)n, pack, k->Denoiser, P, c->stream));
+    return PT_OK;
+}
+
+// Row N9 -- the NRD stand-in (DESIGN.md spec S15): pass (a), pass (b) and the a-trous steps on the context's stream, the history
+// in the context.  Per pixel: two history slots of four float4 (accumulated diffuse / specular, moments, guide), two hit distances,
+// two a-trous ping-pong pairs of float4.
+constexpr uint64_t kDnBytesPerPixel = 2 * 4 * sizeof(float4) + 2 * sizeof(float) + 4 * sizeof(float4);
+
+PtStatus pt_nrd_denoise(PtContext* c, const PtNrdDenoiseSettings* s, const PtNrdDenoiseTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: null pointer");
+    if (s->Denoiser != kNrdReblur && s->Denoiser != kNrdRelax)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: Denoiser must be 2 (NRDReBLUR) or 3 (NRDReLAX)");
+    if (s->AccumulationMode > 2) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: AccumulationMode must be 0, 1 or 2");
+    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: RenderSize must be in [1, 16384]");
+    if (s->AtrousIterations > kDnMaxIterations) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: AtrousIterations must be at most 8");
+    const uint64_t n = (uint64_t)w * h;
+    // (pointer, bytes per pixel, alignment, written, required)
+    struct Use { const void* p; uint32_t bpp, align; bool written, required; const char* name; };
+    const Use use[8] = {
+        {t->ViewZ, 4, 4, false, true, "ViewZ"}, {t->MotionVector, 12, 4, false, true, "MotionVector"},
+        {t->NormalRoughness, 16, 16, false, true, "NormalRoughness"}, {t->BaseColorMetalness, 16, 16, false, false, "BaseColorMetalness"},
+        {t->InDiffuse, 16, 16, false, true, "InDiffuse"}, {t->InSpecular, 16, 16, false, true, "InSpecular"},
+        {t->OutDiffuse, 16, 16, true, true, "OutDiffuse"}, {t->OutSpecular, 16, 16, true, true, "OutSpecular"},
+    };
+    for (const Use& u : use) {
+        if (!u.p) {
+            if (u.required) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + u.name + " is required");
+            continue;
+        }
+        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
+            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
+    }
+    // an output must not share a byte with any input or the other output (the passes read their neighbours' inputs)
+    for (const Use& a : use) {
+        if (!a.written) continue;
+        for (const Use& b : use) {
+            if (&a == &b || !b.p) continue;
+            const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
+            if (pa < pb + n * b.bpp && pb < pa + n * a.bpp)
+                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + a.name + " overlaps " + b.name);
+        }
+    }
+    PT_HIP(c, hipSetDevice(c->device));
+    bool restart = s->AccumulationMode != 0 || !c->dn_valid || c->dn_mode != s->Denoiser;
+    if (!c->d_dn || c->dn_w != w || c->dn_h != h) {
+        if (c->d_dn) PT_HIP(c, hipStreamSynchronize(c->stream));  // (the previous calls may still read the old buffers)
+        free_dev(c->d_dn);
+        c->dn_valid = false;
+        PT_HIP(c, hipMalloc(&c->d_dn, n * kDnBytesPerPixel));
+        c->dn_w = w;
+        c->dn_h = h;
+        restart = true;
+    }
+    float4* f4 = reinterpret_cast<float4*>(c->d_dn);
+    float4* slots[2][4];
+    for (int k = 0; k < 2; k++)
+        for (int j = 0; j < 4; j++) slots[k][j] = f4 + (uint64_t)(4 * k + j) * n;
+    float4* x = f4 + 8 * n;
+    const uint32_t cur = c->dn_slot ^ 1u, prev = c->dn_slot;
+    DnBuffers b{};
+    b.w = w;
+    b.h = h;
+    b.viewz = static_cast<const float*>(t->ViewZ);
+    b.mv = static_cast<const float*>(t->MotionVector);
+    b.nr = static_cast<const float4*>(t->NormalRoughness);
+    b.in_d = static_cast<const float4*>(t->InDiffuse);
+    b.in_s = static_cast<const float4*>(t->InSpecular);
+    b.out_d = static_cast<float4*>(t->OutDiffuse);
+    b.out_s = static_cast<float4*>(t->OutSpecular);
+    b.prev_sig_d = slots[prev][0]; b.prev_sig_s = slots[prev][1]; b.prev_mom = slots[prev][2]; b.prev_guide = slots[prev][3];
+    b.sig_d = slots[cur][0]; b.sig_s = slots[cur][1]; b.mom = slots[cur][2]; b.guide = slots[cur][3];
+    b.xd[0] = x; b.xs[0] = x + n; b.xd[1] = x + 2 * n; b.xs[1] = x + 3 * n;
+    b.hitd = reinterpret_cast<float*>(x + 4 * n);
+    DnParams P{};
+    P.max_d = s->MaxDiffuseFrames ? s->MaxDiffuseFrames : kDnDefaultFrames;
+    P.max_s = s->MaxSpecularFrames ? s->MaxSpecularFrames : kDnDefaultFrames;
+    P.restart = restart ? 1u : 0u;
+    const uint32_t iterations = s->AtrousIterations ? s->AtrousIterations : kDnDefaultIterations;
+    PT_HIP(c, launch_nrd_denoise(b, s->Denoiser, P, iterations, c->stream));
+    c->dn_slot = cur;
+    c->dn_mode = s->Denoiser;
+    c->dn_valid = true;
     return PT_OK;
 }
 

@@ -18,6 +18,8 @@
  *   pt_render_denoiser       Raytracing::Render with GraphicsSettings.Denoiser != None   Shaders/Raytracing.hlsl:377-414, Source/App.cpp:1140-1146
  *   pt_nrd_composition       PostProcessing::NRDComposition::Process (pack and compose around NRD)   Source/NRDComposition.ixx,
  *                            Shaders/NRDComposition.hlsl, driven by App::ProcessNRD  Source/App.cpp:1549-1642
+ *   pt_nrd_denoise           NRD::NewFrame / Tag / SetConstants / Denoise (a stand-in for NRD, spec S15)   Source/NRD.ixx:88-140,
+ *                            Source/App.cpp:1584-1638
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -303,6 +305,27 @@ typedef struct PtNrdCompositionTextures {   /* DEVICE pointers (NRDComposition::
     void *Radiance;                         /* float4  (pt_render_denoiser out): compose */
 } PtNrdCompositionTextures;
 PtStatus pt_nrd_composition(PtContext *ctx, const PtNrdCompositionConstants *constants, const PtNrdCompositionTextures *textures);
+
+/* Row N9 -- the NRD stand-in (NRD::Denoise as App::ProcessNRD drives it, Source/NRD.ixx:88-140, Source/App.cpp:1584-1638; DESIGN.md
+ * spec S15): a ReLAX-style denoiser of the SVGF family -- temporal accumulation reprojected with the motion vectors, a variance
+ * estimate from luminance moments, an edge-stopping a-trous filter -- from the packed In buffers to the Out buffers compose reads.
+ * On the context's stream (asynchronous), ordered like pt_nrd_composition: after the G-buffer and denoiser frames already queued,
+ * before whatever the caller queues there next; it adds nothing to pt_get_totals.  A pixel whose ViewZ is not finite (a miss) is
+ * never written.  The context owns the history (accumulated signal, moments and length per lobe, previous depth and normal),
+ * allocated on first use and freed by pt_destroy; the first call, and a call whose RenderSize or Denoiser differs from the previous
+ * one, acts as CLEAR_AND_RESTART.
+ * PT_ERR_INVALID_ARG: a null argument; Denoiser not 2 or 3; AccumulationMode above 2; a RenderSize of 0 or > 16384; AtrousIterations
+ * above 8; a required buffer missing (all but BaseColorMetalness); a float4 buffer not 16-byte aligned or a float / float3 one not
+ * 4-byte aligned; an output overlapping an input or the other output. */
+typedef struct PtNrdDenoiseTextures {   /* DEVICE pointers; the reference's nrd::ResourceType tags */
+    const void *ViewZ;                  /* IN_VIEWZ: G-buffer LinearDepth, float */
+    const void *MotionVector;           /* IN_MV: G-buffer MotionVector, float3 (previous - current, pixels; .z linear depth) */
+    const void *NormalRoughness;        /* IN_NORMAL_ROUGHNESS: float4 */
+    const void *BaseColorMetalness;     /* IN_BASECOLOR_METALNESS: float4, may be NULL (accepted, not read by S15) */
+    const void *InDiffuse, *InSpecular; /* IN_DIFF / IN_SPEC_RADIANCE_HITDIST: float4, packed by pt_nrd_composition */
+    void *OutDiffuse, *OutSpecular;     /* OUT_DIFF / OUT_SPEC_RADIANCE_HITDIST: float4, what compose reads */
+} PtNrdDenoiseTextures;
+PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, const PtNrdDenoiseTextures *textures);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

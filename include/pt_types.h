@@ -8,6 +8,7 @@
  *   PtSceneData        == SceneData           Source/CommonShaderData.ixx:15-20 (== Shaders/Common.hlsli:7-13), 80 B payload
  *   PtGraphicsSettings == _GraphicsSettings   Source/Raytracing.ixx:151-166 (== Shaders/Raytracing.hlsl:21-39), 80 B
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
+ *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
  * geosphere mesh (Source/Scene.ixx:188-203: scale = 2*radius, z flipped): the
@@ -159,6 +160,18 @@ typedef struct PtNrdCompositionConstants {
     float ReBLURHitDistance[4];   /* 16: hit distance normalisation {A, B, C, D}, read by ReBLUR pack only */
 } PtNrdCompositionConstants;
 
+/* Row N9 (pt_nrd_denoise, the NRD stand-in of DESIGN.md spec S15): what App::ProcessNRD hands NRD through nrd::CommonSettings
+ * (rectSize, frameIndex, accumulationMode) and the denoiser settings (history lengths), plus the a-trous depth of the stand-in. */
+typedef struct PtNrdDenoiseSettings {
+    uint32_t RenderSize[2];       /*  0 */
+    uint32_t Denoiser;            /*  8: 2 NRDReBLUR, 3 NRDReLAX: the encoding of the In / Out buffers */
+    uint32_t AccumulationMode;    /* 12: nrd::AccumulationMode: 0 CONTINUE, 1 RESTART, 2 CLEAR_AND_RESTART */
+    uint32_t FrameIndex;          /* 16: accepted, not read by S15 */
+    uint32_t MaxDiffuseFrames;    /* 20: 0 -> 30 */
+    uint32_t MaxSpecularFrames;   /* 24: 0 -> 30 */
+    uint32_t AtrousIterations;    /* 28: 0 -> 5, at most 8 */
+} PtNrdDenoiseSettings;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -179,6 +192,8 @@ static_assert(sizeof(PtTextureMapInfo) == 16 && sizeof(PtObjectTextures) == 112,
 static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositionConstants, Pack) == 8
               && offsetof(PtNrdCompositionConstants, Denoiser) == 12 && offsetof(PtNrdCompositionConstants, ReBLURHitDistance) == 16,
               "NRDComposition::Constants layout");
+static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
+              && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -188,6 +203,8 @@ _Static_assert(sizeof(PtGraphicsSettings) == 80, "PtGraphicsSettings layout");
 _Static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositionConstants, Pack) == 8
                && offsetof(PtNrdCompositionConstants, Denoiser) == 12 && offsetof(PtNrdCompositionConstants, ReBLURHitDistance) == 16,
                "NRDComposition::Constants layout");
+_Static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
+               && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Render the demo scene on the GPU and write a PNG through the product's own display path: N frames of the path tracer
 with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom] -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
-R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: --frames frames of a resting camera through it with the
+NRD stand-in, row N9).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX]"""
 import argparse
 import os
 import sys
@@ -60,6 +61,9 @@ def main():
     ap.add_argument("--nrd", default=None, choices=["ReBLUR", "ReLAX"],
                     help="one frame through the reference's NRD path with the identity for NRD (row N8): pt_render_gbuffer -> "
                          "pt_render_denoiser -> pack -> copy -> compose, then the tone map (no accumulation)")
+    ap.add_argument("--nrd-denoise", default=None, choices=["ReBLUR", "ReLAX"],
+                    help="--frames frames of a resting camera through the NRD path with pt_nrd_denoise for NRD (row N9): pt_render_gbuffer "
+                         "-> pt_render_denoiser -> pack -> denoise -> compose; the last frame, tone mapped")
     args = ap.parse_args()
     from PIL import Image
 
@@ -103,6 +107,23 @@ def main():
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
+    if args.nrd_denoise:
+        mode = t.DENOISER_NRD_REBLUR if args.nrd_denoise == "ReBLUR" else t.DENOISER_NRD_RELAX
+        r.set_camera(host.camera(w, h, jitter=False))
+        den = r.nrd_denoiser(mode)
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            r.set_constants(gs)
+            x = r.nrd_chain(mode, denoise=den)
+        composed = torch.from_numpy(x["Radiance"].reshape(n, 4)).cuda()
+        torch.cuda.synchronize()
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(composed.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"NRD {args.nrd_denoise} (pt_nrd_denoise, {args.frames} frames) {w}x{h} -> {args.out}")
+        r.close()
+        return
     if args.nrd:
         mode = t.DENOISER_NRD_REBLUR if args.nrd == "ReBLUR" else t.DENOISER_NRD_RELAX
         r.set_camera(host.camera(w, h, jitter_index=0, jitter_count=max(args.frames, 8)))
