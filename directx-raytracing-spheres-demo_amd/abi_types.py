@@ -102,6 +102,11 @@ class PtNrdDenoiseTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NRD_DENOISE_TEXTURES]
 
 
+# pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
+class PtDirectLighting(C.Structure):
+    _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]
+
+
 class PtTextureMapInfo(C.Structure):
     _fields_ = [("Descriptor", C.c_uint32), ("TextureCoordinateIndex", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 

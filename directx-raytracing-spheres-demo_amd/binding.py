@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
-                        PtCamera, PtConfig, PtDenoiserOutputs, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures,
+                        PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtSceneData, PtStats)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -18,7 +18,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_nrd_composition", "pt_nrd_denoise", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -92,6 +92,8 @@ class HipLib:
         lib.pt_render_gbuffer.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBuffer), vp, vp]
         lib.pt_render_denoiser.restype = C.c_int
         lib.pt_render_denoiser.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtDenoiserOutputs), C.POINTER(PtStats)]
+        lib.pt_render_with_di.restype = C.c_int
+        lib.pt_render_with_di.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtDirectLighting), C.POINTER(PtDenoiserOutputs), C.POINTER(PtStats)]
         lib.pt_nrd_composition.restype = C.c_int
         lib.pt_nrd_composition.argtypes = [vp, C.POINTER(PtNrdCompositionConstants), C.POINTER(PtNrdCompositionTextures)]
         lib.pt_nrd_denoise.restype = C.c_int
@@ -400,6 +402,43 @@ class Renderer:
         torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
         self.render_denoiser_device(mode, out.data_ptr(), {name: b.data_ptr() for name, b in bufs.items()}, rect)
         self.synchronize()
+        return out.cpu().numpy(), {name: b.cpu().numpy() for name, b in bufs.items()}
+
+    def render_with_di_device(self, out_ptr, diffuse_ptr, specular_ptr, rect=None, mode=0, buffers=None, want_stats=False):
+        """A frame whose direct illumination is supplied (pt_render_with_di): DI = Diffuse.rgb + Specular.rgb of the device float4 buffers (one per
+        pixel of the rect) in place of row N4's estimate.  mode 0 = Denoiser::None (pt_render); else abi_types.DENOISER_* with `buffers` as
+        for render_denoiser_device.  Asynchronous unless want_stats."""
+        r = PtRect(*rect) if rect is not None else None
+        di = PtDirectLighting(Diffuse=C.c_void_p(int(diffuse_ptr)), Specular=C.c_void_p(int(specular_ptr)))
+        o = PtDenoiserOutputs(Denoiser=mode, **{name: C.c_void_p(int(ptr)) for name, ptr in (buffers or {}).items() if ptr}) if mode else None
+        stats = PtStats()
+        self._check(self._lib.pt_render_with_di(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr), 1, C.byref(di),
+                                                C.byref(o) if o is not None else None, C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_with_di(self, diffuse, specular, rect=None, mode=0, fill=float("nan"), device=None, alias=False):
+        """render_with_di_device with the DI given as numpy float32 (h, w, 4) arrays (or torch CUDA tensors), into torch buffers filled with
+        `fill` -> out (h, w, 4) numpy, or (out, {output name: numpy}) for a denoiser mode.  alias (NRD modes): the DI is placed in the
+        frame's own Diffuse / Specular outputs, as the reference uses them.  Synchronous."""
+        import torch
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+
+        def on_device(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+            return t.to(dev).reshape(h, w, 4).contiguous().clone()
+        dd, ds = on_device(diffuse), on_device(specular)
+        out = torch.from_numpy(np.full((h, w, 4), fill, dtype=np.float32)).to(dev)
+        bufs = {name: torch.from_numpy(np.full((h, w, width), fill, dtype=np.float32)).to(dev) for name, width in DENOISER_OUTPUTS.get(mode, ())}
+        if alias and mode in (2, 3):
+            bufs = {"Diffuse": dd, "Specular": ds}
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        self.render_with_di_device(out.data_ptr(), dd.data_ptr(), ds.data_ptr(), rect, mode, {name: b.data_ptr() for name, b in bufs.items()})
+        self.synchronize()
+        if not mode:
+            return out.cpu().numpy()
         return out.cpu().numpy(), {name: b.cpu().numpy() for name, b in bufs.items()}
 
     def nrd_composition_device(self, mode, pack, width, height, buffers, hit_distance=NRD_REBLUR_HIT_DISTANCE):

@@ -90,6 +90,7 @@ struct Lane {
     bool upload_pending = false;  // h_stage holds spheres that have not been copied to d_sph yet (pt_update_spheres of a small scene: pt_refit_accel's kernel reads them)
     const void* last_out = nullptr;   // output buffer of the lane's latest frame (render_common: repeated buffers inside the window)
     const void* last_dn[3] = {};      // ... and its denoiser buffers (Diffuse, Specular, SpecularHitDistance; null for other frames)
+    const void* last_di[2] = {};      // ... and the DI buffers it read (pt_render_with_di: Diffuse, Specular; null for other frames)
     // object rotations (textured scenes): the lane's own copy, refreshed from PtContext::h_rot when its generation is behind
     float4* d_rot = nullptr;
     float4* h_rot_stage = nullptr;    // pinned
@@ -1006,9 +1007,15 @@ static PtStatus check_environment(PtContext* c)
 // S = PT_TAIL_AFTER for spp == 1; with spp > 1 (sample regeneration keeps the queue full) the host polls the queue
 // size after every pass and switches to the looping kernel when it drops below PT_TAIL_THRESHOLD rays.
 // dn (row N7, pt_render_denoiser): the denoiser outputs of the frame (mode, caller buffers); null = an ordinary frame
-PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, float4* out, PtStats* stats, const DenoiseOut* dn = nullptr)
+// ext (pt_render_with_di): the frame's direct illumination, supplied by the caller; null = the frame's own (row N4), if any
+struct SuppliedDI {
+    const float4* diffuse;
+    const float4* specular;
+};
+PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, float4* out, PtStats* stats, const DenoiseOut* dn = nullptr,
+                       const SuppliedDI* ext = nullptr)
 {
-    const RoctxRange range(c, dn ? "pt_render_denoiser" : (pm.mode == 0 ? "pt_render" : "pt_render_tiles"));
+    const RoctxRange range(c, ext ? "pt_render_with_di" : (dn ? "pt_render_denoiser" : (pm.mode == 0 ? "pt_render" : "pt_render_tiles")));
     const uint32_t bounces = c->gs.Bounces, spp = c->gs.SamplesPerPixel;
     if (const PtStatus st = check_environment(c); st != PT_OK) return st;
     const size_t max_iters = (size_t)spp * bounces + 1;  // passes if everything ran as wavefront
@@ -1028,7 +1035,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         PT_HIP(c, flush_all_counters(L));
         PT_HIP(c, hipStreamSynchronize(L.stream));
     }
-    const bool di = c->gs.IsDIEnabled && c->n_lights > 0;
+    const bool di = ext || (c->gs.IsDIEnabled && c->n_lights > 0);
     // Is the caller waiting for each frame (App::Tick -> Render -> WaitForGPU) or keeping several in flight?  Asked of the streams before this
     // frame queues anything: all lanes drained = one frame at a time, and the frame is scheduled for latency (below: the fused form).
     // (A pt_render_gbuffer call for this very frame has queued work on its lane: that lane counts as idle if every lane was when that call
@@ -1102,18 +1109,26 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         // everything the caller has queued so far, which includes the wait for that earlier frame and whatever consumed it.
         // (Costs the overlap of the frames, never correctness.)
         // (a denoiser frame's Diffuse / Specular / SpecularHitDistance are held to the same rule as `out`)
+        // (and so are the buffers a pt_render_with_di frame READS as its DI: a later frame on another lane that writes one of them waits,
+        // so it cannot overwrite them before that frame's gather has read them)
         const void* mine[4] = { out, dn ? dn->diffuse : nullptr, dn ? dn->specular : nullptr, dn ? dn->spec_hit_dist : nullptr };
         bool reused = false;
         for (uint32_t i = 0; i < c->n_lanes && !reused; i++) {
             if (&c->lanes[i] == &L) continue;
             const Lane& o = c->lanes[i];
-            const void* theirs[4] = { o.last_out, o.last_dn[0], o.last_dn[1], o.last_dn[2] };
+            const void* theirs[6] = { o.last_out, o.last_dn[0], o.last_dn[1], o.last_dn[2], o.last_di[0], o.last_di[1] };
             for (int a = 0; a < 4 && !reused; a++)
-                for (int b = 0; b < 4 && !reused; b++) reused = mine[a] && mine[a] == theirs[b];
+                for (int b = 0; b < 6 && !reused; b++) reused = mine[a] && mine[a] == theirs[b];
         }
+        // A supplied DI is an input that may have been written on the caller's stream right before this call, after the marker above:
+        // the frame waits for everything the caller has queued so far, which includes whatever wrote it.  (With frames in flight this
+        // costs their overlap; a producer queued on this frame's own lane would be ordered without it.)
+        if (ext) reused = true;
         if (reused) PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_in[c->calls % nl], 0));
         L.last_out = out;
         for (int a = 0; a < 3; a++) L.last_dn[a] = mine[a + 1];
+        L.last_di[0] = ext ? ext->diffuse : nullptr;
+        L.last_di[1] = ext ? ext->specular : nullptr;
         c->calls++;
     }
 
@@ -1128,6 +1143,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         scr.dn.di_s = L.scratch.dn.di_s;
     }
     FrameParams fp = make_frame_params(c);
+    if (ext) fp.di_enabled = kDiExternal;  // (whatever IsDIEnabled says: the caller has made the estimate)
     fp.beam_lists = beam_lists;
     fp.beam_job = beam_job;
     fp.refl_lists = refl_lists;
@@ -1205,7 +1221,11 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     // kernels that were launched: the completion event is recorded and waited for either way (the counter parity stays
     // flipped -- the kernels that did run used this parity's counters, and the lane's next frame folds them).
     auto submit = [&]() -> PtStatus {
-        if (fp.di_enabled && split) {
+        if (ext) {
+            // pt_render_with_di: the caller's estimate into the per-slot scratch the passes read (before the first one: the buffers may be the frame's
+            // own denoiser outputs, which it overwrites)
+            PT_HIP(c, bracket(1, [&] { return launch_di_gather(pm, ext->diffuse, ext->specular, L.scratch.di, scr.dn.mode > 1 ? scr.dn.di_s : nullptr, L.stream); }));
+        } else if (fp.di_enabled && split) {
             // row N4, split schedule: the direct-illumination estimate of every primary surface, before the shade passes read it
             // (the fused schedule's primary pass makes the estimate itself, at the first shading of the primary surface)
             const uint32_t di_grid = grid_for(pm.n_slots, trav_threads, trav_cap_wide);
@@ -1758,9 +1778,10 @@ static PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who
     return PT_OK;
 }
 
-// pt_render and pt_render_denoiser: a frame of the rect into `out` (a host buffer is staged through the context's device buffer and
-// copied back); dn = the denoiser outputs of a pt_render_denoiser frame, null for pt_render
-static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats, const DenoiseOut* dn, const char* who)
+// pt_render, pt_render_denoiser and pt_render_with_di: a frame of the rect into `out` (a host buffer is staged through the context's device
+// buffer and copied back); dn = the denoiser outputs of a denoiser frame, null for Denoiser::None; di = the supplied DI (pt_render_with_di)
+static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats, const DenoiseOut* dn, const char* who,
+                            const PtDirectLighting* di = nullptr)
 {
     if (!out) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null output");
     PtStatus st = validate_frame(c);
@@ -1780,7 +1801,12 @@ static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out
         }
         dev_out = c->d_out;
     }
-    st = render_common(c, pm, (uint64_t)r.w * r.h, dev_out, stats, dn);
+    SuppliedDI ext{};
+    if (di) {
+        ext.diffuse = static_cast<const float4*>(di->Diffuse);
+        ext.specular = static_cast<const float4*>(di->Specular);
+    }
+    st = render_common(c, pm, (uint64_t)r.w * r.h, dev_out, stats, dn, di ? &ext : nullptr);
     if (st != PT_OK) return st;
     if (!out_is_device) {
         PT_HIP(c, hipMemcpyAsync(out, dev_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
@@ -1795,27 +1821,51 @@ PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_devic
     return render_rect(c, rect, out, out_is_device, stats, nullptr, "pt_render");
 }
 
+// the DenoiseOut of a PtDenoiserOutputs (pt_render_denoiser, pt_render_with_di), validated
+static PtStatus denoise_out(PtContext* c, const PtDenoiserOutputs* outputs, const char* who, DenoiseOut& dn)
+{
+    const uint32_t mode = outputs->Denoiser;
+    if (mode < 1 || mode > 3) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": Denoiser must be 1 (DLSSRayReconstruction), 2 (NRDReBLUR) or 3 (NRDReLAX)");
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
+    dn = DenoiseOut{};
+    dn.mode = mode;
+    if (mode == 1) {
+        if (!outputs->SpecularHitDistance || misaligned(outputs->SpecularHitDistance, 4))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": DLSSRayReconstruction needs a 4-byte aligned SpecularHitDistance");
+        dn.spec_hit_dist = static_cast<float*>(outputs->SpecularHitDistance);
+    } else {
+        if (!outputs->Diffuse || !outputs->Specular || misaligned(outputs->Diffuse, 16) || misaligned(outputs->Specular, 16))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": the NRD modes need 16-byte aligned Diffuse and Specular");
+        dn.diffuse = static_cast<float4*>(outputs->Diffuse);
+        dn.specular = static_cast<float4*>(outputs->Specular);
+    }
+    return PT_OK;
+}
+
 // Row N7 -- a frame that writes the denoiser outputs of its mode (DESIGN.md spec S13): render_common with the kDn kernel instances
 PtStatus pt_render_denoiser(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtDenoiserOutputs* outputs, PtStats* stats)
 {
     if (!c) return PT_ERR_INVALID_ARG;
     if (!outputs) return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: null outputs");
-    const uint32_t mode = outputs->Denoiser;
-    if (mode < 1 || mode > 3) return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: Denoiser must be 1 (DLSSRayReconstruction), 2 (NRDReBLUR) or 3 (NRDReLAX)");
-    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
     DenoiseOut dn{};
-    dn.mode = mode;
-    if (mode == 1) {
-        if (!outputs->SpecularHitDistance || misaligned(outputs->SpecularHitDistance, 4))
-            return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: DLSSRayReconstruction needs a 4-byte aligned SpecularHitDistance");
-        dn.spec_hit_dist = static_cast<float*>(outputs->SpecularHitDistance);
-    } else {
-        if (!outputs->Diffuse || !outputs->Specular || misaligned(outputs->Diffuse, 16) || misaligned(outputs->Specular, 16))
-            return fail(c, PT_ERR_INVALID_ARG, "pt_render_denoiser: the NRD modes need 16-byte aligned Diffuse and Specular");
-        dn.diffuse = static_cast<float4*>(outputs->Diffuse);
-        dn.specular = static_cast<float4*>(outputs->Specular);
-    }
+    if (const PtStatus st = denoise_out(c, outputs, "pt_render_denoiser", dn); st != PT_OK) return st;
     return render_rect(c, rect, out, out_is_device, stats, &dn, "pt_render_denoiser");
+}
+
+// A frame (pt_render, or pt_render_denoiser with outputs) whose direct illumination the caller supplies: the kernels of the
+// frame without an estimate of their own (kDI = false) read it from the scratch a gather fills first
+PtStatus pt_render_with_di(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtDirectLighting* di, const PtDenoiserOutputs* outputs,
+                           PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!di || !di->Diffuse || !di->Specular) return fail(c, PT_ERR_INVALID_ARG, "pt_render_with_di: null direct lighting buffer");
+    if ((reinterpret_cast<uintptr_t>(di->Diffuse) | reinterpret_cast<uintptr_t>(di->Specular)) & 15u)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_render_with_di: the direct lighting buffers must be 16-byte aligned");
+    DenoiseOut dn{};
+    if (outputs) {
+        if (const PtStatus st = denoise_out(c, outputs, "pt_render_with_di", dn); st != PT_OK) return st;
+    }
+    return render_rect(c, rect, out, out_is_device, stats, outputs ? &dn : nullptr, "pt_render_with_di", di);
 }
 
 // Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12)
@@ -1884,6 +1934,7 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
                     shared = ptrs[k] == c->lanes[i].last_out;
                     for (uint32_t j = 0; j < 13 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_gb[j];
                     for (uint32_t j = 0; j < 3 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_dn[j];
+                    for (uint32_t j = 0; j < 2 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_di[j];
                 }
         }
         if (shared) {

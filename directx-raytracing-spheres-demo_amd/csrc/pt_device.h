@@ -162,11 +162,15 @@ struct FrameParams {
     uint32_t frame_index, bounces, spp, rr_enabled;
     float throughput_threshold;
     float inv_spp;        // 1 / (float)spp
-    uint32_t di_enabled;  // IsDIEnabled and the scene has emitters: Scratch::di holds this frame's estimate
+    uint32_t di_enabled;  // IsDIEnabled and the scene has emitters: Scratch::di holds this frame's estimate; kDiExternal: the caller supplied it
     const uint32_t* beam_lists;  // primary beams: one 16-dword record per 64 slots {count, sphere ids}; null = every primary ray traverses
     BeamJob beam_job;
     const uint32_t* refl_lists;  // reflection beams: one kReflRecord-dword region record per 64 slots (pt_region.h); null = every bounce-1 ray traverses
 };
+
+// FrameParams::di_enabled of a pt_render_with_di frame: the estimate comes from the caller's buffers (gathered into Scratch::di
+// before the first pass), so no pass makes one; the kernels treat it as any non-zero value (DI on), only the host's kernel choice differs
+constexpr uint32_t kDiExternal = 2u;
 
 // Per-frame device counters, double buffered by frame parity so that the first kernel of a frame can append to this
 // frame's counters while its block 0 folds the PREVIOUS frame's into the running totals and zeroes them for the next.

@@ -48,6 +48,9 @@ hipError_t launch_leaf_ids(const uint32_t* sorted_id, const uint32_t* alpha_clas
 // di_s non-null (row N7, NRD modes): di receives the diffuse half of the estimate and di_s the specular half
 hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, float4* di, uint2* primary_hit, unsigned long long* ray_counter, uint32_t grid,
                      hipStream_t stream, float4* di_s = nullptr);
+// pt_render_with_di: per slot of pm, di = dd + ds of its pixel (dd, ds indexed like `out`); di_s non-null (NRD modes): di = dd,
+// di_s = ds.  .w = 0.
+hipError_t launch_di_gather(const PixelMap& pm, const float4* dd, const float4* ds, float4* di, float4* di_s, hipStream_t stream);
 hipError_t launch_tonemap(const float4* hdr, uint32_t* out, uint32_t n, const PtToneMapParams& p, hipStream_t stream);
 hipError_t launch_accumulate(float4* accum, const float4* rad, uint32_t n, uint32_t frames_accumulated, hipStream_t stream);
 // bloom (row N5, pt_bloom.hip): the 9 chain steps and the merge, 10 launches on `stream`.  chain: bloom_chain(width,

@@ -344,6 +344,25 @@ __global__ __launch_bounds__(kTraverseThreads) void di_kernel(SceneView sv, Pixe
     block_atomic_add(ray_counter, my_rays);
 }
 
+// ------------------------------------------------------------------------------------------------ supplied direct illumination
+// pt_render_with_di: the caller's per-pixel DI (Diffuse, Specular: float4, indexed like `out`) -> the per-slot scratch the bounce kernels
+// read when fp.di_enabled is set and they make no estimate themselves: di = Diffuse.rgb + Specular.rgb (Raytracing.hlsl:160), or, with
+// di_s (NRD modes), the two halves apart.  Invalid slots are dead paths and are skipped.
+__global__ void di_gather_kernel(PixelMap pm, const float4* __restrict__ dd, const float4* __restrict__ ds, float4* __restrict__ di, float4* __restrict__ di_s)
+{
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
+        const PixelRef pr = slot_to_pixel(pm, slot);
+        if (!pr.valid) continue;
+        const float4 a = dd[pr.out_index], b = ds[pr.out_index];
+        if (di_s) {
+            di[slot] = make_float4(a.x, a.y, a.z, 0.0f);
+            di_s[slot] = make_float4(b.x, b.y, b.z, 0.0f);
+        } else {
+            di[slot] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, 0.0f);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ test hooks
 template <bool kLds, typename StackT>
 __global__ __launch_bounds__(kTraverseThreads) void trace_kernel(SceneView sv, const float* __restrict__ o, const float* __restrict__ d,
@@ -674,6 +693,13 @@ hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams&
 #undef PT_DI
 #undef PT_DI2
 #undef PT_DI3
+    return hipGetLastError();
+}
+
+hipError_t launch_di_gather(const PixelMap& pm, const float4* dd, const float4* ds, float4* di, float4* di_s, hipStream_t stream)
+{
+    const uint32_t blocks = (pm.n_slots + 255u) / 256u;
+    hipLaunchKernelGGL(di_gather_kernel, dim3(blocks < 8192u ? (blocks ? blocks : 1u) : 8192u), dim3(256), 0, stream, pm, dd, ds, di, di_s);
     return hipGetLastError();
 }
 

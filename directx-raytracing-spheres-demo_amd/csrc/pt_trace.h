@@ -1323,9 +1323,9 @@ hipError_t launch_bounce_for(const SceneView& sv, const PixelMap& pm, const Fram
 /* row N7: a denoiser frame (scratch.dn.mode != 0) runs the kDn instance of the same schedule */
 #define PT_BOUNCE8(P, LP, M, X, I, F, D)                                                                                   \
     do { if (scratch.dn.mode) PT_BOUNCE9(P, LP, M, X, I, F, D, true); else PT_BOUNCE9(P, LP, M, X, I, F, D, false); } while (0)
-/* the direct-illumination estimate (row N4) is made by the compacting primary pass */
+/* the direct-illumination estimate (row N4) is made by the compacting primary pass, unless the caller supplied it (pt_render_with_di) */
 #define PT_BOUNCE7(P, LP, M, X, I, F)                                                                                      \
-    do { if (fp.di_enabled && P && !LP) PT_BOUNCE8(P, LP, M, X, I, F, (P && !LP)); else PT_BOUNCE8(P, LP, M, X, I, F, false); } while (0)
+    do { if (fp.di_enabled && fp.di_enabled != kDiExternal && P && !LP) PT_BOUNCE8(P, LP, M, X, I, F, (P && !LP)); else PT_BOUNCE8(P, LP, M, X, I, F, false); } while (0)
 /* the fused form (the primary pass finishes its own segments) exists only for the compacting primary pass */
 #define PT_BOUNCE6(P, LP, M, X, I)                                                                                         \
     do { if (fc.fuse_loop && P && !LP) PT_BOUNCE7(P, LP, M, X, I, (P && !LP)); else PT_BOUNCE7(P, LP, M, X, I, false); } while (0)

@@ -144,6 +144,38 @@ struct Raytracing {
         return stats;
     }
 
+    // The textures the ReSTIR-DI passes write for Raytracing.hlsl to read as DI (DIFinalShading.hlsl:95-104): DEVICE float4 buffers of
+    // W*H texels, 16-byte aligned.  They may be the frame's own DenoiserBuffers, as the reference uses them.
+    struct DirectLighting {
+        const void* Diffuse = nullptr;
+        const void* Specular = nullptr;
+    };
+
+    // Raytracing::Render with IsDIEnabled = isReSTIRDIEnabled (App.cpp:1262; pt_render_with_di): DI = Diffuse.rgb + Specular.rgb
+    // in place of the library's own estimate.  buffers: the denoiser outputs when GraphicsSettings.Denoiser names one (required then).
+    PtStats Render(std::vector<Float4>& radiance, const DirectLighting& di, DenoiserBuffers* buffers = nullptr)
+    {
+        PtGraphicsSettings constants = m_graphicsSettings;
+        constants.Denoiser = 0;
+        ThrowIfFailed(pt_set_constants(m_ctx, &constants), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtDirectLighting lighting{};
+        lighting.Diffuse = di.Diffuse;
+        lighting.Specular = di.Specular;
+        PtDenoiserOutputs outputs{};
+        if (m_graphicsSettings.Denoiser != 0) {
+            if (!buffers) throw std::invalid_argument("Raytracing::Render: GraphicsSettings.Denoiser needs its DenoiserBuffers");
+            outputs.Denoiser = m_graphicsSettings.Denoiser;
+            outputs.Diffuse = buffers->Diffuse;
+            outputs.Specular = buffers->Specular;
+            outputs.SpecularHitDistance = buffers->SpecularHitDistance;
+        }
+        PtStats stats{};
+        ThrowIfFailed(pt_render_with_di(m_ctx, nullptr, radiance.data(), 0, &lighting, m_graphicsSettings.Denoiser != 0 ? &outputs : nullptr, &stats),
+                      m_ctx, "pt_render_with_di");
+        return stats;
+    }
+
 private:
     PtContext* m_ctx;
     PtGraphicsSettings m_graphicsSettings{};

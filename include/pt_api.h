@@ -18,6 +18,7 @@
  *   pt_render_denoiser       Raytracing::Render with GraphicsSettings.Denoiser != None   Shaders/Raytracing.hlsl:377-414, Source/App.cpp:1140-1146
  *   pt_nrd_composition       PostProcessing::NRDComposition::Process (pack and compose around NRD)   Source/NRDComposition.ixx,
  *                            Shaders/NRDComposition.hlsl, driven by App::ProcessNRD  Source/App.cpp:1549-1642
+ *   pt_render_with_di        Raytracing::Render with IsDIEnabled = isReSTIRDIEnabled   Source/App.cpp:1262, Shaders/Raytracing.hlsl:150-163
  *   pt_nrd_denoise           NRD::NewFrame / Tag / SetConstants / Denoise (a stand-in for NRD, spec S15)   Source/NRD.ixx:88-140,
  *                            Source/App.cpp:1584-1638
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
@@ -280,6 +281,25 @@ typedef struct PtDenoiserOutputs {   /* DEVICE pointers, float4 ones 16-byte ali
 } PtDenoiserOutputs;
 PtStatus pt_render_denoiser(PtContext *ctx, const PtRect *rect, void *out, int out_is_device,
                             const PtDenoiserOutputs *outputs, PtStats *stats);
+
+/* A frame whose direct illumination the caller supplies: the reference's frame with IsDIEnabled = isReSTIRDIEnabled
+ * (Source/App.cpp:1262), whose DI the RTXDI passes make (this library has no such pass yet: the caller brings its own).  In every other respect an ordinary frame under the contract of
+ * pt_render (outputs == NULL: Denoiser::None) or of pt_render_denoiser (outputs: its mode and buffers), whatever
+ * PtGraphicsSettings.IsDIEnabled says.  Only the source of DI changes: per pixel of the rect, DI = Diffuse.rgb + Specular.rgb
+ * (Raytracing.hlsl:160; .w is not read), in place of row N4's estimate, with N4's two gates kept: DI is added only where the primary ray
+ * hit, and the emission a first bounce reaches through the transmission lobe is kept (elsewhere it is dropped, as DI covers it).  The
+ * NRD modes take the two halves apart (Diffuse into the diffuse output, Specular into the specular one).
+ * The buffers are read before the frame's first pass, so they may be the frame's own denoiser outputs (the reference uses them in place
+ * that way).  Written on another stream, they must be complete before the call; the frame waits for everything queued on the
+ * context's stream before it (with frames in flight: at the cost of their overlap).  They are held to the rotation rule of pt_render's
+ * buffers as inputs: a later frame in flight whose out or denoiser buffer is one of them waits until this frame has read them.  The
+ * tile entry points render without supplied DI.
+ * PT_ERR_INVALID_ARG: a null DI buffer, one not 16-byte aligned, and whatever pt_render / pt_render_denoiser reject. */
+typedef struct PtDirectLighting {   /* DEVICE pointers, float4 per pixel of the rect (row-major inside it), 16-byte aligned */
+    const void *Diffuse, *Specular; /* the textures DIFinalShading writes (DIFinalShading.hlsl:95-104) */
+} PtDirectLighting;
+PtStatus pt_render_with_di(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtDirectLighting *di,
+                           const PtDenoiserOutputs *outputs, PtStats *stats);
 
 /* Row N8 -- the NRD composition pass (PostProcessing::NRDComposition, Shaders/NRDComposition.hlsl; DESIGN.md spec S14), on the
  * context's stream (asynchronous): ordered after the G-buffer and the denoiser frames already queued, before whatever the caller
