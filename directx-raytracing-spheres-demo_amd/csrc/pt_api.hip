@@ -19,6 +19,7 @@
 
 #include "../../include/pt_api.h"
 #include "pt_kernels.h"
+#include "pt_beam_cache.h"
 #include "pt_bloom.h"
 #include "pt_nrd.h"
 #include "pt_denoise.h"
@@ -710,53 +711,15 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
     std::memcpy(basis, c->cam.RightDirection, 12); std::memcpy(basis + 3, c->cam.UpDirection, 12); std::memcpy(basis + 6, c->cam.ForwardDirection, 12);
     bool finite_pose = std::isfinite(pos[0]) && std::isfinite(pos[1]) && std::isfinite(pos[2]) && len_r > 0.0 && len_u > 0.0 && len_f > 0.0;
     for (float x : basis) finite_pose = finite_pose && std::isfinite(x);
-    auto dist = [](const float* a, const float* b) {
-        const double dx = (double)a[0] - b[0], dy = (double)a[1] - b[1], dz = (double)a[2] - b[2];
-        return std::sqrt(dx * dx + dy * dy + dz * dz);
-    };
-    // The rotation that takes orientation p to orientation q (both with this lens) as a rotation vector (axis * angle): R = Q * P^T over the
-    // normalised axes; angle from the trace, axis from the antisymmetric part.
-    auto rotation_between = [&](const float* p, const float* q, double w[3]) {
-        double R[3][3] = {};
-        for (int k = 0; k < 3; k++) {
-            const double lp = len3(p + 3 * k), lq = len3(q + 3 * k), inv = lp > 0.0 && lq > 0.0 ? 1.0 / (lp * lq) : 0.0;
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) R[i][j] += (double)q[3 * k + i] * (double)p[3 * k + j] * inv;
-        }
-        const double ax[3] = { R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1] };  // 2 sin(angle) * axis
-        const double s2 = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]), c2 = R[0][0] + R[1][1] + R[2][2] - 1.0;  // 2 sin, 2 cos
-        const double angle = std::atan2(s2, c2);
-        for (int i = 0; i < 3; i++) w[i] = s2 > 0.0 ? ax[i] / s2 * angle : 0.0;
-        return angle;  // in [0, pi]; a half turn has no axis here, and nothing below builds lists for one
-    };
-    // How far, in pixels, a ray's crossing of the image can move when the camera turns by `angle` (any axis): a direction moves by at most that
-    // angle, and at an angle a off the view axis a change of direction moves the crossing by at most f / cos^2(a) pixels per radian (f = the focal
-    // length in pixels) -- taken at the image corner, plus the turn itself.
-    const double fx_px = 0.5 * (double)pm.img_w * len_f / len_r, fy_px = 0.5 * (double)pm.img_h * len_f / len_u;  // (equal for square pixels)
-    const double f_px = std::max(fx_px, fy_px);
-    const double corner = std::atan(std::sqrt(len_r * len_r + len_u * len_u) / len_f);  // the image corner's angle off the view axis
-    auto turn_px = [&](double angle) { const double a = std::min(corner + angle, 1.55), cs = std::cos(a); return angle * f_px / (cs * cs) * 1.01; };
-    // ... and when its axes' lengths differ (by rounding: relative differences times the image's half diagonal, with the tangent at the corner)
-    const double half_diag_px = 0.5 * std::sqrt((double)pm.img_w * pm.img_w + (double)pm.img_h * pm.img_h);
-    auto lens_px = [&](const float* p, const float* q) {
-        double worst = 0.0;
-        for (int k = 0; k < 3; k++) { const double lp = len3(p + 3 * k), lq = len3(q + 3 * k); worst = std::max(worst, lp > 0.0 && lq > 0.0 ? std::fabs(lq / lp - 1.0) : 1e30); }
-        const double cs = std::cos(std::min(corner, 1.55));
-        return 2.0 * worst * half_diag_px / (cs * cs) * 1.01;
-    };
+    // The pixel bounds of a turn and of a change of the axes' lengths, and the test of a later pose against lists: pt_beam_cache.h
+    const BeamLens lens = beam_lens(pm.img_w, pm.img_h, len_r, len_u, len_f);
     const uint64_t call = ++B.calls;
-    auto within = [&](const PtContext::BeamLists& b, const float* q_pos, const float* q_basis) {
-        if (b.slack == 0.0f ? std::memcmp(b.pos, q_pos, 12) != 0 : dist(b.pos, q_pos) > (double)b.slack * (1.0 - 1e-4)) return false;
-        if (std::memcmp(b.basis, q_basis, 36) == 0) return true;
-        if (b.margin_px == 0.0f) return false;
-        double w[3];
-        return turn_px(rotation_between(b.basis, q_basis, w)) + lens_px(b.basis, q_basis) <= (double)b.margin_px * (1.0 - 1e-3);
-    };
+    auto within = [&](const PtContext::BeamLists& b, const float* q_pos, const float* q_basis) { return beam_within(lens, b.pos, b.basis, b.slack, b.margin_px, q_pos, q_basis); };
     auto holds = [&](const PtContext::BeamLists& b) { return !b.key.empty() && b.key == key && call >= b.first_call && within(b, pos, basis); };
-    const bool same_view = finite_pose && key == B.last_key && lens_px(B.last_basis, basis) <= 0.02;  // (the pose may differ)
-    const double step = same_view ? dist(pos, B.last_pos) : 0.0;  // the camera's travel since the previous call ...
+    const bool same_view = finite_pose && key == B.last_key && beam_same_lens(lens, B.last_basis, basis);  // (the pose may differ)
+    const double step = same_view ? beam_dist(pos, B.last_pos) : 0.0;  // the camera's travel since the previous call ...
     double turn[3] = { 0.0, 0.0, 0.0 };
-    const double turned = same_view ? rotation_between(B.last_basis, basis, turn) : 0.0;  // ... and its turn
+    const double turned = same_view ? beam_rotation_between(B.last_basis, basis, turn) : 0.0;  // ... and its turn
     const bool rested = same_view && std::memcmp(B.last_pos, pos, 12) == 0 && std::memcmp(B.last_basis, basis, 36) == 0;
     const float prev[3] = { B.last_pos[0], B.last_pos[1], B.last_pos[2] };
     B.last_key = key;
@@ -855,20 +818,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
     const size_t n_blocks = pm.n_slots >> 6;
     if (n_blocks == 0) return PT_OK;
     const double n_build = (double)((n_blocks + max_job_blocks - 1) / max_job_blocks), a = (double)c->n_lanes;
-    auto ahead = [&](double f, float out_pos[3], float out_basis[9]) {
-        for (int i = 0; i < 3; i++) out_pos[i] = (float)((double)pos[i] + f * v[i]);
-        // this frame's axes turned by f times the last turn (Rodrigues), their lengths kept
-        const double ang = f * turned;
-        std::memcpy(out_basis, basis, 36);
-        if (ang > 0.0 && turned > 0.0) {
-            const double k[3] = { turn[0] / turned, turn[1] / turned, turn[2] / turned }, cs = std::cos(ang), sn = std::sin(ang);
-            for (int x = 0; x < 3; x++) {
-                const double p[3] = { basis[3 * x], basis[3 * x + 1], basis[3 * x + 2] };
-                const double kxp[3] = { k[1] * p[2] - k[2] * p[1], k[2] * p[0] - k[0] * p[2], k[0] * p[1] - k[1] * p[0] }, kp = k[0] * p[0] + k[1] * p[1] + k[2] * p[2];
-                for (int i = 0; i < 3; i++) out_basis[3 * x + i] = (float)(p[i] * cs + kxp[i] * sn + k[i] * kp * (1.0 - cs));
-            }
-        }
-    };
+    auto ahead = [&](double f, float out_pos[3], float out_basis[9]) { beam_ahead(pos, v, basis, turn, turned, f, out_pos, out_basis); };
     float then_pos[3], then_basis[9];
     ahead(n_build + a + 1.0, then_pos, then_basis);
     auto covers = [&](const PtContext::BeamLists& b) { return !b.key.empty() && b.key == key && (b.slack > 0.0f || b.margin_px > 0.0f) && within(b, then_pos, then_basis); };
@@ -882,15 +832,12 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
     // The slack widens every pyramid by an absolute distance: at most the smallest radius (wider lists cost little -- 0.3 % of a frame at half
     // that -- but every block overflows in the end); the margin by pixels: at most PT_BEAM_MAX_MARGIN (8).  A faster camera gets lists for
     // fewer frames; one that jumps or spins gets none until it settles.
-    double span = (double)reach;
     const double max_slack = (double)c->min_radius * 0.01 * (double)knob_or(c->knobs.beam_max_slack_pct, 100u), max_margin = (double)knob_or(c->knobs.beam_max_margin, 8u);
-    auto slack_for = [&](double sp) { const double t = n_build + a + 0.5 * sp; return (0.5 * sp + 2.0) * step + 0.75 * acc * t * t; };
-    auto margin_for = [&](double sp) { const double t = n_build + a + 0.5 * sp; return turned > 0.0 || turn_acc > 0.0 ? turn_px((0.5 * sp + 2.0) * turned + 0.75 * turn_acc * t * t) + 0.05 : 0.0; };
-    while (span >= 4.0 && (slack_for(span) > max_slack || margin_for(span) > max_margin)) span -= 2.0;
-    if (!(span >= 4.0)) return PT_OK;
-    const float slack = (float)slack_for(span), margin_px = (float)margin_for(span);
+    const BeamPlan plan = beam_plan(lens, step, acc, turned, turn_acc, n_build, a, (double)reach, max_slack, max_margin);
+    if (!(plan.span >= 4.0)) return PT_OK;
+    const float slack = plan.slack, margin_px = plan.margin_px;
     float mid[3], mid_basis[9];
-    ahead(n_build - 1.0 + a + 0.5 * span, mid, mid_basis);
+    ahead(plan.centre_ahead, mid, mid_basis);
     bool ok = (slack > 0.0f || margin_px > 0.0f) && std::isfinite(slack) && std::isfinite(margin_px);
     for (float x : mid) ok = ok && std::isfinite(x);
     for (float x : mid_basis) ok = ok && std::isfinite(x);
