@@ -34,9 +34,24 @@ struct Beam {
                   // (same orientation): a point x of the pyramid with apex o' has n.(x - o) = n.(x - o') + n.(o' - o) >= -|o' - o|
 };
 
-// 1 / sqrt(x) for a plane's normalisation: the device's approximate instruction (1 ulp); the host build rounds twice (no tighter)
+// 1 / sqrt(x) for a plane's normalisation: the device's approximate instruction (1 ulp); the host build rounds twice (no tighter).
+// The two are different arithmetic: tests/test_leaf_edges.py runs the bounds below with the host value moved one float either way, and
+// tests/test_gpu_leaf_edges.py runs them on planes and decisions computed by the gfx950 build.  What keeps a block's rays inside is the
+// half pixel of slack of beam_corners (>= 2e-4 rad at a 10 degree lens), far above a plane test's rounding: P1 also holds with the 4e-6
+// factor of beam_meets_box set to 0, on either side.  That factor is a second defence, not what the tests depend on.
 #if defined(__HIPCC__)
 PT_BEAM_FN float beam_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+#elif defined(PT_BEAM_RSQ_TEST)
+// Host test builds only (tests/hostshim/leaf_batch_host.cpp; the product never defines it): the host value moved by
+// pt_beam_rsq_test_ulps floats, so that the CPU tests run the bounds below with the device's error class, in both directions.
+extern int pt_beam_rsq_test_ulps;
+PT_BEAM_FN float beam_rsq(float x)
+{
+    float r = 1.0f / sqrtf(x);
+    for (int k = pt_beam_rsq_test_ulps; k > 0; k--) r = nextafterf(r, kInf);
+    for (int k = pt_beam_rsq_test_ulps; k < 0; k++) r = nextafterf(r, -kInf);
+    return r;
+}
 #else
 PT_BEAM_FN float beam_rsq(float x) { return 1.0f / sqrtf(x); }
 #endif

@@ -12,7 +12,8 @@ is exact and one-sided: zero exceptions, no tolerance.
 - P5: the lists beam_plan plans are accepted for every frame of the span they are planned for.
 Leaves: beam_meets_leaf tests the ball around the box centre with the LARGEST half extent as radius (pt_beam.h; the tree builders make every
 leaf box the padded cube around its sphere, pt_lbvh.cpp), so the spheres a rejected leaf is searched for are those inside that ball -- a
-sphere tucked into a cube's corner fits the box but not the ball, and no builder makes one."""
+sphere tucked into a cube's corner fits the box but not the ball, and no builder makes one.
+The device variant of pt_beam.h (beam_rsq is an instruction there) is tested in test_leaf_edges.py (one ulp either way) and test_gpu_leaf_edges.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,24 +1,21 @@
 """CPU: the reflection-beam header (csrc/pt_region.h, compiled as host C++ by tests/hostshim/region_host.cpp) against float64 brute force.
 - the box test is conservative: rays sampled inside a region never pass a box it rejected;
 - the run-time test accepts only rays that lie in the region its list is built for (origin in O, direction within theta of the axis);
-- records built from pyramids over spheres accept the rays that start on the sphere and reflect within the GGX cap."""
+- records built from pyramids over spheres accept the rays that start on the sphere and reflect within the GGX cap.
+The device variant (atan2f, asinf, acosf, cosf of the device library) runs these same test bodies in test_gpu_leaf_edges.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 GGX_CAP = 2e-3  # kReflGgxCap
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("region") / "libregion_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-fPIC", "-shared", "-Wall", "-o", out,
-                    os.path.join(HERE, "hostshim", "region_host.cpp")], check=True)
-    lib = C.CDLL(out)
+def load_shim():
+    """region_host.cpp as __graft_entry__.build_region_shim() compiles it, with its signatures declared"""
+    import __graft_entry__ as g
+
+    lib = C.CDLL(g.build_region_shim())
     f32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
     lib.rg_make.argtypes = [f32p, f32p, f32p, C.c_float, f32p]
     lib.rg_meets_boxes.argtypes = [f32p, C.c_uint32, f32p, u8p]
@@ -28,6 +25,11 @@ def shim(tmp_path_factory):
     lib.rg_lane.argtypes = [f32p, f32p, f32p, C.c_float, C.c_float, C.c_float, f32p, f32p]
     lib.rg_lane.restype = C.c_int
     return lib
+
+
+@pytest.fixture(scope="module")
+def shim():
+    return load_shim()
 
 
 def fp(a):
