@@ -196,6 +196,7 @@ struct FrameCounters {
     uint32_t n_segs;        // == grid size of the primary pass, <= kMaxSegs
     uint32_t seg_cap;       // entries per segment
     uint32_t fuse_loop;     // 1: the primary pass finishes its own segment itself (no separate looping pass is launched)
+    uint32_t coop_walk;     // 1: the 1-spp looping pass (and the fused form's tail) splits each tree walk over the wave's idle lanes (closest_hit_coop)
 };
 
 constexpr uint32_t kMaxSegs = 2048;

@@ -320,6 +320,164 @@ __device__ __forceinline__ void closest_hit_any(const SceneView& sv, const float
     }
 }
 
+// ------------------------------------------------------------------------------------------------ cooperative walk
+// The looping pass of a 1-spp frame runs on nearly empty waves: while a few lanes walk the tree, the others idle, and the wave
+// takes as long as its longest walk.  closest_hit_coop splits each live ray's walk over k = 2, 4 or 8 lanes: helper j of a ray starts at the
+// j-th node of the tree's cut at depth log2 k, the helpers share the nearest hit distance found so far for culling, and their answers are
+// combined by closest_hit's own rule (nearest t, ties -> lowest original id) -- a closest-hit query does not depend on the order of the
+// tests, so the result is closest_hit's bit for bit.
+
+// The cuts of the binary tree at depths 1, 2 and 3: s_cut[k - 2 + j] = start of helper j of k (a child reference, or kTraversalDone where
+// a leaf above the cut has left the slot empty).  One thread builds it, after stage_scene (n >= 2: the root is an internal node).
+constexpr uint32_t kCutSlots = 16;
+__device__ __forceinline__ void build_cut(const float4* __restrict__ nodes, int* s_cut)
+{
+    auto expand = [&](int ref, int& a, int& b) {
+        if (ref >= 0) {
+            const float4 n3 = nodes[ref * 4 + 3];
+            a = __builtin_bit_cast(int, n3.x); b = __builtin_bit_cast(int, n3.y);
+        } else {
+            a = ref; b = kTraversalDone;  // a leaf keeps one slot, nothing keeps none
+        }
+    };
+    expand(0, s_cut[0], s_cut[1]);
+    for (uint32_t k = 2; k <= 4; k <<= 1)
+        for (uint32_t j = 0; j < k; j++) expand(s_cut[k - 2 + j], s_cut[2 * k - 2 + 2 * j], s_cut[2 * k - 2 + 2 * j + 1]);
+}
+
+// lane l takes `v` of the lane that `ctrl` (a DPP control within a row of 16) names
+template <int kCtrl> __device__ __forceinline__ uint32_t dpp_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xF, 0xF, false); }
+template <int kCtrl> __device__ __forceinline__ float dpp_f32(float v) { return as_float(dpp_u32<kCtrl>(as_uint(v))); }
+constexpr int kDppSwap1 = 0xB1;   // quad_perm [1,0,3,2]: lane ^ 1
+constexpr int kDppSwap2 = 0x4E;   // quad_perm [2,3,0,1]: lane ^ 2
+constexpr int kDppMirror8 = 0x141;  // row_half_mirror: lane -> 7 - lane within 8 (the other quad)
+
+// minimum of v over the lane's group of k consecutive lanes (k wave-uniform; every lane of the wave active)
+__device__ __forceinline__ float group_min(float v, uint32_t k)
+{
+    v = raw_minf(v, dpp_f32<kDppSwap1>(v));
+    if (k >= 4u) v = raw_minf(v, dpp_f32<kDppSwap2>(v));
+    if (k >= 8u) v = raw_minf(v, dpp_f32<kDppMirror8>(v));
+    return v;
+}
+
+// Closest hits of the rays of the wave's `alive` lanes (ballot = __ballot(alive), at most 32 of them, n >= 2), over the LDS-resident binary
+// tree.  EVERY lane of the wave calls this, converged.  Live lane number r (in lane order) owns lanes [r * k, r * k + k) with k the largest
+// of {8, 4, 2} that fits; results come back in t_out / id_out of the alive lanes only.
+template <typename StackT>
+__device__ __forceinline__ void closest_hit_coop(const float4* __restrict__ nodes, const float4* __restrict__ sph, const uint32_t* __restrict__ ids,
+                                                 const int* __restrict__ s_cut, unsigned long long ballot, f3 o, f3 d, float tmin, float tmax,
+                                                 StackT* stack, uint32_t stride, float& t_out, uint32_t& id_out, uint32_t descent_cap = 0)
+{
+    const uint32_t lane = lane_id();
+    const uint32_t n_live = (uint32_t)__builtin_amdgcn_readfirstlane(__popcll(ballot));
+    const uint32_t shift = n_live <= 8u ? 3u : (n_live <= 16u ? 2u : 1u), k = 1u << shift;
+    const uint32_t group = lane >> shift, j = lane & (k - 1u);
+    // the lane of live ray number `group`: the group-th set bit of the ballot (binary search by population counts)
+    uint32_t src;
+    {
+        const uint32_t lo = (uint32_t)ballot, hi = (uint32_t)(ballot >> 32);
+        uint32_t r = group, m = lo, c = __popc(lo);
+        src = 0;
+        if (r >= c) { r -= c; m = hi; src = 32u; }
+#pragma unroll
+        for (uint32_t w = 16; w > 0; w >>= 1) {
+            c = __popc(m & ((1u << w) - 1u));
+            if (r >= c) { r -= c; m >>= w; src += w; }
+        }
+    }
+    const bool has_ray = group < n_live;
+    src = has_ray ? src : lane;
+    const f3 ro = make_f3(__shfl(o.x, (int)src, 64), __shfl(o.y, (int)src, 64), __shfl(o.z, (int)src, 64));
+    const f3 rd = make_f3(__shfl(d.x, (int)src, 64), __shfl(d.y, (int)src, 64), __shfl(d.z, (int)src, 64));
+    const float rtmin = __shfl(tmin, (int)src, 64), rtmax = __shfl(tmax, (int)src, 64);
+    const float ix = slab_rcp(rd.x), iy = slab_rcp(rd.y), iz = slab_rcp(rd.z);
+    const float ox = -ro.x * ix, oy = -ro.y * iy, oz = -ro.z * iz;
+    float best = rtmax;           // this helper's own nearest hit (what best_id names)
+    float cull = rtmax;           // the group's nearest hit so far: a true hit distance of the same ray, culled on with <= as closest_hit culls on its own
+    uint32_t best_id = kMissId;
+    int node = has_ray ? s_cut[k - 2u + j] : kTraversalDone;
+    uint32_t sp = 0;
+    for (;;) {
+        uint32_t budget = descent_cap;
+        while (node >= 0) {
+            const float4 n0 = nodes[node * 4 + 0];
+            const float4 n1 = nodes[node * 4 + 1];
+            const float4 n2 = nodes[node * 4 + 2];
+            const float4 n3 = nodes[node * 4 + 3];
+            const float ax = pt_fma(n0.x, ix, ox), bx = pt_fma(n0.w, ix, ox);
+            const float ay = pt_fma(n0.y, iy, oy), by = pt_fma(n1.x, iy, oy);
+            const float az = pt_fma(n0.z, iz, oz), bz = pt_fma(n1.y, iz, oz);
+            const float lx0 = fminf(ax, bx); const float cx = pt_fma(n1.z, ix, ox);
+            const float ly0 = fminf(ay, by); const float dx = pt_fma(n2.y, ix, ox);
+            const float lz0 = fminf(az, bz); const float cy = pt_fma(n1.w, iy, oy);
+            const float hx0 = fmaxf(ax, bx); const float dy = pt_fma(n2.z, iy, oy);
+            const float hy0 = fmaxf(ay, by); const float cz = pt_fma(n2.x, iz, oz);
+            const float hz0 = fmaxf(az, bz); const float dz = pt_fma(n2.w, iz, oz);
+            const float tn0 = fmaxf(fmaxf(lx0, ly0), raw_maxf(lz0, rtmin));
+            const float tf0 = fminf(fminf(hx0, hy0), raw_minf(hz0, cull));
+            const float tn1 = fmaxf(fmaxf(fminf(cx, dx), fminf(cy, dy)), raw_maxf(fminf(cz, dz), rtmin));
+            const float tf1 = fminf(fminf(fmaxf(cx, dx), fmaxf(cy, dy)), raw_minf(fmaxf(cz, dz), cull));
+            const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
+            const int c0 = __builtin_bit_cast(int, n3.x), c1 = __builtin_bit_cast(int, n3.y);
+            if (h0 && h1) {
+                const bool swap = tn1 < tn0;
+                const int near_c = swap ? c1 : c0, far_c = swap ? c0 : c1;
+                stack[sp] = stack_encode<StackT>(far_c);
+                sp += stride;
+                node = near_c;
+            } else if (h0) {
+                node = c0;
+            } else if (h1) {
+                node = c1;
+            } else if (sp == 0) {
+                node = kTraversalDone;
+            } else {
+                sp -= stride;
+                node = stack_decode(stack[sp]);
+            }
+            if (--budget == 0u) break;
+        }
+        // every lane of the wave is here: with a leaf, mid-descent (the budget ran out), or finished (it stays for the exchange below)
+        if (node < 0 && node != kTraversalDone) {
+            const uint32_t q = ~(uint32_t)node;
+            const float4 s = sph[q];
+            float t;
+            if (intersect_sphere(ro, rd, rtmin, kInf, make_f3(s.x, s.y, s.z), s.w, t)) {
+                const uint32_t idf = ids[q];
+                if ((idf >> kIdClassShift) != kAlphaInvisible) {  // (untextured scenes: no other class needs a test, alpha_candidate<false>)
+                    const uint32_t id = idf & kIdMask;
+                    if (t < best || (t == best && best_id != kMissId && id < best_id)) { best = t; best_id = id; }
+                }
+            }
+            if (sp == 0) {
+                node = kTraversalDone;
+            } else {
+                sp -= stride;
+                node = stack_decode(stack[sp]);
+            }
+        }
+        cull = group_min(raw_minf(cull, best), k);
+        if (__ballot(node != kTraversalDone) == 0ull) break;
+    }
+    // (best, best_id) over the group: nearer t wins, equal t -> lower id (kMissId, the largest, loses to any)
+#define PT_COOP_MERGE(CTRL)                                                                                              \
+    {                                                                                                                    \
+        const float t2 = dpp_f32<CTRL>(best);                                                                            \
+        const uint32_t id2 = dpp_u32<CTRL>(best_id);                                                                     \
+        if (t2 < best || (t2 == best && id2 < best_id)) { best = t2; best_id = id2; }                                    \
+    }
+    PT_COOP_MERGE(kDppSwap1)
+    if (k >= 4u) PT_COOP_MERGE(kDppSwap2)
+    if (k >= 8u) PT_COOP_MERGE(kDppMirror8)
+#undef PT_COOP_MERGE
+    // back to the path's own lane: live ray number r was walked by the group of lanes starting at r * k
+    const uint32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
+    const int owner = (int)((rank << shift) & 63u);
+    t_out = __shfl(best, owner, 64);
+    id_out = __shfl(best_id, owner, 64);
+}
+
 // adds a workgroup's {node visits, sphere tests} to the lane's running totals (two atomics per workgroup)
 __device__ __forceinline__ void flush_visit_counters(unsigned long long* totals, const uint32_t v[2])
 {
@@ -889,7 +1047,7 @@ __device__ __forceinline__ void store_path(const RayQueue& q, uint32_t j, const 
 
 // static LDS of the kernels below (counters, the segment prefix table of the looping pass) on top of their dynamic LDS: the
 // 64 KB default limit counts both, so the opt-in for more is taken this much earlier
-constexpr uint32_t kStaticLdsMargin = (kMaxSegs + 64u) * 4u;
+constexpr uint32_t kStaticLdsMargin = (kMaxSegs + 64u + kCutSlots) * 4u;
 
 // Cold kernel arguments.  A by-value kernel argument is loaded into SGPRs at the kernel's entry and stays there: with ~120 dwords of
 // arguments and 100 SGPRs, the camera and the pixel map -- needed once per batch, to generate the primary rays -- lived in VGPR lanes
@@ -905,6 +1063,32 @@ __device__ __forceinline__ T cold_arg(uint32_t offset)
     T v;
     __builtin_memcpy(&v, p + offset, sizeof(T));
     return v;
+}
+
+// The trace -> shade loop of a wave of 1-spp paths with the cooperative walk: the wave meets at every trace, and a lane whose path has ended
+// (or that never had one) stays as a helper until no lane of the wave holds a live path.  Every path keeps its own state, RNG stream and shading;
+// only who performs which slab and sphere tests changes.  More than 32 live paths leave no helpers: the per-lane walk.  `rays` counts the rays
+// spawned here.
+template <typename StackT, bool kDn>
+__device__ __forceinline__ void coop_bounces(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const Scratch& scratch, float4* __restrict__ out,
+                                             const float4* __restrict__ nodes, const float4* __restrict__ sph, const uint32_t* __restrict__ ids,
+                                             const int* __restrict__ s_cut, StackT* stack, uint32_t stride, PathState& ps, bool alive, uint32_t& rays)
+{
+    for (;;) {
+        const unsigned long long ballot = __ballot(alive);
+        if (ballot == 0ull) break;
+        float t = 0.0f;
+        uint32_t id = kMissId;
+        if (__popcll(ballot) > 32) {
+            if (alive) closest_hit<StackT, false, false, false>(sv, nodes, sph, ids, sv.n, ps.o, ps.d, 0.0f, kInf, stack, stride, t, id, nullptr, sv.descent_cap);
+        } else {
+            closest_hit_coop<StackT>(nodes, sph, ids, s_cut, ballot, ps.o, ps.d, 0.0f, kInf, stack, stride, t, id, sv.descent_cap);
+        }
+        if (alive) {
+            alive = shade_step<false, false, false, 0, kDn>(sv, pm, fp, scratch, out, ps, t, id);
+            if (alive) rays++;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ fused bounce
@@ -940,6 +1124,9 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
     __shared__ uint32_t s_loop_next;                  // fused form: the next 64 entries of the workgroup's own segment
     __shared__ uint32_t s_seg_prefix[kMaxSegs + 1];   // consumer side: s_seg_prefix[b] = entries in segments < b
     __shared__ uint32_t s_refl[2];                    // kIters == 2: waves that traced bounce-1 rays, ... of them served by a region list
+    __shared__ int s_cut[kCutSlots];                  // kCoop: the tree's cuts at depths 1-3 (build_cut)
+    // The cooperative walk (closest_hit_coop): the looping pass of a 1-spp frame over an untextured LDS-resident scene, and the fused form's tail
+    constexpr bool kCoop = kLds && !kMulti && !kTex && !kDI && !kDn && sizeof(StackT) == 2 && ((kLoop && !kPrimary) || kFuse);
     if (kPrimary && blockIdx.x == 0) frame_counters_begin(fc, pm.n_slots);
     const bool seg_out = kPrimary && !kLoop && fc.seg_counts != nullptr;
     const bool seg_in = !kPrimary && kLoop && fc.seg_counts != nullptr;
@@ -985,12 +1172,17 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         sph = smem + sv.n_nodes * 4u;
         ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
         stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
+        if (kCoop && fc.coop_walk != 0u && sv.n > 1u) {
+            if (threadIdx.x == 0) build_cut(smem, s_cut);
+            __syncthreads();
+        }
     } else {
         stack = reinterpret_cast<StackT*>(smem);
     }
     stack += threadIdx.x;
     const uint32_t lane = lane_id();
     const uint32_t wave = threadIdx.x >> 6;
+    const bool coop = kCoop && fc.coop_walk != 0u && sv.n > 1u && (blockDim.x & 63u) == 0u;  // (whole waves only: every lane takes part in the exchanges)
     uint32_t my_rays = 0;
     // A share of the NEXT primary-beam lists of a moving camera (FrameParams::beam_job, pt_api.hip beam_cache_lookup): the first wave of the
     // first workgroups walks 64 blocks' pyramids each, one lane per block, before it joins its workgroup's tiles -- an 8192-block share per
@@ -1050,6 +1242,22 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         }
         bool emit = false;
         PathState ps;
+        if (kCoop && kLoop && coop) {
+            const bool alive = i < count;
+            if (alive) {
+                if (seg_in) {
+                    uint32_t lo = 0, hi = fc.n_segs;
+                    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (s_seg_prefix[mid] <= i) lo = mid; else hi = mid; }
+                    ps = load_path<kDn>(qin, lo * fc.seg_cap + (i - s_seg_prefix[lo]));
+                } else {
+                    ps = load_path<kDn>(qin, i);
+                }
+            } else {
+                ps.o = make_f3(0.f, 0.f, 0.f); ps.d = make_f3(0.f, 0.f, 1.f);  // (a helper from the start: the exchanges read every lane's ray registers)
+            }
+            coop_bounces<StackT, kDn>(sv, pm, fp, scratch, out, nodes, sph, ids, s_cut, stack, blockDim.x, ps, alive, my_rays);
+            continue;  // (a looping pass hands nothing on)
+        }
         // primary beams: this wave's 64 slots are one 8x8-pixel block; its candidate list was made by beam_kernel
         const uint32_t* beam_rec = nullptr;
         uint32_t beam_count = ~0u;
@@ -1183,7 +1391,12 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 w = __builtin_amdgcn_readfirstlane(w);
                 if (w >= n_own) break;
                 const uint32_t i = w + lane;
-                if (i < n_own) {
+                if (kCoop && coop) {
+                    PathState ps;
+                    if (i < n_own) ps = load_path<kDn>(qout, blockIdx.x * fc.seg_cap + i);
+                    else { ps.o = make_f3(0.f, 0.f, 0.f); ps.d = make_f3(0.f, 0.f, 1.f); }
+                    coop_bounces<StackT, kDn>(sv, pm, fp, scratch, out, nodes, sph, ids, s_cut, stack, blockDim.x, ps, i < n_own, my_loop_rays);
+                } else if (i < n_own) {
                     PathState ps = load_path<kDn>(qout, blockIdx.x * fc.seg_cap + i);
                     for (;;) {
                         float t;
