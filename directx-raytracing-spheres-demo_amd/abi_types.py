@@ -102,6 +102,22 @@ class PtNrdDenoiseTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NRD_DENOISE_TEXTURES]
 
 
+# Row N10 (pt_restir_di, the RTXDI stand-in): the settings and the buffers it reads (G-buffer channels) and writes
+RESTIR_DI_INPUTS = ("Position", "GeometricNormal", "LinearDepth", "MotionVector", "BaseColorMetalness", "NormalRoughness", "IOR", "Transmission")
+RESTIR_DI_TEXTURES = RESTIR_DI_INPUTS + ("Diffuse", "Specular")
+RESTIR_BIAS_OFF, RESTIR_BIAS_BASIC, RESTIR_BIAS_PAIRWISE, RESTIR_BIAS_RAYTRACED = 0, 1, 2, 3
+
+
+class PtRestirDiSettings(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("FrameIndex", C.c_uint32), ("ResetHistory", C.c_uint32), ("InitialSamples", C.c_uint32),
+                ("EnableTemporal", C.c_uint32), ("TemporalBiasCorrection", C.c_uint32), ("MaxHistoryLength", C.c_uint32),
+                ("EnableSpatial", C.c_uint32), ("SpatialBiasCorrection", C.c_uint32), ("SpatialSamples", C.c_uint32), ("SpatialRadius", C.c_float)]
+
+
+class PtRestirDiTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in RESTIR_DI_TEXTURES]
+
+
 # pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
 class PtDirectLighting(C.Structure):
     _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]

@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtSceneData, PtStats)
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtRestirDiTextures, PtSceneData, PtStats, RESTIR_DI_TEXTURES)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -18,7 +18,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -98,6 +98,8 @@ class HipLib:
         lib.pt_nrd_composition.argtypes = [vp, C.POINTER(PtNrdCompositionConstants), C.POINTER(PtNrdCompositionTextures)]
         lib.pt_nrd_denoise.restype = C.c_int
         lib.pt_nrd_denoise.argtypes = [vp, C.POINTER(PtNrdDenoiseSettings), C.POINTER(PtNrdDenoiseTextures)]
+        lib.pt_restir_di.restype = C.c_int
+        lib.pt_restir_di.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtRestirDiTextures)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -503,6 +505,40 @@ class Renderer:
                                  MaxDiffuseFrames=max_diffuse_frames, MaxSpecularFrames=max_specular_frames, AtrousIterations=atrous_iterations)
         t = PtNrdDenoiseTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
         self._check(self._lib.pt_nrd_denoise(self._ctx, C.byref(s), C.byref(t)))
+
+    def restir_di_device(self, width, height, buffers, frame_index=0, reset_history=False, initial_samples=0, temporal=True, temporal_bias=1,
+                         max_history=0, spatial=True, spatial_bias=1, spatial_samples=0, spatial_radius=0.0):
+        """The reservoir pass that makes the DI render_with_di_device takes (row N10, DESIGN.md spec S16) over width x height pixels, for
+        the frame the next render call renders: buffers = {RESTIR_DI_TEXTURES name: device pointer}, the G-buffer channels of
+        render_gbuffer_device and the Diffuse / Specular outputs (float4; the caller clears them: pixels without DI are not written).
+        *_bias: abi_types.RESTIR_BIAS_*; 0 for a count or the radius = the library's default.  The context keeps the history between
+        calls.  Asynchronous, ordered like render_gbuffer_device; what is queued on the context's stream later sees the outputs."""
+        unknown = set(buffers) - set(RESTIR_DI_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown ReSTIR DI buffers {sorted(unknown)}")
+        s = PtRestirDiSettings(RenderSize=(C.c_uint32 * 2)(width, height), FrameIndex=frame_index, ResetHistory=1 if reset_history else 0,
+                               InitialSamples=initial_samples, EnableTemporal=int(temporal), TemporalBiasCorrection=temporal_bias,
+                               MaxHistoryLength=max_history, EnableSpatial=int(spatial), SpatialBiasCorrection=spatial_bias,
+                               SpatialSamples=spatial_samples, SpatialRadius=spatial_radius)
+        t = PtRestirDiTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_restir_di(self._ctx, C.byref(s), C.byref(t)))
+
+    def restir_di(self, fill=float("nan"), device=None, previous_spheres=None, previous_rotations=None, **settings):
+        """render_gbuffer_device + restir_di_device for the whole RenderSize into torch buffers (the outputs filled with `fill`, which
+        pixels without DI keep) -> (diffuse, specular, gbuffer): two torch float32 (h, w, 4) tensors and {channel: tensor}.
+        FrameIndex defaults to the constants'.  Synchronous."""
+        import torch
+        w, h = self._gs.RenderSize[0], self._gs.RenderSize[1]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        width = dict(GBUFFER_CHANNELS)
+        gb = {name: torch.zeros((h, w, width[name]), dtype=torch.float32, device=dev) for name in RESTIR_DI_TEXTURES[:8]}
+        dd, ds = (torch.from_numpy(np.full((h, w, 4), fill, dtype=np.float32)).to(dev) for _ in range(2))
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        self.render_gbuffer_device({name: b.data_ptr() for name, b in gb.items()}, None, previous_spheres, previous_rotations)
+        settings.setdefault("frame_index", self._gs.FrameIndex)
+        self.restir_di_device(w, h, dict({name: b.data_ptr() for name, b in gb.items()}, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), **settings)
+        self.synchronize()
+        return dd, ds, gb
 
     def nrd_denoiser(self, mode, rect=None, device=None, **settings):
         """A `denoise(diffuse, specular)` for nrd_chain that runs pt_nrd_denoise (row N9) in place of the identity copy: it carries the

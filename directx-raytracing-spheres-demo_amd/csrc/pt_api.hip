@@ -23,6 +23,7 @@
 #include "pt_bloom.h"
 #include "pt_nrd.h"
 #include "pt_denoise.h"
+#include "pt_restir.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
 
@@ -106,6 +107,7 @@ struct Lane {
     uint32_t prev_cap = 0;            // spheres the two buffers hold room for
     hipEvent_t ev_gb_in = nullptr;
     void* last_gb[13] = {};           // the buffers of the lane's latest G-buffer call (its ordering against the caller's stream)
+    const void* last_ri[2] = {};      // the outputs of the lane's latest pt_restir_di call
 };
 constexpr uint32_t kMaxLanes = 8;
 
@@ -194,6 +196,15 @@ struct PtContext {
     float* d_dn = nullptr;
     uint32_t dn_w = 0, dn_h = 0, dn_mode = 0, dn_slot = 0;
     bool dn_valid = false;
+    // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
+    // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
+    // pt_set_scene count it was made under (emitter indices change with the scene), `ev_ri` = the last call's launches have finished
+    // (consecutive calls run on different lanes and hand the history to each other)
+    float4* d_ri = nullptr;
+    uint32_t ri_w = 0, ri_h = 0, ri_slot = 0;
+    uint64_t ri_scene = 0, set_scene_calls = 0;
+    bool ri_valid = false;
+    hipEvent_t ev_ri = nullptr;
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
     uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists
 
@@ -1434,6 +1445,8 @@ void pt_destroy(PtContext* c)
     free_dev(c->d_out);
     free_dev(c->d_bloom);
     free_dev(c->d_dn);
+    free_dev(c->d_ri);
+    if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
     if (c->gpu_builder) lbvh_gpu_destroy(c->gpu_builder);
     for (auto& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1514,6 +1527,7 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
     c->scene_set = true;
     c->accel_valid = false;
     c->scene_gen++;
+    c->set_scene_calls++;  // (pt_restir_di's history restarts: emitter indices belong to a scene)
     free_textures(c);  // texture maps are per sphere: a new scene starts untextured
     // alpha-tested hits: the spheres that are not Opaque (Scene.ixx:242-243), classified now from their constant alpha and again when
     // texture maps arrive (pt_set_textures)
@@ -2327,6 +2341,187 @@ PtStatus pt_nrd_denoise(PtContext* c, const PtNrdDenoiseSettings* s, const PtNrd
     c->dn_mode = s->Denoiser;
     c->dn_valid = true;
     return PT_OK;
+}
+
+// Row N10 -- the reservoir pass (DESIGN.md spec S16): two launches on the lane of the next render call, ordered like pt_render_gbuffer;
+// the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
+constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
+
+PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: null pointer");
+    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: RenderSize must be in [1, 16384]");
+    if (s->InitialSamples > kRiMaxInitialSamples) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: InitialSamples must be at most 32");
+    if (s->SpatialSamples > kRiMaxSpatialSamples) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: SpatialSamples must be at most 32");
+    if (s->EnableTemporal > 1 || s->EnableSpatial > 1) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: EnableTemporal and EnableSpatial must be 0 or 1");
+    for (const uint32_t mode : { s->TemporalBiasCorrection, s->SpatialBiasCorrection }) {
+        if (mode == kRiBiasPairwise) return fail(c, PT_ERR_UNSUPPORTED, "pt_restir_di: pairwise bias correction (2) is not built");
+        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
+    }
+    if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: SpatialRadius must be finite and >= 0");
+    const uint64_t n = (uint64_t)w * h;
+    // (pointer, bytes per pixel, alignment, written)
+    struct Use { const void* p; uint32_t bpp, align; bool written; const char* name; };
+    const Use use[10] = {
+        {t->Position, 16, 16, false, "Position"}, {t->GeometricNormal, 8, 8, false, "GeometricNormal"}, {t->LinearDepth, 4, 4, false, "LinearDepth"},
+        {t->MotionVector, 12, 4, false, "MotionVector"}, {t->BaseColorMetalness, 16, 16, false, "BaseColorMetalness"},
+        {t->NormalRoughness, 16, 16, false, "NormalRoughness"}, {t->IOR, 4, 4, false, "IOR"}, {t->Transmission, 4, 4, false, "Transmission"},
+        {t->Diffuse, 16, 16, true, "Diffuse"}, {t->Specular, 16, 16, true, "Specular"},
+    };
+    for (const Use& u : use) {
+        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + u.name + " is required");
+        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
+            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
+    }
+    for (const Use& a : use) {
+        if (!a.written) continue;
+        for (const Use& b : use) {
+            if (&a == &b) continue;
+            const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
+            if (pa < pb + n * b.bpp && pb < pa + n * a.bpp)
+                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + a.name + " overlaps " + b.name);
+        }
+    }
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    if ((st = check_environment(c)) != PT_OK) return st;
+    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)
+        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    PT_HIP(c, hipSetDevice(c->device));
+    if (c->n_lights == 0 || c->empty_scene) {  // no emitters: nothing is written, and there is no history to keep
+        c->ri_valid = false;
+        return PT_OK;
+    }
+
+    // the lane of the next frame, brought up to date as pt_render_gbuffer does (its rotation is not advanced)
+    Lane& L = c->lanes[c->next_lane];
+    {
+        const bool again = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
+        bool idle = !again || c->gb_lanes_idle;
+        for (uint32_t i = 0; i < c->n_lanes && idle; i++)
+            if (!(again && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { idle = false; (void)hipGetLastError(); }
+        c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
+    }
+    if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
+    if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
+    if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;
+    if (L.stream != c->stream) {
+        // pt_render_gbuffer's rule.  The pass waits for everything the caller has queued so far before the first render call, when an
+        // input is not a buffer this lane's own G-buffer call wrote (it was made elsewhere: on the caller's stream), and when a buffer
+        // is one another lane's G-buffer, DI pass or frame touched within the window; otherwise for the marker n_lanes - 1 calls ago.
+        // (One-sided for last_ri: only this entry point looks at the outputs of other lanes' DI passes.  pt_render_gbuffer and the
+        // frames do not, so a caller that hands a DI buffer of one lane to them inside the window relies on the rotation rule.)
+        const uint64_t nl = c->n_lanes;
+        bool shared = c->calls == 0;
+        for (uint32_t k = 0; k < 8 && !shared; k++) {
+            bool own = false;
+            for (uint32_t j = 0; j < 13 && !own; j++) own = use[k].p == L.last_gb[j];
+            shared = !own;
+        }
+        for (uint32_t i = 0; i < c->n_lanes && !shared; i++) {
+            if (&c->lanes[i] == &L) continue;
+            for (uint32_t k = 0; k < 10 && !shared; k++) {
+                shared = use[k].p == c->lanes[i].last_out;
+                for (uint32_t j = 0; j < 13 && !shared; j++) shared = use[k].p == c->lanes[i].last_gb[j];
+                for (uint32_t j = 0; j < 3 && !shared; j++) shared = use[k].p == c->lanes[i].last_dn[j];
+                for (uint32_t j = 0; j < 2 && !shared; j++) shared = use[k].p == c->lanes[i].last_di[j] || use[k].p == c->lanes[i].last_ri[j];
+            }
+        }
+        if (shared) {
+            if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
+            PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
+            PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
+        } else {
+            const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
+            if (hipEventQuery(marker) != hipSuccess) {
+                (void)hipGetLastError();  // hipErrorNotReady is not an error here
+                PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
+            }
+        }
+        L.last_ri[0] = t->Diffuse; L.last_ri[1] = t->Specular;
+    }
+    // the history: the previous call (on whichever lane it ran) wrote the slot this one reads and read the slot this one writes
+    bool restart = s->ResetHistory != 0 || !c->ri_valid || c->ri_scene != c->set_scene_calls;
+    if (!c->ev_ri) PT_HIP(c, hipEventCreateWithFlags(&c->ev_ri, hipEventDisableTiming));
+    if (!c->d_ri || c->ri_w != w || c->ri_h != h) {
+        if (c->d_ri) PT_HIP(c, hipEventSynchronize(c->ev_ri));  // (the previous call may still use the old buffers)
+        free_dev(c->d_ri);
+        c->ri_valid = false;
+        void* mem = nullptr;
+        if (hipMalloc(&mem, 2u * n * kRiSlotBytesPerPixel) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, "pt_restir_di: history allocation failed"); }
+        c->d_ri = static_cast<float4*>(mem);
+        c->ri_w = w; c->ri_h = h;
+        restart = true;
+    } else if (L.stream != c->stream || c->n_lanes > 1) {
+        PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_ri, 0));
+    }
+    const uint32_t cur = c->ri_slot ^ 1u, prev = c->ri_slot;
+    RiBuffers b{};
+    b.w = w; b.h = h;
+    b.position = static_cast<const float4*>(t->Position);
+    b.geometric_normal = static_cast<const float*>(t->GeometricNormal);
+    b.linear_depth = static_cast<const float*>(t->LinearDepth);
+    b.motion_vector = static_cast<const float*>(t->MotionVector);
+    b.base_color_metalness = static_cast<const float4*>(t->BaseColorMetalness);
+    b.normal_roughness = static_cast<const float4*>(t->NormalRoughness);
+    b.ior = static_cast<const float*>(t->IOR);
+    b.transmission = static_cast<const float*>(t->Transmission);
+    float4* planes = c->d_ri;                                              // [slot][6 planes][n] float4, then [slot][n] float
+    float* tplanes = reinterpret_cast<float*>(c->d_ri + 12u * n);
+    for (uint32_t k = 0; k < 4; k++) { b.rec[k] = planes + ((uint64_t)cur * 6u + k) * n; b.prev_rec[k] = planes + ((uint64_t)prev * 6u + k) * n; }
+    for (uint32_t k = 0; k < 2; k++) { b.res[k] = planes + ((uint64_t)cur * 6u + 4u + k) * n; b.prev_res[k] = planes + ((uint64_t)prev * 6u + 4u + k) * n; }
+    b.rec_t = tplanes + (uint64_t)cur * n;
+    b.prev_rec_t = tplanes + (uint64_t)prev * n;
+    b.out_diffuse = static_cast<float4*>(t->Diffuse);
+    b.out_specular = static_cast<float4*>(t->Specular);
+    RiParams P{};
+    P.frame_index = s->FrameIndex;
+    P.initial_samples = s->InitialSamples ? s->InitialSamples : kRiDefaultInitialSamples;
+    P.temporal = s->EnableTemporal; P.temporal_bias = s->TemporalBiasCorrection;
+    P.max_history = s->MaxHistoryLength ? s->MaxHistoryLength : kRiDefaultHistory;
+    P.spatial = s->EnableSpatial; P.spatial_bias = s->SpatialBiasCorrection;
+    P.spatial_samples = s->SpatialSamples ? s->SpatialSamples : kRiDefaultSpatialSamples;
+    P.radius = std::min(s->SpatialRadius == 0.0f ? kRiDefaultRadius : s->SpatialRadius, kRiMaxRadius);
+    P.history_valid = restart ? 0u : 1u;
+    P.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
+    P.prev_cam_pos = make_f3(c->cam.PreviousPosition[0], c->cam.PreviousPosition[1], c->cam.PreviousPosition[2]);
+    PixelMap pm{};
+    pm.mode = 0;
+    pm.img_w = w; pm.img_h = h; pm.rx = 0; pm.ry = 0; pm.rw = w; pm.rh = h;
+    pm.blocks_x = (w + 7) / 8;
+    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
+    const uint64_t slots = (uint64_t)pm.blocks_x * ((h + 7) / 8) * 64ull;
+    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;
+    pm.n_slots = (uint32_t)slots;  // (at most 2048^2 * 64 = 2^28)
+    const SceneView sv = make_scene_view(c, &L);
+    const uint32_t threads = traverse_threads(c->lds_scene);
+    const uint32_t grid = std::max(1u, std::min((pm.n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
+    st = PT_OK;
+    for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
+        EventPair* ev = c->profiling ? next_events(c, pass == 0 ? 1 : 2) : nullptr;  // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
+        if (ev) (void)hipEventRecord(ev->a, L.stream);
+        if (const hipError_t e = launch_restir_pass(pass, sv, pm, b, P, grid, L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: launch: ") + hipGetErrorString(e));
+        if (ev) (void)hipEventRecord(ev->b, L.stream);
+    }
+    const hipError_t e0 = hipEventRecord(c->ev_ri, L.stream);
+    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: history event: ") + hipGetErrorString(e0));
+    if (L.stream != c->stream) {
+        // whatever the caller queues next on its stream (pt_render_with_di, pt_download) sees the outputs
+        const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
+        if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: completion event: ") + hipGetErrorString(e2));
+    }
+    if (st == PT_OK) {
+        c->ri_slot = cur;
+        c->ri_scene = c->set_scene_calls;
+        c->ri_valid = true;
+    } else {
+        c->ri_valid = false;
+    }
+    return st;
 }
 
 static PtStatus trace_rays_impl(PtContext* c, const float* origins, const float* directions, uint32_t n, float tmin, int use_bvh, float* out_t,

@@ -1,0 +1,474 @@
+// pt_restir.h -- the reservoir pass that makes row N10's direct light (pt_restir_di, DESIGN.md spec S16): a stand-in for the RTXDI
+// passes the reference runs before its frame (DIInitialSampling.hlsl, DITemporalResampling.hlsl, DISpatialResampling.hlsl,
+// DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli; the RTXDI SDK itself is a submodule the reference tree does not contain).
+// Per-pixel functions, one per pass, that compile on the device (pt_restir.hip) and as host C++ (the bit-parity tests); the
+// visibility query is a functor `trace(o, d, t, id)` -- the ordinary closest-hit query, as di_estimate takes it -- and the radiance
+// of the point a visibility ray reached a functor `emit(sphere, o, d, t)`.
+//
+// A sample is (emitter j of the scene's emitter list, u1, u2); at a surface it becomes a direction through sample_sphere_cone, so a
+// reused sample is re-aimed from the surface that reuses it.  Target function: luminance((Le_j (f_d + f_s)) inv_pdf), Le_j the
+// emitter's untextured radiance, without visibility.
+//
+// Out of scope: ReGIR and Power_RIS presampling; BRDF and environment candidates; the boiling filter; checkerboard rendering;
+// visibility reuse; pairwise MIS (bias mode 2); the DLSS-RR SpecularHitDistance write; dropping pt_render_with_di's whole-stream
+// wait for buffers this pass produced.
+#pragma once
+
+#include "pt_light.h"
+#include "pt_texture.h"
+
+namespace pt {
+
+constexpr uint32_t kRiInitialRngSalt = 0x52494E31u;   // each pass has its own per-pixel stream: rng_init(px, py, FrameIndex ^ salt)
+constexpr uint32_t kRiTemporalRngSalt = 0x52495431u;
+constexpr uint32_t kRiSpatialRngSalt = 0x52495331u;
+constexpr float kRiMinRoughness = 0.05f;       // RAB_GetGBufferSurface: mirror-like pixels get no DI (RTXDIAppBridge.hlsli:295)
+constexpr float kRiDepthThreshold = 0.1f;      // reuse: relative depth difference accepted
+constexpr float kRiNormalThreshold = 0.5f;     // reuse: dot of the shading normals accepted
+constexpr uint32_t kRiNoHit = 0xFFFFFFFFu;
+constexpr float kRiOwnSphere = 1e-3f;          // |d^2 - r^2| <= this * r^2: the surface lies on the emitter itself
+constexpr uint32_t kRiDefaultInitialSamples = 8, kRiMaxInitialSamples = 32, kRiDefaultHistory = 20, kRiDefaultSpatialSamples = 1,
+                   kRiMaxSpatialSamples = 32, kRiNeighbourTable = 32;
+constexpr float kRiDefaultRadius = 32.0f, kRiMaxRadius = 16384.0f;
+enum : uint32_t { kRiBiasOff = 0, kRiBiasBasic = 1, kRiBiasPairwise = 2, kRiBiasRaytraced = 3 };
+
+// The compact surface record the first launch writes per pixel (four float4 planes and one float plane): later passes and the next
+// frame's temporal pass read it instead of eight G-buffer channels.  depth = +inf: no surface.
+struct RiRecord {
+    float4 r0;  // P, PositionOffset
+    float4 r1;  // shading normal, roughness
+    float4 r2;  // base colour, metalness
+    float4 r3;  // geometric normal (signed octahedral), linear depth, IOR
+    float transmission;
+};
+
+struct RiReservoir {
+    uint32_t light;  // index into the emitter list
+    float u1, u2;    // the cone sample
+    float W;         // unbiased contribution weight; 0: the sample carries no light
+    float M;         // candidates seen
+    float p_hat;     // target function of the sample at the surface that holds it
+    uint32_t age;    // frames since the sample was drawn
+};
+
+struct RiBuffers {
+    uint32_t w, h;
+    // what RAB_GetGBufferSurface reads, as pt_render_gbuffer writes it (first launch only)
+    const float4* position;
+    const float* geometric_normal;  // float2
+    const float* linear_depth;
+    const float* motion_vector;     // float3
+    const float4* base_color_metalness;
+    const float4* normal_roughness;
+    const float* ior;
+    const float* transmission;
+    // the context's history: this call's slot and the previous call's
+    float4* rec[4];
+    float* rec_t;
+    float4* res[2];
+    const float4* prev_rec[4];
+    const float* prev_rec_t;
+    const float4* prev_res[2];
+    float4* out_diffuse;
+    float4* out_specular;
+};
+
+struct RiScene {
+    const float4* sph;        // original order
+    const float4* mats;       // PtMaterial as 4 float4
+    const uint32_t* lights;   // ids of the emissive spheres
+    uint32_t n_lights;
+};
+
+struct RiParams {
+    uint32_t frame_index, initial_samples, temporal, temporal_bias, max_history, spatial, spatial_bias, spatial_samples;
+    float radius;
+    uint32_t history_valid;   // 0: the history restarts with this call
+    f3 cam_pos, prev_cam_pos;
+};
+
+PT_HD float4 ri_float4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
+
+// Packing::DecodeUnitVector(v, true): the inverse of encode_unit_vector (pt_gbuffer.h)
+PT_HD f3 decode_unit_vector(float ex, float ey)
+{
+    const float z = 1.0f - pt_abs(ex) - pt_abs(ey);
+    float x = ex, y = ey;
+    if (z < 0.0f) {
+        x = (1.0f - pt_abs(ey)) * (ex >= 0.0f ? 1.0f : -1.0f);
+        y = (1.0f - pt_abs(ex)) * (ey >= 0.0f ? 1.0f : -1.0f);
+    }
+    return normalize(make_f3(x, y, z));
+}
+
+PT_HD RiRecord ri_empty_record()
+{
+    RiRecord r;
+    r.r0 = r.r1 = r.r2 = ri_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    r.r3 = ri_float4(0.0f, 0.0f, kInf, 1.0f);
+    r.transmission = 0.0f;
+    return r;
+}
+
+// RAB_GetGBufferSurface's reads (RTXDIAppBridge.hlsli:292-331)
+PT_HD RiRecord ri_record_from_gbuffer(const RiBuffers& b, uint32_t i)
+{
+    const float depth = b.linear_depth[i];
+    if (!is_finite(depth)) return ri_empty_record();
+    const float4 nr = b.normal_roughness[i];
+    if (nr.w < kRiMinRoughness) return ri_empty_record();
+    RiRecord r;
+    r.r0 = b.position[i];
+    r.r1 = nr;
+    r.r2 = b.base_color_metalness[i];
+    r.r3 = ri_float4(b.geometric_normal[2u * i], b.geometric_normal[2u * i + 1u], depth, b.ior[i]);
+    r.transmission = r.r2.w < 1.0f ? b.transmission[i] : 0.0f;
+    return r;
+}
+
+PT_HD void ri_store_record(float4* const rec[4], float* rec_t, uint32_t i, const RiRecord& r)
+{
+    rec[0][i] = r.r0; rec[1][i] = r.r1; rec[2][i] = r.r2; rec[3][i] = r.r3;
+    rec_t[i] = r.transmission;
+}
+
+template <typename P4>
+PT_HD RiRecord ri_load_record(P4 const rec[4], const float* rec_t, uint32_t i)
+{
+    RiRecord r;
+    r.r3 = rec[3][i];
+    if (!is_finite(r.r3.z)) return ri_empty_record();
+    r.r0 = rec[0][i]; r.r1 = rec[1][i]; r.r2 = rec[2][i];
+    r.transmission = r.r2.w < 1.0f ? rec_t[i] : 0.0f;
+    return r;
+}
+
+PT_HD RiReservoir ri_empty_reservoir()
+{
+    RiReservoir r;
+    r.light = 0u; r.u1 = r.u2 = 1.0f; r.W = 0.0f; r.M = 0.0f; r.p_hat = 0.0f; r.age = 0u;
+    return r;
+}
+
+PT_HD void ri_store_reservoir(float4* const res[2], uint32_t i, const RiReservoir& r)
+{
+    res[0][i] = ri_float4(as_float(r.light), r.u1, r.u2, r.W);
+    res[1][i] = ri_float4(r.M, r.p_hat, as_float(r.age), 0.0f);
+}
+
+template <typename P4>
+PT_HD RiReservoir ri_load_reservoir(P4 const res[2], uint32_t i)
+{
+    const float4 a = res[0][i], c = res[1][i];
+    RiReservoir r;
+    r.light = as_uint(a.x); r.u1 = a.y; r.u2 = a.z; r.W = a.w; r.M = c.x; r.p_hat = c.y; r.age = as_uint(c.z);
+    return r;
+}
+
+// RAB_Surface: what every candidate of a pixel shares (view vector, SurfaceVectors, BSDFSample, lobe weights)
+struct RiSurface {
+    bool valid;
+    f3 P, Ng;
+    float offset, depth;
+    f3 V;
+    Surf surf;
+    Bsdf bsdf;
+    float w[3];
+};
+
+// RTXDIAppBridge.hlsli:333-345
+PT_HD RiSurface ri_surface(const RiRecord& r, f3 cam_pos)
+{
+    RiSurface s;
+    s.valid = is_finite(r.r3.z);
+    s.P = make_f3(r.r0.x, r.r0.y, r.r0.z);
+    s.offset = r.r0.w;
+    s.depth = r.r3.z;
+    s.Ng = make_f3(0.0f, 0.0f, 1.0f);
+    s.V = s.Ng;
+    if (!s.valid) {
+        s.surf = surf_init(true, s.Ng, s.Ng);
+        s.bsdf = bsdf_init(make_f3(0.0f, 0.0f, 0.0f), 0.0f, 1.0f, 1.5f, 0.0f, true);
+        s.w[0] = s.w[1] = s.w[2] = 0.0f;
+        return s;
+    }
+    s.V = normalize(cam_pos - s.P);
+    s.Ng = decode_unit_vector(r.r3.x, r.r3.y);
+    const bool front = dot(s.Ng, s.V) > 0.0f;
+    s.surf = surf_init(front, s.Ng, make_f3(r.r1.x, r.r1.y, r.r1.z));
+    s.bsdf = bsdf_init(make_f3(r.r2.x, r.r2.y, r.r2.z), r.r2.w, r.r1.w, r.r3.w, r.transmission, front);
+    lobe_weights(s.bsdf, s.surf, s.V, s.w);
+    return s;
+}
+
+// a sample aimed from a surface: RAB_SamplePolymorphicLight + RAB_GetLightSampleTargetPdfForSurface
+struct RiShade {
+    uint32_t sphere;   // the emitter's sphere id
+    f3 L;
+    float inv_pdf;
+    f3 f_d, f_s;       // the two reflective lobes times cos; zero where the sample carries nothing
+    f3 le;             // the emitter's untextured radiance
+    float p_hat;
+};
+
+PT_HD RiShade ri_shade(const RiScene& sc, const RiSurface& s, uint32_t j, float u1, float u2)
+{
+    RiShade e;
+    e.sphere = sc.lights[j < sc.n_lights ? j : sc.n_lights - 1u];
+    const float4 ls = sc.sph[e.sphere];
+    const float4 lm = sc.mats[e.sphere * 4u + 1u];  // {EmissiveStrength, EmissiveColor}
+    e.le = make_f3(lm.y, lm.z, lm.w) * lm.x;
+    const f3 C = make_f3(ls.x, ls.y, ls.z);
+    const LightSample c = sample_sphere_cone(s.P, C, ls.w, u1, u2);
+    e.L = c.L;
+    e.inv_pdf = c.inv_pdf;
+    e.f_d = e.f_s = make_f3(0.0f, 0.0f, 0.0f);
+    e.p_hat = 0.0f;
+    const f3 wv = C - s.P;
+    const float r2 = ls.w * ls.w;
+    const bool own = pt_abs(dot(wv, wv) - r2) <= kRiOwnSphere * r2;
+    if (s.valid && c.valid && !own && dot(s.surf.FrontNg, c.L) > 0.0f) {
+        bsdf_eval_reflective_lobes(s.bsdf, s.surf, c.L, s.V, s.w, e.f_d, e.f_s);
+        const float p = luminance((e.le * (e.f_d + e.f_s)) * c.inv_pdf);
+        if (p > 0.0f && is_finite(p)) e.p_hat = p;
+        else e.f_d = e.f_s = make_f3(0.0f, 0.0f, 0.0f);
+    }
+    return e;
+}
+
+// N4's visibility rule: the emitter must be the first thing a closest-hit ray from the spawn origin meets
+template <typename TraceFn>
+PT_HD bool ri_visible(const RiSurface& s, const RiShade& e, TraceFn&& trace, f3& so, float& t2)
+{
+    so = spawn_origin(s.P, s.Ng, s.offset, e.L);
+    uint32_t id2 = kRiNoHit;
+    t2 = kInf;
+    trace(so, e.L, t2, id2);
+    return id2 == e.sphere;
+}
+
+// one step of streaming RIS: returns true when the candidate replaces the selected sample
+PT_HD bool ri_stream(float& w_sum, float w, float rnd)
+{
+    w_sum += w;
+    return w > 0.0f && rnd * w_sum <= w;
+}
+
+// ---- initial sampling (DIInitialSampling.hlsl): InitialSamples uniform candidates through RIS, one visibility ray
+template <typename TraceFn>
+PT_HD RiReservoir ri_initial(const RiScene& sc, const RiParams& p, const RiSurface& s, uint32_t px, uint32_t py, TraceFn&& trace)
+{
+    RiReservoir r = ri_empty_reservoir();
+    float w_sum = 0.0f;
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiInitialRngSalt);
+    const float nl = (float)sc.n_lights;
+    for (uint32_t i = 0; i < p.initial_samples; i++) {
+        const float u0 = rng_float(rng), u1 = rng_float(rng), u2 = rng_float(rng), rnd = rng_float(rng);
+        const uint32_t j = pick_light(u0, sc.n_lights);
+        const RiShade e = ri_shade(sc, s, j, u1, u2);
+        if (ri_stream(w_sum, e.p_hat * nl, rnd)) { r.light = j; r.u1 = u1; r.u2 = u2; r.p_hat = e.p_hat; }
+    }
+    r.M = (float)p.initial_samples;
+    r.W = r.p_hat > 0.0f ? w_sum / (r.M * r.p_hat) : 0.0f;
+    if (r.W > 0.0f) {  // enableInitialVisibility: an occluded sample keeps M and carries nothing
+        const RiShade e = ri_shade(sc, s, r.light, r.u1, r.u2);
+        f3 so;
+        float t2;
+        if (!ri_visible(s, e, trace, so, t2)) r.W = 0.0f;
+    }
+    return r;
+}
+
+// ---- temporal resampling (DITemporalResampling.hlsl): the reservoir of the reprojected pixel of the previous call
+template <typename TraceFn>
+PT_HD RiReservoir ri_temporal(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& cur, uint32_t px,
+                              uint32_t py, f3 mv, TraceFn&& trace)
+{
+    if (!p.temporal || !p.history_valid) return cur;
+    const float fx = pt_floor((float)px + mv.x + 0.5f), fy = pt_floor((float)py + mv.y + 0.5f);
+    if (!(fx >= 0.0f && fx < (float)b.w && fy >= 0.0f && fy < (float)b.h)) return cur;
+    const uint32_t qi = (uint32_t)fy * b.w + (uint32_t)fx;
+    const RiSurface ps = ri_surface(ri_load_record(b.prev_rec, b.prev_rec_t, qi), p.prev_cam_pos);
+    if (!ps.valid) return cur;
+    const float expected = s.depth + mv.z;
+    if (!(pt_abs(ps.depth - expected) <= kRiDepthThreshold * expected)) return cur;
+    if (!(dot(s.surf.Ns, ps.surf.Ns) >= kRiNormalThreshold)) return cur;
+    RiReservoir prev = ri_load_reservoir(b.prev_res, qi);
+    if (!(prev.M > 0.0f)) return cur;
+    prev.M = pt_min(prev.M, (float)p.max_history * cur.M);
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiTemporalRngSalt);
+    const float rnd = rng_float(rng);
+    RiReservoir r = cur;
+    float w_sum = cur.p_hat * cur.W * cur.M;
+    const RiShade e = ri_shade(sc, s, prev.light, prev.u1, prev.u2);  // the history's sample, re-aimed from this surface
+    if (ri_stream(w_sum, e.p_hat * prev.W * prev.M, rnd)) { r.light = prev.light; r.u1 = prev.u1; r.u2 = prev.u2; r.p_hat = e.p_hat; r.age = prev.age + 1u; }
+    r.M = cur.M + prev.M;
+    r.W = 0.0f;
+    if (!(r.p_hat > 0.0f)) return r;
+    float Z = r.M;
+    if (p.temporal_bias != kRiBiasOff) {
+        Z = cur.M;  // this surface holds the sample with p_hat > 0
+        const RiShade ep = ri_shade(sc, ps, r.light, r.u1, r.u2);
+        bool counts = ep.p_hat > 0.0f;
+        if (counts && p.temporal_bias == kRiBiasRaytraced) {
+            f3 so;
+            float t2;
+            counts = ri_visible(ps, ep, trace, so, t2);
+        }
+        if (counts) Z += prev.M;
+    }
+    r.W = w_sum / (Z * r.p_hat);
+    if (!is_finite(r.W)) r.W = 0.0f;
+    return r;
+}
+
+// neighbour k of the fixed table (a golden-angle spiral over the unit disc) scaled by the radius and turned by `rot` (one turn = 1),
+// reflected into view as RAB_ClampSamplePositionIntoView does; false: the pixel itself
+PT_HD bool ri_neighbour(const RiBuffers& b, float radius, uint32_t px, uint32_t py, uint32_t k, float rot, uint32_t& qx, uint32_t& qy)
+{
+    const float rr = pt_sqrt(((float)k + 0.5f) * (1.0f / (float)kRiNeighbourTable)) * radius;
+    float a = pt_fma((float)k, 0.61803399f, rot);
+    a = a - pt_floor(a);
+    float sn, cs;
+    sincos_2pi(a, sn, cs);
+    int x = (int)px + (int)pt_floor(pt_fma(rr, cs, 0.5f)), y = (int)py + (int)pt_floor(pt_fma(rr, sn, 0.5f));
+    const int w = (int)b.w, h = (int)b.h;
+    if (x < 0) x = -x;
+    if (y < 0) y = -y;
+    if (x >= w) x = 2 * w - x - 1;
+    if (y >= h) y = 2 * h - y - 1;
+    x = x < 0 ? 0 : (x >= w ? w - 1 : x);  // (an image narrower than the radius)
+    y = y < 0 ? 0 : (y >= h ? h - 1 : y);
+    qx = (uint32_t)x; qy = (uint32_t)y;
+    return !(qx == px && qy == py);
+}
+
+// RAB_AreMaterialsSimilar (RTXDIAppBridge.hlsli:380-385)
+PT_HD bool ri_materials_similar(const Bsdf& a, const Bsdf& c)
+{
+    return pt_abs(a.Roughness - c.Roughness) <= 0.5f * pt_max(a.Roughness, c.Roughness)
+        && pt_abs(luminance(a.F0) - luminance(c.F0)) <= 0.25f && pt_abs(luminance(a.Albedo) - luminance(c.Albedo)) <= 0.25f;
+}
+
+PT_HD bool ri_neighbour_surface(const RiBuffers& b, const RiParams& p, const RiSurface& s, uint32_t qi, RiSurface& ns)
+{
+    ns = ri_surface(ri_load_record(b.rec, b.rec_t, qi), p.cam_pos);
+    return ns.valid && pt_abs(ns.depth - s.depth) <= kRiDepthThreshold * s.depth && dot(s.surf.Ns, ns.surf.Ns) >= kRiNormalThreshold
+        && ri_materials_similar(s.bsdf, ns.bsdf);
+}
+
+// ---- spatial resampling (DISpatialResampling.hlsl): SpatialSamples neighbours of this call's temporal result
+template <typename TraceFn>
+PT_HD RiReservoir ri_spatial(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& centre, uint32_t px,
+                             uint32_t py, TraceFn&& trace)
+{
+    if (!p.spatial) return centre;
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiSpatialRngSalt);
+    const uint32_t start = rng_next(rng) & (kRiNeighbourTable - 1u);
+    const float rot = rng_float(rng);
+    RiReservoir r = centre;
+    float w_sum = centre.p_hat * centre.W * centre.M;
+    uint32_t accepted = 0u;
+    for (uint32_t i = 0; i < p.spatial_samples; i++) {
+        const float rnd = rng_float(rng);
+        uint32_t qx, qy;
+        if (!ri_neighbour(b, p.radius, px, py, (start + i) & (kRiNeighbourTable - 1u), rot, qx, qy)) continue;
+        const uint32_t qi = qy * b.w + qx;
+        RiSurface ns;
+        if (!ri_neighbour_surface(b, p, s, qi, ns)) continue;
+        const RiReservoir nr = ri_load_reservoir(b.res, qi);
+        if (!(nr.M > 0.0f)) continue;
+        accepted |= 1u << i;
+        const RiShade e = ri_shade(sc, s, nr.light, nr.u1, nr.u2);
+        if (ri_stream(w_sum, e.p_hat * nr.W * nr.M, rnd)) { r.light = nr.light; r.u1 = nr.u1; r.u2 = nr.u2; r.p_hat = e.p_hat; r.age = nr.age; }
+        r.M += nr.M;
+    }
+    if (!accepted) return centre;
+    r.W = 0.0f;
+    if (!(r.p_hat > 0.0f)) return r;
+    float Z = r.M;
+    if (p.spatial_bias != kRiBiasOff) {
+        Z = centre.M;
+        for (uint32_t i = 0; i < p.spatial_samples; i++) {
+            if (!(accepted & (1u << i))) continue;
+            uint32_t qx, qy;
+            (void)ri_neighbour(b, p.radius, px, py, (start + i) & (kRiNeighbourTable - 1u), rot, qx, qy);
+            const uint32_t qi = qy * b.w + qx;
+            const RiSurface ns = ri_surface(ri_load_record(b.rec, b.rec_t, qi), p.cam_pos);
+            const RiShade en = ri_shade(sc, ns, r.light, r.u1, r.u2);
+            bool counts = en.p_hat > 0.0f;
+            if (counts && p.spatial_bias == kRiBiasRaytraced) {
+                f3 so;
+                float t2;
+                counts = ri_visible(ns, en, trace, so, t2);
+            }
+            if (counts) Z += b.res[1][qi].x;
+        }
+    }
+    r.W = w_sum / (Z * r.p_hat);
+    if (!is_finite(r.W)) r.W = 0.0f;
+    return r;
+}
+
+// ---- final shading (DIFinalShading.hlsl:23-103, IsLastRenderPass false): false = the pixel is not written
+template <typename TraceFn, typename EmitFn>
+PT_HD bool ri_final(const RiScene& sc, const RiSurface& s, const RiReservoir& r, TraceFn&& trace, EmitFn&& emit, float4& diffuse, float4& specular)
+{
+    if (!(r.W > 0.0f) || !is_finite(r.W)) return false;
+    const RiShade e = ri_shade(sc, s, r.light, r.u1, r.u2);
+    if (!(e.p_hat > 0.0f)) return false;
+    f3 so;
+    float t2;
+    if (!ri_visible(s, e, trace, so, t2)) return false;
+    const f3 le = emit(e.sphere, so, e.L, t2);  // at the point reached: an emissive map modulates it, as in di_estimate
+    const float k = e.inv_pdf * r.W;
+    const f3 d = (le * e.f_d) * k, sp = (le * e.f_s) * k, sum = d + sp;
+    if (sum.x == 0.0f && sum.y == 0.0f && sum.z == 0.0f) return false;
+    if (!is_finite(sum.x) || !is_finite(sum.y) || !is_finite(sum.z)) return false;
+    diffuse = ri_float4(d.x, d.y, d.z, t2);
+    specular = ri_float4(sp.x, sp.y, sp.z, t2);
+    return true;
+}
+
+// ---- what one lane of each launch does
+// launch 1: the pixel's surface record from the G-buffer, initial sampling, temporal resampling -> this call's slot
+template <typename TraceFn>
+PT_HD void ri_pass1_px(const RiBuffers& b, const RiScene& sc, const RiParams& p, uint32_t px, uint32_t py, TraceFn&& trace)
+{
+    const uint32_t i = py * b.w + px;
+    const RiRecord rec = ri_record_from_gbuffer(b, i);
+    if (!is_finite(rec.r3.z)) {
+        // no surface: the plane that says so is all any reader looks at (ri_load_record; a reservoir is only read behind a valid
+        // record), 16 B written instead of 100 -- most pixels of a frame with sky or mirror-like ground
+        b.rec[3][i] = rec.r3;
+        return;
+    }
+    ri_store_record(b.rec, b.rec_t, i, rec);
+    const RiSurface s = ri_surface(rec, p.cam_pos);
+    RiReservoir r = ri_initial(sc, p, s, px, py, trace);
+    const f3 mv = make_f3(b.motion_vector[3u * i], b.motion_vector[3u * i + 1u], b.motion_vector[3u * i + 2u]);
+    r = ri_temporal(b, sc, p, s, r, px, py, mv, trace);
+    ri_store_reservoir(b.res, i, r);
+}
+
+// launch 2: spatial resampling over launch 1's results, final shading
+template <typename TraceFn, typename EmitFn>
+PT_HD void ri_pass2_px(const RiBuffers& b, const RiScene& sc, const RiParams& p, uint32_t px, uint32_t py, TraceFn&& trace, EmitFn&& emit)
+{
+    const uint32_t i = py * b.w + px;
+    const RiRecord rec = ri_load_record(b.rec, b.rec_t, i);
+    if (!is_finite(rec.r3.z)) return;
+    const RiSurface s = ri_surface(rec, p.cam_pos);
+    const RiReservoir r = ri_spatial(b, sc, p, s, ri_load_reservoir(b.res, i), px, py, trace);
+    float4 d, sp;
+    if (ri_final(sc, s, r, trace, emit, d, sp)) { b.out_diffuse[i] = d; b.out_specular[i] = sp; }
+}
+
+#if defined(__HIPCC__)
+struct SceneView;
+struct PixelMap;
+// pass 0: launch 1 (initial + temporal), pass 1: launch 2 (spatial + final), over the pixels of pm (mode 0, the whole RenderSize)
+hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream);
+#endif
+
+}  // namespace pt

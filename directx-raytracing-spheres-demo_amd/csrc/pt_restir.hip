@@ -1,0 +1,75 @@
+// pt_restir.hip -- the reservoir pass of row N10 (pt_restir_di, DESIGN.md spec S16) as two launches: one lane per pixel, one 8x8
+// pixel block per wave64 (the PixelMap of the primary pass, so that the visibility rays of a wave stay coherent).
+//   launch 1  ri_pass1_px: the pixel's surface record from the G-buffer, initial sampling, temporal resampling -- reads only the
+//             previous call's slot, writes this call's record and reservoir
+//   launch 2  ri_pass2_px: spatial resampling over every pixel's launch-1 result (hence the launch boundary), final shading
+// Visibility rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory).
+#include "pt_trace.h"
+#include "pt_restir.h"
+
+namespace pt {
+
+namespace {
+
+// kPass2 = false: launch 1 (kTex unused: nothing is shaded with maps); kAlpha: the per-crossing alpha test of S10
+template <bool kPass2, bool kLds, typename StackT, bool kTex, bool kAlpha>
+__global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, PixelMap pm, RiBuffers b, RiParams p)
+{
+    extern __shared__ float4 smem[];
+    const float4* nodes = sv.nodes;
+    const float4* sph = sv.sph_sorted;
+    const uint32_t* ids = sv.sorted_id;
+    StackT* stack;
+    if (kLds) {
+        stage_scene(sv, smem);
+        nodes = smem;
+        sph = smem + sv.n_nodes * 4u;
+        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
+        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
+    } else {
+        stack = reinterpret_cast<StackT*>(smem);
+    }
+    stack += threadIdx.x;
+    RiScene sc;
+    sc.sph = sv.sph; sc.mats = sv.mats; sc.lights = sv.lights; sc.n_lights = sv.n_lights;
+    const uint32_t stride = blockDim.x;
+    auto trace = [&](f3 o, f3 d, float& t, uint32_t& id) { closest_hit_any<kLds, StackT, kAlpha>(sv, nodes, sph, ids, o, d, 0.0f, kInf, stack, stride, t, id); };
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
+        const PixelRef pr = slot_to_pixel(pm, slot);
+        if (!pr.valid) continue;
+        if (kPass2) ri_pass2_px(b, sc, p, pr.px, pr.py, trace, [&](uint32_t id, f3 o, f3 d, float t) { return hit_material<kTex>(sv, id, o, d, t, false).emission; });
+        else ri_pass1_px(b, sc, p, pr.px, pr.py, trace);
+    }
+}
+
+template <bool kPass2, bool kTex, bool kAlpha>
+hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream)
+{
+    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
+    const uint32_t threads = traverse_threads(lds_scene);
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
+    const void* fn = lds_scene ? (small ? (const void*)restir_kernel<kPass2, true, uint16_t, kTex, kAlpha> : (const void*)restir_kernel<kPass2, true, uint32_t, kTex, kAlpha>)
+                               : (small ? (const void*)restir_kernel<kPass2, false, uint16_t, kTex, kAlpha> : (const void*)restir_kernel<kPass2, false, uint32_t, kTex, kAlpha>);
+    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds_scene) {
+        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+        else hipLaunchKernelGGL((restir_kernel<kPass2, true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+    } else {
+        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+        else hipLaunchKernelGGL((restir_kernel<kPass2, false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream)
+{
+    // the alpha-tested walk only where some sphere's hits are tested against a map; the textured emission only where textures exist
+    const bool alpha = sv.tex_maps && sv.alpha_tested;
+    if (pass == 0) return alpha ? launch_t<false, false, true>(sv, pm, b, p, grid, stream) : launch_t<false, false, false>(sv, pm, b, p, grid, stream);
+    if (!sv.tex_maps) return launch_t<true, false, false>(sv, pm, b, p, grid, stream);
+    return alpha ? launch_t<true, true, true>(sv, pm, b, p, grid, stream) : launch_t<true, true, false>(sv, pm, b, p, grid, stream);
+}
+
+}  // namespace pt

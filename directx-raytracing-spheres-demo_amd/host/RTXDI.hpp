@@ -1,0 +1,69 @@
+// RTXDI.hpp -- C++ host mirror of the reference's RTXDI pass object as App::Impl::Render drives it (Source/App.cpp:1187-1227:
+// RTXDI::SetConstants, then RTXDI::Render between the G-buffer pass and the frame) over pt_restir_di (row N10, DESIGN.md spec S16), a
+// stand-in for the RTXDI SDK, which the reference does not vendor.  The settings are the subset of ReSTIRDI_Parameters
+// (Source/MyAppData.h:190-250) the stand-in reads; resources are DEVICE pointers of RenderSize texels (the layouts of
+// PtRestirDiTextures) instead of D3D12 textures.
+#pragma once
+
+#include <array>
+#include <cstdint>
+#include <stdexcept>
+
+#include "Raytracing.hpp"
+
+namespace dxrs {
+
+enum class ReSTIRDI_BiasCorrectionMode : uint32_t { Off = 0, Basic = 1, Pairwise = 2, Raytraced = 3 };
+
+struct ReSTIRDISettings {  // MyAppData.h:190-250 (IsEnabled = true is the reference's default frame)
+    struct { uint32_t LocalLightSamples = 8; } InitialSampling;
+    struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t MaxHistoryLength = 20; } TemporalResampling;
+    struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t Samples = 1; float Radius = 32; } SpatialResampling;
+};
+
+class RTXDI {
+public:
+    // the G-buffer textures RAB_GetGBufferSurface reads and the two textures DIFinalShading writes
+    struct Textures {
+        const void *Position{}, *GeometricNormal{}, *LinearDepth{}, *MotionVector{}, *BaseColorMetalness{}, *NormalRoughness{}, *IOR{}, *Transmission{};
+        void *Diffuse{}, *Specular{};
+    } GPUBuffers;
+
+    explicit RTXDI(DeviceContext& deviceContext) : m_ctx(deviceContext.Get())
+    {
+        if (!m_ctx) throw std::invalid_argument("null device context");
+    }
+
+    // RTXDI::SetConstants(settings, resetHistory, renderSize, frameIndex)
+    void SetConstants(const ReSTIRDISettings& settings, bool resetHistory, std::array<uint32_t, 2> renderSize, uint32_t frameIndex)
+    {
+        m_settings = PtRestirDiSettings{};
+        m_settings.RenderSize[0] = renderSize[0];
+        m_settings.RenderSize[1] = renderSize[1];
+        m_settings.FrameIndex = frameIndex;
+        m_settings.ResetHistory = resetHistory ? 1u : 0u;
+        m_settings.InitialSamples = settings.InitialSampling.LocalLightSamples;
+        m_settings.EnableTemporal = settings.TemporalResampling.IsEnabled ? 1u : 0u;
+        m_settings.TemporalBiasCorrection = static_cast<uint32_t>(settings.TemporalResampling.BiasCorrectionMode);
+        m_settings.MaxHistoryLength = settings.TemporalResampling.MaxHistoryLength;
+        m_settings.EnableSpatial = settings.SpatialResampling.IsEnabled ? 1u : 0u;
+        m_settings.SpatialBiasCorrection = static_cast<uint32_t>(settings.SpatialResampling.BiasCorrectionMode);
+        m_settings.SpatialSamples = settings.SpatialResampling.Samples;
+        m_settings.SpatialRadius = settings.SpatialResampling.Radius;
+    }
+
+    // RTXDI::Render: the DI passes of the frame the next render call renders, asynchronous
+    void Render()
+    {
+        const PtRestirDiTextures t{ GPUBuffers.Position, GPUBuffers.GeometricNormal, GPUBuffers.LinearDepth, GPUBuffers.MotionVector,
+                                    GPUBuffers.BaseColorMetalness, GPUBuffers.NormalRoughness, GPUBuffers.IOR, GPUBuffers.Transmission,
+                                    GPUBuffers.Diffuse, GPUBuffers.Specular };
+        ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
+    }
+
+private:
+    PtContext* m_ctx;
+    PtRestirDiSettings m_settings{};
+};
+
+}  // namespace dxrs

@@ -21,6 +21,8 @@
  *   pt_render_with_di        Raytracing::Render with IsDIEnabled = isReSTIRDIEnabled   Source/App.cpp:1262, Shaders/Raytracing.hlsl:150-163
  *   pt_nrd_denoise           NRD::NewFrame / Tag / SetConstants / Denoise (a stand-in for NRD, spec S15)   Source/NRD.ixx:88-140,
  *                            Source/App.cpp:1584-1638
+ *   pt_restir_di             RTXDI::SetConstants / Render: the DI passes (a stand-in for RTXDI, spec S16)   Source/App.cpp:1187-1227,
+ *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -283,7 +285,7 @@ PtStatus pt_render_denoiser(PtContext *ctx, const PtRect *rect, void *out, int o
                             const PtDenoiserOutputs *outputs, PtStats *stats);
 
 /* A frame whose direct illumination the caller supplies: the reference's frame with IsDIEnabled = isReSTIRDIEnabled
- * (Source/App.cpp:1262), whose DI the RTXDI passes make (this library has no such pass yet: the caller brings its own).  In every other respect an ordinary frame under the contract of
+ * (Source/App.cpp:1262), whose DI the RTXDI passes make (pt_restir_di below is this library's such pass; any other source of the two buffers serves as well).  In every other respect an ordinary frame under the contract of
  * pt_render (outputs == NULL: Denoiser::None) or of pt_render_denoiser (outputs: its mode and buffers), whatever
  * PtGraphicsSettings.IsDIEnabled says.  Only the source of DI changes: per pixel of the rect, DI = Diffuse.rgb + Specular.rgb
  * (Raytracing.hlsl:160; .w is not read), in place of row N4's estimate, with N4's two gates kept: DI is added only where the primary ray
@@ -346,6 +348,39 @@ typedef struct PtNrdDenoiseTextures {   /* DEVICE pointers; the reference's nrd:
     void *OutDiffuse, *OutSpecular;     /* OUT_DIFF / OUT_SPEC_RADIANCE_HITDIST: float4, what compose reads */
 } PtNrdDenoiseTextures;
 PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, const PtNrdDenoiseTextures *textures);
+
+/* Row N10 -- the reservoir pass that makes the DI pt_render_with_di takes (RTXDI::Render, Source/App.cpp:1187-1227; DESIGN.md spec S16): a
+ * ReSTIR-DI stand-in for the RTXDI SDK, which the reference does not vendor -- RIS over InitialSamples uniform (emitter, cone) candidates
+ * with one visibility ray, temporal reuse of the reprojected pixel's reservoir, spatial reuse of SpatialSamples neighbours, final shading
+ * with a visibility ray -- from the G-buffer of the frame the next render call renders (current camera and scene; Camera.PreviousPosition
+ * for the history's view vectors) to the two buffers of PtDirectLighting / PtDenoiserOutputs: Diffuse = (Le f_d W / pdf, light distance),
+ * Specular likewise with f_s.  A pixel without a surface (LinearDepth not finite, or roughness < 0.05: RTXDIAppBridge.hlsli:295), without
+ * a valid reservoir, or whose sum is zero or not finite is not written: the caller clears the buffers, as the reference's host does.
+ * With no emitters in the scene the call succeeds and writes nothing.
+ * All buffers are DEVICE pointers, float32, row-major over RenderSize (the whole frame: the rect of the pt_render_gbuffer call that made
+ * the inputs).  Runs asynchronously on the lane of the next render call and is ordered like pt_render_gbuffer (the same rotation rule for
+ * buffers; an input that the lane's own pt_render_gbuffer call did not write makes the pass wait for everything queued on the context's
+ * stream); the context's stream waits for the pass.  It adds nothing to pt_get_totals and does not advance the frame lanes.
+ * The context owns the history -- two alternating slots of a 68-byte surface record and a 32-byte reservoir per pixel -- allocated on
+ * first use and freed by pt_destroy.  The history restarts on the first call, with ResetHistory, when RenderSize changes and after
+ * pt_set_scene (emitter indices change); spheres moved by pt_update_spheres keep it.
+ * Not built (spec S16): ReGIR and Power_RIS presampling, BRDF and environment candidates, the boiling filter, checkerboard rendering,
+ * visibility reuse, pairwise MIS, the DLSS-RR SpecularHitDistance write.
+ * PT_ERR_INVALID_ARG: a null argument; a missing buffer; a float4 buffer not 16-byte aligned, GeometricNormal not 8-byte, another not
+ * 4-byte; an output overlapping an input or the other output; a value outside the ranges of PtRestirDiSettings.  PT_ERR_UNSUPPORTED:
+ * bias correction mode 2 (Pairwise).  PT_ERR_STATE: as pt_render (the pass casts rays). */
+typedef struct PtRestirDiTextures {     /* DEVICE pointers; inputs are what RAB_GetGBufferSurface reads, as pt_render_gbuffer writes them */
+    const void *Position;               /* float4 (P, PositionOffset) */
+    const void *GeometricNormal;        /* float2 */
+    const void *LinearDepth;            /* float */
+    const void *MotionVector;           /* float3 */
+    const void *BaseColorMetalness;     /* float4 */
+    const void *NormalRoughness;        /* float4 */
+    const void *IOR;                    /* float */
+    const void *Transmission;           /* float (read only where metalness < 1) */
+    void *Diffuse, *Specular;           /* float4: outputs */
+} PtRestirDiTextures;
+PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const PtRestirDiTextures *textures);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

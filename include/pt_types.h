@@ -9,6 +9,7 @@
  *   PtGraphicsSettings == _GraphicsSettings   Source/Raytracing.ixx:151-166 (== Shaders/Raytracing.hlsl:21-39), 80 B
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
+ *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
  * geosphere mesh (Source/Scene.ixx:188-203: scale = 2*radius, z flipped): the
@@ -172,6 +173,22 @@ typedef struct PtNrdDenoiseSettings {
     uint32_t AtrousIterations;    /* 28: 0 -> 5, at most 8 */
 } PtNrdDenoiseSettings;
 
+/* Row N10 (pt_restir_di, the RTXDI stand-in of DESIGN.md spec S16): what RTXDI::SetConstants hands the DI passes (Source/App.cpp:1187-1227;
+ * defaults of Source/MyAppData.h:190-250). */
+typedef struct PtRestirDiSettings {
+    uint32_t RenderSize[2];          /*  0: 1..16384 each */
+    uint32_t FrameIndex;             /*  8: seeds the pass's own RNG streams */
+    uint32_t ResetHistory;           /* 12: nonzero = ignore the history (m_resetHistory) */
+    uint32_t InitialSamples;         /* 16: 0 -> 8, at most 32 (InitialSampling.LocalLight.Samples) */
+    uint32_t EnableTemporal;         /* 20: 0 / 1 */
+    uint32_t TemporalBiasCorrection; /* 24: 0 Off, 1 Basic, 3 Raytraced; 2 (Pairwise) -> PT_ERR_UNSUPPORTED */
+    uint32_t MaxHistoryLength;       /* 28: 0 -> 20; a history reservoir's M is capped at this many times the current M */
+    uint32_t EnableSpatial;          /* 32: 0 / 1 */
+    uint32_t SpatialBiasCorrection;  /* 36: as the temporal field */
+    uint32_t SpatialSamples;         /* 40: 0 -> 1, at most 32 */
+    float SpatialRadius;             /* 44: pixels; 0 -> 32; finite and >= 0 (radii above 16384 act as 16384) */
+} PtRestirDiSettings;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -194,6 +211,8 @@ static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositi
               "NRDComposition::Constants layout");
 static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
               && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
+static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
+              && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -205,6 +224,8 @@ _Static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdComposit
                "NRDComposition::Constants layout");
 _Static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
                && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
+_Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
+               && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

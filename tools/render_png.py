@@ -2,10 +2,11 @@
 """Render the demo scene on the GPU and write a PNG through the product's own display path: N frames of the path tracer
 with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom] -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
 R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: --frames frames of a resting camera through it with the
-NRD stand-in, row N9).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through pt_render_gbuffer -> pt_restir_di -> pt_render_with_di,
+row N10, accumulated).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di]"""
 import argparse
 import os
 import sys
@@ -64,6 +65,9 @@ def main():
     ap.add_argument("--nrd-denoise", default=None, choices=["ReBLUR", "ReLAX"],
                     help="--frames frames of a resting camera through the NRD path with pt_nrd_denoise for NRD (row N9): pt_render_gbuffer "
                          "-> pt_render_denoiser -> pack -> denoise -> compose; the last frame, tone mapped")
+    ap.add_argument("--restir-di", action="store_true",
+                    help="--frames frames of a resting camera whose direct illumination the reservoir pass makes (row N10): pt_render_gbuffer "
+                         "-> pt_restir_di (the history running) -> pt_render_with_di, accumulated, tone mapped")
     args = ap.parse_args()
     from PIL import Image
 
@@ -107,6 +111,22 @@ def main():
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
+    if args.restir_di:
+        r.set_camera(host.camera_matrices(w, h, jitter=False))
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            r.set_constants(gs)
+            dd, ds, _ = r.restir_di(fill=0.0, reset_history=k == 0)  # (cleared outputs: a pixel without DI keeps 0)
+            r.render_with_di_device(frame.data_ptr(), dd.data_ptr(), ds.data_ptr())
+            r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
+            r.synchronize()
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(accum.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"ReSTIR DI (pt_restir_di, {args.frames} frames) {w}x{h} -> {args.out}")
+        r.close()
+        return
     if args.nrd_denoise:
         mode = t.DENOISER_NRD_REBLUR if args.nrd_denoise == "ReBLUR" else t.DENOISER_NRD_RELAX
         r.set_camera(host.camera(w, h, jitter=False))
