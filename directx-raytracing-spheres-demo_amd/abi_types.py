@@ -118,6 +118,22 @@ class PtRestirDiTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in RESTIR_DI_TEXTURES]
 
 
+# Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in): the settings, the XeSSResourceType tags it reads and writes, and the modes of
+# pt_upscale_input_size (SuperResolutionMode)
+UPSCALE_TEXTURES = ("Color", "Depth", "Velocity", "Output")
+UPSCALE_AUTO, UPSCALE_NATIVE, UPSCALE_QUALITY, UPSCALE_BALANCED, UPSCALE_PERFORMANCE, UPSCALE_ULTRA_PERFORMANCE = 0, 1, 2, 3, 4, 5
+UPSCALE_MODES = {"auto": 0, "native": 1, "quality": 2, "balanced": 3, "performance": 4, "ultra_performance": 5}
+
+
+class PtUpscaleSettings(C.Structure):
+    _fields_ = [("InputSize", C.c_uint32 * 2), ("OutputSize", C.c_uint32 * 2), ("Jitter", C.c_float * 2), ("Reset", C.c_uint32),
+                ("MaxHistoryWeight", C.c_float)]
+
+
+class PtUpscaleTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in UPSCALE_TEXTURES]
+
+
 # pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
 class PtDirectLighting(C.Structure):
     _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]

@@ -9,7 +9,8 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtGBuffer, PtGraphicsSettings, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtRestirDiTextures, PtSceneData, PtStats, RESTIR_DI_TEXTURES)
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
+                        RESTIR_DI_TEXTURES, UPSCALE_TEXTURES)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -18,7 +19,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_upscale", "pt_upscale_input_size", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -100,6 +101,10 @@ class HipLib:
         lib.pt_nrd_denoise.argtypes = [vp, C.POINTER(PtNrdDenoiseSettings), C.POINTER(PtNrdDenoiseTextures)]
         lib.pt_restir_di.restype = C.c_int
         lib.pt_restir_di.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtRestirDiTextures)]
+        lib.pt_upscale.restype = C.c_int
+        lib.pt_upscale.argtypes = [vp, C.POINTER(PtUpscaleSettings), C.POINTER(PtUpscaleTextures)]
+        lib.pt_upscale_input_size.restype = C.c_int
+        lib.pt_upscale_input_size.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -137,6 +142,14 @@ class HipLib:
         lib.pt_version.restype = C.c_char_p
         lib.pt_version.argtypes = []
 
+
+    def upscale_input_size(self, mode, out_w, out_h):
+        """pt_upscale_input_size (no GPU needed): the RenderSize of a super-resolution mode (abi_types.UPSCALE_*) for an output size"""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        st = self.lib.pt_upscale_input_size(mode, out_w, out_h, C.byref(w), C.byref(h))
+        if st != 0:
+            raise PtError(st, "pt_upscale_input_size")
+        return w.value, h.value
 
     def lbvh_build_host(self, spheres, sah=False):
         """Host LBVH builder, or with sah=True the host SAH builder of small scenes (no GPU needed)
@@ -540,6 +553,24 @@ class Renderer:
         self.synchronize()
         return dd, ds, gb
 
+    def upscale_device(self, input_size, output_size, buffers, jitter=(0.0, 0.0), reset=False, max_history_weight=0.0):
+        """The super-resolution stand-in (row N11, DESIGN.md spec S17): Color / Depth / Velocity at input_size = (w, h) -> Output at
+        output_size = (W, H), with the history the context keeps.  buffers: {UPSCALE_TEXTURES name: device pointer}.  jitter: what the
+        reference hands XeSS, -PtCamera.Jitter.  Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(UPSCALE_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown upscale buffers {sorted(unknown)}")
+        s = PtUpscaleSettings(InputSize=(C.c_uint32 * 2)(*input_size), OutputSize=(C.c_uint32 * 2)(*output_size), Jitter=(C.c_float * 2)(*jitter),
+                              Reset=1 if reset else 0, MaxHistoryWeight=max_history_weight)
+        t = PtUpscaleTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_upscale(self._ctx, C.byref(s), C.byref(t)))
+
+    def upscaler(self, output_size, mode=0, device=None, **settings):
+        """An `upscale(color, depth, velocity, jitter)` that keeps the sizes and settings across frames and runs pt_upscale (row N11):
+        output_size = (W, H); mode: abi_types.UPSCALE_* (its `input_size` is the RenderSize to render at).  settings: upscale_device's
+        keywords.  Successive frames continue the context's history; `reset()` makes the next frame restart it."""
+        return Upscaler(self, output_size, mode, device, settings)
+
     def nrd_denoiser(self, mode, rect=None, device=None, **settings):
         """A `denoise(diffuse, specular)` for nrd_chain that runs pt_nrd_denoise (row N9) in place of the identity copy: it carries the
         MotionVector buffer nrd_chain fills (its `gbuffer` attribute) and the G-buffer's LinearDepth / NormalRoughness it is handed
@@ -617,3 +648,31 @@ class NrdDenoiser:
         self._r.synchronize()
         self._restart = False
         return od, os_
+
+
+class Upscaler:
+    """Renderer.upscaler: render at `input_size`, then call with the frame's torch buffers -> the torch float32 (H, W, 4) frame at
+    output size, backed by pt_upscale."""
+
+    def __init__(self, renderer, output_size, mode, device, settings):
+        import torch
+        self._r, self.mode, self.settings = renderer, mode, dict(settings)
+        self.output_size = tuple(int(x) for x in output_size)
+        self.input_size = load_hip().upscale_input_size(mode, *self.output_size)
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.output = torch.zeros((self.output_size[1], self.output_size[0], 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self._reset = True
+
+    def reset(self):
+        self._reset = True
+
+    def __call__(self, color, depth, velocity, jitter=(0.0, 0.0)):
+        """color (h, w, 4), depth (h, w[, 1]), velocity (h, w, 3): contiguous torch float32 CUDA tensors the context's stream may read
+        (synchronise torch's stream first if it wrote them).  jitter: -PtCamera.Jitter.  Asynchronous; returns `output`."""
+        self._r.upscale_device(self.input_size, self.output_size, dict(Color=color.data_ptr(), Depth=depth.data_ptr(), Velocity=velocity.data_ptr(),
+                                                                       Output=self.output.data_ptr()),
+                               jitter=jitter, reset=self._reset or self.settings.get("reset", False),
+                               **{k: v for k, v in self.settings.items() if k != "reset"})
+        self._reset = False
+        return self.output

@@ -23,6 +23,7 @@
 #include "pt_bloom.h"
 #include "pt_nrd.h"
 #include "pt_denoise.h"
+#include "pt_upscale.h"
 #include "pt_restir.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
@@ -196,6 +197,12 @@ struct PtContext {
     float* d_dn = nullptr;
     uint32_t dn_w = 0, dn_h = 0, dn_mode = 0, dn_slot = 0;
     bool dn_valid = false;
+    // pt_upscale's history (row N11; used on `stream` only): per output pixel two alternating slots of a float4 and a float, allocated
+    // on first use and again when the output size (up_W, up_H) changes; a change of either size restarts it; `up_slot` = the slot the
+    // last call wrote
+    float4* d_up = nullptr;
+    uint32_t up_w = 0, up_h = 0, up_W = 0, up_H = 0, up_slot = 0;
+    bool up_valid = false;
     // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
     // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
     // pt_set_scene count it was made under (emitter indices change with the scene), `ev_ri` = the last call's launches have finished
@@ -1445,6 +1452,7 @@ void pt_destroy(PtContext* c)
     free_dev(c->d_out);
     free_dev(c->d_bloom);
     free_dev(c->d_dn);
+    free_dev(c->d_up);
     free_dev(c->d_ri);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
@@ -2340,6 +2348,82 @@ PtStatus pt_nrd_denoise(PtContext* c, const PtNrdDenoiseSettings* s, const PtNrd
     c->dn_slot = cur;
     c->dn_mode = s->Denoiser;
     c->dn_valid = true;
+    return PT_OK;
+}
+
+// Row N11 -- the super-resolution stand-in (DESIGN.md spec S17): one launch on the context's stream, the history in the context.
+// Per output pixel and slot: a float4 (t-space colour, accumulated weight) and a float (depth).
+constexpr uint64_t kUpSlotBytesPerPixel = sizeof(float4) + sizeof(float);
+
+PtStatus pt_upscale(PtContext* c, const PtUpscaleSettings* s, const PtUpscaleTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: null pointer");
+    const uint32_t w = s->InputSize[0], h = s->InputSize[1], W = s->OutputSize[0], H = s->OutputSize[1];
+    if (w == 0 || h == 0 || w > kUpMaxSize || h > kUpMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: InputSize must be in [1, 16384]");
+    if (W < w || H < h || W > kUpMaxSize || H > kUpMaxSize || (uint64_t)W > (uint64_t)kUpMaxRatio * w || (uint64_t)H > (uint64_t)kUpMaxRatio * h)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: OutputSize must be in [InputSize, 4 * InputSize] per axis and at most 16384");
+    for (const float j : { s->Jitter[0], s->Jitter[1] })
+        if (!is_finite(j) || !(pt_abs(j) <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: Jitter must be finite and within [-1, 1]");
+    float max_a = s->MaxHistoryWeight;
+    if (max_a == 0.0f) max_a = kUpDefaultHistoryWeight;
+    if (!is_finite(max_a) || !(max_a >= kUpMinHistoryWeight && max_a <= kUpMaxHistoryWeight))
+        return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: MaxHistoryWeight must be 0 or in [1, 256]");
+    const uint64_t n_in = (uint64_t)w * h, n_out = (uint64_t)W * H;
+    // (pointer, bytes, alignment)
+    struct Use { const void* p; uint64_t bytes; uint32_t align; const char* name; };
+    const Use use[4] = { {t->Color, n_in * 16, 16, "Color"}, {t->Depth, n_in * 4, 4, "Depth"}, {t->Velocity, n_in * 12, 4, "Velocity"},
+                         {t->Output, n_out * 16, 16, "Output"} };
+    for (const Use& u : use) {
+        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: ") + u.name + " is required");
+        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
+            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
+    }
+    // the output must not share a byte with an input (a workgroup reads the inputs of its neighbours' pixels)
+    for (int i = 0; i < 3; i++) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(use[3].p), pb = reinterpret_cast<uintptr_t>(use[i].p);
+        if (pa < pb + use[i].bytes && pb < pa + use[3].bytes) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: Output overlaps ") + use[i].name);
+    }
+    PT_HIP(c, hipSetDevice(c->device));
+    bool restart = s->Reset != 0 || !c->up_valid || c->up_w != w || c->up_h != h;
+    if (!c->d_up || c->up_W != W || c->up_H != H) {
+        // the history is only used on `stream`: once the calls queued there have finished, the old one is free (the render lanes never
+        // touch it, so their frames in flight go on)
+        if (c->d_up) PT_HIP(c, hipStreamSynchronize(c->stream));
+        free_dev(c->d_up);
+        c->up_valid = false;
+        c->up_W = c->up_H = 0;
+        PT_HIP(c, hipMalloc(&c->d_up, 2 * n_out * kUpSlotBytesPerPixel));
+        c->up_W = W;
+        c->up_H = H;
+        restart = true;
+    }
+    const uint32_t cur = c->up_slot ^ 1u, prev = c->up_slot;
+    float* zs = reinterpret_cast<float*>(c->d_up + 2 * n_out);
+    UpBuffers b{};
+    b.color = static_cast<const float4*>(t->Color);
+    b.depth = static_cast<const float*>(t->Depth);
+    b.velocity = static_cast<const float*>(t->Velocity);
+    b.out = static_cast<float4*>(t->Output);
+    b.prev_hist = c->d_up + prev * n_out;
+    b.prev_z = zs + prev * n_out;
+    b.hist = c->d_up + cur * n_out;
+    b.hist_z = zs + cur * n_out;
+    const UpParams P = up_params(w, h, W, H, s->Jitter[0], s->Jitter[1], max_a);
+    PT_HIP(c, launch_upscale(b, P, restart, c->stream));
+    c->up_slot = cur;
+    c->up_w = w;
+    c->up_h = h;
+    c->up_valid = true;
+    return PT_OK;
+}
+
+PtStatus pt_upscale_input_size(uint32_t mode, uint32_t out_w, uint32_t out_h, uint32_t* w, uint32_t* h)
+{
+    if (!w || !h || mode > kUpModeUltraPerformance || out_w == 0 || out_h == 0) return PT_ERR_INVALID_ARG;
+    const uint32_t r10 = up_ratio10(mode == kUpModeAuto ? up_auto_mode(out_w, out_h) : mode);
+    *w = up_input_extent(out_w, r10);
+    *h = up_input_extent(out_h, r10);
     return PT_OK;
 }
 

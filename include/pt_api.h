@@ -23,6 +23,8 @@
  *                            Source/App.cpp:1584-1638
  *   pt_restir_di             RTXDI::SetConstants / Render: the DI passes (a stand-in for RTXDI, spec S16)   Source/App.cpp:1187-1227,
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
+ *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
+ *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -381,6 +383,35 @@ typedef struct PtRestirDiTextures {     /* DEVICE pointers; inputs are what RAB_
     void *Diffuse, *Specular;           /* float4: outputs */
 } PtRestirDiTextures;
 PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const PtRestirDiTextures *textures);
+
+/* Row N11 -- the super-resolution stand-in (XeSS::Execute as App::ProcessXeSSSuperResolution drives it, Source/App.cpp:1682-1708; DESIGN.md
+ * spec S17): a temporal upscaler of the TAAU / FSR2 family, for XeSS and DLSS-SR, which the reference does not vendor.  From the jittered
+ * radiance of a frame rendered at InputSize (PtCamera.Jitter), its G-buffer LinearDepth and MotionVector, to the frame at OutputSize
+ * that pt_bloom and pt_tonemap take: a Lanczos-2 resample of the 3 x 3 input pixels around each output pixel in a tone-mapped space,
+ * blended with the history reprojected along the nearest-depth tap's motion vector and clamped to the taps' range.
+ * On the context's stream (asynchronous), ordered like pt_nrd_composition and pt_bloom: after what is already queued there, before
+ * whatever the caller queues next; it adds nothing to pt_get_totals and the render lanes never touch its state.  The context owns the
+ * history -- two alternating slots per output pixel of a float4 (tone-space colour, accumulated weight) and a float (depth) --
+ * allocated on first use, allocated again when OutputSize changes (which waits for the context's stream only; its size depends on
+ * OutputSize alone, so a change of InputSize keeps the allocation) and freed by pt_destroy.  The history restarts on the first call,
+ * with Reset, and on any change of InputSize or OutputSize.
+ * Not built (spec S17): exposure handling (ExposureScale), a responsive-pixel mask, a bicubic history tap, FSR2's locks and reactive
+ * masks, sharpening / NIS, DLSS frame generation, tile and multi-GPU entry points.
+ * PT_ERR_INVALID_ARG: a null argument or buffer; a size outside the ranges of PtUpscaleSettings; a Jitter or MaxHistoryWeight that is
+ * not finite or out of range; Color or Output not 16-byte aligned, Depth or Velocity not 4-byte aligned; Output overlapping an input. */
+typedef struct PtUpscaleTextures {      /* DEVICE pointers; the reference's XeSSResourceType tags */
+    const void *Color;                  /* float4, InputSize  (pt_render out / the composed Radiance) */
+    const void *Depth;                  /* float,  InputSize  (G-buffer LinearDepth, +inf on a miss) */
+    const void *Velocity;               /* float3, InputSize  (G-buffer MotionVector: .xy input pixels, .z view depth) */
+    void *Output;                       /* float4, OutputSize */
+} PtUpscaleTextures;
+PtStatus pt_upscale(PtContext *ctx, const PtUpscaleSettings *settings, const PtUpscaleTextures *textures);
+/* xessGetInputResolution plus the reference's Auto rule (Source/App.cpp:1374-1450); needs no context and no GPU.  mode: 0 Auto (by the
+ * output's pixel count: <= 1280*800 Native, <= 1920*1200 Quality, <= 2560*1600 Balanced, <= 3840*2400 Performance, else
+ * UltraPerformance), 1 Native, 2 Quality, 3 Balanced, 4 Performance, 5 UltraPerformance; scale ratios x 10 = {10, 15, 17, 20, 30};
+ * *w = max(1, (out_w * 10 + r10 / 2) / r10) in integer arithmetic, *h likewise.  PT_ERR_INVALID_ARG: an unknown mode, a zero size, a
+ * null pointer. */
+PtStatus pt_upscale_input_size(uint32_t mode, uint32_t out_w, uint32_t out_h, uint32_t *w, uint32_t *h);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

@@ -8,6 +8,7 @@
  *   PtSceneData        == SceneData           Source/CommonShaderData.ixx:15-20 (== Shaders/Common.hlsli:7-13), 80 B payload
  *   PtGraphicsSettings == _GraphicsSettings   Source/Raytracing.ixx:151-166 (== Shaders/Raytracing.hlsl:21-39), 80 B
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
+ *   PtUpscaleSettings     (row N11) the XeSSSettings App::ProcessXeSSSuperResolution fills, plus the output size and the history cap, 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
@@ -189,6 +190,16 @@ typedef struct PtRestirDiSettings {
     float SpatialRadius;             /* 44: pixels; 0 -> 32; finite and >= 0 (radii above 16384 act as 16384) */
 } PtRestirDiSettings;
 
+/* Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in of DESIGN.md spec S17): XeSSSettings as App::ProcessXeSSSuperResolution fills it
+ * (Source/App.cpp:1685-1690; InputSize, Jitter, Reset), the output size XeSS is created with, and the stand-in's history cap. */
+typedef struct PtUpscaleSettings {
+    uint32_t InputSize[2];        /*  0: RenderSize of the inputs, 1..16384 each */
+    uint32_t OutputSize[2];       /*  8: InputSize <= OutputSize <= 4 * InputSize per axis, at most 16384 */
+    float Jitter[2];              /* 16: what the host hands XeSS: -PtCamera.Jitter, in pixels of the input; finite, |.| <= 1 */
+    uint32_t Reset;               /* 24: nonzero = ignore the history (m_resetHistory) */
+    float MaxHistoryWeight;       /* 28: 0 -> 16; finite, 1..256 */
+} PtUpscaleSettings;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -213,6 +224,8 @@ static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSetting
               && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
               && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
+static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
+              && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -226,6 +239,8 @@ _Static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettin
                && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 _Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
                && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
+_Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
+               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

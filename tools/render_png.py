@@ -3,10 +3,11 @@
 with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom] -> pt_tonemap (ACES filmic + sRGB, the reference's SDR default) ->
 R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: --frames frames of a resting camera through it with the
 NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through pt_render_gbuffer -> pt_restir_di -> pt_render_with_di,
-row N10, accumulated).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+row N10, accumulated; --upscale MODE: --frames frames of a resting camera rendered at the mode's input size with Halton jitter and
+upscaled to --width x --height by pt_upscale, row N11).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance]"""
 import argparse
 import os
 import sys
@@ -68,6 +69,10 @@ def main():
     ap.add_argument("--restir-di", action="store_true",
                     help="--frames frames of a resting camera whose direct illumination the reservoir pass makes (row N10): pt_render_gbuffer "
                          "-> pt_restir_di (the history running) -> pt_render_with_di, accumulated, tone mapped")
+    ap.add_argument("--upscale", default=None, metavar="MODE", choices=list(dxrs_amd.types.UPSCALE_MODES),
+                    help="--frames frames of a resting camera rendered at the mode's input size (pt_upscale_input_size) with Halton jitter (row "
+                         "N11): pt_render_gbuffer (LinearDepth, MotionVector) -> pt_render -> pt_upscale to --width x --height [-> pt_bloom with "
+                         "--bloom] -> the tone map at output size; the last frame")
     args = ap.parse_args()
     from PIL import Image
 
@@ -111,6 +116,33 @@ def main():
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
+    if args.upscale:
+        up = r.upscaler((w, h), mode=t.UPSCALE_MODES[args.upscale])
+        iw, ih = up.input_size
+        color = torch.zeros((ih, iw, 4), dtype=torch.float32, device="cuda")
+        depth = torch.zeros((ih, iw), dtype=torch.float32, device="cuda")
+        velocity = torch.zeros((ih, iw, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        gs = t.graphics_settings(iw, ih, bounces=args.bounces, spp=args.spp)
+        prev_cam = None
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            cam = host.camera_matrices(iw, ih, jitter_index=k, jitter_count=32, previous=prev_cam)
+            prev_cam = cam
+            r.set_camera(cam)
+            r.set_constants(gs)
+            r.render_gbuffer_device(dict(LinearDepth=depth.data_ptr(), MotionVector=velocity.data_ptr()))
+            r.render_device(color.data_ptr())
+            hdr = up(color, depth, velocity, jitter=(-cam.Jitter[0], -cam.Jitter[1]))
+        if args.bloom is not None:
+            r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"upscale {args.upscale} (pt_upscale, {args.frames} frames) {iw}x{ih} -> {w}x{h} -> {args.out}")
+        r.close()
+        return
     if args.restir_di:
         r.set_camera(host.camera_matrices(w, h, jitter=False))
         for k in range(args.frames):
