@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
     "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_upscale", "pt_upscale_input_size", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
-    "pt_accel_download_order", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
+    "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
 
@@ -113,6 +113,8 @@ class HipLib:
         lib.pt_accel_download.argtypes = [vp, vp, u32]
         lib.pt_accel_download_order.restype = C.c_int
         lib.pt_accel_download_order.argtypes = [vp, vp, u32]
+        lib.pt_accel_download_wide.restype = C.c_int
+        lib.pt_accel_download_wide.argtypes = [vp, vp, u32, C.POINTER(u32)]
         lib.pt_lbvh_build_host.restype = C.c_int
         lib.pt_lbvh_build_host.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
         lib.pt_sah_build_host.restype = C.c_int
@@ -612,6 +614,15 @@ class Renderer:
         order = np.zeros(self.accel.leaf_count, dtype=np.uint32)
         self._check(self._lib.pt_accel_download_order(self._ctx, order.ctypes.data, len(order)))
         return nodes, order
+
+    def download_wide(self):
+        """The 4-wide view of the tree (pt_accel_download_wide) -> (node_count, 16) uint32, record i in row i (rows of odd-depth
+        nodes are zero); None when the scene is not walked through one (LDS-resident, a single node, PT_WIDE=0)."""
+        n = self.accel.node_count
+        words = np.zeros((max(n, 1), 16), dtype=np.uint32)
+        has = C.c_uint32(0)
+        self._check(self._lib.pt_accel_download_wide(self._ctx, words.ctypes.data, n, C.byref(has)))
+        return words[:n] if has.value else None
 
 
 class NrdDenoiser:

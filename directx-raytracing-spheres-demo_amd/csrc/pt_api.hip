@@ -257,6 +257,7 @@ struct PtContext {
         bool have_vel = false;
     } beam;
     uint64_t scene_gen = 0;  // bumped by everything that changes what a ray can hit
+    float slab_tiny = 1e-30f;  // SceneView::slab_tiny of the tree pt_build_accel made
     float min_radius = 0.0f;  // smallest sphere of the scene set by pt_set_scene (bounds the slack of a moving camera's beam lists)
 
     // multi-GPU exchange (pt_comm_init / pt_gather): the RCCL communicator of this rank
@@ -547,6 +548,7 @@ SceneView make_scene_view(const PtContext* c, const Lane* L = nullptr)
     // heavy tail): 3.99 -> 2.54 ms per frame there with any bound from 2 to 24; LDS-resident scenes (coherent, shallow) gain nothing.
     sv.descent_cap = c->lds_scene ? 0u : knob_or(c->knobs.descent, 8u);
     sv.lds_scene = c->lds_scene ? 1u : 0u;
+    sv.slab_tiny = c->slab_tiny;  // (of the tree pt_build_accel made: a lane's refitted private tree keeps it, pt_update_spheres does not look at coordinates)
     for (int i = 0; i < 4; i++) sv.env[i] = c->sd.EnvironmentLightColor[i];
     if (c->has_textures) { sv.tex = c->d_tex; sv.tex_maps = c->d_tex_maps; sv.rot = (c->rot_gen != c->rot_master_gen && L && L->d_rot && L->rot_gen == c->rot_gen) ? L->d_rot : c->d_rot; }
     sv.env_tex = c->sd.EnvironmentLightTextureDescriptor;  // ~0u == kNoTexture; render_common has checked it against the table
@@ -1613,6 +1615,13 @@ PtStatus pt_build_accel(PtContext* c, PtAccelInfo* info)
         c->lbvh.pad = gi.pad;
         for (int a = 0; a < 3; a++) { c->lbvh.bounds_min[a] = gi.bounds_min[a]; c->lbvh.bounds_max[a] = gi.bounds_max[a]; }
     }
+    // A zero ray-direction component is walked as +-1e-30 (slab_rcp, pt_trace.h), which needs |coordinate| * 1e30 and a node's extent * 1e30 to
+    // stay finite.  Beyond that the component's axis takes no part in the slab tests: NaN ray parameters, which their min / max drop.
+    {
+        float smax = 0.0f;
+        for (int a = 0; a < 3; a++) smax = std::max(smax, std::max(std::fabs(c->lbvh.bounds_min[a]), std::fabs(c->lbvh.bounds_max[a])));
+        c->slab_tiny = smax < 1e8f ? 1e-30f : std::numeric_limits<float>::quiet_NaN();
+    }
     // stage the BVH in LDS when scene + stacks leave room for two workgroups per CU
     const uint32_t scene_bytes = traverse_lds_bytes_for(c->n_nodes, n, 0, true);
     c->lds_scene = !(c->flags & PT_FLAG_NO_LDS_SCENE) && scene_bytes <= kLdsSceneBudget
@@ -1622,6 +1631,8 @@ PtStatus pt_build_accel(PtContext* c, PtAccelInfo* info)
     free_dev(c->d_wide);
     if (!c->lds_scene && c->n_nodes > 1 && knob_or(c->knobs.wide, 1u) != 0) {
         PT_HIP(c, hipMalloc(&c->d_wide, (size_t)c->n_nodes * 4u * sizeof(float4)));
+        // only the even-depth slots are written: the others read as zero (pt_accel_download_wide is deterministic)
+        PT_HIP(c, hipMemsetAsync(c->d_wide, 0, (size_t)c->n_nodes * 4u * sizeof(float4), c->stream));
         PT_HIP(c, lbvh_gpu_collapse4(reinterpret_cast<const PtBvhNode*>(c->d_nodes), c->n_nodes, c->d_wide, c->stream));
         PT_HIP(c, hipStreamSynchronize(c->stream));
     }
@@ -2674,6 +2685,21 @@ PtStatus pt_accel_download_order(PtContext* c, uint32_t* sorted_id, uint32_t cap
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipMemcpyAsync(sorted_id, c->d_sorted_id, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     PT_HIP(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+PtStatus pt_accel_download_wide(PtContext* c, uint32_t* words, uint32_t capacity_nodes, uint32_t* has_wide)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!c->accel_valid) return fail(c, PT_ERR_STATE, "pt_accel_download_wide: no accel");
+    if (!has_wide) return fail(c, PT_ERR_INVALID_ARG, "pt_accel_download_wide: null pointer");
+    *has_wide = 0;
+    if (!c->d_wide) return PT_OK;  // LDS-resident scene, a single node, or PT_WIDE=0: the binary records are what is walked
+    if (!words || capacity_nodes < c->n_nodes) return fail(c, PT_ERR_INVALID_ARG, "pt_accel_download_wide: buffer too small");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipMemcpyAsync(words, c->d_wide, (size_t)c->n_nodes * 16u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    *has_wide = 1;
     return PT_OK;
 }
 

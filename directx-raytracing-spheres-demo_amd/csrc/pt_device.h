@@ -58,6 +58,7 @@ struct SceneView {
     uint32_t stack_depth;       // traversal stack entries per lane
     uint32_t descent_cap;       // global-memory scenes: node visits per lane before the wave turns to its sphere tests (0 = unbounded)
     uint32_t lds_scene;         // 1: kernels stage nodes + sph_sorted + sorted_id in LDS
+    float slab_tiny;            // what slab_rcp puts in place of a zero direction component: 1e-30, or NaN where the scene's coordinates are too large for it
     float env[4];               // SceneData.EnvironmentLightColor
     // row N1 (textured spheres); null when the scene has no textures
     const TexView* tex;         // texture table

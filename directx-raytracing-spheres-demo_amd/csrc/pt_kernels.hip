@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void traverse_dyn_kernel(SceneView sv, RayQueu
             if (!active && my < count) {
                 const float4 a = q.q0[my], b = q.q1[my];
                 o = make_f3(a.x, a.y, a.z); d = make_f3(b.x, b.y, b.z);
-                ix = slab_rcp(d.x); iy = slab_rcp(d.y); iz = slab_rcp(d.z);
+                ix = slab_rcp(d.x, sv.slab_tiny); iy = slab_rcp(d.y, sv.slab_tiny); iz = slab_rcp(d.z, sv.slab_tiny);
                 ox = -o.x * ix; oy = -o.y * iy; oz = -o.z * iz;
                 node = 0; sp = 0; best = kInf; best_id = kMissId;
                 idx = my; active = true;

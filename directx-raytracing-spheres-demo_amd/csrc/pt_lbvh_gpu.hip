@@ -545,7 +545,8 @@ constexpr int kEmptyChild = (int)0x80000000;
 
 __device__ __forceinline__ float wide_cell(float extent, uint32_t& biased_exp)
 {
-    // smallest power of two c with 254 * c >= extent (one step of headroom for the outward rounding below)
+    // smallest power of two c ABOVE x = fp32(extent * fp32(1 / 254)), so 254 * c >= extent (one step of headroom for the outward rounding
+    // below); an x that is itself a power of two takes the next one.  No extent: 2^-100; never below 2^-120.  tests/wide_reference.py restates this.
     int e = 0;
     const float m = frexpf(extent * (1.0f / 254.0f), &e);  // extent / 254 = m * 2^e, m in [0.5, 1)
     (void)m;

@@ -20,14 +20,17 @@ __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcp
 
 // Reciprocal of a ray-direction component for the slab test t = fma(plane, inv, -o * inv).  A zero (or denormal-tiny)
 // component would give inv = inf and then inf - inf = NaN for the planes on one side of the origin, and fmax(-inf, NaN)
-// = -inf would wrongly close the slab: the component is replaced by +-1e-30, which keeps every product finite (scene
-// coordinates are far below 1e8) and makes the slab interval (-huge, +huge) when the origin lies between the planes and
-// empty otherwise -- the exact behaviour of an axis-parallel ray.  Found by tests/test_gpu_fuzz.py (centre column of
-// an odd-width frame with zero jitter: d.x == 0).
-__device__ __forceinline__ float slab_rcp(float d)
+// = -inf would wrongly close the slab: the component is replaced by +-`tiny` (SceneView::slab_tiny).  In a scene whose
+// coordinates stay below 1e8 that is 1e-30, which keeps -o * inv finite for every origin between two planes and makes the
+// slab interval (-huge, +huge) when the origin lies between the planes and empty otherwise -- the exact behaviour of an
+// axis-parallel ray.  Found by tests/test_gpu_fuzz.py (centre column of an odd-width frame with zero jitter: d.x == 0).
+// In a larger scene -o * 1e30 (and the wide walk's cell * 1e30) would overflow to an infinity of ONE sign for both planes
+// of a slab that holds the origin and close it; there `tiny` is NaN, every ray parameter of that axis is NaN, and the
+// min / max of the slab test drop them: the axis does not cull, which is conservative.  Found by tests/test_gpu_wide.py
+// (`geometric`: coordinates up to 1e25).
+__device__ __forceinline__ float slab_rcp(float d, float tiny)
 {
-    const float kTiny = 1e-30f;
-    return fast_rcp(__builtin_fabsf(d) < kTiny ? __builtin_copysignf(kTiny, d) : d);
+    return fast_rcp(__builtin_fabsf(d) < 1e-30f ? __builtin_copysignf(tiny, d) : d);
 }
 
 // Adds the sum of `v` over the workgroup to *counter with ONE atomic (wave shuffle -> LDS -> thread 0).  Same-address
@@ -227,7 +230,7 @@ __device__ __forceinline__ void closest_hit(const SceneView& sv, const float4* _
         t_out = best; id_out = best_id;
         return;
     }
-    const float ix = slab_rcp(d.x), iy = slab_rcp(d.y), iz = slab_rcp(d.z);
+    const float ix = slab_rcp(d.x, sv.slab_tiny), iy = slab_rcp(d.y, sv.slab_tiny), iz = slab_rcp(d.z, sv.slab_tiny);
     const float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
     int node = 0;
     uint32_t sp = 0;  // stack offset in elements: a multiple of `stride` (entry e of this lane lives at stack[e * stride])
@@ -367,7 +370,7 @@ __device__ __forceinline__ float group_min(float v, uint32_t k)
 template <typename StackT>
 __device__ __forceinline__ void closest_hit_coop(const float4* __restrict__ nodes, const float4* __restrict__ sph, const uint32_t* __restrict__ ids,
                                                  const int* __restrict__ s_cut, unsigned long long ballot, f3 o, f3 d, float tmin, float tmax,
-                                                 StackT* stack, uint32_t stride, float& t_out, uint32_t& id_out, uint32_t descent_cap = 0)
+                                                 StackT* stack, uint32_t stride, float& t_out, uint32_t& id_out, uint32_t descent_cap, float slab_tiny)
 {
     const uint32_t lane = lane_id();
     const uint32_t n_live = (uint32_t)__builtin_amdgcn_readfirstlane(__popcll(ballot));
@@ -391,7 +394,7 @@ __device__ __forceinline__ void closest_hit_coop(const float4* __restrict__ node
     const f3 ro = make_f3(__shfl(o.x, (int)src, 64), __shfl(o.y, (int)src, 64), __shfl(o.z, (int)src, 64));
     const f3 rd = make_f3(__shfl(d.x, (int)src, 64), __shfl(d.y, (int)src, 64), __shfl(d.z, (int)src, 64));
     const float rtmin = __shfl(tmin, (int)src, 64), rtmax = __shfl(tmax, (int)src, 64);
-    const float ix = slab_rcp(rd.x), iy = slab_rcp(rd.y), iz = slab_rcp(rd.z);
+    const float ix = slab_rcp(rd.x, slab_tiny), iy = slab_rcp(rd.y, slab_tiny), iz = slab_rcp(rd.z, slab_tiny);
     const float ox = -ro.x * ix, oy = -ro.y * iy, oz = -ro.z * iz;
     float best = rtmax;           // this helper's own nearest hit (what best_id names)
     float cull = rtmax;           // the group's nearest hit so far: a true hit distance of the same ray, culled on with <= as closest_hit culls on its own
@@ -1082,7 +1085,7 @@ __device__ __forceinline__ void coop_bounces(const SceneView& sv, const PixelMap
         if (__popcll(ballot) > 32) {
             if (alive) closest_hit<StackT, false, false, false>(sv, nodes, sph, ids, sv.n, ps.o, ps.d, 0.0f, kInf, stack, stride, t, id, nullptr, sv.descent_cap);
         } else {
-            closest_hit_coop<StackT>(nodes, sph, ids, s_cut, ballot, ps.o, ps.d, 0.0f, kInf, stack, stride, t, id, sv.descent_cap);
+            closest_hit_coop<StackT>(nodes, sph, ids, s_cut, ballot, ps.o, ps.d, 0.0f, kInf, stack, stride, t, id, sv.descent_cap, sv.slab_tiny);
         }
         if (alive) {
             alive = shade_step<false, false, false, 0, kDn>(sv, pm, fp, scratch, out, ps, t, id);

@@ -427,6 +427,12 @@ PtStatus pt_trace_rays_stats(PtContext *ctx, const float *origins, const float *
  * original sphere id is sorted_id[~c] (pt_accel_download_order: sorted_id[leaf_count]). */
 PtStatus pt_accel_download(PtContext *ctx, PtBvhNode *nodes, uint32_t capacity);
 PtStatus pt_accel_download_order(PtContext *ctx, uint32_t *sorted_id, uint32_t capacity);
+/* Copy the 4-wide, quantised view of the tree that scenes traversed in global memory are walked through:
+ * words[node_count * 16], record i at words[16 * i] (the layout is the comment above collapse4_kernel, csrc/pt_lbvh_gpu.hip).  Only
+ * the slots of binary nodes at even depth hold a record; the others are zero.  *has_wide = 0, and nothing is copied, when the
+ * context has no wide view: an LDS-resident scene, node_count <= 1, or PT_WIDE=0.  Synchronises the context's stream.
+ * PT_ERR_STATE: no accel; PT_ERR_INVALID_ARG: has_wide null, or a wide view and words null or capacity_nodes < node_count. */
+PtStatus pt_accel_download_wide(PtContext *ctx, uint32_t *words, uint32_t capacity_nodes, uint32_t *has_wide);
 /* Host LBVH builder (the PT_FLAG_HOST_LBVH path), callable without a context or a GPU, for structural tests:
  * nodes[n-1], sorted_id[n]; returns the tree depth through *depth. */
 PtStatus pt_lbvh_build_host(const PtSphere *spheres, uint32_t n, PtBvhNode *nodes, uint32_t *sorted_id, uint32_t *depth);

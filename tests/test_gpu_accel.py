@@ -1,11 +1,11 @@
 """LBVH on the device: traversal result == brute force (GPU kernel and CPU oracle) bit-for-bit, structural invariants of
 the tree the kernels actually traverse, for LDS-resident and global-memory BVHs."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from test_abi import check_lbvh
+from util import assert_hits_match_oracle
+from wide_reference import check_wide
 
 pytestmark = pytest.mark.gpu
 
@@ -62,18 +62,8 @@ def test_bvh_equals_brute_force(dxrs, host, oracle, name, count, flags):
             assert (id_bvh != 0xFFFFFFFF).mean() > 0.3
         # CPU oracle on a subset: same closest hit, bit-exact t
         sub = slice(0, 2000 if len(spheres) < 50000 else 300)
-        lib = oracle.lib
         t_bvh, id_bvh = r.trace_rays(o[sub], d[sub], tmin=0.0, use_bvh=True)
-        for i in range(len(t_bvh)):
-            best, best_id = np.float32(np.inf), 0xFFFFFFFF
-            tt = C.c_float()
-            oi, di = np.ascontiguousarray(o[sub][i]), np.ascontiguousarray(d[sub][i])
-            cand = np.nonzero(candidates(spheres, oi, di))[0]
-            for sid in cand:
-                if lib.oracle_intersect_sphere(oi.ctypes.data_as(C.POINTER(C.c_float)), di.ctypes.data_as(C.POINTER(C.c_float)),
-                                               C.c_float(0.0), C.c_float(best), spheres[sid:sid + 1].ctypes.data, C.byref(tt)):
-                    best, best_id = np.float32(tt.value), sid
-            assert best_id == id_bvh[i] and (best_id == 0xFFFFFFFF or best == t_bvh[i])
+        assert_hits_match_oracle(oracle.lib, spheres, o[sub], d[sub], t_bvh, id_bvh)
     finally:
         r.close()
 
@@ -129,16 +119,6 @@ def test_degenerate_layouts_bvh_equals_brute_force(dxrs, host, kind, n, flags):
         r.close()
 
 
-def candidates(spheres, o, d):
-    """cheap float64 prefilter so the per-ray oracle loop only visits spheres the ray passes near (margin 1e-3 r)"""
-    c = np.stack([spheres["cx"], spheres["cy"], spheres["cz"]], 1).astype(np.float64) - o.astype(np.float64)
-    d = d.astype(np.float64); d = d / np.linalg.norm(d)  # a float32 "unit" vector is off by 6e-8: matters at b ~ 100
-    b = c @ d
-    dist2 = (c * c).sum(1) - b * b
-    rr = spheres["r"].astype(np.float64) * 1.01 + 1e-3
-    return dist2 <= rr * rr
-
-
 @pytest.mark.parametrize("name,count,fast_build", [("small", 0, False), ("demo", 0, False), ("small", 0, True), ("demo", 0, True),
                                                    ("procedural", 4000, False), ("procedural", 50000, False), ("procedural", 1 << 20, False)])
 def test_device_tree_structure(dxrs, host, name, count, fast_build):
@@ -155,6 +135,10 @@ def test_device_tree_structure(dxrs, host, name, count, fast_build):
         nodes, order = r.download_accel()
         if len(spheres) <= 100000:  # the Python invariant walk is O(n) with numpy per node: minutes at 2^20
             check_lbvh(spheres, nodes, order, info.depth)
+        wide = r.download_wide()  # scenes walked in global memory: through the 4-wide view of these records
+        assert (wide is None) == bool(info.lds_resident)
+        if wide is not None and len(spheres) <= 100000:  # (vectorised: under a second at 50000)
+            check_wide(nodes, wide)
         if name != "procedural":
             assert info.lds_resident == 1  # small scenes: whole BVH staged in LDS
         hn, ho, hd = dxrs.load_hip().lbvh_build_host(spheres, sah=sah)

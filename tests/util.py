@@ -1,3 +1,5 @@
+import ctypes as C
+
 import numpy as np
 
 
@@ -29,3 +31,27 @@ def render_rested(renderer, rect=None, expect_beams=None):
     assert st.rays == st1.rays
     assert np.array_equal(bits(img), bits(first)), "beam-list frame differs from the per-ray traversal frame"
     return img, st
+
+
+def candidates(spheres, o, d):
+    """cheap float64 prefilter so the per-ray oracle loop only visits spheres the ray passes near (margin 1e-3 r)"""
+    c = np.stack([spheres["cx"], spheres["cy"], spheres["cz"]], 1).astype(np.float64) - o.astype(np.float64)
+    d = d.astype(np.float64); d = d / np.linalg.norm(d)  # a float32 "unit" vector is off by 6e-8: matters at b ~ 100
+    b = c @ d
+    dist2 = (c * c).sum(1) - b * b
+    rr = spheres["r"].astype(np.float64) * 1.01 + 1e-3
+    return dist2 <= rr * rr
+
+
+def assert_hits_match_oracle(lib, spheres, o, d, t_gpu, id_gpu, tmin=0.0):
+    """every ray's closest hit (id, and t bit for bit) is the one the CPU oracle's oracle_intersect_sphere finds, sphere by sphere in id
+    order; lib = the `oracle` fixture's .lib"""
+    fp = C.POINTER(C.c_float)
+    for i in range(len(t_gpu)):
+        best, best_id = np.float32(np.inf), 0xFFFFFFFF
+        tt = C.c_float()
+        oi, di = np.ascontiguousarray(o[i]), np.ascontiguousarray(d[i])
+        for sid in np.nonzero(candidates(spheres, oi, di))[0]:
+            if lib.oracle_intersect_sphere(oi.ctypes.data_as(fp), di.ctypes.data_as(fp), C.c_float(tmin), C.c_float(best), spheres[sid:sid + 1].ctypes.data, C.byref(tt)):
+                best, best_id = np.float32(tt.value), sid
+        assert best_id == id_gpu[i] and (best_id == 0xFFFFFFFF or best == t_gpu[i]), (i, best_id, id_gpu[i], best, t_gpu[i])
