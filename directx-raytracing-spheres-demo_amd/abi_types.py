@@ -134,6 +134,19 @@ class PtUpscaleTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in UPSCALE_TEXTURES]
 
 
+# Row N12 (pt_nis_sharpen, the NIS stand-in): sl::NISOptions' sharpness and hdrMode plus the size, and the two tagged buffers
+NIS_TEXTURES = ("Color", "Output")
+NIS_HDR_NONE, NIS_HDR_LINEAR, NIS_HDR_PQ = 0, 1, 2
+
+
+class PtNisSettings(C.Structure):
+    _fields_ = [("Size", C.c_uint32 * 2), ("Sharpness", C.c_float), ("HdrMode", C.c_uint32)]
+
+
+class PtNisTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in NIS_TEXTURES]
+
+
 # pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
 class PtDirectLighting(C.Structure):
     _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]

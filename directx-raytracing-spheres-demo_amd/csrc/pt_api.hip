@@ -24,6 +24,7 @@
 #include "pt_nrd.h"
 #include "pt_denoise.h"
 #include "pt_upscale.h"
+#include "pt_nis.h"
 #include "pt_restir.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
@@ -2435,6 +2436,28 @@ PtStatus pt_upscale_input_size(uint32_t mode, uint32_t out_w, uint32_t out_h, ui
     const uint32_t r10 = up_ratio10(mode == kUpModeAuto ? up_auto_mode(out_w, out_h) : mode);
     *w = up_input_extent(out_w, r10);
     *h = up_input_extent(out_h, r10);
+    return PT_OK;
+}
+
+// Row N12 -- the sharpening stand-in (DESIGN.md spec S18): one launch on the context's stream, no state
+PtStatus pt_nis_sharpen(PtContext* c, const PtNisSettings* s, const PtNisTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: null pointer");
+    const uint32_t w = s->Size[0], h = s->Size[1];
+    if (w == 0 || h == 0 || w > kNisMaxSize || h > kNisMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Size must be in [1, 16384]");
+    if (!(s->Sharpness >= 0.0f && s->Sharpness <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Sharpness must be in [0, 1]");
+    if (s->HdrMode > kNisHdrPQ) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: HdrMode must be 0 (None), 1 (Linear) or 2 (PQ)");
+    if (!t->Color || !t->Output) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Color and Output are required");
+    const uintptr_t pc = reinterpret_cast<uintptr_t>(t->Color), po = reinterpret_cast<uintptr_t>(t->Output);
+    if (pc % 16 || po % 16) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Color and Output must be 16-byte aligned");
+    // the output must not share a byte with the input (a lane reads its neighbours' texels): no in-place call
+    const uint64_t bytes = (uint64_t)w * h * sizeof(float4);
+    if (po < pc + bytes && pc < po + bytes) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Output overlaps Color");
+    if (s->HdrMode == kNisHdrPQ) return fail(c, PT_ERR_UNSUPPORTED, "pt_nis_sharpen: HdrMode 2 (PQ) is not built");
+    PT_HIP(c, hipSetDevice(c->device));
+    const NisConfig k = nis_config(s->Sharpness, s->HdrMode);
+    PT_HIP(c, launch_nis(static_cast<const float4*>(t->Color), static_cast<float4*>(t->Output), w, h, k, s->HdrMode, c->stream));
     return PT_OK;
 }
 

@@ -25,6 +25,8 @@
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
+ *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
+ *                            Source/App.cpp:1710-1721, Source/Streamline.ixx:73-74
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -396,7 +398,7 @@ PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const 
  * OutputSize alone, so a change of InputSize keeps the allocation) and freed by pt_destroy.  The history restarts on the first call,
  * with Reset, and on any change of InputSize or OutputSize.
  * Not built (spec S17): exposure handling (ExposureScale), a responsive-pixel mask, a bicubic history tap, FSR2's locks and reactive
- * masks, sharpening / NIS, DLSS frame generation, tile and multi-GPU entry points.
+ * masks, DLSS frame generation, tile and multi-GPU entry points.
  * PT_ERR_INVALID_ARG: a null argument or buffer; a size outside the ranges of PtUpscaleSettings; a Jitter or MaxHistoryWeight that is
  * not finite or out of range; Color or Output not 16-byte aligned, Depth or Velocity not 4-byte aligned; Output overlapping an input. */
 typedef struct PtUpscaleTextures {      /* DEVICE pointers; the reference's XeSSResourceType tags */
@@ -412,6 +414,25 @@ PtStatus pt_upscale(PtContext *ctx, const PtUpscaleSettings *settings, const PtU
  * *w = max(1, (out_w * 10 + r10 / 2) / r10) in integer arithmetic, *h likewise.  PT_ERR_INVALID_ARG: an unknown mode, a zero size, a
  * null pointer. */
 PtStatus pt_upscale_input_size(uint32_t mode, uint32_t out_w, uint32_t out_h, uint32_t *w, uint32_t *h);
+
+/* Row N12 -- the sharpening stand-in (Streamline's NIS feature as App::ProcessNIS drives it, Source/App.cpp:1710-1721; DESIGN.md spec S18):
+ * the reference follows its upscaler with NVIDIA Image Scaling in sharpen mode; the Streamline plugin is not vendored.  A directional
+ * unsharp mask in the form of NIS v1's NVSharpen: per texel the luma of a 5 x 5 neighbourhood (coordinates clamped into the image), an
+ * edge map over four directions on its inner 3 x 3, a five-tap unsharp mask along the detected directions whose strength and limit
+ * fall with the luma, scaled down at hard steps, added to the colour (HdrMode None) or applied as a luma ratio (Linear).  A flat
+ * neighbourhood leaves the sanitised colour (NaN -> 0, else clamped to [0, 65504]) unchanged; alpha passes through bit for bit.
+ * Color and Output are both at output size (kBufferTypeScalingInputColor / kBufferTypeScalingOutputColor).
+ * On the context's stream (asynchronous), ordered like pt_bloom and pt_upscale: after what is already queued there, before whatever
+ * the caller queues next.  Stateless: no context state, nothing added to pt_get_totals, the render lanes are never touched.
+ * Not built: NIS's scaler mode, HdrMode PQ, tile and multi-GPU entry points.
+ * PT_ERR_INVALID_ARG: a null argument or buffer; a size of 0 or above 16384; a Sharpness that is NaN or outside [0, 1]; a buffer not
+ * 16-byte aligned; Output overlapping Color, Output == Color included (the pass reads neighbours, so unlike pt_bloom it cannot run in
+ * place); an HdrMode above 2.  PT_ERR_UNSUPPORTED: HdrMode 2 (PQ). */
+typedef struct PtNisTextures {          /* DEVICE pointers, float4 per texel, Size[0] x Size[1] texels, row-major */
+    const void *Color;                  /* kBufferTypeScalingInputColor  (pt_upscale's Output, or the radiance at output size) */
+    void *Output;                       /* kBufferTypeScalingOutputColor (what pt_bloom and pt_tonemap take) */
+} PtNisTextures;
+PtStatus pt_nis_sharpen(PtContext *ctx, const PtNisSettings *settings, const PtNisTextures *textures);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

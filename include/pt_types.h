@@ -9,6 +9,7 @@
  *   PtGraphicsSettings == _GraphicsSettings   Source/Raytracing.ixx:151-166 (== Shaders/Raytracing.hlsl:21-39), 80 B
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *   PtUpscaleSettings     (row N11) the XeSSSettings App::ProcessXeSSSuperResolution fills, plus the output size and the history cap, 32 B
+ *   PtNisSettings         (row N12) the sl::NISOptions App::ProcessNIS fills (sharpness, hdrMode; mode is always eSharpen), plus the size, 16 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
@@ -200,6 +201,14 @@ typedef struct PtUpscaleSettings {
     float MaxHistoryWeight;       /* 28: 0 -> 16; finite, 1..256 */
 } PtUpscaleSettings;
 
+/* Row N12 (pt_nis_sharpen, the NIS stand-in of DESIGN.md spec S18): sl::NISOptions as App::ProcessNIS fills it (Source/App.cpp:1710-1721;
+ * mode = eSharpen always) and the size of the two tagged buffers, which is the output size. */
+typedef struct PtNisSettings {
+    uint32_t Size[2];             /*  0: texels of Color and Output, 1..16384 each */
+    float Sharpness;              /*  8: PostProcessing.NIS.Sharpness, in [0, 1]; the reference's default is 0.5 */
+    uint32_t HdrMode;             /* 12: sl::NISHDR: 0 None (what the reference passes), 1 Linear; 2 PQ is PT_ERR_UNSUPPORTED */
+} PtNisSettings;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -226,6 +235,7 @@ static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, R
               && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
+static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -241,6 +251,7 @@ _Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, 
                && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
+_Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

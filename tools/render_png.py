@@ -4,10 +4,11 @@ with jittered cameras -> pt_accumulate (running mean) [-> pt_bloom with --bloom]
 R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: --frames frames of a resting camera through it with the
 NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through pt_render_gbuffer -> pt_restir_di -> pt_render_with_di,
 row N10, accumulated; --upscale MODE: --frames frames of a resting camera rendered at the mode's input size with Halton jitter and
-upscaled to --width x --height by pt_upscale, row N11).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_sharpen, row N12, on the frame at output size, after the
+upscaler when there is one and before bloom).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5]"""
 import argparse
 import os
 import sys
@@ -73,7 +74,12 @@ def main():
                     help="--frames frames of a resting camera rendered at the mode's input size (pt_upscale_input_size) with Halton jitter (row "
                          "N11): pt_render_gbuffer (LinearDepth, MotionVector) -> pt_render -> pt_upscale to --width x --height [-> pt_bloom with "
                          "--bloom] -> the tone map at output size; the last frame")
+    ap.add_argument("--nis", type=float, default=None, metavar="SHARPNESS",
+                    help="pt_nis_sharpen (row N12; the reference's default sharpness is 0.5) at output size: after pt_upscale with --upscale, "
+                         "else on the accumulated radiance; before pt_bloom")
     args = ap.parse_args()
+    if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
+        ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
 
     t = dxrs_amd.types
@@ -134,6 +140,9 @@ def main():
             r.render_gbuffer_device(dict(LinearDepth=depth.data_ptr(), MotionVector=velocity.data_ptr()))
             r.render_device(color.data_ptr())
             hdr = up(color, depth, velocity, jitter=(-cam.Jitter[0], -cam.Jitter[1]))
+        if args.nis is not None:
+            r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
+            hdr = frame
         if args.bloom is not None:
             r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
         op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
@@ -197,9 +206,12 @@ def main():
         r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
     op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
     hdr = accum
+    if args.nis is not None:
+        r.nis_sharpen_device((w, h), dict(Color=accum.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
+        hdr = frame
     if args.bloom is not None:
-        hdr = torch.empty_like(accum)  # the running mean stays as it is
-        r.bloom(accum.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+        src, hdr = hdr, torch.empty_like(accum)  # the running mean stays as it is
+        r.bloom(src.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
     r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
     r.synchronize()
     rgba = ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)
