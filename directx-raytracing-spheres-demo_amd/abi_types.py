@@ -147,6 +147,19 @@ class PtNisTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NIS_TEXTURES]
 
 
+# Row N13 (pt_frame_gen, the DLSS-G stand-in): the sizes, the packing of the tone-mapped colour and the reset flag, and the tagged buffers
+FRAME_GEN_TEXTURES = ("Color", "Depth", "MotionVector", "Output")
+FRAME_GEN_RGBA8, FRAME_GEN_RGB10A2 = 0, 1
+
+
+class PtFrameGenSettings(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("OutputSize", C.c_uint32 * 2), ("Format", C.c_uint32), ("Reset", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class PtFrameGenTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in FRAME_GEN_TEXTURES]
+
+
 # pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
 class PtDirectLighting(C.Structure):
     _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]

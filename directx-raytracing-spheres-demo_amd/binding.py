@@ -7,8 +7,8 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
-                        PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
+from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
+                        PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         RESTIR_DI_TEXTURES, UPSCALE_TEXTURES)
 
@@ -19,7 +19,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -107,6 +107,8 @@ class HipLib:
         lib.pt_upscale_input_size.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
         lib.pt_nis_sharpen.restype = C.c_int
         lib.pt_nis_sharpen.argtypes = [vp, C.POINTER(PtNisSettings), C.POINTER(PtNisTextures)]
+        lib.pt_frame_gen.restype = C.c_int
+        lib.pt_frame_gen.argtypes = [vp, C.POINTER(PtFrameGenSettings), C.POINTER(PtFrameGenTextures), C.POINTER(u32)]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -579,6 +581,21 @@ class Renderer:
         s = PtNisSettings(Size=(C.c_uint32 * 2)(*size), Sharpness=sharpness, HdrMode=hdr_mode)
         t = PtNisTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
         self._check(self._lib.pt_nis_sharpen(self._ctx, C.byref(s), C.byref(t)))
+
+    def frame_gen_device(self, render_size, output_size, buffers, fmt=0, reset=False):
+        """The frame-interpolation stand-in (row N13, DESIGN.md spec S19): the frame half way between the previous call's frame and this
+        one.  buffers: {FRAME_GEN_TEXTURES name: device pointer}: Color and Output packed uint32 at output_size = (W, H) (pt_tonemap's
+        out), Depth (float) and MotionVector (float3) at render_size = (w, h); Output must not overlap an input.  fmt:
+        abi_types.FRAME_GEN_RGBA8 or FRAME_GEN_RGB10A2.  Returns True when a frame was generated, False on a restart (the first call,
+        reset, a change of a size or of fmt), where Output is Color.  Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(FRAME_GEN_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown frame generation buffers {sorted(unknown)}")
+        s = PtFrameGenSettings(RenderSize=(C.c_uint32 * 2)(*render_size), OutputSize=(C.c_uint32 * 2)(*output_size), Format=fmt, Reset=1 if reset else 0)
+        t = PtFrameGenTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        generated = C.c_uint32(0)
+        self._check(self._lib.pt_frame_gen(self._ctx, C.byref(s), C.byref(t), C.byref(generated)))
+        return bool(generated.value)
 
     def upscaler(self, output_size, mode=0, device=None, **settings):
         """An `upscale(color, depth, velocity, jitter)` that keeps the sizes and settings across frames and runs pt_upscale (row N11):

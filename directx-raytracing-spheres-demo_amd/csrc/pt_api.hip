@@ -25,6 +25,7 @@
 #include "pt_denoise.h"
 #include "pt_upscale.h"
 #include "pt_nis.h"
+#include "pt_framegen.h"
 #include "pt_restir.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
@@ -204,6 +205,12 @@ struct PtContext {
     float4* d_up = nullptr;
     uint32_t up_w = 0, up_h = 0, up_W = 0, up_H = 0, up_slot = 0;
     bool up_valid = false;
+    // pt_frame_gen's buffers (row N13; used on `stream` only): the motion field (8 B per render pixel), then two alternating history
+    // slots of the previous Color (4 B per output pixel) and two of the previous Depth (4 B per render pixel); allocated on first use
+    // and again when a size changes; a change of either size or of the Format restarts the history; `fg_slot` = the slot the last call wrote
+    unsigned long long* d_fg = nullptr;
+    uint32_t fg_w = 0, fg_h = 0, fg_W = 0, fg_H = 0, fg_format = 0, fg_slot = 0;
+    bool fg_valid = false;
     // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
     // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
     // pt_set_scene count it was made under (emitter indices change with the scene), `ev_ri` = the last call's launches have finished
@@ -1456,6 +1463,7 @@ void pt_destroy(PtContext* c)
     free_dev(c->d_bloom);
     free_dev(c->d_dn);
     free_dev(c->d_up);
+    free_dev(c->d_fg);
     free_dev(c->d_ri);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
@@ -2458,6 +2466,72 @@ PtStatus pt_nis_sharpen(PtContext* c, const PtNisSettings* s, const PtNisTexture
     PT_HIP(c, hipSetDevice(c->device));
     const NisConfig k = nis_config(s->Sharpness, s->HdrMode);
     PT_HIP(c, launch_nis(static_cast<const float4*>(t->Color), static_cast<float4*>(t->Output), w, h, k, s->HdrMode, c->stream));
+    return PT_OK;
+}
+
+// Row N13 -- the frame-interpolation stand-in (DESIGN.md spec S19): a clear, a scatter and a gather on the context's stream; the motion
+// field and the previous frame's Color and Depth live in the context.  *generated is decided here, before anything is queued.
+PtStatus pt_frame_gen(PtContext* c, const PtFrameGenSettings* s, const PtFrameGenTextures* t, uint32_t* generated)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: null pointer");
+    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1], W = s->OutputSize[0], H = s->OutputSize[1];
+    if (w == 0 || h == 0 || w > kFgMaxSize || h > kFgMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: RenderSize must be in [1, 16384]");
+    if (W < w || H < h || W > kFgMaxSize || H > kFgMaxSize || (uint64_t)W > (uint64_t)kFgMaxRatio * w || (uint64_t)H > (uint64_t)kFgMaxRatio * h)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: OutputSize must be in [RenderSize, 4 * RenderSize] per axis and at most 16384");
+    if (s->Format > kFgFormatRGB10A2) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: Format must be 0 (R8G8B8A8_UNORM) or 1 (R10G10B10A2_UNORM)");
+    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: padding must be 0");
+    const uint64_t n_in = (uint64_t)w * h, n_out = (uint64_t)W * H;
+    struct Use { const void* p; uint64_t bytes; const char* name; };
+    const Use use[4] = { {t->Color, n_out * 4, "Color"}, {t->Depth, n_in * 4, "Depth"}, {t->MotionVector, n_in * 12, "MotionVector"}, {t->Output, n_out * 4, "Output"} };
+    for (const Use& u : use) {
+        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: ") + u.name + " is required");
+        if (reinterpret_cast<uintptr_t>(u.p) % 4) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: ") + u.name + " is not 4-byte aligned");
+    }
+    // the output must not share a byte with an input (a lane reads the colour of other lanes' pixels)
+    for (int i = 0; i < 3; i++) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(use[3].p), pb = reinterpret_cast<uintptr_t>(use[i].p);
+        if (pa < pb + use[i].bytes && pb < pa + use[3].bytes) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: Output overlaps ") + use[i].name);
+    }
+    PT_HIP(c, hipSetDevice(c->device));
+    bool restart = s->Reset != 0 || !c->fg_valid || c->fg_format != s->Format;
+    if (!c->d_fg || c->fg_w != w || c->fg_h != h || c->fg_W != W || c->fg_H != H) {
+        // the buffers are only used on `stream`: once the calls queued there have finished, the old ones are free (the render lanes
+        // never touch them, so their frames in flight go on)
+        if (c->d_fg) PT_HIP(c, hipStreamSynchronize(c->stream));
+        free_dev(c->d_fg);
+        c->fg_valid = false;
+        c->fg_w = c->fg_h = c->fg_W = c->fg_H = 0;
+        PT_HIP(c, hipMalloc(&c->d_fg, n_in * 8 + 2 * n_out * 4 + 2 * n_in * 4));
+        c->fg_w = w; c->fg_h = h; c->fg_W = W; c->fg_H = H;
+        restart = true;
+    }
+    const uint32_t cur = c->fg_slot ^ 1u, prev = c->fg_slot;
+    uint32_t* colors = reinterpret_cast<uint32_t*>(c->d_fg + n_in);
+    float* zs = reinterpret_cast<float*>(colors + 2 * n_out);
+    FgBuffers b{};
+    b.color = static_cast<const uint32_t*>(t->Color);
+    b.depth = static_cast<const float*>(t->Depth);
+    b.mv = static_cast<const float*>(t->MotionVector);
+    b.out = static_cast<uint32_t*>(t->Output);
+    b.prev_color = colors + prev * n_out;
+    b.prev_z = zs + prev * n_in;
+    b.hist_color = colors + cur * n_out;
+    b.hist_z = zs + cur * n_in;
+    b.field = c->d_fg;
+    if (generated) *generated = restart ? 0u : 1u;
+    if (restart) {
+        // step 0: Output = Color bit for bit, the current slot takes Color and Depth
+        PT_HIP(c, hipMemcpyAsync(b.out, b.color, n_out * 4, hipMemcpyDeviceToDevice, c->stream));
+        PT_HIP(c, hipMemcpyAsync(b.hist_color, b.color, n_out * 4, hipMemcpyDeviceToDevice, c->stream));
+        PT_HIP(c, hipMemcpyAsync(b.hist_z, b.depth, n_in * 4, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        PT_HIP(c, hipMemsetAsync(b.field, 0xFF, n_in * 8, c->stream));
+        PT_HIP(c, launch_framegen(b, fg_params(w, h, W, H, s->Format), c->stream));
+    }
+    c->fg_slot = cur;
+    c->fg_format = s->Format;
+    c->fg_valid = true;
     return PT_OK;
 }
 

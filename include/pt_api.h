@@ -27,6 +27,8 @@
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
  *                            Source/App.cpp:1710-1721, Source/Streamline.ixx:73-74
+ *   pt_frame_gen             App::ProcessDLSSFrameGeneration's tags + Streamline's DLSS-G plugin (a stand-in, spec S19)
+ *                            Source/App.cpp:1673-1680, 1460-1525
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -398,7 +400,7 @@ PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const 
  * OutputSize alone, so a change of InputSize keeps the allocation) and freed by pt_destroy.  The history restarts on the first call,
  * with Reset, and on any change of InputSize or OutputSize.
  * Not built (spec S17): exposure handling (ExposureScale), a responsive-pixel mask, a bicubic history tap, FSR2's locks and reactive
- * masks, DLSS frame generation, tile and multi-GPU entry points.
+ * masks, tile and multi-GPU entry points.
  * PT_ERR_INVALID_ARG: a null argument or buffer; a size outside the ranges of PtUpscaleSettings; a Jitter or MaxHistoryWeight that is
  * not finite or out of range; Color or Output not 16-byte aligned, Depth or Velocity not 4-byte aligned; Output overlapping an input. */
 typedef struct PtUpscaleTextures {      /* DEVICE pointers; the reference's XeSSResourceType tags */
@@ -433,6 +435,33 @@ typedef struct PtNisTextures {          /* DEVICE pointers, float4 per texel, Si
     void *Output;                       /* kBufferTypeScalingOutputColor (what pt_bloom and pt_tonemap take) */
 } PtNisTextures;
 PtStatus pt_nis_sharpen(PtContext *ctx, const PtNisSettings *settings, const PtNisTextures *textures);
+
+/* Row N13 -- the frame-interpolation stand-in (DLSS frame generation as App::ProcessDLSSFrameGeneration feeds it, Source/App.cpp:1673-1680;
+ * DESIGN.md spec S19): after the tone map the reference tags the G-buffer depth, the motion vectors and the tone-mapped HUD-less colour,
+ * and Streamline's DLSS-G plugin, a closed SDK that is not vendored, presents one generated frame between every two rendered ones.
+ * Here: the frame at time n - 1/2 from frame n's Color, Depth and MotionVector and frame n - 1's Color and Depth, which the context
+ * keeps.  Every render pixel is scattered half its vector back into a motion field through a depth-tested 64-bit min (the nearest
+ * surface wins, equal depths go to the lowest pixel index); every output pixel then samples Color half a vector ahead and the previous
+ * Color half a vector behind (bilinear), drops a side that is outside the image or, for the previous frame, fails S17's depth test, and
+ * averages what is left; a pixel no vector reached copies the previous frame.  Alpha is Color's.  A resting view with equal frames
+ * returns them bit for bit.
+ * On the context's stream (asynchronous), ordered like pt_bloom, pt_upscale and pt_nis_sharpen.  Nothing is added to pt_get_totals, the
+ * render lanes never touch its state.  The context owns two alternating history slots (Color, uint32 x OutputSize, and Depth, float x
+ * RenderSize) and the motion field (uint64 x RenderSize): allocated on first use, again when a size changes (which waits for the
+ * context's stream only), freed by pt_destroy.
+ * *generated (may be NULL) is decided on the host before anything is queued: 0 on a restart -- the first call, Reset, or a change of
+ * RenderSize, OutputSize or Format -- where Output is Color bit for bit and the history takes Color and Depth; 1 otherwise.
+ * Not built (spec S19): optical flow, a forward scatter from the previous frame's own vectors, inpainting of holes beyond the
+ * previous-frame copy, UI / HUD handling, pacing / Reflex, more than one generated frame per pair, tile and multi-GPU entry points.
+ * PT_ERR_INVALID_ARG: a null argument or buffer; a size outside the ranges of PtFrameGenSettings; Format > 1; nonzero padding; a
+ * buffer not 4-byte aligned; Output overlapping any input, Output == Color included. */
+typedef struct PtFrameGenTextures {     /* DEVICE pointers */
+    const void *Color;                  /* uint32 per pixel, OutputSize: pt_tonemap's out for frame n (kBufferTypeHUDLessColor) */
+    const void *Depth;                  /* float, RenderSize: G-buffer LinearDepth, +inf on a miss (as pt_upscale; the reference tags NormalizedDepth) */
+    const void *MotionVector;           /* float3, RenderSize: .xy render pixels towards the previous frame, .z view depth (kBufferTypeMotionVectors) */
+    void *Output;                       /* uint32 per pixel, OutputSize: the frame at time n - 1/2 */
+} PtFrameGenTextures;
+PtStatus pt_frame_gen(PtContext *ctx, const PtFrameGenSettings *settings, const PtFrameGenTextures *textures, uint32_t *generated);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

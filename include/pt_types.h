@@ -10,6 +10,7 @@
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *   PtUpscaleSettings     (row N11) the XeSSSettings App::ProcessXeSSSuperResolution fills, plus the output size and the history cap, 32 B
  *   PtNisSettings         (row N12) the sl::NISOptions App::ProcessNIS fills (sharpness, hdrMode; mode is always eSharpen), plus the size, 16 B
+ *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
@@ -209,6 +210,16 @@ typedef struct PtNisSettings {
     uint32_t HdrMode;             /* 12: sl::NISHDR: 0 None (what the reference passes), 1 Linear; 2 PQ is PT_ERR_UNSUPPORTED */
 } PtNisSettings;
 
+/* Row N13 (pt_frame_gen, the DLSS-G stand-in of DESIGN.md spec S19): App::ProcessDLSSFrameGeneration (Source/App.cpp:1673-1680) only
+ * tags resources; their sizes, the packing of the tone-mapped colour and m_resetHistory travel here. */
+typedef struct PtFrameGenSettings {
+    uint32_t RenderSize[2];       /*  0: size of Depth and MotionVector, 1..16384 each */
+    uint32_t OutputSize[2];       /*  8: size of Color and Output; RenderSize <= OutputSize <= 4 * RenderSize per axis, at most 16384 */
+    uint32_t Format;              /* 16: 0 R8G8B8A8_UNORM, 1 R10G10B10A2_UNORM: pt_tonemap's two packings */
+    uint32_t Reset;               /* 20: nonzero = ignore the history (m_resetHistory) */
+    uint32_t _pad[2];             /* 24: must be 0 */
+} PtFrameGenSettings;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -236,6 +247,8 @@ static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, R
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
+static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
+              && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -252,6 +265,8 @@ _Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, 
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
+_Static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
+               && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

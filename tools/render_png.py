@@ -5,10 +5,11 @@ R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: 
 NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through pt_render_gbuffer -> pt_restir_di -> pt_render_with_di,
 row N10, accumulated; --upscale MODE: --frames frames of a resting camera rendered at the mode's input size with Halton jitter and
 upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_sharpen, row N12, on the frame at output size, after the
-upscaler when there is one and before bloom).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+upscaler when there is one and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
+pt_frame_gen, row N13, makes between them).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1]"""
 import argparse
 import os
 import sys
@@ -77,7 +78,14 @@ def main():
     ap.add_argument("--nis", type=float, default=None, metavar="SHARPNESS",
                     help="pt_nis_sharpen (row N12; the reference's default sharpness is 0.5) at output size: after pt_upscale with --upscale, "
                          "else on the accumulated radiance; before pt_bloom")
+    ap.add_argument("--frame-gen", default=None, metavar="MID.png",
+                    help="render the scene at --time minus --dt and at --time (one frame each: pt_render_gbuffer with the earlier pose as the "
+                         "previous one -> pt_render [-> pt_bloom] -> pt_tonemap) and write the frame pt_frame_gen (row N13) makes between the "
+                         "two to MID.png; the frame at --time goes to the positional output")
+    ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
+    if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
+        ap.error("--frame-gen applies to the plain path-traced frame")
     if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
@@ -122,6 +130,38 @@ def main():
     frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     accum = torch.empty((n, 4), dtype=torch.float32, device="cuda")
     ldr = torch.empty(n, dtype=torch.int32, device="cuda")
+    if args.frame_gen:
+        sd.IsStatic = 0
+        r.set_scene(spheres, materials, sd)
+        if textured or args.env_map:
+            r.set_textures(ts)
+        depth = torch.zeros((h, w), dtype=torch.float32, device="cuda")
+        velocity = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        mid = torch.zeros(n, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.set_camera(host.camera_matrices(w, h, jitter=False))
+        earlier = None
+        for k, time in enumerate((args.time - args.dt, args.time)):
+            moved = host.scene_at_time(0, time)
+            r.update_spheres(moved)
+            gs.FrameIndex = k
+            r.set_constants(gs)
+            r.render_gbuffer_device(dict(LinearDepth=depth.data_ptr(), MotionVector=velocity.data_ptr()), previous_spheres=earlier)
+            r.render_device(frame.data_ptr())
+            if args.bloom is not None:
+                r.bloom(frame.data_ptr(), frame.data_ptr(), w, h, args.bloom)
+            r.tonemap(frame.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+            generated = r.frame_gen_device((w, h), (w, h), dict(Color=ldr.data_ptr(), Depth=depth.data_ptr(), MotionVector=velocity.data_ptr(),
+                                                                Output=mid.data_ptr()), reset=k == 0)
+            earlier = moved
+        r.synchronize()
+        assert generated
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        Image.fromarray(mid.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.frame_gen)
+        print(f"frame generation (pt_frame_gen) {w}x{h}: time {args.time} -> {args.out}, time {args.time - args.dt / 2} -> {args.frame_gen}")
+        r.close()
+        return
     if args.upscale:
         up = r.upscaler((w, h), mode=t.UPSCALE_MODES[args.upscale])
         iw, ih = up.input_size
