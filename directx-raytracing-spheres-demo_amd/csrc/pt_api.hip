@@ -50,7 +50,7 @@ struct EventPair {
 struct Knobs {
     int split = -1, traverse_blocks_per_cu = -1, fused_threads = -1, no_adaptive_grid = -1, shade_blocks_per_cu = -1, tail_threshold = -1,
         tail_blocks_per_cu = -1, loop_threads = -1, inline2_min_slots = -1, tail_after = -1, seg = -1, loop_use_tail = -1, fuse_loop = -1,
-        ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1, refl_beams = -1, coop_walk = -1;
+        ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1, refl_beams = -1, coop_walk = -1, tile_order = -1, sky_fast = -1, tile_table = -1;
 };
 
 // Per-frame-in-flight state (see PtContext::lanes).
@@ -598,6 +598,7 @@ Knobs read_knobs()
     k.loop_use_tail = std::getenv("PT_LOOP_USE_TAIL") ? 1 : -1; k.fuse_loop = env_knob("PT_FUSE_LOOP"); k.beam_reach = env_knob("PT_BEAM_REACH"); k.beam_max_slack_pct = env_knob("PT_BEAM_MAX_SLACK_PCT"); k.beam_max_margin = env_knob("PT_BEAM_MAX_MARGIN"); k.beam_share_wgs = env_knob("PT_BEAM_SHARE_WGS"); k.lane_priority = env_knob("PT_LANE_PRIORITY"); k.fused_refit = env_knob("PT_FUSED_REFIT"); k.ray_replacement = env_knob("PT_RAY_REPLACEMENT");
     k.dyn_blocks_per_cu = env_knob("PT_DYN_BLOCKS_PER_CU"); k.debug_counts = std::getenv("PT_DEBUG_COUNTS") ? 1 : -1; k.sah = env_knob("PT_SAH");
     k.sah_max_spheres = env_knob("PT_SAH_MAX_SPHERES"); k.beams = env_knob("PT_BEAMS"); k.refl_beams = env_knob("PT_REFL_BEAMS"); k.coop_walk = env_knob("PT_COOP_WALK"); k.wide = env_knob("PT_WIDE"); k.descent = env_knob("PT_DESCENT"); k.roctx = env_knob("PT_ROCTX");
+    k.tile_order = env_knob("PT_TILE_ORDER"); k.sky_fast = env_knob("PT_SKY_FAST"); k.tile_table = env_knob("PT_TILE_TABLE");
     return k;
 }
 
@@ -1125,6 +1126,11 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     L.parity ^= 1u;
     FrameCounters fc = make_counters(L, L.parity);
     fc.coop_walk = knob_or(c->knobs.coop_walk, 1u) != 0 ? 1u : 0u;  // PT_COOP_WALK=0: the per-lane walk everywhere (A/B runs, tests)
+    // The primary pass over a view with beam lists: every workgroup draws its tiles with a non-empty list first (PT_TILE_ORDER=0: raster order;
+    // PT_TILE_TABLE caps the order table below kTileTable, for tests of the fallback), and a tile with an empty list takes the short path
+    // (PT_SKY_FAST=0: the general one)
+    fc.tile_opts = (knob_or(c->knobs.tile_order, 1u) != 0 ? std::min(knob_or(c->knobs.tile_table, kTileTable), kTileTable) : 0u)
+                   | (knob_or(c->knobs.sky_fast, 1u) != 0 ? 1u << 16 : 0u);
     uint32_t* counts = fc.counts;
 
     // Launch grids: a kernel's queue size lives on the device; the host sizes the grid from the queue sizes an

@@ -86,14 +86,15 @@ __device__ __forceinline__ void frame_counters_begin(const FrameCounters& fc, ui
 }
 
 // Stage the BVH (nodes, Morton-ordered spheres, ids) into LDS.  Layout: [nodes | spheres | ids].
-__device__ __forceinline__ void stage_scene(const SceneView& sv, float4* lds)
+// (sync = false: the caller has more to put in LDS before the barrier, and makes it itself)
+__device__ __forceinline__ void stage_scene(const SceneView& sv, float4* lds, bool sync = true)
 {
     const uint32_t n_vec = sv.n_nodes * 4u + sv.n;
     for (uint32_t i = threadIdx.x; i < n_vec; i += blockDim.x)
         lds[i] = i < sv.n_nodes * 4u ? sv.nodes[i] : sv.sph_sorted[i - sv.n_nodes * 4u];
     uint32_t* ids = reinterpret_cast<uint32_t*>(lds + n_vec);
     for (uint32_t i = threadIdx.x; i < sv.n; i += blockDim.x) ids[i] = sv.sorted_id[i];
-    __syncthreads();
+    if (sync) __syncthreads();
 }
 
 __host__ __device__ inline uint32_t scene_lds_bytes(uint32_t n_nodes, uint32_t n) { return (n_nodes * 4u + n) * 16u + ((n * 4u + 15u) & ~15u); }
@@ -1058,6 +1059,7 @@ constexpr uint32_t kStaticLdsMargin = (kMaxSegs + 64u + kCutSlots) * 4u;
 // kernarg segment where it is used (s_load, scalar cache): the laundered pointer keeps the loads inside the loop.
 // The leading arguments of bounce_kernel, as the kernarg segment lays them out (in order, each at its natural alignment = a C struct):
 struct BounceArgHead { SceneView sv; PixelMap pm; FrameParams fp; };
+struct BounceArgs { SceneView sv; PixelMap pm; FrameParams fp; RayQueue qin, qout; Scratch scratch; float4* out; const uint32_t* count_in; uint32_t* count_out; FrameCounters fc; };  // ... and all of them
 template <typename T>
 __device__ __forceinline__ T cold_arg(uint32_t offset)
 {
@@ -1128,6 +1130,8 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
     __shared__ uint32_t s_seg_prefix[kMaxSegs + 1];   // consumer side: s_seg_prefix[b] = entries in segments < b
     __shared__ uint32_t s_refl[2];                    // kIters == 2: waves that traced bounce-1 rays, ... of them served by a region list
     __shared__ int s_cut[kCutSlots];                  // kCoop: the tree's cuts at depths 1-3 (build_cut)
+    __shared__ uint16_t s_tile_order[kTileTable];     // seg_out over beam lists: the workgroup's tiles in the order its waves draw them (below)
+    __shared__ uint32_t s_tile_n;                     // ... and how many the table holds (0: none, the slot order)
     // The cooperative walk (closest_hit_coop): the looping pass of a 1-spp frame over an untextured LDS-resident scene, and the fused form's tail
     constexpr bool kCoop = kLds && !kMulti && !kTex && !kDI && !kDn && sizeof(StackT) == 2 && ((kLoop && !kPrimary) || kFuse);
     if (kPrimary && blockIdx.x == 0) frame_counters_begin(fc, pm.n_slots);
@@ -1164,13 +1168,61 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         if (seg_out && threadIdx.x == 0) fc.seg_counts[blockIdx.x] = 0;
         return;
     }
-    if ((seg_out || kIters > 1u) && !kLds) __syncthreads();  // (with kLds the barrier of stage_scene orders the reset)
+    // Tile order.  A workgroup's waves draw its 64-slot tiles from s_seg_next; in slot order those run down the image, so every wave would
+    // END on a ground tile (1 400-2 200 wave instructions against ~100 for a sky tile) and wait at the closing barrier for the slowest of
+    // eight, with the wave slots of all of them held.  Over a view with beam lists the class of a tile is known beforehand -- the count word of
+    // its list, 0 = every ray misses -- so the tiles with a non-empty list are drawn first and the empty ones fill the end (longest
+    // processing time first, inside the workgroup; each class keeps its slot order).  The last wave of the workgroup builds the table with
+    // ballots: no counter to reset, one order whatever the timing.  Its loads are issued here and used after the scene is staged.  A
+    // workgroup visits fc.seg_cap / 64 tiles (those past the end of the frame count as empty: they stay the last ones drawn).  Without lists,
+    // or with more tiles than the table holds, the order is the slot order.  (The table's size lives in LDS with it: the draw reads both with
+    // the lane that made the atomic, and the tile loop carries nothing in registers for them.)
+    // spp > 1 keeps the slot order: its primary pass is a tenth of the frame, and the 4K 16-spp frame was 3 % slower with the table.
+    constexpr bool kTileOrder = kPrimary && !kLoop && !kMulti;
+    const uint32_t n_tiles = (kTileOrder && seg_out && fp.beam_lists != nullptr && (fc.seg_cap >> 6) <= (fc.tile_opts & 0xFFFFu)) ? fc.seg_cap >> 6 : 0u;  // (0: no table)
+    const bool tile_builder = n_tiles != 0u && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1u;
+    constexpr uint32_t kTileChunks = kTileTable / 64u;
+    constexpr uint32_t kNoTile = ~0u;  // (a draw past the end of the table: the tiles of the workgroup are all taken)
+    uint32_t tile_class[kTileChunks];
+    if (tile_builder) {
+        const uint32_t waves = blockDim.x >> 6;
+#pragma unroll
+        for (uint32_t k = 0; k < kTileChunks; k++) {
+            const uint32_t w = k * 64u + lane_id();
+            const uint32_t i0 = (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x + (w % waves) * 64u;
+            tile_class[k] = (w < n_tiles && i0 < count) ? fp.beam_lists[(size_t)(i0 >> 6) * kBeamRecord] : 0u;
+        }
+    }
+    auto build_tile_order = [&]() {
+        unsigned long long heavy[kTileChunks];
+        uint32_t n_heavy = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kTileChunks; k++) { heavy[k] = __ballot(tile_class[k] != 0u); n_heavy += __popcll(heavy[k]); }
+        const unsigned long long below = (1ull << lane_id()) - 1ull;
+        uint32_t at_heavy = 0, at_light = n_heavy;
+#pragma unroll
+        for (uint32_t k = 0; k < kTileChunks; k++) {
+            const uint32_t w = k * 64u + lane_id();
+            const bool h = tile_class[k] != 0u;
+            const uint32_t pos = h ? at_heavy + __popcll(heavy[k] & below) : at_light + __popcll(~heavy[k] & below);
+            if (w < n_tiles) s_tile_order[pos] = (uint16_t)w;
+            at_heavy += __popcll(heavy[k]);
+            at_light += 64u - __popcll(heavy[k]);
+        }
+    };
+    if (kTileOrder && seg_out && threadIdx.x == 0) s_tile_n = n_tiles;
+    if (!kLds) {
+        if (tile_builder) build_tile_order();
+        if (seg_out || kIters > 1u) __syncthreads();  // (with kLds the barrier after stage_scene orders the reset and the table)
+    }
     const float4* nodes = sv.nodes;
     const float4* sph = sv.sph_sorted;
     const uint32_t* ids = sv.sorted_id;
     StackT* stack;
     if (kLds) {
-        stage_scene(sv, smem);
+        stage_scene(sv, smem, false);
+        if (tile_builder) build_tile_order();
+        __syncthreads();
         nodes = smem;
         sph = smem + sv.n_nodes * 4u;
         ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
@@ -1233,8 +1285,15 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             // the workgroup's batches are the same strided set as below, but its waves take the 64-slot tiles of them from a
             // counter in LDS: a wave that drew sky tiles moves on instead of idling behind its neighbours
             uint32_t w = 0;
-            if (lane == 0) w = atomicAdd(&s_seg_next, 1u);
+            if (lane == 0) {
+                w = atomicAdd(&s_seg_next, 1u);
+                if (kTileOrder) {
+                    const uint32_t n = s_tile_n;
+                    if (n != 0u) w = w < n ? s_tile_order[w] : kNoTile;
+                }
+            }
             w = __builtin_amdgcn_readfirstlane(w);
+            if (w == kNoTile) break;
             const uint32_t waves = blockDim.x >> 6;
             const uint32_t b = (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x;
             if (b >= count) break;
@@ -1268,6 +1327,14 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             beam_rec = fp.beam_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kBeamRecord;
             beam_count = __builtin_amdgcn_readfirstlane(beam_rec[0]);
         }
+        // Sky tiles: an empty list says that every ray of the block misses, and a primary miss of these instances ends the pixel with one
+        // store (shade_step_ex, shade_miss).  The short path stores the environment's colour in the primary direction, as primary_ray makes
+        // it, and is done: no tmin / tmax, no RNG stream, no list walk, no shade_step, no second slot -> pixel mapping.
+        // (spp > 1 also leaves Scratch::primary_hit on a miss and the textured instances may sample an environment map: the general path.)
+        constexpr bool kSky = kPrimary && !kLoop && !kMulti && !kTex;
+        // (wave-uniform, and used up before the trace: the knob's word is read from the kernarg segment only behind an empty list, and nothing of
+        // this is carried through the loop's body, where the scalar registers are short)
+        const bool sky = kSky && beam_count == 0u && (cold_arg<uint32_t>(offsetof(BounceArgs, fc) + offsetof(FrameCounters, tile_opts)) >> 16) != 0u;
         if (i < count) {
             bool live = true;
             float tmin = 0.0f, tmax = kInf;
@@ -1281,10 +1348,16 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                 if (live) {
                     const CameraParams cam_c = cold_arg<CameraParams>(offsetof(BounceArgHead, fp) + offsetof(FrameParams, cam));
                     primary_ray(cam_c, pr.px, pr.py, ps.o, ps.d, tmin, tmax);
-                    ps.rng = rng_init(pr.px, pr.py, fp.frame_index);
+                    if (kSky && sky) {
+                        const f3 env = environment_color(sv.env[0], sv.env[1], sv.env[2], sv.env[3], ps.d);
+                        out[pr.out_index] = make_float4(env.x, env.y, env.z, 1.0f);
+                    } else {
+                        ps.rng = rng_init(pr.px, pr.py, fp.frame_index);
+                    }
                 } else if (pm_c.mode == 1) {
                     out[pr.out_index] = make_float4(0.f, 0.f, 0.f, 0.f);  // padding pixel of an edge tile
                 }
+                if (kSky && sky) live = false;
             } else if (seg_in) {
                 // dense index -> (segment, offset): the last segment whose prefix is <= i
                 uint32_t lo = 0, hi = fc.n_segs;
@@ -1353,8 +1426,9 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             // cost 18 % of the primary pass at C2: 132 -> 109 us measured with the compaction compiled out).
             const unsigned long long mask = __ballot(emit);
             const uint32_t wave_n = __popcll(mask);
+            if (wave_n == 0u) continue;  // (nothing to hand over: a sky tile, a tile whose paths all ended)
             uint32_t base = 0;
-            if (lane == 0 && wave_n) base = atomicAdd(&s_seg_count, wave_n);
+            if (lane == 0) base = atomicAdd(&s_seg_count, wave_n);
             base = __shfl(base, 0, 64);
             if (emit) store_path<kDn>(qout, blockIdx.x * fc.seg_cap + base + __popcll(mask & ((1ull << lane) - 1ull)), ps);
         } else if (!kLoop) {
