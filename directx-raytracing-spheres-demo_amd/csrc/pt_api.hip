@@ -1,8 +1,7 @@
 // pt_api.hip -- implementation of the C-ABI (include/pt_api.h) on the HIP runtime: context, device
-// memory, LBVH upload, and the per-frame launch sequence of the wavefront kernel set.
+// memory, LBVH upload, and the per-frame launch sequence of the wavefront kernel set.  (The passes that only use the context's stream
+// -- tone mapping to frame interpolation -- are in pt_api_post.hip; the context itself is pt_context.h.)
 // There is no CPU fallback here by design: without a HIP device pt_create fails.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>  // types and prototypes only: the library itself is loaded at run time (pt_comm_init)
 #include <dlfcn.h>
 #include <link.h>
 
@@ -17,268 +16,15 @@
 #include <limits>
 #include <vector>
 
-#include "../../include/pt_api.h"
-#include "pt_kernels.h"
+#include "pt_context.h"
 #include "pt_beam_cache.h"
-#include "pt_bloom.h"
-#include "pt_nrd.h"
-#include "pt_denoise.h"
-#include "pt_upscale.h"
-#include "pt_nis.h"
-#include "pt_framegen.h"
 #include "pt_restir.h"
-#include "pt_lbvh.h"
-#include "pt_lbvh_gpu.h"
-
-using namespace pt;
 
 namespace {
 
 constexpr uint32_t kMaxLdsBytes = 160u * 1024u;  // gfx950 LDS per CU / per workgroup
 constexpr uint32_t kSahMaxSpheres = 4096u;        // host SAH topology up to here, device LBVH above (pt_build_accel)
 constexpr uint32_t kLdsSceneBudget = 64u * 1024u; // stage the BVH in LDS only while two 512-thread blocks still fit per CU
-
-struct EventPair {
-    hipEvent_t a, b;
-    int kind;  // 0 primary, 1 traverse / fused bounce, 2 shade, 3 looping pass
-};
-
-}  // namespace
-
-// PT_* tuning knobs (DESIGN.md "Tuning knobs"): environment variables for A/B runs, read ONCE when the context is created --
-// the render path never touches the environment.  -1 = not set (the measured default applies).
-struct Knobs {
-    int split = -1, traverse_blocks_per_cu = -1, fused_threads = -1, no_adaptive_grid = -1, shade_blocks_per_cu = -1, tail_threshold = -1,
-        tail_blocks_per_cu = -1, loop_threads = -1, inline2_min_slots = -1, tail_after = -1, seg = -1, loop_use_tail = -1, fuse_loop = -1,
-        ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1, refl_beams = -1, coop_walk = -1, tile_order = -1, sky_fast = -1, tile_table = -1;
-};
-
-// Per-frame-in-flight state (see PtContext::lanes).
-struct Lane {
-    hipStream_t stream = nullptr;  // == PtContext::stream when there is a single lane
-    hipEvent_t ev_done = nullptr;
-    size_t cap_slots = 0;
-    RayQueue q[2]{};
-    Scratch scratch{};
-    bool scratch_spp = false;
-    uint32_t* d_counts = nullptr;  // two parities: [0, cap_counts) and [cap_counts, 2 cap_counts)
-    size_t cap_counts = 0;
-    uint32_t parity = 0;           // parity of the frame being (or last) submitted on this lane
-    uint32_t* h_counts = nullptr;  // pinned
-    // queue sizes of a recent frame (pinned, written by an async copy, read without waiting): they only size the
-    // launch grids -- every kernel is a grid-stride loop, so a stale or missing estimate costs time, never correctness
-    uint32_t* h_prev_counts = nullptr;   // host-mapped: the GPU writes it when it folds a frame's counters (no copy call)
-    uint32_t* d_prev_counts = nullptr;   // device address of h_prev_counts
-    uint64_t prev_signature = 0;
-    uint32_t* d_seg_counts = nullptr;        // kMaxSegs segment sizes of the primary pass -> looping pass hand-over
-    static constexpr uint32_t kTotals = 10;
-    unsigned long long* d_totals = nullptr;  // [0] running secondary-ray total, [1] last folded frame, [2],[3] tail counters,
-                                             // [4] running count of in-register secondary rays of primary passes, [5] unused,
-                                             // [6] node visits, [7] sphere tests of the global-memory traversal kernels,
-                                             // [8] waves of primary passes that traced in-register bounce-1 rays, [9] ... of them from a
-                                             // reflection-beam list (pt_get_refl_stats)
-    // private copy of the moving part of the scene (pt_update_spheres / pt_refit_accel): spheres, Morton-ordered spheres
-    // and node boxes; null = this lane renders the context's master scene
-    float4* d_sph = nullptr;
-    float4* d_sph_sorted = nullptr;
-    float4* d_nodes = nullptr;
-    uint32_t* d_refit_flags = nullptr;
-    uint32_t* d_refit_hdr = nullptr;
-    PtSphere* h_stage = nullptr;      // pinned upload staging, host-mapped ...
-    const float4* d_stage = nullptr;  // ... and its device address (the single-launch refit of small scenes reads the staging buffer itself)
-    hipEvent_t ev_upload = nullptr;   // the last upload from h_stage has been consumed
-    hipEvent_t ev_poll[4] = {};       // queue-size read-backs of the last passes (spp > 1 lagged polling)
-    uint32_t scene_n = 0;             // sphere count the private copy was allocated for
-    bool scene_private = false;
-    uint64_t sph_gen = 0;         // the pt_update_spheres generation this lane's private scene holds (PtContext::sph_gen)
-    bool needs_refit = false;     // spheres were staged on this lane and its boxes / Morton-ordered copy have not been redone yet
-    bool upload_pending = false;  // h_stage holds spheres that have not been copied to d_sph yet (pt_update_spheres of a small scene: pt_refit_accel's kernel reads them)
-    const void* last_out = nullptr;   // output buffer of the lane's latest frame (render_common: repeated buffers inside the window)
-    const void* last_dn[3] = {};      // ... and its denoiser buffers (Diffuse, Specular, SpecularHitDistance; null for other frames)
-    const void* last_di[2] = {};      // ... and the DI buffers it read (pt_render_with_di: Diffuse, Specular; null for other frames)
-    // object rotations (textured scenes): the lane's own copy, refreshed from PtContext::h_rot when its generation is behind
-    float4* d_rot = nullptr;
-    float4* h_rot_stage = nullptr;    // pinned
-    hipEvent_t ev_rot = nullptr;      // the last upload from h_rot_stage has been consumed
-    uint64_t rot_gen = 0;
-    uint32_t rot_n = 0;
-    // pt_render_gbuffer: the caller's previous poses (spheres, then rotations) as the lane's calls read them, their pinned staging
-    // buffer, and the marker that orders a G-buffer call after what the caller queued on `stream`
-    float4* d_prev_pose = nullptr;
-    float4* h_prev_stage = nullptr;
-    hipEvent_t ev_prev = nullptr;     // the last upload from h_prev_stage has been consumed
-    uint32_t prev_cap = 0;            // spheres the two buffers hold room for
-    hipEvent_t ev_gb_in = nullptr;
-    void* last_gb[13] = {};           // the buffers of the lane's latest G-buffer call (its ordering against the caller's stream)
-    const void* last_ri[2] = {};      // the outputs of the lane's latest pt_restir_di call
-};
-constexpr uint32_t kMaxLanes = 8;
-
-struct PtContext {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint32_t flags = 0;
-    uint32_t tile_size = 32;
-    uint32_t num_cus = 256;
-    Knobs knobs;
-    std::string err;
-
-    // scene
-    uint32_t n = 0;
-    float4* d_sph = nullptr;
-    float4* d_mats = nullptr;
-    PtSceneData sd{};
-    std::vector<PtSphere> h_sph;
-    bool scene_set = false;
-
-    // textures (row N1): table of linear float4 images + per-sphere map indices and rotations
-    std::vector<float4*> d_tex_images;
-    std::vector<std::pair<uint32_t, uint32_t>> tex_dims;  // width, height of every table entry
-    TexView* d_tex = nullptr;
-    uint32_t* d_tex_maps = nullptr;  // n * 8
-    float4* d_rot = nullptr;         // n: the rotations as of pt_set_textures (single-lane contexts update it in stream order)
-    std::vector<float4> h_rot;       // latest rotations (pt_update_rotations); lanes pick them up when they next render
-    uint64_t rot_gen = 0;            // generation of h_rot (never reset) ...
-    uint64_t rot_master_gen = 0;     // ... and the generation d_rot holds: while they are equal every lane reads d_rot
-    bool has_textures = false;
-
-    // emissive spheres (row N4)
-    uint32_t* d_lights = nullptr;
-    uint32_t n_lights = 0;
-
-    // alpha-tested hits (spec S10): the spheres whose AlphaMode is not Opaque, their class per sphere on the device (null while
-    // every sphere is kAlphaVisible) and the leaf ids carrying it (Morton order; null = the traversal reads d_sorted_id)
-    struct AlphaMat { uint32_t id; float base[4]; float cutoff; uint32_t base_map; };
-    std::vector<AlphaMat> alpha_mats;
-    uint32_t* d_alpha_class = nullptr;
-    uint32_t* d_leaf_ids = nullptr;
-    bool alpha_tested = false;
-
-    // accel
-    float4* d_nodes = nullptr;
-    float4* d_wide = nullptr;        // 4-wide view of the tree (global-memory scenes only; null otherwise)
-    float4* d_sph_sorted = nullptr;
-    uint32_t* d_sorted_id = nullptr;
-    uint32_t n_nodes = 0, depth = 0;
-    bool lds_scene = false;
-    bool accel_valid = false;
-    LbvhResult lbvh;  // host copy (download / info); filled by either builder
-    LbvhGpu* gpu_builder = nullptr;
-
-    // frame state
-    PtCamera cam{};
-    PtGraphicsSettings gs{};
-    bool cam_set = false, gs_set = false;
-    uint32_t rank = 0, world = 1;                       // pt_set_partition (kept for pt_tiles_count(rank))
-    uint32_t part_first = 0, part_run = 1, part_stride = 1;  // the residue range this context renders (pt_set_partition_ex)
-
-    // work buffers: one set per frame in flight.  Frame f runs on lane f % n_lanes, on that lane's own stream, so the
-    // latency-bound looping pass of one frame overlaps the throughput-bound first passes of the next.
-    Lane lanes[kMaxLanes];
-    uint32_t n_lanes = 1;
-    uint32_t next_lane = 0;
-    uint32_t last_lane = 0;
-    hipEvent_t ev_in[kMaxLanes] = {};  // markers on `stream` at the start of the last n_lanes render calls
-    uint64_t calls = 0;
-    uint64_t sph_gen = 0;      // counts pt_update_spheres calls since pt_set_scene; latest_lane: the lane whose staging buffer holds the newest spheres
-    int latest_lane = -1;
-    bool empty_scene = false;  // pt_set_scene(n = 0): one internal sphere that no ray can hit stands in (see pt_set_scene)
-    float4* d_out = nullptr;
-    size_t cap_out = 0;
-    // pt_render_gbuffer before the render call that will take lane `gb_lane` as frame number `gb_frame`: whether every lane was idle
-    // when it was made (render_common's one-frame-at-a-time test must not mistake that frame's own G-buffer work for a frame in flight)
-    uint64_t frames = 0;  // render calls that took a lane
-    uint64_t gb_frame = ~0ull;
-    uint32_t gb_lane = 0;
-    bool gb_lanes_idle = false;
-    float4* d_bloom = nullptr;  // pt_bloom's blur chain (used on `stream` only), grown on demand
-    uint64_t cap_bloom = 0;     // texels
-    // pt_nrd_denoise's history and work buffers (used on `stream` only): one allocation of kDnBytesPerPixel per pixel, made on first
-    // use and again when RenderSize changes; `slot` = the history slot the last call wrote
-    float* d_dn = nullptr;
-    uint32_t dn_w = 0, dn_h = 0, dn_mode = 0, dn_slot = 0;
-    bool dn_valid = false;
-    // pt_upscale's history (row N11; used on `stream` only): per output pixel two alternating slots of a float4 and a float, allocated
-    // on first use and again when the output size (up_W, up_H) changes; a change of either size restarts it; `up_slot` = the slot the
-    // last call wrote
-    float4* d_up = nullptr;
-    uint32_t up_w = 0, up_h = 0, up_W = 0, up_H = 0, up_slot = 0;
-    bool up_valid = false;
-    // pt_frame_gen's buffers (row N13; used on `stream` only): the motion field (8 B per render pixel), then two alternating history
-    // slots of the previous Color (4 B per output pixel) and two of the previous Depth (4 B per render pixel); allocated on first use
-    // and again when a size changes; a change of either size or of the Format restarts the history; `fg_slot` = the slot the last call wrote
-    unsigned long long* d_fg = nullptr;
-    uint32_t fg_w = 0, fg_h = 0, fg_W = 0, fg_H = 0, fg_format = 0, fg_slot = 0;
-    bool fg_valid = false;
-    // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
-    // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
-    // pt_set_scene count it was made under (emitter indices change with the scene), `ev_ri` = the last call's launches have finished
-    // (consecutive calls run on different lanes and hand the history to each other)
-    float4* d_ri = nullptr;
-    uint32_t ri_w = 0, ri_h = 0, ri_slot = 0;
-    uint64_t ri_scene = 0, set_scene_calls = 0;
-    bool ri_valid = false;
-    hipEvent_t ev_ri = nullptr;
-    uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
-    uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists
-
-    // Primary beams (DESIGN.md "Primary beams"): per-8x8-block candidate sphere lists for the primary pass.  They depend on the
-    // camera's lens, the frame geometry and the scene, on the camera's POSITION up to the slack (Beam::slack) and on its ORIENTATION
-    // up to the pixel margin (make_beam) they were built with -- not on the frame index or the jitter (the beams are a pixel wider
-    // than the blocks).  A view that RESTS gets exact lists on its second frame (one launch on a side stream); a camera that
-    // travels and turns gets lists centred and oriented some frames ahead of it, with a slack of a few frames' travel and a margin
-    // of a few frames' turn, built in shares inside the frames' own primary passes
-    // while the frames use the previous ones -- a frame never waits for a build of the moving kind: it takes the newest lists that
-    // are readable and hold for its pose, or traverses per ray.
-    struct BeamLists {
-        uint32_t* d_lists = nullptr;   // n_blocks records of 16 dwords
-        size_t cap_blocks = 0;
-        uint32_t* d_regions = nullptr; // reflection beams: n_blocks region records of kReflRecord dwords (pt_region.h) ...
-        size_t cap_regions = 0;
-        bool regions = false;          // ... that d_regions holds for these lists (resting views' builds only)
-        std::vector<uint32_t> key;     // orientation, frame geometry, scene generation of the lists in d_lists; empty = none
-        float pos[3] = { 0, 0, 0 };    // the camera position they were built around ...
-        float slack = 0.0f;            // ... and how far from it they hold
-        float basis[9] = {};           // the orientation (Right, Up, Forward) they were built for ...
-        float margin_px = 0.0f;        // ... and by how many pixels a ray's crossing of the image may differ from that orientation's
-        hipEvent_t ev_ready = nullptr;   // the build has finished
-        bool building = false;         // launched, ev_ready not yet seen complete
-        bool used = false;             // read by a frame since the build (a rebuild must wait for the lanes)
-        uint64_t first_call = 0;       // the first render call whose frame may read them (BeamCache::calls)
-        uint64_t last_use_call = 0;    // the last render call whose frame was handed them
-        uint64_t built_call = 0;       // the render call that started (resting view) or completed (moving camera) their build
-    };
-    struct BeamCache {
-        BeamLists buf[2];
-        int cur = 0;                     // the lists frames use; the other buffer is the one a build goes to
-        uint64_t calls = 0;              // render calls that consulted the cache
-        std::vector<uint32_t> last_key;  // key / position of the previous render call
-        float last_pos[3] = { 0, 0, 0 };
-        hipStream_t stream = nullptr;      // side stream (the builds of resting views)
-        hipEvent_t ev_last_use = nullptr;  // scratch event of a rebuild (orders it after the lanes' frames in flight)
-        // a moving camera's next lists, built a share per frame inside the frames' primary passes (FrameParams::beam_job)
-        struct { bool active = false; BeamLists* dst = nullptr; std::vector<uint32_t> key; float centre[3] = { 0, 0, 0 }; float slack = 0.0f; float basis[9] = {}; float margin_px = 0.0f; uint32_t next_block = 0, n_blocks = 0; } inc;
-        float last_vel[3] = { 0, 0, 0 };   // the camera's travel between the two calls before this one (its change bounds how far to trust the extrapolation)
-        double last_turn[3] = { 0, 0, 0 }; // ... and its turn (rotation vector)
-        float last_basis[9] = {};          // orientation of the previous render call
-        bool have_vel = false;
-    } beam;
-    uint64_t scene_gen = 0;  // bumped by everything that changes what a ray can hit
-    float slab_tiny = 1e-30f;  // SceneView::slab_tiny of the tree pt_build_accel made
-    float min_radius = 0.0f;  // smallest sphere of the scene set by pt_set_scene (bounds the slack of a moving camera's beam lists)
-
-    // multi-GPU exchange (pt_comm_init / pt_gather): the RCCL communicator of this rank
-    ncclComm_t comm = nullptr;
-    uint32_t comm_rank = 0, comm_world = 1;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool profiling = false;
-    std::vector<EventPair> ev_pool;
-    size_t ev_used = 0;
-};
-
-namespace {
 
 // roctx ranges (the reference brackets its passes with PIX events): with PT_ROCTX=1 every render call and BVH build /
 // refit is a named range on rocprofv3's marker timeline (rocprofv3 --marker-trace --kernel-trace).  libroctx64 is resolved at run
@@ -361,27 +107,6 @@ Rccl& rccl()
     r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(sym("ncclGetErrorString"));
     if (!r.error.empty()) { dlclose(r.handle); r.handle = nullptr; }
     return r;
-}
-
-PtStatus fail(PtContext* ctx, PtStatus st, const std::string& msg)
-{
-    if (ctx) ctx->err = msg;
-    return st;
-}
-
-#define PT_HIP(ctx, expr)                                                                              \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP,                      \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                            \
-        }                                                                                              \
-    } while (0)
-
-template <typename T>
-void free_dev(T*& p)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
 }
 
 void free_lane_scene(Lane& L)
@@ -973,6 +698,118 @@ static PtStatus check_environment(PtContext* c)
     return PT_OK;
 }
 
+// the tree walk's traversal stack must fit a workgroup's LDS (render_common, pt_render_gbuffer, pt_restir_di)
+static PtStatus check_tree_lds(PtContext* c)
+{
+    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)  // (the kernels' static LDS comes on top)
+        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    return PT_OK;
+}
+
+// The lane side of a frame and of its side passes (pt_render_gbuffer, pt_restir_di: work for the frame the NEXT render call renders,
+// queued on the lane that frame will take; the lane rotation is not advanced, the render call finds the lane up to date).
+//
+// Is the caller waiting for each frame or keeping several in flight?  Asked of the streams before the call queues anything: all lanes
+// drained = one frame at a time.  A side pass of this very frame has queued work on its lane: that lane counts as idle if every lane
+// was when the frame's first side pass was made (side_pass_begin).
+static bool lanes_idle_for_next_frame(PtContext* c)
+{
+    const bool own = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
+    bool idle = !own || c->gb_lanes_idle;
+    for (uint32_t i = 0; i < c->n_lanes && idle; i++)
+        if (!(own && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { idle = false; (void)hipGetLastError(); }
+    return idle;
+}
+
+// the lane's copies of what moves: rotations, spheres, and the boxes of spheres updated without pt_refit_accel (the frame refits by itself)
+static PtStatus lane_catch_up(PtContext* c, Lane& L)
+{
+    if (const PtStatus st = sync_lane_rotations(c, L); st != PT_OK) return st;
+    if (const PtStatus st = sync_lane_spheres(c, L); st != PT_OK) return st;
+    return L.needs_refit ? refit_lane(c, L) : PT_OK;
+}
+
+// a side pass starts: the idle test made for the frame it belongs to (render_common must not mistake the pass for a frame in flight;
+// a second pass for the same frame finds its own lane busy with the first one), then the lane brought up to date
+static PtStatus side_pass_begin(PtContext* c, Lane& L)
+{
+    const bool idle = lanes_idle_for_next_frame(c);
+    c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
+    return lane_catch_up(c, L);
+}
+
+// is p a buffer that the latest frame, G-buffer call or (with_ri) DI pass of a lane other than L wrote, or that its frame read as DI?
+static bool other_lane_uses(const PtContext* c, const Lane& L, const void* p, bool with_ri)
+{
+    for (uint32_t i = 0; i < c->n_lanes; i++) {
+        const Lane& o = c->lanes[i];
+        if (&o == &L) continue;
+        bool hit = p == o.last_out;
+        for (const void* q : o.last_gb) hit = hit || p == q;
+        for (const void* q : o.last_dn) hit = hit || p == q;
+        for (const void* q : o.last_di) hit = hit || p == q;
+        for (const void* q : o.last_ri) hit = hit || (with_ri && p == q);
+        if (hit) return true;
+    }
+    return false;
+}
+
+// A side pass is ordered as the frame it belongs to (render_common): the caller rotates over n_lanes sets of buffers, so the pass waits
+// for the marker recorded on the caller's stream at the start of the render call n_lanes - 1 calls ago (after the consumer of this
+// lane's previous buffers), not for the frames in between.  shared (before the first render call, or a buffer that was touched elsewhere
+// within that window): it waits for everything the caller has queued so far instead.
+static PtStatus order_lane_after_caller(PtContext* c, Lane& L, bool shared)
+{
+    if (shared) {
+        if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
+        PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
+        PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
+        return PT_OK;
+    }
+    const uint64_t nl = c->n_lanes;
+    const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
+    if (hipEventQuery(marker) != hipSuccess) {
+        (void)hipGetLastError();  // hipErrorNotReady is not an error here
+        PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
+    }
+    return PT_OK;
+}
+
+// whatever the caller queues next on its stream (a gather, a copy, pt_download, the next use of the buffers) sees what the lane has
+// finished -- also after a failed launch: the caller's stream must stay ordered behind the kernels that did run.  Returns st, or the
+// event's failure if st was PT_OK.
+static PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus st)
+{
+    if (L.stream == c->stream) return st;
+    const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
+    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
+    if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": completion event: " + hipGetErrorString(e2));
+    return st;
+}
+
+// the slot map of the primary pass over a rect of the image: 8x8-pixel blocks of the rect, one per wave
+static uint64_t rect_slots(const PtRect& r) { return (uint64_t)((r.w + 7) / 8) * ((r.h + 7) / 8) * 64ull; }
+static PixelMap make_pixel_map(uint32_t img_w, uint32_t img_h, const PtRect& r)
+{
+    PixelMap pm{};
+    pm.mode = 0;
+    pm.img_w = img_w; pm.img_h = img_h;
+    pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
+    pm.blocks_x = (r.w + 7) / 8;
+    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
+    const uint64_t slots = rect_slots(r);
+    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
+    pm.n_slots = (uint32_t)slots;
+    return pm;
+}
+
+// the launch grid of a side pass: LDS-resident scenes stage the tree once per workgroup, so a few workgroups per CU walk the whole frame
+static uint32_t side_pass_grid(const PtContext* c, uint32_t n_slots)
+{
+    const uint32_t threads = traverse_threads(c->lds_scene);
+    return std::max(1u, std::min((n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
+}
+
 // The per-frame launch sequence.  out: device float4 buffer addressed by PixelRef::out_index.
 //
 // Fused schedule (default):  bounce<primary> -> bounce (x S) -> bounce<loop>
@@ -1001,8 +838,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     // reaches 4) -- measured 4.3 vs 5.3 ms per frame on the 2^20-sphere scene.
     const bool split = (c->flags & PT_FLAG_SPLIT_KERNELS) || knob_or(c->knobs.split, c->lds_scene ? 0u : 1u) != 0;
     // every check that can reject the frame comes before any state change (lane rotation, counter parity, markers)
-    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)  // (the kernels' static LDS comes on top)
-        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    if (const PtStatus st = check_tree_lds(c); st != PT_OK) return st;
     // frames in flight: this frame runs on the next lane (its own stream and work buffers); the rotation itself happens
     // below, once the lane's buffers exist
     Lane& L = c->lanes[c->next_lane];
@@ -1012,14 +848,9 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         PT_HIP(c, hipStreamSynchronize(L.stream));
     }
     const bool di = ext || (c->gs.IsDIEnabled && c->n_lights > 0);
-    // Is the caller waiting for each frame (App::Tick -> Render -> WaitForGPU) or keeping several in flight?  Asked of the streams before this
-    // frame queues anything: all lanes drained = one frame at a time, and the frame is scheduled for latency (below: the fused form).
-    // (A pt_render_gbuffer call for this very frame has queued work on its lane: that lane counts as idle if every lane was when that call
-    // was made.)
-    const bool gb_before = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
-    bool lanes_idle = !gb_before || c->gb_lanes_idle;
-    for (uint32_t i = 0; i < c->n_lanes && lanes_idle; i++)
-        if (!(gb_before && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { lanes_idle = false; (void)hipGetLastError(); }
+    // Is the caller waiting for each frame (App::Tick -> Render -> WaitForGPU) or keeping several in flight?  Asked before this frame
+    // queues anything: one frame at a time is scheduled for latency (below: the fused form).
+    const bool lanes_idle = lanes_idle_for_next_frame(c);
     // Persistent workgroups: with the BVH staged into LDS per workgroup, 2 per CU (= the 4 waves/SIMD the kernel is built
     // for) amortise the 37 KB staging over ~4 batches of rays at 1080p / 1 spp (0.121 -> 0.116 ms per frame), from about
     // 1.5 M slots: below that 8 per CU is 4-10 % faster.  (Since the waves of a workgroup draw their tiles dynamically the
@@ -1041,9 +872,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     // reallocated with the lane's other per-slot buffers
     if (dn && !L.scratch.dn.rec) PT_HIP(c, hipMalloc(&L.scratch.dn.rec, L.cap_slots * sizeof(float4)));
     if (dn && dn->mode != 1 && di && !L.scratch.dn.di_s) PT_HIP(c, hipMalloc(&L.scratch.dn.di_s, L.cap_slots * sizeof(float4)));
-    if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
-    if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
-    if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;  // pt_update_spheres without pt_refit_accel: the frame refits by itself
+    if ((st = lane_catch_up(c, L)) != PT_OK) return st;
     c->last_lane = c->next_lane;
     c->next_lane = (c->next_lane + 1) % c->n_lanes;
     c->frames++;
@@ -1295,13 +1124,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     }
     // this frame's queue sizes reach h_prev_counts when the lane's next frame folds them (frame_counters_begin): no copy call
     L.prev_signature = signature;  // (the launch-grid estimates above only use them at 1 spp; pt_get_queue_sizes reports them always)
-    if (L.stream != c->stream) {
-        // whatever the caller queues next on its stream (a gather, a copy, the next use of `out`) sees the finished frame
-        const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
-        if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("render: completion event: ") + hipGetErrorString(e2));
-    }
-    if (st != PT_OK) return st;
+    if ((st = publish_lane_to_caller(c, L, "render", st)) != PT_OK) return st;
     c->tot_pixels += valid_pixels;
     c->tot_paths += valid_pixels * spp;
     c->tot_fixed_bytes += fixed_bytes(split, pm.n_slots, valid_pixels, spp > 1 ? valid_pixels * spp : 0);
@@ -1467,9 +1290,7 @@ void pt_destroy(PtContext* c)
     if (c->beam.stream) (void)hipStreamDestroy(c->beam.stream);
     free_dev(c->d_out);
     free_dev(c->d_bloom);
-    free_dev(c->d_dn);
-    free_dev(c->d_up);
-    free_dev(c->d_fg);
+    for (History* H : { &c->dn, &c->up, &c->fg }) free_dev(H->mem);
     free_dev(c->d_ri);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
@@ -1689,7 +1510,6 @@ PtStatus pt_update_spheres(PtContext* c, const PtSphere* spheres, uint32_t n)
     return PT_OK;
 }
 
-
 PtStatus pt_refit_accel(PtContext* c)
 {
     if (!c) return PT_ERR_INVALID_ARG;
@@ -1755,22 +1575,14 @@ uint32_t pt_tiles_count_ex(PtContext* c, uint32_t first, uint32_t run, uint32_t 
     return count_tiles(frame_tiles(c), first, run, stride);
 }
 
-// rect (NULL = the whole RenderSize) -> the slot map of the primary pass (8x8-pixel blocks of the rect, one per wave)
+// rect (NULL = the whole RenderSize), validated -> the slot map of the primary pass (make_pixel_map)
 static PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who, PtRect& r, PixelMap& pm)
 {
     r = rect ? *rect : PtRect{ 0, 0, c->gs.RenderSize[0], c->gs.RenderSize[1] };
     if (r.w == 0 || r.h == 0 || r.x >= c->gs.RenderSize[0] || r.w > c->gs.RenderSize[0] - r.x || r.y >= c->gs.RenderSize[1] || r.h > c->gs.RenderSize[1] - r.y)
         return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect is empty or outside RenderSize");
-    pm = PixelMap{};
-    pm.mode = 0;
-    pm.img_w = c->gs.RenderSize[0]; pm.img_h = c->gs.RenderSize[1];
-    pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
-    pm.blocks_x = (r.w + 7) / 8;
-    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
-    const uint64_t slots = (uint64_t)pm.blocks_x * ((r.h + 7) / 8) * 64ull;
-    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
-    if (slots > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect too large");
-    pm.n_slots = (uint32_t)slots;
+    if (rect_slots(r) > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect too large");
+    pm = make_pixel_map(c->gs.RenderSize[0], c->gs.RenderSize[1], r);
     return PT_OK;
 }
 
@@ -1886,8 +1698,7 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
     PixelMap pm{};
     if ((st = rect_pixel_map(c, rect, "pt_render_gbuffer", r, pm)) != PT_OK) return st;
     if ((st = check_environment(c)) != PT_OK) return st;
-    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)
-        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    if ((st = check_tree_lds(c)) != PT_OK) return st;
     // previous poses (PreviousObjectToWorld): only while the scene is not static; the empty scene has none
     const uint32_t n = c->empty_scene ? 0u : c->n;
     const bool use_prev_sph = previous_spheres && !c->sd.IsStatic && n > 0, use_prev_rot = previous_rotations && !c->sd.IsStatic && n > 0;
@@ -1900,50 +1711,13 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
         if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous rotation " + std::to_string(i / 4) + " is not finite");
     PT_HIP(c, hipSetDevice(c->device));
 
-    // the lane of the next frame, brought up to date as render_common does (its rotation is not advanced: the next pt_render finds it
-    // synchronised)
-    Lane& L = c->lanes[c->next_lane];
-    // asked before anything is queued: are all lanes idle (render_common's one-frame-at-a-time test, made for the frame this G-buffer
-    // belongs to)?  A second call for the same frame finds its own lane busy with the first one.
-    {
-        const bool again = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
-        bool idle = !again || c->gb_lanes_idle;
-        for (uint32_t i = 0; i < c->n_lanes && idle; i++)
-            if (!(again && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { idle = false; (void)hipGetLastError(); }
-        c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
-    }
-    if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
-    if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
-    if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;
+    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
+    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
     if (L.stream != c->stream) {
-        // Ordered as the frame it belongs to (render_common): the caller rotates over n_lanes sets of G-buffer buffers as it does over
-        // frame buffers, so the pass waits for the marker recorded on the caller's stream at the start of the render call n_lanes - 1
-        // calls ago (after the consumer of this lane's previous buffers), not for the frames in between.  Before the first render call,
-        // or when a buffer is one that another lane's G-buffer or frame wrote within that window, it waits for everything the caller has
-        // queued so far instead.
-        const uint64_t nl = c->n_lanes;
+        // shared: a buffer is one that another lane's G-buffer or frame wrote within the window
         bool shared = c->calls == 0;
-        for (uint32_t i = 0; i < c->n_lanes && !shared; i++) {
-            if (&c->lanes[i] == &L) continue;
-            for (uint32_t k = 0; k < 13 && !shared; k++)
-                if (ptrs[k]) {
-                    shared = ptrs[k] == c->lanes[i].last_out;
-                    for (uint32_t j = 0; j < 13 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_gb[j];
-                    for (uint32_t j = 0; j < 3 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_dn[j];
-                    for (uint32_t j = 0; j < 2 && !shared; j++) shared = ptrs[k] == c->lanes[i].last_di[j];
-                }
-        }
-        if (shared) {
-            if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
-            PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
-            PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
-        } else {
-            const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
-            if (hipEventQuery(marker) != hipSuccess) {
-                (void)hipGetLastError();  // hipErrorNotReady is not an error here
-                PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
-            }
-        }
+        for (uint32_t k = 0; k < 13 && !shared; k++) shared = ptrs[k] && other_lane_uses(c, L, ptrs[k], false);
+        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
         for (uint32_t k = 0; k < 13; k++) L.last_gb[k] = ptrs[k];
     }
     const SceneView sv = make_scene_view(c, &L);
@@ -1996,19 +1770,10 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
     out.IOR = static_cast<float*>(gb->IOR);
     out.Transmission = static_cast<float*>(gb->Transmission);
     out.Radiance = static_cast<f3*>(gb->Radiance);
-    const uint32_t threads = traverse_threads(c->lds_scene);
-    // LDS-resident scenes stage the tree once per workgroup: a few workgroups per CU walk the whole frame
-    const uint32_t grid = std::max(1u, std::min((pm.n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
     st = PT_OK;
-    if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, grid, L.stream); e != hipSuccess)
+    if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
         st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: launch: ") + hipGetErrorString(e));
-    if (L.stream != c->stream) {
-        // whatever the caller queues next on its stream (pt_download, pt_bloom, the next use of the buffers) sees the G-buffer
-        const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
-        if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: completion event: ") + hipGetErrorString(e2));
-    }
-    return st;
+    return publish_lane_to_caller(c, L, "pt_render_gbuffer", st);
 }
 
 PtStatus pt_render_tiles(PtContext* c, void* out_device_packed, PtStats* stats)
@@ -2186,361 +1951,6 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
     return PT_OK;
 }
 
-PtStatus pt_tonemap(PtContext* c, const void* hdr, uint32_t n_pixels, const PtToneMapParams* params, void* out)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!hdr || !out || !params) return fail(c, PT_ERR_INVALID_ARG, "pt_tonemap: null pointer");
-    if (params->Operator > kToneACESFilmic || params->TransferFunction > kTransferST2084 || params->ColorRotation > kRotate709toP3D65)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_tonemap: unknown operator / transfer function / colour rotation");
-    if (n_pixels == 0) return PT_OK;
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, launch_tonemap(static_cast<const float4*>(hdr), static_cast<uint32_t*>(out), n_pixels, *params, c->stream));
-    return PT_OK;
-}
-
-PtStatus pt_accumulate(PtContext* c, void* accum, const void* radiance, uint32_t n_pixels, uint32_t frames_accumulated)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!accum || !radiance) return fail(c, PT_ERR_INVALID_ARG, "pt_accumulate: null pointer");
-    if (frames_accumulated == 0xFFFFFFFFu) return fail(c, PT_ERR_INVALID_ARG, "pt_accumulate: frame count overflow");
-    if (n_pixels == 0) return PT_OK;
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, launch_accumulate(static_cast<float4*>(accum), static_cast<const float4*>(radiance), n_pixels, frames_accumulated, c->stream));
-    return PT_OK;
-}
-
-PtStatus pt_bloom(PtContext* c, const void* hdr, void* out, uint32_t width, uint32_t height, float strength)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!hdr || !out) return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: null pointer");
-    // >= 32: every level of the 5-mip half-size chain is at least one texel; <= 16384: the largest D3D12 2-D texture
-    if (width < kBloomMinSize || height < kBloomMinSize || width > 16384u || height > 16384u)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: width and height must be in [32, 16384]");
-    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_bloom: strength must be in [0, 1]");
-    PT_HIP(c, hipSetDevice(c->device));
-    const uint64_t need = bloom_chain(width, height).texels;
-    if (need > c->cap_bloom) {
-        // the chain is only used on `stream`: once the bloom calls queued there have finished, the old one is free (the render
-        // lanes never touch it, so their frames in flight go on)
-        PT_HIP(c, hipStreamSynchronize(c->stream));
-        free_dev(c->d_bloom);
-        c->cap_bloom = 0;
-        PT_HIP(c, hipMalloc(&c->d_bloom, need * sizeof(float4)));
-        c->cap_bloom = need;
-    }
-    PT_HIP(c, launch_bloom(static_cast<const float4*>(hdr), static_cast<float4*>(out), c->d_bloom, width, height, strength, c->stream));
-    return PT_OK;
-}
-
-// Row N8 -- the NRD composition pass (DESIGN.md spec S14): one launch of pack or compose on the context's stream
-PtStatus pt_nrd_composition(PtContext* c, const PtNrdCompositionConstants* k, const PtNrdCompositionTextures* t)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!k || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: null pointer");
-    if (k->Denoiser != kNrdReblur && k->Denoiser != kNrdRelax)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: Denoiser must be 2 (NRDReBLUR) or 3 (NRDReLAX)");
-    const uint32_t w = k->RenderSize[0], h = k->RenderSize[1];
-    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_composition: RenderSize must be in [1, 16384]");
-    const bool pack = k->Pack != 0, reblur = k->Denoiser == kNrdReblur;
-    const uint64_t n = (uint64_t)w * h;
-    // the buffers this direction uses: (pointer, bytes per pixel, alignment, written)
-    struct Use { const void* p; uint32_t bpp, align; bool written; const char* name; };
-    Use use[7];
-    uint32_t nu = 0;
-    use[nu++] = {t->LinearDepth, 4, 4, false, "LinearDepth"};
-    use[nu++] = {t->DiffuseAlbedo, 12, 4, false, "DiffuseAlbedo"};
-    use[nu++] = {t->SpecularAlbedo, 12, 4, false, "SpecularAlbedo"};
-    if (pack) {
-        if (reblur) use[nu++] = {t->NormalRoughness, 16, 16, false, "NormalRoughness"};
-        use[nu++] = {t->NoisyDiffuse, 16, 16, true, "NoisyDiffuse"};
-        use[nu++] = {t->NoisySpecular, 16, 16, true, "NoisySpecular"};
-    } else {
-        use[nu++] = {t->DenoisedDiffuse, 16, 16, false, "DenoisedDiffuse"};
-        use[nu++] = {t->DenoisedSpecular, 16, 16, false, "DenoisedSpecular"};
-        use[nu++] = {t->Radiance, 16, 16, true, "Radiance"};
-    }
-    for (uint32_t i = 0; i < nu; i++) {
-        if (!use[i].p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " is required");
-        if (reinterpret_cast<uintptr_t>(use[i].p) % use[i].align)
-            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " is not " + std::to_string(use[i].align) + "-byte aligned");
-    }
-    // a buffer the pass writes must not share a byte with any other buffer it uses (each lane reads its pixel of a written buffer
-    // before it writes it, so a written buffer may only overlap itself)
-    for (uint32_t i = 0; i < nu; i++)
-        for (uint32_t j = 0; j < nu; j++) {
-            if (i == j || !use[i].written) continue;
-            const uintptr_t a = reinterpret_cast<uintptr_t>(use[i].p), b = reinterpret_cast<uintptr_t>(use[j].p);
-            if (a < b + n * use[j].bpp && b < a + n * use[i].bpp)
-                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_composition: ") + use[i].name + " overlaps " + use[j].name);
-        }
-    NrdBuffers b{};
-    b.linear_depth = static_cast<const float*>(t->LinearDepth);
-    b.diffuse_albedo = static_cast<const float*>(t->DiffuseAlbedo);
-    b.specular_albedo = static_cast<const float*>(t->SpecularAlbedo);
-    if (pack) {
-        b.normal_roughness = reblur ? static_cast<const float4*>(t->NormalRoughness) : nullptr;
-        b.noisy_diffuse = static_cast<float4*>(t->NoisyDiffuse);
-        b.noisy_specular = static_cast<float4*>(t->NoisySpecular);
-    } else {
-        b.denoised_diffuse = static_cast<const float4*>(t->DenoisedDiffuse);
-        b.denoised_specular = static_cast<const float4*>(t->DenoisedSpecular);
-        b.radiance = static_cast<float4*>(t->Radiance);
-    }
-    const NrdHitDistParams P{k->ReBLURHitDistance[0], k->ReBLURHitDistance[1], k->ReBLURHitDistance[2], k->ReBLURHitDistance[3]};
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, launch_nrd_composition(b, (uint32_t)n, pack, k->Denoiser, P, c->stream));
-    return PT_OK;
-}
-
-// Row N9 -- the NRD stand-in (DESIGN.md spec S15): pass (a), pass (b) and the a-trous steps on the context's stream, the history
-// in the context.  Per pixel: two history slots of four float4 (accumulated diffuse / specular, moments, guide), two hit distances,
-// two a-trous ping-pong pairs of float4.
-constexpr uint64_t kDnBytesPerPixel = 2 * 4 * sizeof(float4) + 2 * sizeof(float) + 4 * sizeof(float4);
-
-PtStatus pt_nrd_denoise(PtContext* c, const PtNrdDenoiseSettings* s, const PtNrdDenoiseTextures* t)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: null pointer");
-    if (s->Denoiser != kNrdReblur && s->Denoiser != kNrdRelax)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: Denoiser must be 2 (NRDReBLUR) or 3 (NRDReLAX)");
-    if (s->AccumulationMode > 2) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: AccumulationMode must be 0, 1 or 2");
-    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
-    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: RenderSize must be in [1, 16384]");
-    if (s->AtrousIterations > kDnMaxIterations) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_denoise: AtrousIterations must be at most 8");
-    const uint64_t n = (uint64_t)w * h;
-    // (pointer, bytes per pixel, alignment, written, required)
-    struct Use { const void* p; uint32_t bpp, align; bool written, required; const char* name; };
-    const Use use[8] = {
-        {t->ViewZ, 4, 4, false, true, "ViewZ"}, {t->MotionVector, 12, 4, false, true, "MotionVector"},
-        {t->NormalRoughness, 16, 16, false, true, "NormalRoughness"}, {t->BaseColorMetalness, 16, 16, false, false, "BaseColorMetalness"},
-        {t->InDiffuse, 16, 16, false, true, "InDiffuse"}, {t->InSpecular, 16, 16, false, true, "InSpecular"},
-        {t->OutDiffuse, 16, 16, true, true, "OutDiffuse"}, {t->OutSpecular, 16, 16, true, true, "OutSpecular"},
-    };
-    for (const Use& u : use) {
-        if (!u.p) {
-            if (u.required) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + u.name + " is required");
-            continue;
-        }
-        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
-            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
-    }
-    // an output must not share a byte with any input or the other output (the passes read their neighbours' inputs)
-    for (const Use& a : use) {
-        if (!a.written) continue;
-        for (const Use& b : use) {
-            if (&a == &b || !b.p) continue;
-            const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
-            if (pa < pb + n * b.bpp && pb < pa + n * a.bpp)
-                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_nrd_denoise: ") + a.name + " overlaps " + b.name);
-        }
-    }
-    PT_HIP(c, hipSetDevice(c->device));
-    bool restart = s->AccumulationMode != 0 || !c->dn_valid || c->dn_mode != s->Denoiser;
-    if (!c->d_dn || c->dn_w != w || c->dn_h != h) {
-        if (c->d_dn) PT_HIP(c, hipStreamSynchronize(c->stream));  // (the previous calls may still read the old buffers)
-        free_dev(c->d_dn);
-        c->dn_valid = false;
-        PT_HIP(c, hipMalloc(&c->d_dn, n * kDnBytesPerPixel));
-        c->dn_w = w;
-        c->dn_h = h;
-        restart = true;
-    }
-    float4* f4 = reinterpret_cast<float4*>(c->d_dn);
-    float4* slots[2][4];
-    for (int k = 0; k < 2; k++)
-        for (int j = 0; j < 4; j++) slots[k][j] = f4 + (uint64_t)(4 * k + j) * n;
-    float4* x = f4 + 8 * n;
-    const uint32_t cur = c->dn_slot ^ 1u, prev = c->dn_slot;
-    DnBuffers b{};
-    b.w = w;
-    b.h = h;
-    b.viewz = static_cast<const float*>(t->ViewZ);
-    b.mv = static_cast<const float*>(t->MotionVector);
-    b.nr = static_cast<const float4*>(t->NormalRoughness);
-    b.in_d = static_cast<const float4*>(t->InDiffuse);
-    b.in_s = static_cast<const float4*>(t->InSpecular);
-    b.out_d = static_cast<float4*>(t->OutDiffuse);
-    b.out_s = static_cast<float4*>(t->OutSpecular);
-    b.prev_sig_d = slots[prev][0]; b.prev_sig_s = slots[prev][1]; b.prev_mom = slots[prev][2]; b.prev_guide = slots[prev][3];
-    b.sig_d = slots[cur][0]; b.sig_s = slots[cur][1]; b.mom = slots[cur][2]; b.guide = slots[cur][3];
-    b.xd[0] = x; b.xs[0] = x + n; b.xd[1] = x + 2 * n; b.xs[1] = x + 3 * n;
-    b.hitd = reinterpret_cast<float*>(x + 4 * n);
-    DnParams P{};
-    P.max_d = s->MaxDiffuseFrames ? s->MaxDiffuseFrames : kDnDefaultFrames;
-    P.max_s = s->MaxSpecularFrames ? s->MaxSpecularFrames : kDnDefaultFrames;
-    P.restart = restart ? 1u : 0u;
-    const uint32_t iterations = s->AtrousIterations ? s->AtrousIterations : kDnDefaultIterations;
-    PT_HIP(c, launch_nrd_denoise(b, s->Denoiser, P, iterations, c->stream));
-    c->dn_slot = cur;
-    c->dn_mode = s->Denoiser;
-    c->dn_valid = true;
-    return PT_OK;
-}
-
-// Row N11 -- the super-resolution stand-in (DESIGN.md spec S17): one launch on the context's stream, the history in the context.
-// Per output pixel and slot: a float4 (t-space colour, accumulated weight) and a float (depth).
-constexpr uint64_t kUpSlotBytesPerPixel = sizeof(float4) + sizeof(float);
-
-PtStatus pt_upscale(PtContext* c, const PtUpscaleSettings* s, const PtUpscaleTextures* t)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: null pointer");
-    const uint32_t w = s->InputSize[0], h = s->InputSize[1], W = s->OutputSize[0], H = s->OutputSize[1];
-    if (w == 0 || h == 0 || w > kUpMaxSize || h > kUpMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: InputSize must be in [1, 16384]");
-    if (W < w || H < h || W > kUpMaxSize || H > kUpMaxSize || (uint64_t)W > (uint64_t)kUpMaxRatio * w || (uint64_t)H > (uint64_t)kUpMaxRatio * h)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: OutputSize must be in [InputSize, 4 * InputSize] per axis and at most 16384");
-    for (const float j : { s->Jitter[0], s->Jitter[1] })
-        if (!is_finite(j) || !(pt_abs(j) <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: Jitter must be finite and within [-1, 1]");
-    float max_a = s->MaxHistoryWeight;
-    if (max_a == 0.0f) max_a = kUpDefaultHistoryWeight;
-    if (!is_finite(max_a) || !(max_a >= kUpMinHistoryWeight && max_a <= kUpMaxHistoryWeight))
-        return fail(c, PT_ERR_INVALID_ARG, "pt_upscale: MaxHistoryWeight must be 0 or in [1, 256]");
-    const uint64_t n_in = (uint64_t)w * h, n_out = (uint64_t)W * H;
-    // (pointer, bytes, alignment)
-    struct Use { const void* p; uint64_t bytes; uint32_t align; const char* name; };
-    const Use use[4] = { {t->Color, n_in * 16, 16, "Color"}, {t->Depth, n_in * 4, 4, "Depth"}, {t->Velocity, n_in * 12, 4, "Velocity"},
-                         {t->Output, n_out * 16, 16, "Output"} };
-    for (const Use& u : use) {
-        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: ") + u.name + " is required");
-        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
-            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
-    }
-    // the output must not share a byte with an input (a workgroup reads the inputs of its neighbours' pixels)
-    for (int i = 0; i < 3; i++) {
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(use[3].p), pb = reinterpret_cast<uintptr_t>(use[i].p);
-        if (pa < pb + use[i].bytes && pb < pa + use[3].bytes) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_upscale: Output overlaps ") + use[i].name);
-    }
-    PT_HIP(c, hipSetDevice(c->device));
-    bool restart = s->Reset != 0 || !c->up_valid || c->up_w != w || c->up_h != h;
-    if (!c->d_up || c->up_W != W || c->up_H != H) {
-        // the history is only used on `stream`: once the calls queued there have finished, the old one is free (the render lanes never
-        // touch it, so their frames in flight go on)
-        if (c->d_up) PT_HIP(c, hipStreamSynchronize(c->stream));
-        free_dev(c->d_up);
-        c->up_valid = false;
-        c->up_W = c->up_H = 0;
-        PT_HIP(c, hipMalloc(&c->d_up, 2 * n_out * kUpSlotBytesPerPixel));
-        c->up_W = W;
-        c->up_H = H;
-        restart = true;
-    }
-    const uint32_t cur = c->up_slot ^ 1u, prev = c->up_slot;
-    float* zs = reinterpret_cast<float*>(c->d_up + 2 * n_out);
-    UpBuffers b{};
-    b.color = static_cast<const float4*>(t->Color);
-    b.depth = static_cast<const float*>(t->Depth);
-    b.velocity = static_cast<const float*>(t->Velocity);
-    b.out = static_cast<float4*>(t->Output);
-    b.prev_hist = c->d_up + prev * n_out;
-    b.prev_z = zs + prev * n_out;
-    b.hist = c->d_up + cur * n_out;
-    b.hist_z = zs + cur * n_out;
-    const UpParams P = up_params(w, h, W, H, s->Jitter[0], s->Jitter[1], max_a);
-    PT_HIP(c, launch_upscale(b, P, restart, c->stream));
-    c->up_slot = cur;
-    c->up_w = w;
-    c->up_h = h;
-    c->up_valid = true;
-    return PT_OK;
-}
-
-PtStatus pt_upscale_input_size(uint32_t mode, uint32_t out_w, uint32_t out_h, uint32_t* w, uint32_t* h)
-{
-    if (!w || !h || mode > kUpModeUltraPerformance || out_w == 0 || out_h == 0) return PT_ERR_INVALID_ARG;
-    const uint32_t r10 = up_ratio10(mode == kUpModeAuto ? up_auto_mode(out_w, out_h) : mode);
-    *w = up_input_extent(out_w, r10);
-    *h = up_input_extent(out_h, r10);
-    return PT_OK;
-}
-
-// Row N12 -- the sharpening stand-in (DESIGN.md spec S18): one launch on the context's stream, no state
-PtStatus pt_nis_sharpen(PtContext* c, const PtNisSettings* s, const PtNisTextures* t)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: null pointer");
-    const uint32_t w = s->Size[0], h = s->Size[1];
-    if (w == 0 || h == 0 || w > kNisMaxSize || h > kNisMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Size must be in [1, 16384]");
-    if (!(s->Sharpness >= 0.0f && s->Sharpness <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Sharpness must be in [0, 1]");
-    if (s->HdrMode > kNisHdrPQ) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: HdrMode must be 0 (None), 1 (Linear) or 2 (PQ)");
-    if (!t->Color || !t->Output) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Color and Output are required");
-    const uintptr_t pc = reinterpret_cast<uintptr_t>(t->Color), po = reinterpret_cast<uintptr_t>(t->Output);
-    if (pc % 16 || po % 16) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Color and Output must be 16-byte aligned");
-    // the output must not share a byte with the input (a lane reads its neighbours' texels): no in-place call
-    const uint64_t bytes = (uint64_t)w * h * sizeof(float4);
-    if (po < pc + bytes && pc < po + bytes) return fail(c, PT_ERR_INVALID_ARG, "pt_nis_sharpen: Output overlaps Color");
-    if (s->HdrMode == kNisHdrPQ) return fail(c, PT_ERR_UNSUPPORTED, "pt_nis_sharpen: HdrMode 2 (PQ) is not built");
-    PT_HIP(c, hipSetDevice(c->device));
-    const NisConfig k = nis_config(s->Sharpness, s->HdrMode);
-    PT_HIP(c, launch_nis(static_cast<const float4*>(t->Color), static_cast<float4*>(t->Output), w, h, k, s->HdrMode, c->stream));
-    return PT_OK;
-}
-
-// Row N13 -- the frame-interpolation stand-in (DESIGN.md spec S19): a clear, a scatter and a gather on the context's stream; the motion
-// field and the previous frame's Color and Depth live in the context.  *generated is decided here, before anything is queued.
-PtStatus pt_frame_gen(PtContext* c, const PtFrameGenSettings* s, const PtFrameGenTextures* t, uint32_t* generated)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: null pointer");
-    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1], W = s->OutputSize[0], H = s->OutputSize[1];
-    if (w == 0 || h == 0 || w > kFgMaxSize || h > kFgMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: RenderSize must be in [1, 16384]");
-    if (W < w || H < h || W > kFgMaxSize || H > kFgMaxSize || (uint64_t)W > (uint64_t)kFgMaxRatio * w || (uint64_t)H > (uint64_t)kFgMaxRatio * h)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: OutputSize must be in [RenderSize, 4 * RenderSize] per axis and at most 16384");
-    if (s->Format > kFgFormatRGB10A2) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: Format must be 0 (R8G8B8A8_UNORM) or 1 (R10G10B10A2_UNORM)");
-    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, "pt_frame_gen: padding must be 0");
-    const uint64_t n_in = (uint64_t)w * h, n_out = (uint64_t)W * H;
-    struct Use { const void* p; uint64_t bytes; const char* name; };
-    const Use use[4] = { {t->Color, n_out * 4, "Color"}, {t->Depth, n_in * 4, "Depth"}, {t->MotionVector, n_in * 12, "MotionVector"}, {t->Output, n_out * 4, "Output"} };
-    for (const Use& u : use) {
-        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: ") + u.name + " is required");
-        if (reinterpret_cast<uintptr_t>(u.p) % 4) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: ") + u.name + " is not 4-byte aligned");
-    }
-    // the output must not share a byte with an input (a lane reads the colour of other lanes' pixels)
-    for (int i = 0; i < 3; i++) {
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(use[3].p), pb = reinterpret_cast<uintptr_t>(use[i].p);
-        if (pa < pb + use[i].bytes && pb < pa + use[3].bytes) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_frame_gen: Output overlaps ") + use[i].name);
-    }
-    PT_HIP(c, hipSetDevice(c->device));
-    bool restart = s->Reset != 0 || !c->fg_valid || c->fg_format != s->Format;
-    if (!c->d_fg || c->fg_w != w || c->fg_h != h || c->fg_W != W || c->fg_H != H) {
-        // the buffers are only used on `stream`: once the calls queued there have finished, the old ones are free (the render lanes
-        // never touch them, so their frames in flight go on)
-        if (c->d_fg) PT_HIP(c, hipStreamSynchronize(c->stream));
-        free_dev(c->d_fg);
-        c->fg_valid = false;
-        c->fg_w = c->fg_h = c->fg_W = c->fg_H = 0;
-        PT_HIP(c, hipMalloc(&c->d_fg, n_in * 8 + 2 * n_out * 4 + 2 * n_in * 4));
-        c->fg_w = w; c->fg_h = h; c->fg_W = W; c->fg_H = H;
-        restart = true;
-    }
-    const uint32_t cur = c->fg_slot ^ 1u, prev = c->fg_slot;
-    uint32_t* colors = reinterpret_cast<uint32_t*>(c->d_fg + n_in);
-    float* zs = reinterpret_cast<float*>(colors + 2 * n_out);
-    FgBuffers b{};
-    b.color = static_cast<const uint32_t*>(t->Color);
-    b.depth = static_cast<const float*>(t->Depth);
-    b.mv = static_cast<const float*>(t->MotionVector);
-    b.out = static_cast<uint32_t*>(t->Output);
-    b.prev_color = colors + prev * n_out;
-    b.prev_z = zs + prev * n_in;
-    b.hist_color = colors + cur * n_out;
-    b.hist_z = zs + cur * n_in;
-    b.field = c->d_fg;
-    if (generated) *generated = restart ? 0u : 1u;
-    if (restart) {
-        // step 0: Output = Color bit for bit, the current slot takes Color and Depth
-        PT_HIP(c, hipMemcpyAsync(b.out, b.color, n_out * 4, hipMemcpyDeviceToDevice, c->stream));
-        PT_HIP(c, hipMemcpyAsync(b.hist_color, b.color, n_out * 4, hipMemcpyDeviceToDevice, c->stream));
-        PT_HIP(c, hipMemcpyAsync(b.hist_z, b.depth, n_in * 4, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        PT_HIP(c, hipMemsetAsync(b.field, 0xFF, n_in * 8, c->stream));
-        PT_HIP(c, launch_framegen(b, fg_params(w, h, W, H, s->Format), c->stream));
-    }
-    c->fg_slot = cur;
-    c->fg_format = s->Format;
-    c->fg_valid = true;
-    return PT_OK;
-}
-
 // Row N10 -- the reservoir pass (DESIGN.md spec S16): two launches on the lane of the next render call, ordered like pt_render_gbuffer;
 // the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
 constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
@@ -2560,84 +1970,36 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
     }
     if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: SpatialRadius must be finite and >= 0");
     const uint64_t n = (uint64_t)w * h;
-    // (pointer, bytes per pixel, alignment, written)
-    struct Use { const void* p; uint32_t bpp, align; bool written; const char* name; };
-    const Use use[10] = {
-        {t->Position, 16, 16, false, "Position"}, {t->GeometricNormal, 8, 8, false, "GeometricNormal"}, {t->LinearDepth, 4, 4, false, "LinearDepth"},
-        {t->MotionVector, 12, 4, false, "MotionVector"}, {t->BaseColorMetalness, 16, 16, false, "BaseColorMetalness"},
-        {t->NormalRoughness, 16, 16, false, "NormalRoughness"}, {t->IOR, 4, 4, false, "IOR"}, {t->Transmission, 4, 4, false, "Transmission"},
-        {t->Diffuse, 16, 16, true, "Diffuse"}, {t->Specular, 16, 16, true, "Specular"},
+    // the eight inputs, then the two outputs
+    const BufferUse use[10] = {
+        {t->Position, n * 16, 16, false, true, "Position"}, {t->GeometricNormal, n * 8, 8, false, true, "GeometricNormal"},
+        {t->LinearDepth, n * 4, 4, false, true, "LinearDepth"}, {t->MotionVector, n * 12, 4, false, true, "MotionVector"},
+        {t->BaseColorMetalness, n * 16, 16, false, true, "BaseColorMetalness"}, {t->NormalRoughness, n * 16, 16, false, true, "NormalRoughness"},
+        {t->IOR, n * 4, 4, false, true, "IOR"}, {t->Transmission, n * 4, 4, false, true, "Transmission"},
+        {t->Diffuse, n * 16, 16, true, true, "Diffuse"}, {t->Specular, n * 16, 16, true, true, "Specular"},
     };
-    for (const Use& u : use) {
-        if (!u.p) return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + u.name + " is required");
-        if (reinterpret_cast<uintptr_t>(u.p) % u.align)
-            return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + u.name + " is not " + std::to_string(u.align) + "-byte aligned");
-    }
-    for (const Use& a : use) {
-        if (!a.written) continue;
-        for (const Use& b : use) {
-            if (&a == &b) continue;
-            const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
-            if (pa < pb + n * b.bpp && pb < pa + n * a.bpp)
-                return fail(c, PT_ERR_INVALID_ARG, std::string("pt_restir_di: ") + a.name + " overlaps " + b.name);
-        }
-    }
-    PtStatus st = validate_frame(c);
+    PtStatus st = buffers_ok(c, "pt_restir_di", use, 10);
     if (st != PT_OK) return st;
+    if ((st = validate_frame(c)) != PT_OK) return st;
     if ((st = check_environment(c)) != PT_OK) return st;
-    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)
-        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    if ((st = check_tree_lds(c)) != PT_OK) return st;
     PT_HIP(c, hipSetDevice(c->device));
     if (c->n_lights == 0 || c->empty_scene) {  // no emitters: nothing is written, and there is no history to keep
         c->ri_valid = false;
         return PT_OK;
     }
 
-    // the lane of the next frame, brought up to date as pt_render_gbuffer does (its rotation is not advanced)
-    Lane& L = c->lanes[c->next_lane];
-    {
-        const bool again = c->gb_frame == c->frames && c->gb_lane == c->next_lane;
-        bool idle = !again || c->gb_lanes_idle;
-        for (uint32_t i = 0; i < c->n_lanes && idle; i++)
-            if (!(again && i == c->next_lane) && hipStreamQuery(c->lanes[i].stream) != hipSuccess) { idle = false; (void)hipGetLastError(); }
-        c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
-    }
-    if ((st = sync_lane_rotations(c, L)) != PT_OK) return st;
-    if ((st = sync_lane_spheres(c, L)) != PT_OK) return st;
-    if (L.needs_refit && (st = refit_lane(c, L)) != PT_OK) return st;
+    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
+    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
     if (L.stream != c->stream) {
-        // pt_render_gbuffer's rule.  The pass waits for everything the caller has queued so far before the first render call, when an
-        // input is not a buffer this lane's own G-buffer call wrote (it was made elsewhere: on the caller's stream), and when a buffer
-        // is one another lane's G-buffer, DI pass or frame touched within the window; otherwise for the marker n_lanes - 1 calls ago.
+        // pt_render_gbuffer's rule, and shared also when an input is not a buffer this lane's own G-buffer call wrote (it was made
+        // elsewhere: on the caller's stream), or when a buffer is one another lane's DI pass wrote within the window.
         // (One-sided for last_ri: only this entry point looks at the outputs of other lanes' DI passes.  pt_render_gbuffer and the
         // frames do not, so a caller that hands a DI buffer of one lane to them inside the window relies on the rotation rule.)
-        const uint64_t nl = c->n_lanes;
         bool shared = c->calls == 0;
-        for (uint32_t k = 0; k < 8 && !shared; k++) {
-            bool own = false;
-            for (uint32_t j = 0; j < 13 && !own; j++) own = use[k].p == L.last_gb[j];
-            shared = !own;
-        }
-        for (uint32_t i = 0; i < c->n_lanes && !shared; i++) {
-            if (&c->lanes[i] == &L) continue;
-            for (uint32_t k = 0; k < 10 && !shared; k++) {
-                shared = use[k].p == c->lanes[i].last_out;
-                for (uint32_t j = 0; j < 13 && !shared; j++) shared = use[k].p == c->lanes[i].last_gb[j];
-                for (uint32_t j = 0; j < 3 && !shared; j++) shared = use[k].p == c->lanes[i].last_dn[j];
-                for (uint32_t j = 0; j < 2 && !shared; j++) shared = use[k].p == c->lanes[i].last_di[j] || use[k].p == c->lanes[i].last_ri[j];
-            }
-        }
-        if (shared) {
-            if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
-            PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
-            PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
-        } else {
-            const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
-            if (hipEventQuery(marker) != hipSuccess) {
-                (void)hipGetLastError();  // hipErrorNotReady is not an error here
-                PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
-            }
-        }
+        for (uint32_t k = 0; k < 8 && !shared; k++) shared = std::find(L.last_gb, L.last_gb + 13, use[k].p) == L.last_gb + 13;
+        for (uint32_t k = 0; k < 10 && !shared; k++) shared = other_lane_uses(c, L, use[k].p, true);
+        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
         L.last_ri[0] = t->Diffuse; L.last_ri[1] = t->Specular;
     }
     // the history: the previous call (on whichever lane it ran) wrote the slot this one reads and read the slot this one writes
@@ -2685,17 +2047,9 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
     P.history_valid = restart ? 0u : 1u;
     P.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
     P.prev_cam_pos = make_f3(c->cam.PreviousPosition[0], c->cam.PreviousPosition[1], c->cam.PreviousPosition[2]);
-    PixelMap pm{};
-    pm.mode = 0;
-    pm.img_w = w; pm.img_h = h; pm.rx = 0; pm.ry = 0; pm.rw = w; pm.rh = h;
-    pm.blocks_x = (w + 7) / 8;
-    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
-    const uint64_t slots = (uint64_t)pm.blocks_x * ((h + 7) / 8) * 64ull;
-    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;
-    pm.n_slots = (uint32_t)slots;  // (at most 2048^2 * 64 = 2^28)
+    const PixelMap pm = make_pixel_map(w, h, PtRect{ 0, 0, w, h });  // (at most 2048^2 * 64 = 2^28 slots)
     const SceneView sv = make_scene_view(c, &L);
-    const uint32_t threads = traverse_threads(c->lds_scene);
-    const uint32_t grid = std::max(1u, std::min((pm.n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
+    const uint32_t grid = side_pass_grid(c, pm.n_slots);
     st = PT_OK;
     for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
         EventPair* ev = c->profiling ? next_events(c, pass == 0 ? 1 : 2) : nullptr;  // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
@@ -2706,12 +2060,7 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
     }
     const hipError_t e0 = hipEventRecord(c->ev_ri, L.stream);
     if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: history event: ") + hipGetErrorString(e0));
-    if (L.stream != c->stream) {
-        // whatever the caller queues next on its stream (pt_render_with_di, pt_download) sees the outputs
-        const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
-        if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: completion event: ") + hipGetErrorString(e2));
-    }
+    st = publish_lane_to_caller(c, L, "pt_restir_di", st);
     if (st == PT_OK) {
         c->ri_slot = cur;
         c->ri_scene = c->set_scene_calls;

@@ -46,7 +46,7 @@ def u32(a):
 
 
 class HostFrameGen:
-    """pt_frame_gen on the host-compiled header, with the history logic of pt_api.hip: the first call, Reset and a change of a size or
+    """pt_frame_gen on the host-compiled header, with the history logic of pt_api_post.hip: the first call, Reset and a change of a size or
     of the Format restart (Output = Color, the slot takes Color and Depth); two history slots alternate."""
 
     def __init__(self, shim, tiled=False):

@@ -49,7 +49,7 @@ def c32(a):
 
 
 class HostDenoiser:
-    """pt_nrd_denoise on the host-compiled header, with the history logic of pt_api.hip: the first call, and a call with another size
+    """pt_nrd_denoise on the host-compiled header, with the history logic of pt_api_post.hip: the first call, and a call with another size
     or mode, restarts; two history slots alternate."""
 
     def __init__(self, shim):

@@ -59,7 +59,7 @@ def c32(a):
 
 
 class HostUpscaler:
-    """pt_upscale on the host-compiled header, with the history logic of pt_api.hip: the first call, Reset and a change of either size
+    """pt_upscale on the host-compiled header, with the history logic of pt_api_post.hip: the first call, Reset and a change of either size
     restart; two history slots alternate, re-made when the output size changes."""
 
     def __init__(self, shim, tiled=False):
@@ -469,7 +469,7 @@ def test_gpu_bit_exact_random_sequences(renderer, shim, sizes):
 @pytest.mark.gpu
 def test_gpu_restart_rules(renderer, shim):
     """Reset in the middle of a sequence, then an output-size change, then an input-size change: the GPU restarts where the host class,
-    which restates pt_api.hip's rule, does"""
+    which restates pt_api_post.hip's rule, does"""
     rng = np.random.default_rng(12)
     plan = [((40, 30), (80, 60), False), ((40, 30), (80, 60), False), ((40, 30), (80, 60), True), ((40, 30), (80, 60), False),
             ((40, 30), (100, 75), False), ((40, 30), (100, 75), False), ((50, 38), (100, 75), False), ((50, 38), (100, 75), False)]
