@@ -118,6 +118,17 @@ class PtRestirDiTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in RESTIR_DI_TEXTURES]
 
 
+# Row N14 (pt_render_sharc, the SHARC stand-in): SHARCSettings plus the cache's accumulation constants and the stages of a call
+SHARC_UPDATE, SHARC_RESOLVE, SHARC_QUERY = 1, 2, 4
+SHARC_VOXEL_DTYPE = np.dtype([("sum", "<u4", (3,)), ("w", "<u4")])  # w = samples | frames << 16 | stale << 24
+
+
+class PtSharcSettings(C.Structure):
+    _fields_ = [("Capacity", C.c_uint32), ("DownscaleFactor", C.c_uint32), ("SceneScale", C.c_float), ("RoughnessThreshold", C.c_float),
+                ("AccumulationFrames", C.c_uint32), ("MaxStaleFrames", C.c_uint32), ("IsAntiFireflyEnabled", C.c_uint32),
+                ("IsHashGridVisualizationEnabled", C.c_uint32), ("ResetHistory", C.c_uint32), ("Stages", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
 # Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in): the settings, the XeSSResourceType tags it reads and writes, and the modes of
 # pt_upscale_input_size (SuperResolutionMode)
 UPSCALE_TEXTURES = ("Color", "Depth", "Velocity", "Output")

@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         RESTIR_DI_TEXTURES, UPSCALE_TEXTURES)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -19,7 +19,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -101,6 +101,12 @@ class HipLib:
         lib.pt_nrd_denoise.argtypes = [vp, C.POINTER(PtNrdDenoiseSettings), C.POINTER(PtNrdDenoiseTextures)]
         lib.pt_restir_di.restype = C.c_int
         lib.pt_restir_di.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtRestirDiTextures)]
+        lib.pt_render_sharc.restype = C.c_int
+        lib.pt_render_sharc.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtSharcSettings), C.POINTER(PtStats)]
+        lib.pt_sharc_download.restype = C.c_int
+        lib.pt_sharc_download.argtypes = [vp, vp, vp, u32]
+        lib.pt_sharc_upload.restype = C.c_int
+        lib.pt_sharc_upload.argtypes = [vp, vp, vp, u32]
         lib.pt_upscale.restype = C.c_int
         lib.pt_upscale.argtypes = [vp, C.POINTER(PtUpscaleSettings), C.POINTER(PtUpscaleTextures)]
         lib.pt_upscale_input_size.restype = C.c_int
@@ -559,6 +565,45 @@ class Renderer:
         self.synchronize()
         return dd, ds, gb
 
+    def render_sharc_device(self, out_ptr, rect=None, want_stats=False, **settings):
+        """The frame through the radiance cache (row N14, DESIGN.md spec S20; pt_render_sharc) into device memory: settings = the fields of
+        PtSharcSettings in snake case (capacity, downscale_factor, scene_scale, roughness_threshold, accumulation_frames, max_stale_frames,
+        anti_firefly, visualize, reset_history, stages = SHARC_UPDATE | SHARC_RESOLVE | SHARC_QUERY); 0 = the library's default.  Runs on
+        the lane of the next render call; asynchronous unless want_stats."""
+        r = PtRect(*rect) if rect is not None else None
+        s = sharc_settings(**settings)
+        stats = PtStats()
+        self._check(self._lib.pt_render_sharc(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr or 0), 1, C.byref(s),
+                                              C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_sharc(self, rect=None, want_stats=True, **settings):
+        """render_sharc_device to a host numpy array (h, w, 4) float32 -> (image, stats); a call without the query stage returns
+        (None, stats).  Synchronous."""
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        r = PtRect(*rect)
+        s = sharc_settings(**settings)
+        query = s.Stages == 0 or bool(s.Stages & 4)
+        out = np.empty((r.h, r.w, 4), dtype=np.float32) if query else None
+        stats = PtStats()
+        self._check(self._lib.pt_render_sharc(self._ctx, C.byref(r), out.ctypes.data if query else None, 0, C.byref(s), C.byref(stats) if want_stats else None))
+        if not want_stats:
+            self.synchronize()
+        return out, stats
+
+    def sharc_download(self, capacity):
+        """The cache as the last render_sharc call left it (pt_sharc_download) -> (keys uint64[capacity], voxels uint32[capacity, 4])"""
+        keys, voxels = np.zeros(capacity, np.uint64), np.zeros((capacity, 4), np.uint32)
+        self._check(self._lib.pt_sharc_download(self._ctx, keys.ctypes.data, voxels.ctypes.data, capacity))
+        return keys, voxels
+
+    def sharc_upload(self, keys, voxels):
+        """Installs a cache made elsewhere (pt_sharc_upload): keys uint64[capacity], voxels uint32[capacity, 4]"""
+        keys, voxels = np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(voxels, np.uint32)
+        assert voxels.shape == (len(keys), 4)
+        self._check(self._lib.pt_sharc_upload(self._ctx, keys.ctypes.data, voxels.ctypes.data, len(keys)))
+
     def upscale_device(self, input_size, output_size, buffers, jitter=(0.0, 0.0), reset=False, max_history_weight=0.0):
         """The super-resolution stand-in (row N11, DESIGN.md spec S17): Color / Depth / Velocity at input_size = (w, h) -> Output at
         output_size = (W, H), with the history the context keeps.  buffers: {UPSCALE_TEXTURES name: device pointer}.  jitter: what the
@@ -653,6 +698,14 @@ class Renderer:
         has = C.c_uint32(0)
         self._check(self._lib.pt_accel_download_wide(self._ctx, words.ctypes.data, n, C.byref(has)))
         return words[:n] if has.value else None
+
+
+def sharc_settings(capacity=0, downscale_factor=0, scene_scale=0.0, roughness_threshold=0.0, accumulation_frames=0, max_stale_frames=0, anti_firefly=False,
+                   visualize=False, reset_history=False, stages=0):
+    """PtSharcSettings from keywords (0 = the library's default)"""
+    return PtSharcSettings(Capacity=capacity, DownscaleFactor=downscale_factor, SceneScale=scene_scale, RoughnessThreshold=roughness_threshold,
+                           AccumulationFrames=accumulation_frames, MaxStaleFrames=max_stale_frames, IsAntiFireflyEnabled=1 if anti_firefly else 0,
+                           IsHashGridVisualizationEnabled=1 if visualize else 0, ResetHistory=1 if reset_history else 0, Stages=stages)
 
 
 class NrdDenoiser:

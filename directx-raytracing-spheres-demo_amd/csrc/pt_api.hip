@@ -19,6 +19,7 @@
 #include "pt_context.h"
 #include "pt_beam_cache.h"
 #include "pt_restir.h"
+#include "pt_sharc.h"
 
 namespace {
 
@@ -1293,6 +1294,8 @@ void pt_destroy(PtContext* c)
     for (History* H : { &c->dn, &c->up, &c->fg }) free_dev(H->mem);
     free_dev(c->d_ri);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
+    free_dev(c->d_sh);
+    if (c->ev_sh) (void)hipEventDestroy(c->ev_sh);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
     if (c->gpu_builder) lbvh_gpu_destroy(c->gpu_builder);
     for (auto& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2069,6 +2072,187 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
         c->ri_valid = false;
     }
     return st;
+}
+
+// Row N14 -- the frame through the radiance cache (DESIGN.md spec S20): up to three stages on the lane of the next render call, ordered
+// like pt_restir_di; the cache (keys, two voxel arrays that swap at every resolve, two counters) lives in the context.
+static PtStatus sharc_allocate(PtContext* c, uint32_t capacity)
+{
+    if (!c->ev_sh) PT_HIP(c, hipEventCreateWithFlags(&c->ev_sh, hipEventDisableTiming));
+    if (c->d_sh && c->sh_capacity == capacity) return PT_OK;
+    if (c->d_sh) PT_HIP(c, hipEventSynchronize(c->ev_sh));  // (the previous call may still use the old arrays)
+    free_dev(c->d_sh);
+    c->sh_valid = false;
+    c->sh_capacity = 0;
+    const size_t bytes = (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)) + 2u * sizeof(unsigned long long);
+    if (hipMalloc(&c->d_sh, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_sh = nullptr; return fail(c, PT_ERR_OOM, "pt_render_sharc: cache allocation failed"); }
+    char* base = static_cast<char*>(c->d_sh);
+    c->sh_accum = reinterpret_cast<uint4*>(base);
+    c->sh_resolved = reinterpret_cast<uint4*>(base + (size_t)capacity * sizeof(uint4));
+    c->sh_keys = reinterpret_cast<uint64_t*>(base + 2u * (size_t)capacity * sizeof(uint4));
+    c->d_sh_counters = reinterpret_cast<unsigned long long*>(base + (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)));
+    c->sh_capacity = capacity;
+    return PT_OK;
+}
+
+static bool sharc_capacity_ok(uint32_t capacity) { return capacity >= kShBucket && capacity <= (1u << 28) && (capacity & (capacity - 1u)) == 0u; }
+
+PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: null settings");
+    const uint32_t stages = s->Stages ? s->Stages : (uint32_t)(PT_SHARC_UPDATE | PT_SHARC_RESOLVE | PT_SHARC_QUERY);
+    if (stages & ~7u) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: Stages must be a mask of PT_SHARC_UPDATE, PT_SHARC_RESOLVE and PT_SHARC_QUERY");
+    if ((stages & PT_SHARC_QUERY) && !out) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: null output");
+    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: the padding words must be 0");
+    const uint32_t capacity = s->Capacity ? s->Capacity : kShDefaultCapacity, downscale = s->DownscaleFactor ? s->DownscaleFactor : kShDefaultDownscale;
+    const float scene_scale = s->SceneScale == 0.0f ? kShDefaultSceneScale : s->SceneScale;
+    const uint32_t acc_frames = s->AccumulationFrames ? s->AccumulationFrames : kShDefaultAccumulationFrames;
+    const uint32_t max_stale = s->MaxStaleFrames ? s->MaxStaleFrames : kShDefaultMaxStaleFrames;
+    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: Capacity must be a power of two in [16, 1 << 28]");
+    if (downscale > 4u) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: DownscaleFactor must be in [1, 4]");
+    if (!(scene_scale >= 5.0f && scene_scale <= 100.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: SceneScale must be in [5, 100]");
+    if (!(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: RoughnessThreshold must be in [0, 1]");
+    if (acc_frames > kShMaxFrames) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: AccumulationFrames must be at most 255");
+    if (max_stale > kShMaxStale) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: MaxStaleFrames must be at most 254");
+    if (s->IsAntiFireflyEnabled) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_sharc: the anti-firefly filter is not built");
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    if (c->gs.IsDIEnabled || c->gs.Denoiser) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_sharc: IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs through the cache are not built)");
+    PtRect r;
+    PixelMap pm{};
+    if ((st = rect_pixel_map(c, rect, "pt_render_sharc", r, pm)) != PT_OK) return st;
+    if ((st = check_environment(c)) != PT_OK) return st;
+    if ((st = check_tree_lds(c)) != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    const bool query = (stages & PT_SHARC_QUERY) != 0;
+    float4* dev_out = static_cast<float4*>(out);
+    const size_t out_px = (size_t)r.w * r.h;
+    if (query && !out_is_device) {
+        if (out_px > c->cap_out) {
+            PT_HIP(c, sync_all(c));
+            free_dev(c->d_out);
+            c->cap_out = 0;
+            PT_HIP(c, hipMalloc(&c->d_out, out_px * sizeof(float4)));
+            c->cap_out = out_px;
+        }
+        dev_out = c->d_out;
+    }
+    if (query && (reinterpret_cast<uintptr_t>(dev_out) & 15u)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: the output must be 16-byte aligned");
+
+    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
+    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
+    if (L.stream != c->stream) {
+        const bool shared = c->calls == 0 || (query && other_lane_uses(c, L, dev_out, true));
+        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
+    }
+    // the cache: the previous call (on whichever lane it ran) has finished with it before this one touches it
+    const bool had = c->d_sh && c->sh_capacity == capacity;
+    if ((st = sharc_allocate(c, capacity)) != PT_OK) return st;
+    if (had) PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_sh, 0));
+    const bool restart = s->ResetHistory != 0 || !c->sh_valid || c->sh_scene != c->set_scene_calls;
+    c->sh_valid = false;  // (until the call has been queued whole)
+    const bool timed = stats != nullptr;
+    if (timed) PT_HIP(c, hipEventRecord(c->ev0, L.stream));
+    if (restart) PT_HIP(c, hipMemsetAsync(c->d_sh, 0, (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)), L.stream));
+    else if (stages & (PT_SHARC_UPDATE | PT_SHARC_RESOLVE)) PT_HIP(c, hipMemsetAsync(c->sh_accum, 0, (size_t)capacity * sizeof(uint4), L.stream));  // Raytracing.ixx:124
+    PT_HIP(c, hipMemsetAsync(c->d_sh_counters, 0, 2u * sizeof(unsigned long long), L.stream));
+
+    const SceneView sv = make_scene_view(c, &L);
+    const uint32_t w = c->gs.RenderSize[0], h = c->gs.RenderSize[1];
+    ShFrame fr{};
+    fr.cam = camera_params(c->cam, w, h);
+    fr.frame_index = c->gs.FrameIndex; fr.bounces = c->gs.Bounces; fr.spp = c->gs.SamplesPerPixel;
+    fr.rr_enabled = c->gs.IsRussianRouletteEnabled ? 1u : 0u;
+    fr.throughput_threshold = c->gs.ThroughputThreshold;
+    fr.inv_spp = 1.0f / (float)c->gs.SamplesPerPixel;
+    fr.roughness_threshold = s->RoughnessThreshold;
+    fr.visualize = s->IsHashGridVisualizationEnabled ? 1u : 0u;
+    ShGrid g{};
+    g.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
+    g.scene_scale = scene_scale;
+    auto map = [&] { ShMap m{}; m.keys = c->sh_keys; m.accum = c->sh_accum; m.resolved = c->sh_resolved; m.capacity = capacity; return m; };
+    st = PT_OK;
+    const uint32_t gw = w / downscale, gh = h / downscale;
+    if ((stages & PT_SHARC_UPDATE) && gw && gh) {
+        ShFrame fu = fr;
+        fu.cam = camera_params(c->cam, gw, gh);  // (InvW, InvH of the update grid; the jitter is the path's own)
+        const PixelMap pu = make_pixel_map(gw, gh, PtRect{ 0, 0, gw, gh });
+        EventPair* ev = c->profiling ? next_events(c, 1) : nullptr;  // pt_get_profile: the update under ms_traverse
+        if (ev) (void)hipEventRecord(ev->a, L.stream);
+        if (const hipError_t e = launch_sharc_update(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: update launch: ") + hipGetErrorString(e));
+        if (ev) (void)hipEventRecord(ev->b, L.stream);
+    }
+    if (st == PT_OK && (stages & PT_SHARC_RESOLVE)) {
+        EventPair* ev = c->profiling ? next_events(c, 3) : nullptr;  // ... the resolve under ms_tail
+        if (ev) (void)hipEventRecord(ev->a, L.stream);
+        if (const hipError_t e = launch_sharc_resolve(map(), acc_frames, max_stale, L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: resolve launch: ") + hipGetErrorString(e));
+        else std::swap(c->sh_accum, c->sh_resolved);  // Raytracing.ixx:147
+        if (ev) (void)hipEventRecord(ev->b, L.stream);
+    }
+    if (st == PT_OK && query) {
+        EventPair* ev = c->profiling ? next_events(c, 2) : nullptr;  // ... the query under ms_shade
+        if (ev) (void)hipEventRecord(ev->a, L.stream);
+        if (const hipError_t e = launch_sharc_query(sv, pm, fr, g, map(), dev_out, c->d_sh_counters, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: query launch: ") + hipGetErrorString(e));
+        if (ev) (void)hipEventRecord(ev->b, L.stream);
+    }
+    const hipError_t e0 = hipEventRecord(c->ev_sh, L.stream);
+    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: cache event: ") + hipGetErrorString(e0));
+    if (st == PT_OK && timed) {
+        unsigned long long counters[2] = { 0, 0 };
+        PT_HIP(c, hipEventRecord(c->ev1, L.stream));
+        PT_HIP(c, hipMemcpyAsync(counters, c->d_sh_counters, sizeof counters, hipMemcpyDeviceToHost, L.stream));
+        PT_HIP(c, hipStreamSynchronize(L.stream));
+        std::memset(stats, 0, sizeof *stats);
+        float ms = 0;
+        PT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        stats->ms_total = ms;
+        stats->rays = counters[0];
+        stats->pixels = query ? out_px : 0;
+        stats->paths = (query ? out_px * c->gs.SamplesPerPixel : 0) + ((stages & PT_SHARC_UPDATE) ? (uint64_t)gw * gh : 0);
+    }
+    st = publish_lane_to_caller(c, L, "pt_render_sharc", st);
+    if (st != PT_OK) return st;
+    c->sh_valid = true;
+    c->sh_scene = c->set_scene_calls;
+    if (query && !out_is_device) {
+        PT_HIP(c, hipMemcpyAsync(out, dev_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        PT_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return PT_OK;
+}
+
+PtStatus pt_sharc_download(PtContext* c, void* keys, void* voxels, uint32_t capacity)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!keys || !voxels) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_download: null pointer");
+    if (!c->d_sh || !c->sh_valid) return fail(c, PT_ERR_STATE, "pt_sharc_download: there is no cache (no pt_render_sharc call has completed)");
+    if (capacity != c->sh_capacity) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_download: capacity differs from the cache's");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipEventSynchronize(c->ev_sh));
+    PT_HIP(c, hipMemcpy(keys, c->sh_keys, (size_t)capacity * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    PT_HIP(c, hipMemcpy(voxels, c->sh_resolved, (size_t)capacity * sizeof(uint4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+PtStatus pt_sharc_upload(PtContext* c, const void* keys, const void* voxels, uint32_t capacity)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!keys || !voxels) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_upload: null pointer");
+    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_upload: capacity must be a power of two in [16, 1 << 28]");
+    PT_HIP(c, hipSetDevice(c->device));
+    if (const PtStatus st = sharc_allocate(c, capacity); st != PT_OK) return st;
+    PT_HIP(c, hipEventSynchronize(c->ev_sh));
+    PT_HIP(c, hipMemcpy(c->sh_keys, keys, (size_t)capacity * sizeof(uint64_t), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->sh_resolved, voxels, (size_t)capacity * sizeof(uint4), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemset(c->sh_accum, 0, (size_t)capacity * sizeof(uint4)));
+    PT_HIP(c, hipDeviceSynchronize());  // (a memset may return before the device has finished it: the lanes' streams do not wait for the null stream)
+    c->sh_valid = true;
+    c->sh_scene = c->set_scene_calls;
+    return PT_OK;
 }
 
 static PtStatus trace_rays_impl(PtContext* c, const float* origins, const float* directions, uint32_t n, float tmin, int use_bvh, float* out_t,

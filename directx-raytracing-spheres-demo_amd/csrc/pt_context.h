@@ -197,6 +197,18 @@ struct PtContext {
     uint64_t ri_scene = 0, set_scene_calls = 0;
     bool ri_valid = false;
     hipEvent_t ev_ri = nullptr;
+    // pt_render_sharc's cache (row N14): `sh_capacity` keys and two voxel arrays in one allocation (sh_accum = this frame's accumulators,
+    // sh_resolved = the previous frame's resolved voxels: they swap at every resolve), two device counters (rays, failed inserts),
+    // `sh_scene` = the pt_set_scene count the cache was filled under, `ev_sh` = the last call's launches have finished
+    void* d_sh = nullptr;
+    uint64_t* sh_keys = nullptr;
+    uint4* sh_accum = nullptr;
+    uint4* sh_resolved = nullptr;
+    unsigned long long* d_sh_counters = nullptr;
+    uint32_t sh_capacity = 0;
+    uint64_t sh_scene = 0;
+    bool sh_valid = false;
+    hipEvent_t ev_sh = nullptr;
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
     uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists
 

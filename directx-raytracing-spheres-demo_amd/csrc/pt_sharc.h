@@ -1,0 +1,451 @@
+// pt_sharc.h -- the radiance cache of row N14 (pt_render_sharc, DESIGN.md spec S20): a stand-in for the SHARC library the reference's
+// default frame runs (Raytracing::Render(..., SHARC&, SHARCSettings), Source/Raytracing.ixx:114-148; the SHARC_UPDATE and SHARC_QUERY
+// permutations of Shaders/Raytracing.hlsl:103-375; the resolve of Shaders/SHARC.hlsl:35-57).  SharcCommon.h / HashGridCommon.h are a
+// submodule the reference tree does not contain: this header follows the reference's call sites and the library's published structure,
+// and its arithmetic is the spec's.  Everything here compiles on the device (pt_sharc.hip) and as host C++ (the bit-parity tests):
+//   sh_grid_level / sh_voxel_size / sh_key   the hash grid
+//   sh_find / sh_insert                      the hash map: buckets of kShBucket keys, find-then-claim, no loop waits on another lane
+//   sh_add / sh_resolve_slot                 the voxel: 32-bit integer sums (order-independent), the per-frame resolve
+//   sh_update_path                           one path of the sparse update pass
+//   sh_query_pixel                           one pixel of the frame: pt_render's loop with the cache look-up in it
+// The closest-hit query is a functor trace(o, d, tmin, tmax, t, id), the surface a functor material(id, o, d, t, primary) -> HitMaterial,
+// the radiance of a ray that left the scene a functor env(d).
+//
+// Out of scope: the anti-firefly filter; the compaction pass and its HashCopyOffset buffer (SHARC.hlsl:58-61: a hole an eviction
+// leaves is reused by the next insert instead); DI and denoiser outputs through the cache; re-loading the update path's first vertex
+// from a G-buffer (the path traces its own primary ray).
+#pragma once
+
+#include "pt_surface.h"
+
+#if defined(__HIPCC__)
+#define PT_SH_UNROLL _Pragma("unroll")
+#else
+#define PT_SH_UNROLL
+#endif
+
+namespace pt {
+
+constexpr uint32_t kShBucket = 16;             // keys per bucket: 128 B, one L2 line
+constexpr int kShLevelBias = 2;                // HASH_GRID_LEVEL_BIAS; the logarithm base is 2
+constexpr float kShRadianceScale = 1024.0f;    // fixed point: round(x * scale)
+constexpr float kShMaxContribution = 256.0f;   // a component above this (inf included) is clamped to it before quantisation
+constexpr uint32_t kShPropagationDepth = 4;    // a vertex feeds itself and the kShPropagationDepth - 1 vertices before it
+constexpr uint32_t kShNoSlot = 0xFFFFFFFFu;
+constexpr uint32_t kShSampleBits = 16, kShFrameBits = 8;  // voxel.w = samples | frames << 16 | stale << 24
+constexpr uint32_t kShMaxSamples = (1u << kShSampleBits) - 1u, kShMaxFrames = 255u, kShMaxStale = 254u;
+constexpr uint32_t kShDefaultCapacity = 1u << 22, kShDefaultDownscale = 4, kShDefaultAccumulationFrames = 10, kShDefaultMaxStaleFrames = 64;
+constexpr float kShDefaultSceneScale = 50.0f;
+
+struct alignas(16) ShKeyPair { uint64_t k[2]; };  // two keys per 128-bit load
+
+struct ShGrid {
+    f3 cam_pos;
+    float scene_scale;
+};
+
+struct ShMap {
+    uint64_t* keys;    // capacity keys, 0 = empty
+    uint4* accum;      // this frame's accumulators: fixed-point RGB sums, sample count
+    uint4* resolved;   // the previous frame's resolved voxels: sums, samples | frames << 16 | stale << 24
+    uint32_t capacity; // a power of two, at least kShBucket
+};
+
+struct ShFrame {
+    CameraParams cam;       // the frame's camera (query), or the update grid's: InvW / InvH of the grid, jitter set per path
+    uint32_t frame_index, bounces, spp, rr_enabled;
+    float throughput_threshold, inv_spp;
+    float roughness_threshold;  // update
+    uint32_t visualize;         // query: IsHashGridVisualizationEnabled
+};
+
+// ---------------------------------------------------------------------------------------------------- hash grid
+// level = clamp(floor(log2(d2) / 2) + bias, 1, 1023), the logarithm from the exponent bits: floor(log2(d2) / 2) = e >> 1 for d2 = m 2^e
+PT_HD uint32_t sh_grid_level(float dist2)
+{
+    const int e = (int)((as_uint(dist2) >> 23) & 0xFFu) - 127;  // (zero and denormals: -127; the sign bit of a squared length is clear)
+    const int level = (e >> 1) + kShLevelBias;
+    return (uint32_t)(level < 1 ? 1 : (level > 1023 ? 1023 : level));
+}
+
+// voxelSize = 2^level / (SceneScale 2^bias)
+PT_HD float sh_voxel_size(uint32_t level, float scene_scale)
+{
+    const float p = level <= 127u ? as_float((level + 127u) << 23) : kInf;
+    return p / (scene_scale * (float)(1 << kShLevelBias));
+}
+
+PT_HD float sh_dist2(f3 P, f3 cam) { const f3 v = P - cam; return dot(v, v); }
+
+// floor(x / voxelSize) as a 17-bit two's complement field (clamped to the field's range; NaN -> the lowest cell)
+PT_HD uint64_t sh_cell(float x, float voxel)
+{
+    float g = pt_floor(x / voxel);
+    g = !(g > -65536.0f) ? -65536.0f : (g > 65535.0f ? 65535.0f : g);
+    return (uint64_t)((uint32_t)(int)g & 0x1FFFFu);
+}
+
+// bits 0-16, 17-33, 34-50: the cell; 51-60: the level; 61-63: the sign octant of the front flat normal (bit set: component < 0).
+// The level is at least 1, so the key is never 0 (empty): the level field is the tag.
+PT_HD uint64_t sh_key(f3 P, f3 front_normal, uint32_t level, float voxel)
+{
+    level = level < 1u ? 1u : (level > 1023u ? 1023u : level);
+    const uint64_t oct = (front_normal.x < 0.0f ? 1u : 0u) | (front_normal.y < 0.0f ? 2u : 0u) | (front_normal.z < 0.0f ? 4u : 0u);
+    return sh_cell(P.x, voxel) | (sh_cell(P.y, voxel) << 17) | (sh_cell(P.z, voxel) << 34) | ((uint64_t)level << 51) | (oct << 61);
+}
+
+PT_HD uint64_t sh_key_at(const ShGrid& g, f3 P, f3 front_normal, float& voxel)
+{
+    const uint32_t level = sh_grid_level(sh_dist2(P, g.cam_pos));
+    voxel = sh_voxel_size(level, g.scene_scale);
+    return sh_key(P, front_normal, level, voxel);
+}
+
+PT_HD uint32_t sh_bucket_base(uint64_t key, uint32_t capacity)
+{
+    const uint32_t h = hash32((uint32_t)key ^ hash32((uint32_t)(key >> 32)));
+    return (h & (capacity / kShBucket - 1u)) * kShBucket;
+}
+
+// ---------------------------------------------------------------------------------------------------- hash map
+// the whole bucket is scanned (an eviction may have left holes in front of the key)
+PT_HD uint32_t sh_find(const uint64_t* keys, uint32_t capacity, uint64_t key)
+{
+    const uint32_t base = sh_bucket_base(key, capacity);
+    const ShKeyPair* pairs = reinterpret_cast<const ShKeyPair*>(keys + base);
+    uint32_t found = kShNoSlot;
+    for (uint32_t i = 0; i < kShBucket / 2u; i++) {
+        const ShKeyPair p = pairs[i];
+        if (p.k[0] == key) found = base + 2u * i;
+        if (p.k[1] == key) found = base + 2u * i + 1u;
+    }
+    return found;
+}
+
+// 0 -> key if the slot is empty; returns what the slot held
+PT_HD uint64_t sh_claim(uint64_t* slot, uint64_t key)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicCAS(reinterpret_cast<unsigned long long*>(slot), 0ull, (unsigned long long)key);
+#else
+    const uint64_t old = *slot;
+    if (old == 0u) *slot = key;
+    return old;
+#endif
+}
+
+// find, then claim: one walk of the bucket in order, one compare-and-swap per slot seen empty; the slot is taken if it held 0 or the
+// key itself (another lane claimed it for the same key), else the walk goes on.  kShNoSlot: the bucket is full.
+// Within a launch a slot only changes from 0 to a key, every inserter of a key walks the same order, so a key never takes two slots.
+PT_HD uint32_t sh_insert(uint64_t* keys, uint32_t capacity, uint64_t key)
+{
+    const uint32_t found = sh_find(keys, capacity, key);
+    if (found != kShNoSlot) return found;
+    const uint32_t base = sh_bucket_base(key, capacity);
+    for (uint32_t i = 0; i < kShBucket; i++) {
+        uint64_t seen = keys[base + i];
+        if (seen == 0u) seen = sh_claim(keys + base + i, key);
+        if (seen == 0u || seen == key) return base + i;
+    }
+    return kShNoSlot;
+}
+
+// ---------------------------------------------------------------------------------------------------- voxel
+// a component that is NaN or not positive counts 0, one above kShMaxContribution (inf included) counts kShMaxContribution
+PT_HD uint32_t sh_quantise(float x)
+{
+    const float c = !(x > 0.0f) ? 0.0f : (x > kShMaxContribution ? kShMaxContribution : x);
+    return (uint32_t)pt_fma(c, kShRadianceScale, 0.5f);
+}
+
+PT_HD void sh_add_u32(uint32_t* p, uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (v) atomicAdd(p, v);
+#else
+    *p += v;
+#endif
+}
+
+PT_HD void sh_add(uint4* accum, uint32_t slot, f3 radiance, uint32_t samples)
+{
+    uint32_t* v = reinterpret_cast<uint32_t*>(accum + slot);
+    sh_add_u32(v + 0, sh_quantise(radiance.x));
+    sh_add_u32(v + 1, sh_quantise(radiance.y));
+    sh_add_u32(v + 2, sh_quantise(radiance.z));
+    sh_add_u32(v + 3, samples);
+}
+
+PT_HD uint32_t sh_samples(const uint4& v) { return v.w & kShMaxSamples; }
+PT_HD uint32_t sh_frames(const uint4& v) { return (v.w >> kShSampleBits) & 0xFFu; }
+PT_HD uint32_t sh_stale(const uint4& v) { return v.w >> (kShSampleBits + kShFrameBits); }
+
+// sum / (n kRadianceScale) of a resolved voxel with samples
+PT_HD f3 sh_radiance(const uint4& v)
+{
+    const float d = (float)sh_samples(v) * kShRadianceScale;
+    return make_f3((float)v.x / d, (float)v.y / d, (float)v.z / d);
+}
+
+// One slot of the resolve (SHARC.hlsl:35-57): this frame's accumulators joined to the previous resolved voxel.  Returns the new
+// resolved voxel; clear = the slot's key is to be erased (the voxel returned is zero).
+//   sums and samples add (64-bit); frames = previous frames + 1;
+//   frames > AccumulationFrames: sums and samples are scaled by AccumulationFrames / frames (integer, rounding down; a voxel with
+//   samples keeps at least one), frames = AccumulationFrames;
+//   while samples exceed kShMaxSamples or a sum exceeds 32 bits: everything is halved;
+//   no sample this frame: stale + 1, and above MaxStaleFrames the slot is cleared; else stale = 0.
+PT_HD uint4 sh_resolve_slot(const uint4& acc, const uint4& prev, uint32_t accumulation_frames, uint32_t max_stale_frames, bool& clear)
+{
+    uint64_t s[3] = { (uint64_t)acc.x + prev.x, (uint64_t)acc.y + prev.y, (uint64_t)acc.z + prev.z };
+    uint64_t n = (uint64_t)acc.w + sh_samples(prev);
+    uint32_t frames = sh_frames(prev) + 1u;
+    uint32_t stale = acc.w ? 0u : sh_stale(prev) + 1u;
+    uint4 r;
+    r.x = r.y = r.z = r.w = 0u;
+    clear = stale > max_stale_frames;
+    if (clear) return r;
+    if (frames > accumulation_frames) {
+        const uint64_t n0 = n;
+        for (int k = 0; k < 3; k++) s[k] = s[k] * accumulation_frames / frames;
+        n = n * accumulation_frames / frames;
+        if (n0 && !n) n = 1u;
+        frames = accumulation_frames;
+    }
+    for (int it = 0; it < 33 && (n > kShMaxSamples || s[0] > 0xFFFFFFFFull || s[1] > 0xFFFFFFFFull || s[2] > 0xFFFFFFFFull); it++) {
+        for (int k = 0; k < 3; k++) s[k] >>= 1;
+        n >>= 1;
+    }
+    r.x = (uint32_t)s[0]; r.y = (uint32_t)s[1]; r.z = (uint32_t)s[2];
+    r.w = (uint32_t)n | (frames << kShSampleBits) | (stale << (kShSampleBits + kShFrameBits));
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------------- update (SHARC_UPDATE)
+struct ShState {
+    uint32_t slot[kShPropagationDepth - 1u];
+    f3 weight[kShPropagationDepth - 1u];
+    uint32_t length;   // stored vertices
+    bool skipped;      // the last vertex found no slot: its segment's throughput joins the stored one
+};
+
+// SharcUpdateMiss, and the tail of SharcUpdateHit: the radiance through the stored weights into every stored vertex, without samples
+PT_HD void sh_propagate(const ShMap& m, const ShState& st, f3 radiance)
+{
+PT_SH_UNROLL
+    for (uint32_t i = 0; i < kShPropagationDepth - 1u; i++) {  // (fixed bounds: the state stays in registers)
+        if (i < st.length) {
+            radiance = radiance * st.weight[i];
+            sh_add(m.accum, st.slot[i], radiance, 0u);
+        }
+    }
+}
+
+// SharcUpdateHit: false = the path ends here (it took the previous frame's radiance of the voxel)
+PT_HD bool sh_update_hit(const ShGrid& g, const ShMap& m, ShState& st, f3 P, f3 front_normal, f3 emission, float rnd, uint32_t& failed)
+{
+    float voxel;
+    const uint64_t key = sh_key_at(g, P, front_normal, voxel);
+    const uint32_t slot = sh_insert(m.keys, m.capacity, key);
+    if (slot == kShNoSlot) {  // the bucket is full: the path goes on without this vertex
+        failed++;
+        sh_propagate(m, st, emission);
+        st.skipped = true;
+        return true;
+    }
+    bool go_on = true;
+    f3 radiance = emission;
+    const uint32_t depth = (uint32_t)pt_fma(2.0f, rnd, 1.5f);  // round(lerp(1, kShPropagationDepth - 1, rnd))
+    if (depth <= st.length) {
+        const uint4 v = m.resolved[slot];
+        if (sh_samples(v) > 0u) { radiance = sh_radiance(v); go_on = false; }
+    }
+    if (go_on) sh_add(m.accum, slot, emission, 1u);
+    sh_propagate(m, st, radiance);
+PT_SH_UNROLL
+    for (uint32_t i = kShPropagationDepth - 2u; i > 0u; i--) { st.slot[i] = st.slot[i - 1u]; st.weight[i] = st.weight[i - 1u]; }
+    st.slot[0] = slot;
+    st.weight[0] = make_f3(1.0f, 1.0f, 1.0f);
+    st.length = st.length + 1u < kShPropagationDepth - 1u ? st.length + 1u : kShPropagationDepth - 1u;
+    st.skipped = false;
+    return go_on;
+}
+
+// SharcSetThroughput
+PT_HD void sh_set_throughput(ShState& st, f3 T)
+{
+    if (!st.length) return;
+    st.weight[0] = st.skipped ? st.weight[0] * T : T;
+}
+
+// One path of the update pass: path (x, y) of the grid fr.cam was made for (InvW, InvH = 1 / grid size).
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_path(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                          uint32_t& rays, uint32_t& failed)
+{
+    uint32_t rng = rng_init(x, y, fr.frame_index);
+    CameraParams cam = fr.cam;
+    cam.JitterX = cam.JitterY = rng_float(rng) - 0.5f;  // Raytracing.hlsl:110-116
+    f3 o, d;
+    float tmin, tmax;
+    primary_ray(cam, x, y, o, d, tmin, tmax);
+    ShState st;
+    st.length = 0u;
+    st.skipped = false;
+PT_SH_UNROLL
+    for (uint32_t i = 0; i < kShPropagationDepth - 1u; i++) { st.slot[i] = 0u; st.weight[i] = make_f3(1.0f, 1.0f, 1.0f); }
+    for (uint32_t bounce = 0;; bounce++) {
+        float t;
+        uint32_t id;
+        trace(o, d, tmin, tmax, t, id);
+        rays++;
+        if (id == 0xFFFFFFFFu) {
+            sh_propagate(m, st, env(d));
+            return;
+        }
+        HitMaterial hm = material(id, o, d, t, bounce == 0u);
+        hm.bsdf.Roughness = pt_max(hm.bsdf.Roughness, fr.roughness_threshold);  // :307
+        const f3 front_normal = hm.hf.front ? hm.hf.N : -hm.hf.N;
+        if (!sh_update_hit(g, m, st, hm.hf.P, front_normal, hm.emission, rng_float(rng), failed)) return;
+        if (bounce == fr.bounces) return;
+        const Surf surf = surf_init(hm.hf.front, hm.hf.N, hm.Ns);
+        const f3 V = -d;
+        float w[3];
+        lobe_weights(hm.bsdf, surf, V, w);
+        float rnd[4];
+        rnd[0] = rng_float(rng); rnd[1] = rng_float(rng); rnd[2] = rng_float(rng); rnd[3] = rng_float(rng);
+        f3 L;
+        int lobe;
+        if (!bsdf_sample(hm.bsdf, surf, V, w, rnd, L, lobe)) return;
+        float pdf;
+        f3 f;
+        if (!bsdf_pdf_eval(hm.bsdf, surf, L, V, w, lobe, pdf, f)) return;
+        if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f) return;
+        f3 T = f * pt_rcp(pdf);  // throughput restarts from 1 at every vertex (:215-217)
+        if (fr.rr_enabled && bounce > 3u) {
+            const float p = pt_max(T.x, pt_max(T.y, T.z));
+            if (rng_float(rng) >= p) return;
+            T = T * pt_rcp(p);
+        }
+        sh_set_throughput(st, T);  // no luminance cut-off (:358-360)
+        o = spawn_origin(hm.hf.P, hm.hf.N, hm.hf.offset, L);
+        d = L;
+        tmin = 0.0f; tmax = kInf;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- query (SHARC_QUERY)
+// Raytracing.hlsl:265-274: the hit is far enough for its voxel, and the path has spread wider than the voxel
+PT_HD bool sh_valid_hit(float distance, float voxel, float& previous_roughness)
+{
+    bool valid = distance > voxel * 1.7320508075688772f;
+    previous_roughness = pt_min(previous_roughness, 0.99f);
+    const float alpha = previous_roughness * previous_roughness;
+    const float footprint = distance * pt_sqrt(0.5f * alpha * alpha / (1.0f - alpha * alpha));
+    return valid && footprint > voxel;
+}
+
+// HashGridDebugColoredHash: a colour of the key's hash
+PT_HD f3 sh_debug_colour(uint64_t key)
+{
+    const uint32_t h = hash32((uint32_t)key ^ hash32((uint32_t)(key >> 32)));
+    return make_f3((float)(h & 0xFFu) * (1.0f / 255.0f), (float)((h >> 8) & 0xFFu) * (1.0f / 255.0f), (float)((h >> 16) & 0xFFu) * (1.0f / 255.0f));
+}
+
+// One pixel of the frame: pt_render's loop (one primary hit shared by the samples, the RNG running on across them) with the cache
+// look-up at every hit; m.keys = null: the cache is off.  With no voxel found the arithmetic is pt_render's, operation for operation.
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t px, uint32_t py, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                        uint32_t& rays)
+{
+    f3 o0, d0;
+    float tmin, tmax, t0;
+    uint32_t id0;
+    primary_ray(fr.cam, px, py, o0, d0, tmin, tmax);
+    trace(o0, d0, tmin, tmax, t0, id0);
+    rays++;
+    if (id0 == 0xFFFFFFFFu) return env(d0);
+    uint32_t rng = rng_init(px, py, fr.frame_index);
+    f3 acc = make_f3(0.0f, 0.0f, 0.0f);
+    for (uint32_t sample = 0;;) {
+        f3 o = o0, d = d0, T = make_f3(1.0f, 1.0f, 1.0f), srad = make_f3(0.0f, 0.0f, 0.0f);
+        float t = t0, previous_roughness = 0.0f;
+        uint32_t id = id0;
+        for (uint32_t bounce = 0;; bounce++) {
+            if (id == 0xFFFFFFFFu) {
+                srad = srad + T * env(d);  // :254
+                break;
+            }
+            const HitMaterial hm = material(id, o, d, t, bounce == 0u);
+            if (m.keys) {
+                float voxel;
+                const uint64_t key = sh_key_at(g, hm.hf.P, hm.hf.front ? hm.hf.N : -hm.hf.N, voxel);
+                if (sh_valid_hit(t, voxel, previous_roughness)) {
+                    const uint32_t slot = sh_find(m.keys, m.capacity, key);
+                    if (slot != kShNoSlot) {
+                        const uint4 v = m.resolved[slot];
+                        if (sh_samples(v) > 0u) {
+                            if (fr.visualize) {  // :279-284: the primary hit's cell
+                                const HitMaterial h0 = material(id0, o0, d0, t0, true);
+                                float v0;
+                                return sh_debug_colour(sh_key_at(g, h0.hf.P, h0.hf.front ? h0.hf.N : -h0.hf.N, v0));
+                            }
+                            srad = srad + T * sh_radiance(v);  // :286
+                            break;
+                        }
+                    }
+                }
+            }
+            const bool t_finite = is_finite(T.x) && is_finite(T.y) && is_finite(T.z);
+            if (hm.emission.x != 0.0f || hm.emission.y != 0.0f || hm.emission.z != 0.0f || !t_finite) srad = srad + T * hm.emission;  // :320
+            const bool last = bounce == fr.bounces;
+            if (last && sample + 1u == fr.spp) break;  // the sample drawn on the final iteration is never used
+            const Surf surf = surf_init(hm.hf.front, hm.hf.N, hm.Ns);
+            const f3 V = -d;
+            float w[3];
+            lobe_weights(hm.bsdf, surf, V, w);
+            float rnd[4];
+            rnd[0] = rng_float(rng); rnd[1] = rng_float(rng); rnd[2] = rng_float(rng); rnd[3] = rng_float(rng);  // :330
+            f3 L;
+            int lobe;
+            if (!bsdf_sample(hm.bsdf, surf, V, w, rnd, L, lobe)) break;
+            float pdf;
+            f3 f;
+            if (!bsdf_pdf_eval(hm.bsdf, surf, L, V, w, lobe, pdf, f)) break;
+            if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f) break;
+            { const float inv_pdf = pt_rcp(pdf); T = T * (f * inv_pdf); }  // :346
+            if (fr.rr_enabled && bounce > 3u) {  // :348-356
+                const float p = pt_max(T.x, pt_max(T.y, T.z));
+                if (rng_float(rng) >= p) break;
+                T = T * pt_rcp(p);
+            }
+            if (luminance(T) <= fr.throughput_threshold) break;  // :361
+            if (last) break;
+            previous_roughness += lobe == kLobeDiffuse ? 1.0f : hm.bsdf.Roughness;  // :366
+            o = spawn_origin(hm.hf.P, hm.hf.N, hm.hf.offset, L);
+            d = L;
+            trace(o, d, 0.0f, kInf, t, id);
+            rays++;
+        }
+        const f3 total = acc + srad;  // :373
+        sample++;
+        if (sample == fr.spp) {
+            if (is_finite(total.x) && is_finite(total.y) && is_finite(total.z)) return total * fr.inv_spp;
+            return make_f3(0.0f, 0.0f, 0.0f);
+        }
+        acc = total;
+    }
+}
+
+#if defined(__HIPCC__)
+struct SceneView;
+struct PixelMap;
+// update: one lane per path of pm (the update grid as a frame of its own); query: one lane per pixel of pm into out[out_index];
+// counters: [0] rays traced, [1] inserts that found their bucket full
+hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
+                               hipStream_t stream);
+hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream);
+hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                              uint32_t grid, hipStream_t stream);
+#endif
+
+}  // namespace pt

@@ -1,0 +1,124 @@
+// pt_sharc.hip -- the three kernels of row N14 (pt_render_sharc, DESIGN.md spec S20) over pt_sharc.h:
+//   update   one lane per path of the downscaled grid, one 8x8 block of paths per wave64 (PixelMap): sh_update_path
+//   resolve  one lane per slot of the hash map, streaming: sh_resolve_slot, 128-bit loads and stores
+//   query    one lane per pixel, one 8x8 pixel block per wave64: sh_query_pixel
+// Rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory), chosen as
+// pt_restir.hip chooses it.
+#include "pt_trace.h"
+#include "pt_sharc.h"
+
+namespace pt {
+
+namespace {
+
+template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha>
+__global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, PixelMap pm, ShFrame fr, ShGrid g, ShMap m, float4* __restrict__ out,
+                                                                 unsigned long long* __restrict__ counters)
+{
+    extern __shared__ float4 smem[];
+    const float4* nodes = sv.nodes;
+    const float4* sph = sv.sph_sorted;
+    const uint32_t* ids = sv.sorted_id;
+    StackT* stack;
+    if (kLds) {
+        stage_scene(sv, smem);
+        nodes = smem;
+        sph = smem + sv.n_nodes * 4u;
+        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
+        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
+    } else {
+        stack = reinterpret_cast<StackT*>(smem);
+    }
+    stack += threadIdx.x;
+    const uint32_t stride = blockDim.x;
+    auto trace = [&](f3 o, f3 d, float tmin, float tmax, float& t, uint32_t& id) {
+        closest_hit_any<kLds, StackT, kAlpha>(sv, nodes, sph, ids, o, d, tmin, tmax, stack, stride, t, id);
+    };
+    auto material = [&](uint32_t id, f3 o, f3 d, float t, bool primary) { return hit_material<kTex>(sv, id, o, d, t, primary); };
+    auto env = [&](f3 d) {
+        if (kTex && sv.env_tex != kNoTexture)
+            return sv.env_cube ? environment_cube(sv.tex + sv.env_tex, sv.env_xf, d) : environment_texture(sv.tex[sv.env_tex], sv.env_xf, d);
+        return environment_color(sv.env[0], sv.env[1], sv.env[2], sv.env[3], d);
+    };
+    uint32_t rays = 0, failed = 0;
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
+        const PixelRef pr = slot_to_pixel(pm, slot);
+        if (!pr.valid) continue;
+        if (kQuery) {
+            const f3 c = sh_query_pixel(fr, g, m, pr.px, pr.py, trace, material, env, rays);
+            out[pr.out_index] = make_float4(c.x, c.y, c.z, 1.0f);
+        } else {
+            sh_update_path(fr, g, m, pr.px, pr.py, trace, material, env, rays, failed);
+        }
+    }
+    block_atomic_add(counters, rays);
+    if (!kQuery) block_atomic_add(counters + 1, failed);
+}
+
+template <bool kQuery, bool kTex, bool kAlpha>
+hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                    uint32_t grid, hipStream_t stream)
+{
+    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
+    const uint32_t threads = traverse_threads(lds_scene);
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
+    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha>)
+                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha>);
+    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds_scene) {
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+    } else {
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+    }
+    return hipGetLastError();
+}
+
+template <bool kQuery>
+hipError_t launch_any(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                      uint32_t grid, hipStream_t stream)
+{
+    // the textured variants only where textures exist; the alpha-tested walk only where some sphere's hits are tested against a map
+    if (!sv.tex_maps) return launch_t<kQuery, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    if (sv.alpha_tested) return launch_t<kQuery, true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_t<kQuery, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+}
+
+constexpr uint32_t kResolveThreads = 256;
+
+// one lane per slot: key (8 B) and two voxels (16 B each) in, one voxel out, the key only where the slot is evicted
+__global__ __launch_bounds__(kResolveThreads) void sharc_resolve_kernel(ShMap m, uint32_t accumulation_frames, uint32_t max_stale_frames)
+{
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < m.capacity; slot += gridDim.x * blockDim.x) {
+        if (m.keys[slot] == 0u) continue;  // (an empty slot's accumulators were cleared with the array and nothing adds to them)
+        const uint4 acc = m.accum[slot], prev = m.resolved[slot];
+        bool clear;
+        const uint4 r = sh_resolve_slot(acc, prev, accumulation_frames, max_stale_frames, clear);
+        m.accum[slot] = r;
+        if (clear) m.keys[slot] = 0u;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
+                               hipStream_t stream)
+{
+    return launch_any<false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+}
+
+hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                              uint32_t grid, hipStream_t stream)
+{
+    return launch_any<true>(sv, pm, fr, g, m, out, counters, grid, stream);
+}
+
+hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream)
+{
+    const uint32_t grid = std::min((m.capacity + kResolveThreads - 1u) / kResolveThreads, 4096u);
+    hipLaunchKernelGGL(sharc_resolve_kernel, dim3(grid), dim3(kResolveThreads), 0, stream, m, accumulation_frames, max_stale_frames);
+    return hipGetLastError();
+}
+
+}  // namespace pt

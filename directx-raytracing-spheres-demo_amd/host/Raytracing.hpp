@@ -1,5 +1,6 @@
 // Raytracing.hpp -- host mirror of the reference's pass objects for this path, on top of the C-ABI:
 //   Raytracing        Source/Raytracing.ixx:29-112  { GraphicsSettings, SetConstants(...) noexcept, Render(...) }
+//                     Render(..., SHARC&, SHARCSettings) Source/Raytracing.ixx:114-148 (SHARC.hpp; row N14)
 //   (GBufferGeneration Source/GBufferGeneration.ixx:27-117 is folded in: Render traces the primary hit too.)
 // Same names, argument meaning and error behaviour: errors surface as C++ exceptions
 // (reference: ThrowIfFailed -> std::system_error, Source/ErrorHelpers.ixx:16-32); SetConstants is noexcept.
@@ -13,6 +14,7 @@
 #include "../../include/pt_api.h"
 #include "Camera.hpp"
 #include "HaltonSampler.hpp"
+#include "SHARC.hpp"
 #include "Scene.hpp"
 
 namespace dxrs {
@@ -50,6 +52,12 @@ struct Raytracing {
         float ThroughputThreshold = 1e-3f;
         bool IsRussianRouletteEnabled{}, IsShaderExecutionReorderingEnabled{}, IsDIEnabled{};
         dxrs::Denoiser Denoiser = dxrs::Denoiser::None;
+    };
+
+    struct SHARCSettings : SHARC::Constants {  // Raytracing.ixx:38-42; the values of MyAppData.h:256-265
+        uint32_t DownscaleFactor = 4;
+        float RoughnessThreshold = 0.4f;
+        uint32_t IsHashGridVisualizationEnabled{};
     };
 
     explicit Raytracing(DeviceContext& deviceContext) noexcept(false) : m_ctx(deviceContext.Get())
@@ -173,6 +181,28 @@ struct Raytracing {
         PtStats stats{};
         ThrowIfFailed(pt_render_with_di(m_ctx, nullptr, radiance.data(), 0, &lighting, m_graphicsSettings.Denoiser != 0 ? &outputs : nullptr, &stats),
                       m_ctx, "pt_render_with_di");
+        return stats;
+    }
+
+    // Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings) (Raytracing.ixx:114-148; row N14, pt_render_sharc): the sparse update
+    // pass, the resolve and the frame through the cache.  The context owns the cache the reference's SHARC object owns.
+    PtStats Render(std::vector<Float4>& radiance, SHARC& sharc, const SHARCSettings& settings)
+    {
+        ThrowIfFailed(pt_set_constants(m_ctx, &m_graphicsSettings), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtSharcSettings s{};
+        s.Capacity = sharc.GetCapacity();
+        s.DownscaleFactor = settings.DownscaleFactor;
+        s.SceneScale = settings.SceneScale;
+        s.RoughnessThreshold = settings.RoughnessThreshold;
+        s.AccumulationFrames = settings.AccumulationFrames;
+        s.MaxStaleFrames = settings.MaxStaleFrames;
+        s.IsAntiFireflyEnabled = settings.IsAntiFireflyEnabled ? 1u : 0u;
+        s.IsHashGridVisualizationEnabled = settings.IsHashGridVisualizationEnabled;
+        s.ResetHistory = sharc.NeedsReset() ? 1u : 0u;
+        PtStats stats{};
+        ThrowIfFailed(pt_render_sharc(m_ctx, nullptr, radiance.data(), 0, &s, &stats), m_ctx, "pt_render_sharc");
+        sharc.ClearReset();  // (only now: a call that threw has restarted nothing)
         return stats;
     }
 

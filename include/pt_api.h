@@ -388,6 +388,32 @@ typedef struct PtRestirDiTextures {     /* DEVICE pointers; inputs are what RAB_
 } PtRestirDiTextures;
 PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const PtRestirDiTextures *textures);
 
+/* Row N14 -- the frame through the radiance cache (Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings), Source/Raytracing.ixx:114-148;
+ * DESIGN.md spec S20): a stand-in for the SHARC library, which the reference does not vendor.  Three stages on the lane of the next render
+ * call, in this order:
+ *   UPDATE   the accumulators are cleared; (W / DownscaleFactor) x (H / DownscaleFactor) paths (the SHARC_UPDATE permutation of
+ *            Shaders/Raytracing.hlsl) insert their vertices into the hash grid and add their radiance to them and to the vertices before;
+ *   RESOLVE  every voxel joins this frame's sums to its history (Shaders/SHARC.hlsl:35-57), ages, and is evicted when stale;
+ *   QUERY    the frame of pt_render (the SHARC_QUERY permutation): a path that meets a voxel with samples, far and wide enough, ends there
+ *            with the voxel's radiance.  With an empty cache the frame is pt_render's, bit for bit.
+ * Frame settings (RenderSize, FrameIndex, Bounces, SamplesPerPixel, Russian roulette, ThroughputThreshold) come from pt_set_constants;
+ * IsDIEnabled and Denoiser must be 0.  rect / out / out_is_device / stats: as pt_render (the update pass always covers the whole frame);
+ * stats->rays counts the update's and the query's rays; a stage that is not run writes nothing (without QUERY `out` may be NULL).
+ * Runs like pt_restir_di: on the lane of the next render call, ordered like pt_render_gbuffer; consecutive calls are ordered on the cache
+ * whichever lane they use; the lanes are not advanced and pt_get_totals does not count the call.  The context owns the cache -- Capacity
+ * keys of 8 bytes and two voxels of 16 bytes each -- allocated on first use and again when Capacity changes.  The cache restarts empty on
+ * the first call, with ResetHistory, after pt_set_scene and when Capacity changes.
+ * PT_ERR_INVALID_ARG: a null argument; a value outside the ranges of PtSharcSettings; a rect outside RenderSize.  PT_ERR_UNSUPPORTED:
+ * IsAntiFireflyEnabled; IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as pt_render. */
+PtStatus pt_render_sharc(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtSharcSettings *settings, PtStats *stats);
+
+/* Test hooks of row N14: the cache as the last pt_render_sharc call left it -- `capacity` keys (uint64, 0 = empty) and resolved voxels
+ * (4 x uint32: fixed-point RGB sums, samples | frames << 16 | stale << 24) to HOST memory -- and the reverse, which installs a cache made
+ * elsewhere (allocating for `capacity`, a power of two >= 16) as if a call with that Capacity had left it.  Both synchronise.
+ * pt_sharc_download: PT_ERR_STATE when there is no cache, PT_ERR_INVALID_ARG when capacity differs from the cache's. */
+PtStatus pt_sharc_download(PtContext *ctx, void *keys, void *voxels, uint32_t capacity);
+PtStatus pt_sharc_upload(PtContext *ctx, const void *keys, const void *voxels, uint32_t capacity);
+
 /* Row N11 -- the super-resolution stand-in (XeSS::Execute as App::ProcessXeSSSuperResolution drives it, Source/App.cpp:1682-1708; DESIGN.md
  * spec S17): a temporal upscaler of the TAAU / FSR2 family, for XeSS and DLSS-SR, which the reference does not vendor.  From the jittered
  * radiance of a frame rendered at InputSize (PtCamera.Jitter), its G-buffer LinearDepth and MotionVector, to the frame at OutputSize

@@ -12,6 +12,7 @@
  *   PtNisSettings         (row N12) the sl::NISOptions App::ProcessNIS fills (sharpness, hdrMode; mode is always eSharpen), plus the size, 16 B
  *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
+ *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
@@ -108,7 +109,7 @@ typedef struct PtGraphicsSettings {
     uint32_t IsDIEnabled;                        /* 32: 1 = sphere-light direct illumination of the primary surface (row N4, a stand-in for ReSTIR-DI) */
     uint32_t Denoiser;                           /* 36: must be 0 == Denoiser::None */
     uint32_t _pad0[2];                           /* 40 */
-    uint32_t SHARC_Capacity;                     /* 48: SHARC block ignored (dropped) */
+    uint32_t SHARC_Capacity;                     /* 48: SHARC block ignored by pt_set_constants: pt_render_sharc takes PtSharcSettings */
     float SHARC_SceneScale;                      /* 52 */
     float SHARC_RoughnessThreshold;              /* 56 */
     uint32_t SHARC_IsAntiFireflyEnabled;         /* 60 */
@@ -220,6 +221,24 @@ typedef struct PtFrameGenSettings {
     uint32_t _pad[2];             /* 24: must be 0 */
 } PtFrameGenSettings;
 
+/* Row N14 (pt_render_sharc, the SHARC stand-in of DESIGN.md spec S20): SHARCSettings as Raytracing::Render(..., SHARC&, SHARCSettings) takes
+ * them (Source/MyAppData.h:256-265, Source/Raytracing.ixx:114-148), the cache's accumulation constants and the stages of the call. */
+typedef struct PtSharcSettings {
+    uint32_t Capacity;                        /*  0: slots of the hash map; 0 -> 1 << 22; a power of two, 16 .. 1 << 28 */
+    uint32_t DownscaleFactor;                 /*  4: the update pass traces (W / f) x (H / f) paths; 0 -> 4; 1 .. 4 */
+    float SceneScale;                         /*  8: 0 -> 50; 5 .. 100 */
+    float RoughnessThreshold;                 /* 12: 0 .. 1: the update pass's surfaces are at least this rough */
+    uint32_t AccumulationFrames;              /* 16: 0 -> 10; 1 .. 255 */
+    uint32_t MaxStaleFrames;                  /* 20: 0 -> 64; 1 .. 254 */
+    uint32_t IsAntiFireflyEnabled;            /* 24: nonzero -> PT_ERR_UNSUPPORTED (not built) */
+    uint32_t IsHashGridVisualizationEnabled;  /* 28: a pixel whose path met the cache shows a colour of its primary hit's cell */
+    uint32_t ResetHistory;                    /* 32: nonzero = the cache restarts empty with this call */
+    uint32_t Stages;                          /* 36: PT_SHARC_UPDATE | PT_SHARC_RESOLVE | PT_SHARC_QUERY; 0 -> all three */
+    uint32_t _pad[2];                         /* 40: must be 0 */
+} PtSharcSettings;
+
+enum { PT_SHARC_UPDATE = 1, PT_SHARC_RESOLVE = 2, PT_SHARC_QUERY = 4 };
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -249,6 +268,8 @@ static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, Out
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
 static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
               && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
+static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16
+              && offsetof(PtSharcSettings, ResetHistory) == 32 && offsetof(PtSharcSettings, Stages) == 36, "PtSharcSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -267,6 +288,8 @@ _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, Ou
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
 _Static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
                && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
+_Static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16
+               && offsetof(PtSharcSettings, ResetHistory) == 32 && offsetof(PtSharcSettings, Stages) == 36, "PtSharcSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

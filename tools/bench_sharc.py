@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Time pt_render_sharc (row N14, the SHARC stand-in) with device events and print one JSON line.  The scene is C2 (demo scene seed 0,
+1 spp, 8 bounces, a resting camera) with the reference's SHARC settings (Capacity 1 << 22, DownscaleFactor 4, SceneScale 50,
+RoughnessThreshold 0.4), after --fill whole calls that fill the cache.
+
+Per size (1920x1080 and 3840x2160), the median of --calls single-call event timings of: the whole call (UPDATE | RESOLVE | QUERY), the
+call without its query (UPDATE | RESOLVE), the update alone, the query alone, and pt_render at the same settings in the same process.
+Every timed stage runs over the WARM cache: the filled cache is downloaded once and installed again (pt_sharc_upload) before each stage
+is timed.  Whole calls and UPDATE | RESOLVE calls keep a cache warm by themselves; update-only and query-only calls leave the resolved
+voxels as they are.  A resolve-only call is never timed: without an update in front of it every voxel ages, and MaxStaleFrames such
+calls empty the cache.  A call with a single stage pays inside its event pair what the whole call pays once -- the clear of the
+accumulators (update), the counters' memset, the host's enqueue gap -- so single-stage times do not add up to the call.  The stage
+times are therefore derived from differences of combined calls: resolve = (UPDATE | RESOLVE) - UPDATE, query in the call = call -
+(UPDATE | RESOLVE); the stand-alone times are reported beside them.  Also: the rays per frame of the call, of its query and of
+pt_render.  The resolve's
+bytes per second against a device-to-device copy that moves the same number of bytes; byte model of the resolve: per slot the key read
+(8 B); per OCCUPIED slot two voxels read and one written (48 B) -- an empty slot's voxels are not touched.
+Then the image quality on the same scene at --quality-size: the RMSE of a 1-spp pt_render_sharc frame and of a 1-spp pt_render frame
+against --reference-frames accumulated pt_render frames.
+
+    python tools/bench_sharc.py [--calls 100 --warmup 10 --fill 12 --sizes 1920x1080,3840x2160 --quality-size 480x270 --reference-frames 2048]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402  (device buffers and events only)
+import dxrs_amd_loader  # noqa: E402,F401
+import dxrs_amd  # noqa: E402
+
+UPDATE, RESOLVE, QUERY = 1, 2, 4
+RESOLVE_BYTES_PER_SLOT, RESOLVE_BYTES_PER_OCCUPIED_SLOT = 8, 48
+
+
+def median_ms(stream, fn, calls, warmup):
+    for _ in range(warmup):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+    for a, b in ev:
+        a.record(stream)
+        fn()
+        b.record(stream)
+    torch.cuda.synchronize()
+    return float(np.median([a.elapsed_time(b) for a, b in ev]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--fill", type=int, default=12, help="whole calls that fill the cache before anything is timed")
+    ap.add_argument("--sizes", default="1920x1080,3840x2160")
+    ap.add_argument("--capacity", type=int, default=1 << 22)
+    ap.add_argument("--quality-size", default="480x270")
+    ap.add_argument("--reference-frames", type=int, default=2048)
+    args = ap.parse_args()
+    torch.cuda.init()
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    t = dxrs_amd.types
+    host = dxrs_amd.load_host()
+    spheres, materials, sd = host.scene(dxrs_amd.host.SCENE_DEMO, seed=0)
+    r = dxrs_amd.Renderer(stream=stream.cuda_stream)
+    r.set_scene(spheres, materials, sd)
+    st = dict(capacity=args.capacity, downscale_factor=4, scene_scale=50.0, roughness_threshold=0.4)
+    res = {"metric": "pt_render_sharc", "calls": args.calls, "statistic": "median of single-call device-event timings", "capacity": args.capacity,
+           "resolve_bytes_per_slot": RESOLVE_BYTES_PER_SLOT, "resolve_bytes_per_occupied_slot": RESOLVE_BYTES_PER_OCCUPIED_SLOT, "sizes": {}}
+    frame = [0]
+
+    def next_frame(w, h):
+        frame[0] += 1
+        r.set_constants(t.graphics_settings(w, h, frame_index=frame[0], bounces=8, spp=1))
+
+    for W, H in [tuple(map(int, s.split("x"))) for s in args.sizes.split(",")]:
+        out = torch.zeros((H * W, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        r.set_camera(host.camera_matrices(W, H, jitter=False))
+        for k in range(args.fill):
+            next_frame(W, H)
+            r.render_sharc_device(out.data_ptr(), reset_history=k == 0, **st)
+        r.synchronize()
+        keys, voxels = r.sharc_download(args.capacity)
+        occupied = int((keys != 0).sum())
+
+        def stage(stages):
+            next_frame(W, H)
+            r.render_sharc_device(out.data_ptr() if stages & QUERY else 0, stages=stages, **st)
+
+        def plain():
+            next_frame(W, H)
+            r.render_device(out.data_ptr())
+
+        def warm(fn):
+            """fn timed over the filled cache: installed again first, and checked afterwards to be still as full"""
+            r.sharc_upload(keys, voxels)
+            ms_ = median_ms(stream, fn, args.calls, args.warmup)
+            r.synchronize()
+            left = int((r.sharc_download(args.capacity)[0] != 0).sum())
+            assert left >= occupied * 9 // 10, f"the cache drained while a stage was timed: {left} of {occupied} slots left"
+            return ms_
+
+        ms = {name: warm(fn) for name, fn in (("call", lambda: stage(7)), ("update_resolve", lambda: stage(UPDATE | RESOLVE)), ("update_alone", lambda: stage(UPDATE)),
+                                              ("query_alone", lambda: stage(QUERY)))}
+        ms["pt_render"] = median_ms(stream, plain, args.calls, args.warmup)
+        ms["resolve"] = ms["update_resolve"] - ms["update_alone"]
+        ms["query_in_call"] = ms["call"] - ms["update_resolve"]
+        clear = torch.zeros(args.capacity * 4, dtype=torch.int32, device="cuda")
+        ms["clear"] = median_ms(stream, lambda: clear.zero_(), args.calls, args.warmup)
+        model = RESOLVE_BYTES_PER_SLOT * args.capacity + RESOLVE_BYTES_PER_OCCUPIED_SLOT * occupied
+        src = torch.zeros(model // 8 + 1, dtype=torch.float32, device="cuda")
+        dst = torch.zeros(model // 8 + 1, dtype=torch.float32, device="cuda")
+        ms["copy"] = median_ms(stream, lambda: dst.copy_(src), args.calls, args.warmup)
+        r.sharc_upload(keys, voxels)
+        next_frame(W, H)
+        rays_call = r.render_sharc_device(out.data_ptr(), want_stats=True, **st).rays
+        rays_query = r.render_sharc_device(out.data_ptr(), want_stats=True, stages=QUERY, **st).rays
+        rays_plain = r.render_device(out.data_ptr(), want_stats=True).rays
+        res["sizes"][f"{W}x{H}"] = dict({k + "_ms": round(v, 5) for k, v in ms.items()}, call_over_pt_render=round(ms["call"] / ms["pt_render"], 3),
+                                        rays_call=int(rays_call), rays_query=int(rays_query), rays_pt_render=int(rays_plain), occupied_slots=occupied, resolve_bytes=model,
+                                        resolve_TBps=round(model / (ms["resolve"] * 1e-3) / 1e12, 3), copy_TBps=round(model / (ms["copy"] * 1e-3) / 1e12, 3),
+                                        resolve_fraction_of_copy=round(ms["copy"] / ms["resolve"], 3))
+        del out, clear, src, dst
+    # image quality: 1 spp through the cache and without it against a converged pt_render accumulation
+    W, H = map(int, args.quality_size.split("x"))
+    n = W * H
+    out = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+    accum = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    r.set_camera(host.camera_matrices(W, H, jitter=False))
+    for k in range(args.reference_frames):
+        r.set_constants(t.graphics_settings(W, H, frame_index=100000 + k, bounces=8, spp=1))
+        r.render_device(out.data_ptr())
+        r.accumulate(accum.data_ptr(), out.data_ptr(), n, k)
+    r.synchronize()
+    truth = accum.cpu().numpy()[:, :3].astype(np.float64)
+    for k in range(args.fill):
+        r.set_constants(t.graphics_settings(W, H, frame_index=k, bounces=8, spp=1))
+        r.render_sharc_device(out.data_ptr(), reset_history=k == 0, **st)
+    r.synchronize()
+    cached = out.cpu().numpy()[:, :3].astype(np.float64)
+    r.render_device(out.data_ptr())
+    r.synchronize()
+    plain_img = out.cpu().numpy()[:, :3].astype(np.float64)
+    res["quality"] = {"size": f"{W}x{H}", "reference_frames": args.reference_frames, "rmse_pt_render_sharc_1spp": round(float(np.sqrt(((cached - truth) ** 2).mean())), 5),
+                      "rmse_pt_render_1spp": round(float(np.sqrt(((plain_img - truth) ** 2).mean())), 5), "mean_radiance": round(float(truth.mean()), 5)}
+    r.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

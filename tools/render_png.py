@@ -6,10 +6,11 @@ NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through p
 row N10, accumulated; --upscale MODE: --frames frames of a resting camera rendered at the mode's input size with Halton jitter and
 upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_sharpen, row N12, on the frame at output size, after the
 upscaler when there is one and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
-pt_frame_gen, row N13, makes between them).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting camera through pt_render_sharc, row N14, the last one tone
+mapped).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]"""
 import argparse
 import os
 import sys
@@ -82,10 +83,15 @@ def main():
                     help="render the scene at --time minus --dt and at --time (one frame each: pt_render_gbuffer with the earlier pose as the "
                          "previous one -> pt_render [-> pt_bloom] -> pt_tonemap) and write the frame pt_frame_gen (row N13) makes between the "
                          "two to MID.png; the frame at --time goes to the positional output")
+    ap.add_argument("--sharc", action="store_true",
+                    help="--frames frames of a resting camera through the radiance cache (row N14): pt_render_sharc with the reference's "
+                         "SHARC settings (update at a quarter of the size, resolve, query); the last frame, tone mapped (no accumulation)")
     ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--frame-gen applies to the plain path-traced frame")
+    if args.sharc and (args.frame_gen or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
+        ap.error("--sharc applies to the plain path-traced frame")
     if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
@@ -160,6 +166,23 @@ def main():
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
         Image.fromarray(mid.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.frame_gen)
         print(f"frame generation (pt_frame_gen) {w}x{h}: time {args.time} -> {args.out}, time {args.time - args.dt / 2} -> {args.frame_gen}")
+        r.close()
+        return
+    if args.sharc:
+        r.set_camera(host.camera_matrices(w, h, jitter=False))
+        rays = 0
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            r.set_constants(gs)
+            rays = r.render_sharc_device(frame.data_ptr(), want_stats=True, roughness_threshold=0.4, reset_history=k == 0).rays
+        hdr = frame
+        if args.bloom is not None:
+            r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"SHARC (pt_render_sharc, {args.frames} frames, {rays} rays in the last) {w}x{h} -> {args.out}")
         r.close()
         return
     if args.upscale:
