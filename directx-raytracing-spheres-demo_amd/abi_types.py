@@ -171,6 +171,40 @@ class PtFrameGenTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in FRAME_GEN_TEXTURES]
 
 
+# Row N15 (pt_ray_reconstruction, the DLSS-RR stand-in): the sizes, jitter, reset and history cap, the camera fields by value
+# (Position and PtCamera.Matrices[6], [7], [2]), and the tagged buffers with their float32 counts per pixel
+RAY_RECONSTRUCTION_INPUTS = (("Color", 4), ("Depth", 1), ("MotionVector", 3), ("NormalRoughness", 4), ("DiffuseAlbedo", 3), ("SpecularAlbedo", 3),
+                             ("SpecularHitDistance", 1))
+RAY_RECONSTRUCTION_TEXTURES = tuple(name for name, _ in RAY_RECONSTRUCTION_INPUTS) + ("Output",)
+CAMERA_PREVIOUS_WORLD_TO_PROJECTION, CAMERA_PROJECTION_TO_VIEW, CAMERA_VIEW_TO_WORLD = 2, 6, 7  # indices into PtCamera.Matrices
+
+
+class PtRayReconstructionSettings(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("OutputSize", C.c_uint32 * 2), ("Jitter", C.c_float * 2), ("Reset", C.c_uint32),
+                ("MaxHistoryWeight", C.c_float), ("Position", C.c_float * 3), ("_pad", C.c_float), ("ProjectionToView", C.c_float * 16),
+                ("ViewToWorld", C.c_float * 16), ("PreviousWorldToProjection", C.c_float * 16)]
+
+
+class PtRayReconstructionTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in RAY_RECONSTRUCTION_TEXTURES]
+
+
+def ray_reconstruction_settings(render_size, output_size, camera, jitter=None, reset=False, max_history_weight=0.0):
+    """PtRayReconstructionSettings from a PtCamera: its Position and three matrices by value; jitter defaults to -camera.Jitter, what
+    the reference hands its upscalers"""
+    s = PtRayReconstructionSettings(RenderSize=(C.c_uint32 * 2)(*render_size), OutputSize=(C.c_uint32 * 2)(*output_size), Reset=1 if reset else 0,
+                                    MaxHistoryWeight=max_history_weight)
+    jitter = (-camera.Jitter[0], -camera.Jitter[1]) if jitter is None else jitter
+    s.Jitter[0], s.Jitter[1] = jitter
+    for k in range(3):
+        s.Position[k] = camera.Position[k]
+    for k in range(16):
+        s.ProjectionToView[k] = camera.Matrices[CAMERA_PROJECTION_TO_VIEW][k]
+        s.ViewToWorld[k] = camera.Matrices[CAMERA_VIEW_TO_WORLD][k]
+        s.PreviousWorldToProjection[k] = camera.Matrices[CAMERA_PREVIOUS_WORLD_TO_PROJECTION][k]
+    return s
+
+
 # pt_render_with_di: the frame's direct illumination, supplied by the caller (device pointers, float4 per pixel of the rect)
 class PtDirectLighting(C.Structure):
     _fields_ = [("Diffuse", C.c_void_p), ("Specular", C.c_void_p)]
@@ -242,6 +276,7 @@ class PtBvhNode(C.Structure):
 
 assert C.sizeof(PtSphere) == 16 and C.sizeof(PtMaterial) == 64 and C.sizeof(PtCamera) == 608
 assert C.sizeof(PtSceneData) == 80 and C.sizeof(PtGraphicsSettings) == 80 and C.sizeof(PtBvhNode) == 64
+assert C.sizeof(PtRayReconstructionSettings) == 240 and PtRayReconstructionSettings.PreviousWorldToProjection.offset == 176
 
 SPHERE_DTYPE = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("r", "<f4")])
 MATERIAL_DTYPE = np.dtype([

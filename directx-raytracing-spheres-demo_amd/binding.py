@@ -10,7 +10,8 @@ import numpy as np
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
-                        RESTIR_DI_TEXTURES, UPSCALE_TEXTURES)
+                        PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
+                        ray_reconstruction_settings)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -19,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -115,6 +116,10 @@ class HipLib:
         lib.pt_nis_sharpen.argtypes = [vp, C.POINTER(PtNisSettings), C.POINTER(PtNisTextures)]
         lib.pt_frame_gen.restype = C.c_int
         lib.pt_frame_gen.argtypes = [vp, C.POINTER(PtFrameGenSettings), C.POINTER(PtFrameGenTextures), C.POINTER(u32)]
+        lib.pt_ray_reconstruction.restype = C.c_int
+        lib.pt_ray_reconstruction.argtypes = [vp, C.POINTER(PtRayReconstructionSettings), C.POINTER(PtRayReconstructionTextures)]
+        lib.pt_ray_reconstruction_history.restype = C.c_int
+        lib.pt_ray_reconstruction_history.argtypes = [vp, vp, vp, vp]
         lib.pt_trace_rays.restype = C.c_int
         lib.pt_trace_rays.argtypes = [vp, vp, vp, u32, C.c_float, C.c_int, vp, vp]
         lib.pt_trace_rays_stats.restype = C.c_int
@@ -641,6 +646,27 @@ class Renderer:
         generated = C.c_uint32(0)
         self._check(self._lib.pt_frame_gen(self._ctx, C.byref(s), C.byref(t), C.byref(generated)))
         return bool(generated.value)
+
+    def ray_reconstruction_device(self, render_size, output_size, buffers, camera, jitter=None, reset=False, max_history_weight=0.0):
+        """The ray-reconstruction stand-in (row N15, DESIGN.md spec S21): the noisy radiance of render_denoiser's mode 1 with the
+        G-buffer's guides at render_size = (w, h) -> the denoised Output at output_size = (W, H), with the history the context keeps.
+        buffers: {RAY_RECONSTRUCTION_TEXTURES name: device pointer}; Output must not overlap an input.  camera: the frame's PtCamera
+        (host.camera_matrices), whose Position and matrices travel by value; jitter: -PtCamera.Jitter unless given.  Asynchronous on
+        the context's stream."""
+        unknown = set(buffers) - set(RAY_RECONSTRUCTION_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown ray reconstruction buffers {sorted(unknown)}")
+        s = ray_reconstruction_settings(render_size, output_size, camera, jitter, reset, max_history_weight)
+        t = PtRayReconstructionTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_ray_reconstruction(self._ctx, C.byref(s), C.byref(t)))
+
+    def ray_reconstruction_history(self, output_size):
+        """The history slot the last ray_reconstruction_device call wrote (pt_ray_reconstruction_history; synchronous) ->
+        (history (H, W, 4), normal (H, W, 4), depth (H, W)) float32"""
+        W, H = output_size
+        hist, nrm, z = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.float32)
+        self._check(self._lib.pt_ray_reconstruction_history(self._ctx, hist.ctypes.data, nrm.ctypes.data, z.ctypes.data))
+        return hist, nrm, z
 
     def upscaler(self, output_size, mode=0, device=None, **settings):
         """An `upscale(color, depth, velocity, jitter)` that keeps the sizes and settings across frames and runs pt_upscale (row N11):

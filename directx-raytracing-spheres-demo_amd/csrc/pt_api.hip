@@ -1291,7 +1291,7 @@ void pt_destroy(PtContext* c)
     if (c->beam.stream) (void)hipStreamDestroy(c->beam.stream);
     free_dev(c->d_out);
     free_dev(c->d_bloom);
-    for (History* H : { &c->dn, &c->up, &c->fg }) free_dev(H->mem);
+    for (History* H : { &c->dn, &c->up, &c->fg, &c->rr }) free_dev(H->mem);
     free_dev(c->d_ri);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     free_dev(c->d_sh);

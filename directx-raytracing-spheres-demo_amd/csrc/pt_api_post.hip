@@ -1,5 +1,6 @@
 // pt_api_post.hip -- the entry points of the C-ABI (include/pt_api.h) that touch nothing but the context's stream and their own state:
-// tone mapping, accumulation, bloom, the NRD composition and stand-in, super-resolution, sharpening and frame interpolation.
+// tone mapping, accumulation, bloom, the NRD composition and stand-in, super-resolution, sharpening, frame interpolation and ray
+// reconstruction.
 // Everything that knows lanes, the scene, the tree or the beam cache is in pt_api.hip.
 #include <algorithm>
 #include <string>
@@ -11,6 +12,7 @@
 #include "pt_upscale.h"
 #include "pt_nis.h"
 #include "pt_framegen.h"
+#include "pt_rr.h"
 
 namespace {
 
@@ -19,6 +21,9 @@ namespace {
 constexpr uint64_t kDnBytesPerPixel = 2 * 4 * sizeof(float4) + 2 * sizeof(float) + 4 * sizeof(float4);
 // Row N11's history per output pixel and slot: a float4 (t-space colour, accumulated weight) and a float (depth).
 constexpr uint64_t kUpSlotBytesPerPixel = sizeof(float4) + sizeof(float);
+// Row N15's history per output pixel and slot: two float4 (t-space colour + weight, normal + roughness) and a float (depth); its
+// prepare pass's records per render pixel: three float4.
+constexpr uint64_t kRrSlotBytesPerPixel = 2 * sizeof(float4) + sizeof(float), kRrRecordBytesPerPixel = 3 * sizeof(float4);
 
 // The two-slot history of a pass (PtContext::dn, up, fg).  history_begin: allocated on first use and again when `dims` change -- the
 // history is only used on `stream`, so once the calls queued there have finished the old one is free (the render lanes never touch it,
@@ -312,6 +317,80 @@ PtStatus pt_frame_gen(PtContext* c, const PtFrameGenSettings* s, const PtFrameGe
         PT_HIP(c, launch_framegen(b, fg_params(w, h, W, H, s->Format), c->stream));
     }
     history_commit(c->fg, s->Format);
+    return PT_OK;
+}
+
+// Row N15 -- the ray-reconstruction stand-in (DESIGN.md spec S21): the prepare and the resolve launch on the context's stream, the
+// history and the prepare pass's records in the context (kRrSlotBytesPerPixel, kRrRecordBytesPerPixel).
+PtStatus pt_ray_reconstruction(PtContext* c, const PtRayReconstructionSettings* s, const PtRayReconstructionTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: null pointer");
+    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1], W = s->OutputSize[0], H = s->OutputSize[1];
+    if (w == 0 || h == 0 || w > kUpMaxSize || h > kUpMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: RenderSize must be in [1, 16384]");
+    if (W < w || H < h || W > kUpMaxSize || H > kUpMaxSize || (uint64_t)W > (uint64_t)kUpMaxRatio * w || (uint64_t)H > (uint64_t)kUpMaxRatio * h)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: OutputSize must be in [RenderSize, 4 * RenderSize] per axis and at most 16384");
+    for (const float j : { s->Jitter[0], s->Jitter[1] })
+        if (!is_finite(j) || !(pt_abs(j) <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: Jitter must be finite and within [-1, 1]");
+    float max_a = s->MaxHistoryWeight;
+    if (max_a == 0.0f) max_a = kUpDefaultHistoryWeight;
+    if (!is_finite(max_a) || !(max_a >= kUpMinHistoryWeight && max_a <= kUpMaxHistoryWeight))
+        return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: MaxHistoryWeight must be 0 or in [1, 256]");
+    for (const float v : s->Position)
+        if (!is_finite(v)) return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: Position must be finite");
+    for (int i = 0; i < 16; i++)
+        if (!is_finite(s->ProjectionToView[i]) || !is_finite(s->ViewToWorld[i]) || !is_finite(s->PreviousWorldToProjection[i]))
+            return fail(c, PT_ERR_INVALID_ARG, "pt_ray_reconstruction: every matrix entry must be finite");
+    const uint64_t n_in = (uint64_t)w * h, n_out = (uint64_t)W * H;
+    // the output must not share a byte with an input (a workgroup reads the inputs of its neighbours' pixels)
+    const BufferUse use[8] = { {t->Color, n_in * 16, 16, false, true, "Color"}, {t->Depth, n_in * 4, 4, false, true, "Depth"},
+                               {t->MotionVector, n_in * 12, 4, false, true, "MotionVector"}, {t->NormalRoughness, n_in * 16, 16, false, true, "NormalRoughness"},
+                               {t->DiffuseAlbedo, n_in * 12, 4, false, true, "DiffuseAlbedo"}, {t->SpecularAlbedo, n_in * 12, 4, false, true, "SpecularAlbedo"},
+                               {t->SpecularHitDistance, n_in * 4, 4, false, true, "SpecularHitDistance"}, {t->Output, n_out * 16, 16, true, true, "Output"} };
+    if (const PtStatus st = buffers_ok(c, "pt_ray_reconstruction", use, 8); st != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    bool restart = s->Reset != 0 || !c->rr.valid;  // (a change of any size makes a new allocation, which restarts)
+    if (const PtStatus st = history_begin(c, c->rr, {W, H, w, h}, 2 * n_out * kRrSlotBytesPerPixel + n_in * kRrRecordBytesPerPixel, restart); st != PT_OK) return st;
+    // the allocation: hist[2], hist_n[2], the three records (float4 each), then hist_z[2] (float)
+    float4* const f4 = static_cast<float4*>(c->rr.mem);
+    float* const zs = reinterpret_cast<float*>(f4 + 4 * n_out + 3 * n_in);
+    const uint32_t cur = c->rr.slot ^ 1u, prev = c->rr.slot;
+    RrBuffers b{};
+    b.color = static_cast<const float4*>(t->Color);
+    b.depth = static_cast<const float*>(t->Depth);
+    b.motion = static_cast<const float*>(t->MotionVector);
+    b.normal_roughness = static_cast<const float4*>(t->NormalRoughness);
+    b.diffuse_albedo = static_cast<const float*>(t->DiffuseAlbedo);
+    b.specular_albedo = static_cast<const float*>(t->SpecularAlbedo);
+    b.hit_distance = static_cast<const float*>(t->SpecularHitDistance);
+    b.out = static_cast<float4*>(t->Output);
+    b.prev_hist = f4 + prev * n_out;
+    b.hist = f4 + cur * n_out;
+    b.prev_n = f4 + (2 + prev) * n_out;
+    b.hist_n = f4 + (2 + cur) * n_out;
+    b.rec_tz = f4 + 4 * n_out;
+    b.rec_nr = b.rec_tz + n_in;
+    b.rec_virt = b.rec_nr + n_in;
+    b.prev_z = zs + prev * n_out;
+    b.hist_z = zs + cur * n_out;
+    const RrParams R = rr_params(w, h, W, H, s->Jitter[0], s->Jitter[1], max_a, s->Position, s->ProjectionToView, s->ViewToWorld, s->PreviousWorldToProjection);
+    PT_HIP(c, launch_ray_reconstruction(b, R, restart, c->stream));
+    history_commit(c->rr, 0);
+    return PT_OK;
+}
+
+PtStatus pt_ray_reconstruction_history(PtContext* c, void* history, void* normal, void* depth)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!c->rr.valid || !c->rr.mem) return fail(c, PT_ERR_STATE, "pt_ray_reconstruction_history: no pt_ray_reconstruction call has been made");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t n_out = (uint64_t)c->rr.dims[0] * c->rr.dims[1], n_in = (uint64_t)c->rr.dims[2] * c->rr.dims[3];
+    const float4* const f4 = static_cast<const float4*>(c->rr.mem);
+    const float* const zs = reinterpret_cast<const float*>(f4 + 4 * n_out + 3 * n_in);
+    if (history) PT_HIP(c, hipMemcpy(history, f4 + c->rr.slot * n_out, n_out * sizeof(float4), hipMemcpyDeviceToHost));
+    if (normal) PT_HIP(c, hipMemcpy(normal, f4 + (2 + c->rr.slot) * n_out, n_out * sizeof(float4), hipMemcpyDeviceToHost));
+    if (depth) PT_HIP(c, hipMemcpy(depth, zs + c->rr.slot * n_out, n_out * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

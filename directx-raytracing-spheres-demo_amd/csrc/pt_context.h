@@ -187,7 +187,9 @@ struct PtContext {
     //   up  pt_upscale (row N11): per output pixel and slot a float4 and a float; dims = OutputSize, tag = InputSize
     //   fg  pt_frame_gen (row N13): the motion field (8 B per render pixel), then per slot the previous Color (4 B per output pixel) and
     //       Depth (4 B per render pixel); dims = RenderSize, OutputSize, tag = the Format
-    History dn, up, fg;
+    //   rr  pt_ray_reconstruction (row N15): per slot and output pixel two float4 and a float, then the prepare pass's three float4
+    //       records per render pixel; dims = OutputSize, RenderSize, no tag
+    History dn, up, fg, rr;
     // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
     // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
     // pt_set_scene count it was made under (emitter indices change with the scene), `ev_ri` = the last call's launches have finished

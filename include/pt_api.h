@@ -29,6 +29,8 @@
  *                            Source/App.cpp:1710-1721, Source/Streamline.ixx:73-74
  *   pt_frame_gen             App::ProcessDLSSFrameGeneration's tags + Streamline's DLSS-G plugin (a stand-in, spec S19)
  *                            Source/App.cpp:1673-1680, 1460-1525
+ *   pt_ray_reconstruction    Streamline::SetConstants(DLSSDOptions) / Tag / Evaluate(kFeatureDLSS_RR) (a stand-in for DLSS-RR, spec S21)
+ *                            App::ProcessDLSSRayReconstruction, Source/App.cpp:1654-1671
  *   pt_render_tiles / pt_unpack_tiles / pt_set_partition
  *                            (no reference analogue: single adapter) tile partition for multi-GPU, SURVEY 8e
  *   pt_last_error            ThrowIfFailed -> std::system_error text  Source/ErrorHelpers.ixx:16-32
@@ -488,6 +490,46 @@ typedef struct PtFrameGenTextures {     /* DEVICE pointers */
     void *Output;                       /* uint32 per pixel, OutputSize: the frame at time n - 1/2 */
 } PtFrameGenTextures;
 PtStatus pt_frame_gen(PtContext *ctx, const PtFrameGenSettings *settings, const PtFrameGenTextures *textures, uint32_t *generated);
+
+/* Row N15 -- the ray-reconstruction stand-in (DLSS-RR as App::ProcessDLSSRayReconstruction drives it, Source/App.cpp:1654-1671; DESIGN.md
+ * spec S21): the reference's default denoiser is one Streamline feature, a closed SDK that is not vendored, which denoises and upscales
+ * at once.  Here: from the noisy radiance of pt_render_denoiser's mode 1 at RenderSize, with the G-buffer's LinearDepth, MotionVector,
+ * NormalRoughness, DiffuseAlbedo and SpecularAlbedo and mode 1's SpecularHitDistance, to the colour at OutputSize that pt_nis_sharpen,
+ * pt_bloom and pt_tonemap take.  Two launches.  Prepare, per render pixel: the sanitised colour divided by DiffuseAlbedo +
+ * SpecularAlbedo (a miss is left alone), into S17's tone space; the virtual motion of the specular reflection (the world position
+ * rebuilt from LinearDepth as Camera::ReconstructWorldPosition does, pushed along the view ray by the hit distance, through
+ * PreviousWorldToProjection) and its weight.  Resolve, per output pixel whose nearest input pixel is a surface: the history read at the
+ * surface motion and, where there is one, at the virtual motion (bilinear corners rejected by previous depth and previous normal); the
+ * weighted first and second moments of the 5 x 5 input pixels around it, each weight a jitter-aware spatial kernel (wide while the
+ * history is short, S17's Lanczos-2 on the inner 3 x 3 once it is long) times edge-stopping terms in depth, normal and roughness; the
+ * history clipped to mean +- 1.5 sigma and blended as S17 blends; Output = the inverse tone map times the albedo of the nearest input
+ * pixel, alpha from Color.  A pixel whose nearest input pixel is a miss is pt_upscale's pixel, arithmetic unchanged.
+ * On the context's stream (asynchronous), ordered like pt_upscale: after what is already queued there, before whatever the caller
+ * queues next; it adds nothing to pt_get_totals and the render lanes never touch its state.  The context owns the history -- two
+ * alternating slots per output pixel of two float4 (tone-space demodulated colour + accumulated weight, normal + roughness) and a float
+ * (depth) -- and three float4 records per render pixel: allocated on first use, again when a size changes (which waits for the
+ * context's stream only), freed by pt_destroy.  The history restarts on the first call, with Reset, and on any change of a size.
+ * The camera travels by value in PtRayReconstructionSettings (Position and three of PtCamera.Matrices), so the call does not depend
+ * on what pt_set_camera last took.
+ * Not built (spec S21): a learned model, exposure, transparency and particle layers, DLSS-RR's presets, tile and multi-GPU entry points.
+ * PT_ERR_INVALID_ARG: a null argument or buffer; a size outside the ranges of PtRayReconstructionSettings; a Jitter or
+ * MaxHistoryWeight that is not finite or out of range; a Position or matrix entry that is not finite; Color, NormalRoughness or Output
+ * not 16-byte aligned, another buffer not 4-byte aligned; Output overlapping any input. */
+typedef struct PtRayReconstructionTextures { /* DEVICE pointers; the reference's sl::BufferType tags */
+    const void *Color;                  /* float4, RenderSize (pt_render_denoiser mode 1's out: kBufferTypeScalingInputColor) */
+    const void *Depth;                  /* float,  RenderSize (G-buffer LinearDepth, +inf on a miss, as pt_upscale takes it) */
+    const void *MotionVector;           /* float3, RenderSize (.xy render pixels towards the previous frame, .z view depth) */
+    const void *NormalRoughness;        /* float4, RenderSize (kBufferTypeNormalRoughness) */
+    const void *DiffuseAlbedo;          /* float3, RenderSize (kBufferTypeAlbedo) */
+    const void *SpecularAlbedo;         /* float3, RenderSize (kBufferTypeSpecularAlbedo) */
+    const void *SpecularHitDistance;    /* float,  RenderSize (kBufferTypeSpecularHitDistance: cleared to 0 by the caller; 0 or not finite = none) */
+    void *Output;                       /* float4, OutputSize (kBufferTypeScalingOutputColor) */
+} PtRayReconstructionTextures;
+PtStatus pt_ray_reconstruction(PtContext *ctx, const PtRayReconstructionSettings *settings, const PtRayReconstructionTextures *textures);
+/* Test / tooling hook: the history slot the last pt_ray_reconstruction call wrote, to HOST arrays of OutputSize texels (any may be
+ * NULL): history float4 (tone-space demodulated colour, accumulated weight), normal float4 (normal, roughness), depth float.  Waits
+ * for the context's stream.  PT_ERR_STATE: no call has been made yet. */
+PtStatus pt_ray_reconstruction_history(PtContext *ctx, void *history, void *normal, void *depth);
 
 /* Test / tooling hooks. */
 /* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in

@@ -10,6 +10,7 @@
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *   PtUpscaleSettings     (row N11) the XeSSSettings App::ProcessXeSSSuperResolution fills, plus the output size and the history cap, 32 B
  *   PtNisSettings         (row N12) the sl::NISOptions App::ProcessNIS fills (sharpness, hdrMode; mode is always eSharpen), plus the size, 16 B
+ *   PtRayReconstructionSettings (row N15) the sizes, jitter and reset of sl::DLSSDOptions / sl::Constants plus the camera fields the stand-in reads, 240 B
  *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
@@ -221,6 +222,22 @@ typedef struct PtFrameGenSettings {
     uint32_t _pad[2];             /* 24: must be 0 */
 } PtFrameGenSettings;
 
+/* Row N15 (pt_ray_reconstruction, the DLSS-RR stand-in of DESIGN.md spec S21): what App::ProcessDLSSRayReconstruction hands Streamline
+ * in sl::DLSSDOptions and sl::Constants (Source/App.cpp:1654-1671): the sizes, the jitter, the reset flag, and -- by value, in place of
+ * worldToCameraView / cameraViewToWorld and the constants' matrices -- the camera fields the stand-in reads, as PtCamera holds them. */
+typedef struct PtRayReconstructionSettings {
+    uint32_t RenderSize[2];               /*   0: 1..16384 each */
+    uint32_t OutputSize[2];               /*   8: RenderSize <= OutputSize <= 4 * RenderSize per axis, at most 16384 */
+    float Jitter[2];                      /*  16: -PtCamera.Jitter, in render pixels, as PtUpscaleSettings.Jitter; finite, |.| <= 1 */
+    uint32_t Reset;                       /*  24: nonzero = ignore the history (m_resetHistory) */
+    float MaxHistoryWeight;               /*  28: 0 -> 16; finite, 1..256 */
+    float Position[3];                    /*  32: PtCamera.Position */
+    float _pad;                           /*  44 */
+    float ProjectionToView[16];           /*  48: PtCamera.Matrices[6] */
+    float ViewToWorld[16];                /* 112: PtCamera.Matrices[7] */
+    float PreviousWorldToProjection[16];  /* 176: PtCamera.Matrices[2] */
+} PtRayReconstructionSettings;
+
 /* Row N14 (pt_render_sharc, the SHARC stand-in of DESIGN.md spec S20): SHARCSettings as Raytracing::Render(..., SHARC&, SHARCSettings) takes
  * them (Source/MyAppData.h:256-265, Source/Raytracing.ixx:114-148), the cache's accumulation constants and the stages of the call. */
 typedef struct PtSharcSettings {
@@ -270,6 +287,10 @@ static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, O
               && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16
               && offsetof(PtSharcSettings, ResetHistory) == 32 && offsetof(PtSharcSettings, Stages) == 36, "PtSharcSettings layout");
+static_assert(sizeof(PtRayReconstructionSettings) == 240 && offsetof(PtRayReconstructionSettings, Jitter) == 16 && offsetof(PtRayReconstructionSettings, Reset) == 24
+              && offsetof(PtRayReconstructionSettings, MaxHistoryWeight) == 28 && offsetof(PtRayReconstructionSettings, Position) == 32
+              && offsetof(PtRayReconstructionSettings, ProjectionToView) == 48 && offsetof(PtRayReconstructionSettings, ViewToWorld) == 112
+              && offsetof(PtRayReconstructionSettings, PreviousWorldToProjection) == 176, "PtRayReconstructionSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
@@ -290,6 +311,10 @@ _Static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, 
                && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 _Static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16
                && offsetof(PtSharcSettings, ResetHistory) == 32 && offsetof(PtSharcSettings, Stages) == 36, "PtSharcSettings layout");
+_Static_assert(sizeof(PtRayReconstructionSettings) == 240 && offsetof(PtRayReconstructionSettings, Jitter) == 16 && offsetof(PtRayReconstructionSettings, Reset) == 24
+               && offsetof(PtRayReconstructionSettings, MaxHistoryWeight) == 28 && offsetof(PtRayReconstructionSettings, Position) == 32
+               && offsetof(PtRayReconstructionSettings, ProjectionToView) == 48 && offsetof(PtRayReconstructionSettings, ViewToWorld) == 112
+               && offsetof(PtRayReconstructionSettings, PreviousWorldToProjection) == 176, "PtRayReconstructionSettings layout");
 #endif
 
 #endif /* PT_TYPES_H */

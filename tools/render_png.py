@@ -7,10 +7,12 @@ row N10, accumulated; --upscale MODE: --frames frames of a resting camera render
 upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_sharpen, row N12, on the frame at output size, after the
 upscaler when there is one and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
 pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting camera through pt_render_sharc, row N14, the last one tone
-mapped).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendered at the mode's input size through pt_render_gbuffer ->
+pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]"""
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]
+                                        [--ray-reconstruction [performance]]"""
 import argparse
 import os
 import sys
@@ -86,12 +88,19 @@ def main():
     ap.add_argument("--sharc", action="store_true",
                     help="--frames frames of a resting camera through the radiance cache (row N14): pt_render_sharc with the reference's "
                          "SHARC settings (update at a quarter of the size, resolve, query); the last frame, tone mapped (no accumulation)")
+    ap.add_argument("--ray-reconstruction", nargs="?", const="native", default=None, metavar="MODE", choices=list(dxrs_amd.types.UPSCALE_MODES),
+                    help="--frames frames of a resting camera through the reference's default denoiser path (row N15): rendered at the "
+                         "mode's input size (pt_upscale_input_size; native without a mode) with Halton jitter: pt_render_gbuffer -> "
+                         "pt_render_denoiser mode 1 -> pt_ray_reconstruction to --width x --height [-> pt_nis_sharpen with --nis] [-> pt_bloom "
+                         "with --bloom] -> the tone map; the last frame")
     ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--frame-gen applies to the plain path-traced frame")
     if args.sharc and (args.frame_gen or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--sharc applies to the plain path-traced frame")
+    if args.ray_reconstruction and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale):
+        ap.error("--ray-reconstruction is a path of its own: it takes --nis and --bloom only")
     if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
@@ -183,6 +192,37 @@ def main():
         r.synchronize()
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
         print(f"SHARC (pt_render_sharc, {args.frames} frames, {rays} rays in the last) {w}x{h} -> {args.out}")
+        r.close()
+        return
+    if args.ray_reconstruction:
+        iw, ih = dxrs_amd.load_hip().upscale_input_size(t.UPSCALE_MODES[args.ray_reconstruction], w, h)
+        b = {name: torch.zeros((ih, iw, width), dtype=torch.float32, device="cuda") for name, width in t.RAY_RECONSTRUCTION_INPUTS}
+        b["Output"] = accum
+        torch.cuda.synchronize()
+        gs = t.graphics_settings(iw, ih, bounces=args.bounces, spp=args.spp)
+        prev_cam = None
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            cam = host.camera_matrices(iw, ih, jitter_index=k, jitter_count=32, previous=prev_cam)
+            prev_cam = cam
+            r.set_camera(cam)
+            r.set_constants(gs)
+            r.render_gbuffer_device(dict(LinearDepth=b["Depth"].data_ptr(), MotionVector=b["MotionVector"].data_ptr(), NormalRoughness=b["NormalRoughness"].data_ptr(),
+                                         DiffuseAlbedo=b["DiffuseAlbedo"].data_ptr(), SpecularAlbedo=b["SpecularAlbedo"].data_ptr()))
+            r.render_denoiser_device(t.DENOISER_DLSS_RR, b["Color"].data_ptr(), dict(SpecularHitDistance=b["SpecularHitDistance"].data_ptr()))
+            r.ray_reconstruction_device((iw, ih), (w, h), {name: v.data_ptr() for name, v in b.items()}, cam, reset=k == 0)
+            b["SpecularHitDistance"].zero_()  # cleared by the caller, after the call that read it
+        hdr = accum
+        if args.nis is not None:
+            r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
+            hdr = frame
+        if args.bloom is not None:
+            r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"ray reconstruction {args.ray_reconstruction} (pt_ray_reconstruction, {args.frames} frames) {iw}x{ih} -> {w}x{h} -> {args.out}")
         r.close()
         return
     if args.upscale:
