@@ -118,6 +118,21 @@ class PtRestirDiTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in RESTIR_DI_TEXTURES]
 
 
+# Row N16 (pt_restir_di_sampled): the local-light sampling mode and the sizes of the presampled structures; 0 = the library's default
+LIGHT_SAMPLING_UNIFORM, LIGHT_SAMPLING_POWER_RIS, LIGHT_SAMPLING_REGIR_RIS = 0, 1, 2
+LIGHT_RIS_ENTRY_DTYPE = np.dtype([("light", "<u4"), ("inv_pdf", "<f4")])  # light = 0xFFFFFFFF: the entry carries nothing
+
+
+class PtLightSamplingSettings(C.Structure):
+    _fields_ = [("Mode", C.c_uint32), ("TileSize", C.c_uint32), ("TileCount", C.c_uint32), ("ReGIRGridSize", C.c_uint32),
+                ("ReGIRLightsPerCell", C.c_uint32), ("ReGIRBuildSamples", C.c_uint32), ("ReGIRCellSize", C.c_float), ("_pad", C.c_uint32)]
+
+
+def light_sampling_settings(mode=0, tile_size=0, tile_count=0, grid_size=0, lights_per_cell=0, build_samples=0, cell_size=0.0):
+    return PtLightSamplingSettings(Mode=mode, TileSize=tile_size, TileCount=tile_count, ReGIRGridSize=grid_size, ReGIRLightsPerCell=lights_per_cell,
+                                   ReGIRBuildSamples=build_samples, ReGIRCellSize=cell_size)
+
+
 # Row N14 (pt_render_sharc, the SHARC stand-in): SHARCSettings plus the cache's accumulation constants and the stages of a call
 SHARC_UPDATE, SHARC_RESOLVE, SHARC_QUERY = 1, 2, 4
 SHARC_VOXEL_DTYPE = np.dtype([("sum", "<u4", (3,)), ("w", "<u4")])  # w = samples | frames << 16 | stale << 24

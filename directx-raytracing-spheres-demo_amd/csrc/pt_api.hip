@@ -19,6 +19,7 @@
 #include "pt_context.h"
 #include "pt_beam_cache.h"
 #include "pt_restir.h"
+#include "pt_lightris.h"
 #include "pt_sharc.h"
 
 namespace {
@@ -1293,6 +1294,8 @@ void pt_destroy(PtContext* c)
     free_dev(c->d_bloom);
     for (History* H : { &c->dn, &c->up, &c->fg, &c->rr }) free_dev(H->mem);
     free_dev(c->d_ri);
+    free_dev(c->d_lr_pyramid);
+    free_dev(c->d_lr_ris);
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     free_dev(c->d_sh);
     if (c->ev_sh) (void)hipEventDestroy(c->ev_sh);
@@ -1958,20 +1961,43 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
 // the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
 constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
 
-PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t)
+// The body of pt_restir_di and pt_restir_di_sampled (row N16, spec S22); ls null or Mode 0 = Uniform: nothing is presampled.
+static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t)
 {
     if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: null pointer");
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null pointer");
     const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
-    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: RenderSize must be in [1, 16384]");
-    if (s->InitialSamples > kRiMaxInitialSamples) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: InitialSamples must be at most 32");
-    if (s->SpatialSamples > kRiMaxSpatialSamples) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: SpatialSamples must be at most 32");
-    if (s->EnableTemporal > 1 || s->EnableSpatial > 1) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: EnableTemporal and EnableSpatial must be 0 or 1");
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": RenderSize must be in [1, 16384]");
+    if (s->InitialSamples > kRiMaxInitialSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": InitialSamples must be at most 32");
+    if (s->SpatialSamples > kRiMaxSpatialSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialSamples must be at most 32");
+    if (s->EnableTemporal > 1 || s->EnableSpatial > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": EnableTemporal and EnableSpatial must be 0 or 1");
     for (const uint32_t mode : { s->TemporalBiasCorrection, s->SpatialBiasCorrection }) {
-        if (mode == kRiBiasPairwise) return fail(c, PT_ERR_UNSUPPORTED, "pt_restir_di: pairwise bias correction (2) is not built");
-        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
+        if (mode == kRiBiasPairwise) return fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": pairwise bias correction (2) is not built");
+        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
     }
-    if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di: SpatialRadius must be finite and >= 0");
+    if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialRadius must be finite and >= 0");
+    // the candidates' source (spec S22): defaults applied, ranges checked
+    const uint32_t mode = ls ? ls->Mode : kLrUniform;
+    LrGrid lg{};
+    if (mode != kLrUniform) {
+        if (mode > kLrRegirRis) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": Mode must be 0 (Uniform), 1 (Power_RIS) or 2 (ReGIR_RIS)");
+        if (ls->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": PtLightSamplingSettings._pad must be 0");
+        if (ls->TileSize > kLrMaxTileSize) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": TileSize must be at most 8192");
+        if (ls->TileCount > kLrMaxTileCount) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": TileCount must be at most 1024");
+        if (ls->ReGIRGridSize > kLrMaxGrid) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRGridSize must be at most 32");
+        if (ls->ReGIRLightsPerCell > kLrMaxLightsPerCell) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRLightsPerCell must be at most 1024");
+        if (ls->ReGIRBuildSamples > kLrMaxBuildSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRBuildSamples must be at most 32");
+        if (ls->ReGIRCellSize != 0.0f && !(std::isfinite(ls->ReGIRCellSize) && ls->ReGIRCellSize >= kLrMinCellSize && ls->ReGIRCellSize <= kLrMaxCellSize))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRCellSize must be 0 or finite and in [0.1, 10]");
+        lg.tile_size = ls->TileSize ? ls->TileSize : kLrDefaultTileSize;
+        lg.tile_count = ls->TileCount ? ls->TileCount : kLrDefaultTileCount;
+        lg.grid = ls->ReGIRGridSize ? ls->ReGIRGridSize : kLrDefaultGrid;
+        lg.lights_per_cell = ls->ReGIRLightsPerCell ? ls->ReGIRLightsPerCell : kLrDefaultLightsPerCell;
+        lg.build_samples = ls->ReGIRBuildSamples ? ls->ReGIRBuildSamples : kLrDefaultBuildSamples;
+        lg.cell_size = ls->ReGIRCellSize != 0.0f ? ls->ReGIRCellSize : kLrDefaultCellSize;
+        if ((uint64_t)lg.tile_size * lg.tile_count + (uint64_t)lg.grid * lg.grid * lg.grid * lg.lights_per_cell > kLrMaxEntries)
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": the Power_RIS and ReGIR segments together hold more than 2^24 entries");
+    }
     const uint64_t n = (uint64_t)w * h;
     // the eight inputs, then the two outputs
     const BufferUse use[10] = {
@@ -1981,7 +2007,7 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
         {t->IOR, n * 4, 4, false, true, "IOR"}, {t->Transmission, n * 4, 4, false, true, "Transmission"},
         {t->Diffuse, n * 16, 16, true, true, "Diffuse"}, {t->Specular, n * 16, 16, true, true, "Specular"},
     };
-    PtStatus st = buffers_ok(c, "pt_restir_di", use, 10);
+    PtStatus st = buffers_ok(c, who, use, 10);
     if (st != PT_OK) return st;
     if ((st = validate_frame(c)) != PT_OK) return st;
     if ((st = check_environment(c)) != PT_OK) return st;
@@ -2013,7 +2039,7 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
         free_dev(c->d_ri);
         c->ri_valid = false;
         void* mem = nullptr;
-        if (hipMalloc(&mem, 2u * n * kRiSlotBytesPerPixel) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, "pt_restir_di: history allocation failed"); }
+        if (hipMalloc(&mem, 2u * n * kRiSlotBytesPerPixel) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": history allocation failed"); }
         c->d_ri = static_cast<float4*>(mem);
         c->ri_w = w; c->ri_h = h;
         restart = true;
@@ -2054,16 +2080,58 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
     const SceneView sv = make_scene_view(c, &L);
     const uint32_t grid = side_pass_grid(c, pm.n_slots);
     st = PT_OK;
+    // Presampling (spec S22): pyramid -> Power_RIS -> ReGIR on the lane's stream, in front of launch 1.  The previous call's launch 1 read
+    // the two buffers: this call is ordered after it by what orders the history above -- the stream itself on a one-lane context, the
+    // ev_ri wait otherwise, and a host-side wait where the history was reallocated (a first call has no predecessor) -- so the existing
+    // condition suffices.  The kernels read the lane's own spheres (sv.sph): an emitter moved by pt_update_spheres is seen.
+    LrView lr{};
+    if (mode != kLrUniform) {
+        const uint32_t lv = lr_levels(c->n_lights), n_pyr = lr_pyramid_floats(lv);
+        const uint32_t n_power = lg.tile_size * lg.tile_count;
+        const uint32_t n_ris = n_power + (mode == kLrRegirRis ? lg.grid * lg.grid * lg.grid * lg.lights_per_cell : 0u);
+        if (n_pyr > c->lr_cap_pyramid || n_ris > c->lr_cap_ris) {
+            PT_HIP(c, hipEventSynchronize(c->ev_ri));  // (the previous call, on whichever lane, may still read the old buffers; a no-op before the first record)
+            if (n_pyr > c->lr_cap_pyramid) {
+                free_dev(c->d_lr_pyramid);
+                c->lr_cap_pyramid = 0; c->lr_n_pyramid = 0;
+                if (hipMalloc(reinterpret_cast<void**>(&c->d_lr_pyramid), (size_t)n_pyr * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": pyramid allocation failed"); }
+                c->lr_cap_pyramid = n_pyr;
+            }
+            if (n_ris > c->lr_cap_ris) {
+                free_dev(c->d_lr_ris);
+                c->lr_cap_ris = 0; c->lr_n_ris = 0;
+                if (hipMalloc(&c->d_lr_ris, (size_t)n_ris * sizeof(LrEntry)) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": RIS buffer allocation failed"); }
+                c->lr_cap_ris = n_ris;
+            }
+        }
+        lg.cam = P.cam_pos;
+        LrBuild lb{};
+        lb.sph = sv.sph; lb.mats = sv.mats; lb.lights = sv.lights; lb.n_lights = sv.n_lights; lb.frame_index = s->FrameIndex;
+        lb.pyramid = c->d_lr_pyramid;
+        lb.ris = static_cast<LrEntry*>(c->d_lr_ris);
+        lb.grid = lg;
+        EventPair* ev = c->profiling ? next_events(c, 3) : nullptr;  // pt_get_profile: the presampling launches, as one interval, under ms_tail
+        if (ev) (void)hipEventRecord(ev->a, L.stream);
+        hipError_t e = launch_lr_pyramid(lb, L.stream);
+        if (e == hipSuccess) e = launch_lr_power(lb, L.stream);
+        if (e == hipSuccess && mode == kLrRegirRis) e = launch_lr_regir(lb, L.stream);
+        if (ev) (void)hipEventRecord(ev->b, L.stream);
+        if (e != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": presampling launch: " + hipGetErrorString(e));
+        c->lr_n_pyramid = e == hipSuccess ? n_pyr : 0u;  // (pt_light_ris_download returns only what was built whole)
+        c->lr_n_ris = e == hipSuccess ? n_ris : 0u;
+        lr.ris = lb.ris;
+        lr.tile_size = lg.tile_size; lr.tile_count = lg.tile_count; lr.grid = lg.grid; lr.lights_per_cell = lg.lights_per_cell; lr.cell_size = lg.cell_size;
+    }
     for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
         EventPair* ev = c->profiling ? next_events(c, pass == 0 ? 1 : 2) : nullptr;  // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
         if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = launch_restir_pass(pass, sv, pm, b, P, grid, L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: launch: ") + hipGetErrorString(e));
+        if (const hipError_t e = launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(e));
         if (ev) (void)hipEventRecord(ev->b, L.stream);
     }
     const hipError_t e0 = hipEventRecord(c->ev_ri, L.stream);
-    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_restir_di: history event: ") + hipGetErrorString(e0));
-    st = publish_lane_to_caller(c, L, "pt_restir_di", st);
+    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": history event: " + hipGetErrorString(e0));
+    st = publish_lane_to_caller(c, L, who, st);
     if (st == PT_OK) {
         c->ri_slot = cur;
         c->ri_scene = c->set_scene_calls;
@@ -2072,6 +2140,43 @@ PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirD
         c->ri_valid = false;
     }
     return st;
+}
+
+PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, t); }
+
+PtStatus pt_restir_di_sampled(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t)
+{
+    return restir_di_common(c, "pt_restir_di_sampled", s, ls, t);
+}
+
+PtStatus pt_restir_di_history(PtContext* c, uint32_t which, void* planes, void* transmission)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (which > 1u || !planes || !transmission) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di_history: which must be 0 or 1 and the arrays non-null");
+    if (!c->ri_valid || !c->d_ri) return fail(c, PT_ERR_STATE, "pt_restir_di_history: no pt_restir_di call has left a history");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipEventSynchronize(c->ev_ri));
+    const uint64_t n = (uint64_t)c->ri_w * c->ri_h;
+    const uint32_t slot = c->ri_slot ^ which;
+    PT_HIP(c, hipMemcpy(planes, c->d_ri + (uint64_t)slot * 6u * n, 6u * n * sizeof(float4), hipMemcpyDeviceToHost));
+    PT_HIP(c, hipMemcpy(transmission, reinterpret_cast<const float*>(c->d_ri + 12u * n) + (uint64_t)slot * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+PtStatus pt_light_ris_download(PtContext* c, float* pyramid, uint32_t* n_pyramid, uint32_t* ris, uint32_t* n_entries)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!n_pyramid || !n_entries) return fail(c, PT_ERR_INVALID_ARG, "pt_light_ris_download: null count");
+    if (!c->lr_n_pyramid || !c->d_lr_pyramid || !c->d_lr_ris) return fail(c, PT_ERR_STATE, "pt_light_ris_download: no pt_restir_di_sampled call with a presampling mode has been made");
+    const uint32_t cap_p = *n_pyramid, cap_r = *n_entries;
+    *n_pyramid = c->lr_n_pyramid;
+    *n_entries = c->lr_n_ris;
+    if ((pyramid && cap_p < c->lr_n_pyramid) || (ris && cap_r < c->lr_n_ris)) return fail(c, PT_ERR_INVALID_ARG, "pt_light_ris_download: capacity below the count");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipEventSynchronize(c->ev_ri));
+    if (pyramid) PT_HIP(c, hipMemcpy(pyramid, c->d_lr_pyramid, (size_t)c->lr_n_pyramid * sizeof(float), hipMemcpyDeviceToHost));
+    if (ris) PT_HIP(c, hipMemcpy(ris, c->d_lr_ris, (size_t)c->lr_n_ris * sizeof(LrEntry), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 // Row N14 -- the frame through the radiance cache (DESIGN.md spec S20): up to three stages on the lane of the next render call, ordered

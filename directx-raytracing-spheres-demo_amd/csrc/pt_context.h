@@ -199,6 +199,12 @@ struct PtContext {
     uint64_t ri_scene = 0, set_scene_calls = 0;
     bool ri_valid = false;
     hipEvent_t ev_ri = nullptr;
+    // pt_restir_di_sampled's presampled structures (row N16): the power pyramid and the RIS buffer (Power segment, then ReGIR segment),
+    // rebuilt by every call with a presampling mode, grown on demand, protected by ev_ri like the history; lr_n_*: what the last such
+    // call built (pt_light_ris_download)
+    float* d_lr_pyramid = nullptr;
+    void* d_lr_ris = nullptr;
+    uint32_t lr_cap_pyramid = 0, lr_cap_ris = 0, lr_n_pyramid = 0, lr_n_ris = 0;
     // pt_render_sharc's cache (row N14): `sh_capacity` keys and two voxel arrays in one allocation (sh_accum = this frame's accumulators,
     // sh_resolved = the previous frame's resolved voxels: they swap at every resolve), two device counters (rays, failed inserts),
     // `sh_scene` = the pt_set_scene count the cache was filled under, `ev_sh` = the last call's launches have finished

@@ -9,12 +9,16 @@
 // reused sample is re-aimed from the surface that reuses it.  Target function: luminance((Le_j (f_d + f_s)) inv_pdf), Le_j the
 // emitter's untextured radiance, without visibility.
 //
-// Out of scope: ReGIR and Power_RIS presampling; BRDF and environment candidates; the boiling filter; checkerboard rendering;
+// The initial candidates come from one of three sources (row N16, spec S22, pt_lightris.h): uniformly from the emitter list (S16 as
+// it was; pt_restir_di), from a Power_RIS tile, or from a ReGIR cell with the Power_RIS tile as its fallback (pt_restir_di_sampled).
+//
+// Out of scope: ReGIR's onion mode; BRDF and environment candidates; the boiling filter; checkerboard rendering;
 // visibility reuse; pairwise MIS (bias mode 2); the DLSS-RR SpecularHitDistance write; dropping pt_render_with_di's whole-stream
 // wait for buffers this pass produced.
 #pragma once
 
 #include "pt_light.h"
+#include "pt_lightris.h"
 #include "pt_texture.h"
 
 namespace pt {
@@ -78,6 +82,7 @@ struct RiScene {
     const float4* mats;       // PtMaterial as 4 float4
     const uint32_t* lights;   // ids of the emissive spheres
     uint32_t n_lights;
+    LrView lr;                // the presampled candidates of spec S22 (read by ri_initial<kLrPowerRis / kLrRegirRis> only; all zero: none)
 };
 
 struct RiParams {
@@ -254,19 +259,50 @@ PT_HD bool ri_stream(float& w_sum, float w, float rnd)
     return w > 0.0f && rnd * w_sum <= w;
 }
 
-// ---- initial sampling (DIInitialSampling.hlsl): InitialSamples uniform candidates through RIS, one visibility ray
-template <typename TraceFn>
+// ---- initial sampling (DIInitialSampling.hlsl): InitialSamples candidates through RIS, one visibility ray.  kMode = the candidates'
+// source (spec S22): uniform over the emitter list (source weight n_lights), an entry of the pixel block's Power_RIS tile, or an entry
+// of the ReGIR cell of the jittered surface point (outside the grid: the Power_RIS tile).  The per-candidate draws are (u0, u1, u2, rnd)
+// in every mode; an invalid entry weighs 0 and still counts in M.
+template <uint32_t kMode = kLrUniform, typename TraceFn>
 PT_HD RiReservoir ri_initial(const RiScene& sc, const RiParams& p, const RiSurface& s, uint32_t px, uint32_t py, TraceFn&& trace)
 {
     RiReservoir r = ri_empty_reservoir();
     float w_sum = 0.0f;
     uint32_t rng = rng_init(px, py, p.frame_index ^ kRiInitialRngSalt);
     const float nl = (float)sc.n_lights;
+    const LrEntry* src = nullptr;  // the tile or cell the pixel's candidates come from
+    uint32_t src_n = 0u;
+    if (kMode != kLrUniform) {
+        bool in_cell = false;
+        if (kMode == kLrRegirRis) {
+            const float x0 = rng_float(rng), x1 = rng_float(rng), x2 = rng_float(rng);
+            uint32_t cell = 0u;
+            in_cell = lr_cell_of(s.P, make_f3(x0, x1, x2), p.cam_pos, sc.lr.grid, sc.lr.cell_size, cell);
+            if (in_cell) {
+                src = sc.lr.ris + ((size_t)sc.lr.tile_size * sc.lr.tile_count + (size_t)cell * sc.lr.lights_per_cell);
+                src_n = sc.lr.lights_per_cell;
+            }
+        }
+        if (!in_cell) {
+            src = sc.lr.ris + (size_t)lr_pixel_tile(px, py, p.frame_index, sc.lr.tile_count) * sc.lr.tile_size;
+            src_n = sc.lr.tile_size;
+        }
+    }
     for (uint32_t i = 0; i < p.initial_samples; i++) {
         const float u0 = rng_float(rng), u1 = rng_float(rng), u2 = rng_float(rng), rnd = rng_float(rng);
-        const uint32_t j = pick_light(u0, sc.n_lights);
-        const RiShade e = ri_shade(sc, s, j, u1, u2);
-        if (ri_stream(w_sum, e.p_hat * nl, rnd)) { r.light = j; r.u1 = u1; r.u2 = u2; r.p_hat = e.p_hat; }
+        if (kMode == kLrUniform) {
+            const uint32_t j = pick_light(u0, sc.n_lights);
+            const RiShade e = ri_shade(sc, s, j, u1, u2);
+            if (ri_stream(w_sum, e.p_hat * nl, rnd)) { r.light = j; r.u1 = u1; r.u2 = u2; r.p_hat = e.p_hat; }
+        } else {
+            const LrEntry c = src[pick_light(u0, src_n)];
+            float w = 0.0f, p_hat = 0.0f;
+            if (c.light != kLrInvalid) {
+                p_hat = ri_shade(sc, s, c.light, u1, u2).p_hat;
+                w = p_hat * c.inv_pdf;
+            }
+            if (ri_stream(w_sum, w, rnd)) { r.light = c.light; r.u1 = u1; r.u2 = u2; r.p_hat = p_hat; }
+        }
     }
     r.M = (float)p.initial_samples;
     r.W = r.p_hat > 0.0f ? w_sum / (r.M * r.p_hat) : 0.0f;
@@ -432,7 +468,7 @@ PT_HD bool ri_final(const RiScene& sc, const RiSurface& s, const RiReservoir& r,
 
 // ---- what one lane of each launch does
 // launch 1: the pixel's surface record from the G-buffer, initial sampling, temporal resampling -> this call's slot
-template <typename TraceFn>
+template <uint32_t kMode = kLrUniform, typename TraceFn>
 PT_HD void ri_pass1_px(const RiBuffers& b, const RiScene& sc, const RiParams& p, uint32_t px, uint32_t py, TraceFn&& trace)
 {
     const uint32_t i = py * b.w + px;
@@ -445,7 +481,7 @@ PT_HD void ri_pass1_px(const RiBuffers& b, const RiScene& sc, const RiParams& p,
     }
     ri_store_record(b.rec, b.rec_t, i, rec);
     const RiSurface s = ri_surface(rec, p.cam_pos);
-    RiReservoir r = ri_initial(sc, p, s, px, py, trace);
+    RiReservoir r = ri_initial<kMode>(sc, p, s, px, py, trace);
     const f3 mv = make_f3(b.motion_vector[3u * i], b.motion_vector[3u * i + 1u], b.motion_vector[3u * i + 2u]);
     r = ri_temporal(b, sc, p, s, r, px, py, mv, trace);
     ri_store_reservoir(b.res, i, r);
@@ -467,8 +503,10 @@ PT_HD void ri_pass2_px(const RiBuffers& b, const RiScene& sc, const RiParams& p,
 #if defined(__HIPCC__)
 struct SceneView;
 struct PixelMap;
-// pass 0: launch 1 (initial + temporal), pass 1: launch 2 (spatial + final), over the pixels of pm (mode 0, the whole RenderSize)
-hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream);
+// pass 0: launch 1 (initial + temporal), pass 1: launch 2 (spatial + final), over the pixels of pm (mode 0, the whole RenderSize);
+// mode, lr: the source of launch 1's candidates (kLrUniform: lr is not read)
+hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t mode, const LrView& lr,
+                              uint32_t grid, hipStream_t stream);
 #endif
 
 }  // namespace pt

@@ -11,9 +11,10 @@ namespace pt {
 
 namespace {
 
-// kPass2 = false: launch 1 (kTex unused: nothing is shaded with maps); kAlpha: the per-crossing alpha test of S10
-template <bool kPass2, bool kLds, typename StackT, bool kTex, bool kAlpha>
-__global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, PixelMap pm, RiBuffers b, RiParams p)
+// kPass2 = false: launch 1 (kTex unused: nothing is shaded with maps); kAlpha: the per-crossing alpha test of S10; kMode: the source of
+// launch 1's candidates (spec S22; launch 2 has the Uniform form only and reads no `lr`)
+template <bool kPass2, bool kLds, typename StackT, bool kTex, bool kAlpha, uint32_t kMode>
+__global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, PixelMap pm, RiBuffers b, RiParams p, LrView lr)
 {
     extern __shared__ float4 smem[];
     const float4* nodes = sv.nodes;
@@ -32,44 +33,54 @@ __global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, 
     stack += threadIdx.x;
     RiScene sc;
     sc.sph = sv.sph; sc.mats = sv.mats; sc.lights = sv.lights; sc.n_lights = sv.n_lights;
+    sc.lr = lr;
     const uint32_t stride = blockDim.x;
     auto trace = [&](f3 o, f3 d, float& t, uint32_t& id) { closest_hit_any<kLds, StackT, kAlpha>(sv, nodes, sph, ids, o, d, 0.0f, kInf, stack, stride, t, id); };
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
         if (!pr.valid) continue;
         if (kPass2) ri_pass2_px(b, sc, p, pr.px, pr.py, trace, [&](uint32_t id, f3 o, f3 d, float t) { return hit_material<kTex>(sv, id, o, d, t, false).emission; });
-        else ri_pass1_px(b, sc, p, pr.px, pr.py, trace);
+        else ri_pass1_px<kMode>(b, sc, p, pr.px, pr.py, trace);
     }
 }
 
-template <bool kPass2, bool kTex, bool kAlpha>
-hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream)
+template <bool kPass2, bool kTex, bool kAlpha, uint32_t kMode = kLrUniform>
+hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, const LrView& lr, uint32_t grid, hipStream_t stream)
 {
     const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
     const uint32_t threads = traverse_threads(lds_scene);
     const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)restir_kernel<kPass2, true, uint16_t, kTex, kAlpha> : (const void*)restir_kernel<kPass2, true, uint32_t, kTex, kAlpha>)
-                               : (small ? (const void*)restir_kernel<kPass2, false, uint16_t, kTex, kAlpha> : (const void*)restir_kernel<kPass2, false, uint32_t, kTex, kAlpha>);
+    const void* fn = lds_scene ? (small ? (const void*)restir_kernel<kPass2, true, uint16_t, kTex, kAlpha, kMode> : (const void*)restir_kernel<kPass2, true, uint32_t, kTex, kAlpha, kMode>)
+                               : (small ? (const void*)restir_kernel<kPass2, false, uint16_t, kTex, kAlpha, kMode> : (const void*)restir_kernel<kPass2, false, uint32_t, kTex, kAlpha, kMode>);
     if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (lds_scene) {
-        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
-        else hipLaunchKernelGGL((restir_kernel<kPass2, true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, true, uint16_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
+        else hipLaunchKernelGGL((restir_kernel<kPass2, true, uint32_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
     } else {
-        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
-        else hipLaunchKernelGGL((restir_kernel<kPass2, false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p);
+        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, false, uint16_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
+        else hipLaunchKernelGGL((restir_kernel<kPass2, false, uint32_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
     }
     return hipGetLastError();
 }
 
+template <bool kAlpha>
+hipError_t launch_pass1(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t mode, const LrView& lr, uint32_t grid, hipStream_t stream)
+{
+    if (mode == kLrPowerRis) return launch_t<false, false, kAlpha, kLrPowerRis>(sv, pm, b, p, lr, grid, stream);
+    if (mode == kLrRegirRis) return launch_t<false, false, kAlpha, kLrRegirRis>(sv, pm, b, p, lr, grid, stream);
+    return launch_t<false, false, kAlpha>(sv, pm, b, p, LrView{}, grid, stream);
+}
+
 }  // namespace
 
-hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t grid, hipStream_t stream)
+hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t mode, const LrView& lr,
+                              uint32_t grid, hipStream_t stream)
 {
     // the alpha-tested walk only where some sphere's hits are tested against a map; the textured emission only where textures exist
     const bool alpha = sv.tex_maps && sv.alpha_tested;
-    if (pass == 0) return alpha ? launch_t<false, false, true>(sv, pm, b, p, grid, stream) : launch_t<false, false, false>(sv, pm, b, p, grid, stream);
-    if (!sv.tex_maps) return launch_t<true, false, false>(sv, pm, b, p, grid, stream);
-    return alpha ? launch_t<true, true, true>(sv, pm, b, p, grid, stream) : launch_t<true, true, false>(sv, pm, b, p, grid, stream);
+    if (pass == 0) return alpha ? launch_pass1<true>(sv, pm, b, p, mode, lr, grid, stream) : launch_pass1<false>(sv, pm, b, p, mode, lr, grid, stream);
+    if (!sv.tex_maps) return launch_t<true, false, false>(sv, pm, b, p, LrView{}, grid, stream);
+    return alpha ? launch_t<true, true, true>(sv, pm, b, p, LrView{}, grid, stream) : launch_t<true, true, false>(sv, pm, b, p, LrView{}, grid, stream);
 }
 
 }  // namespace pt

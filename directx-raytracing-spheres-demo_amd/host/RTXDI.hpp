@@ -2,7 +2,8 @@
 // RTXDI::SetConstants, then RTXDI::Render between the G-buffer pass and the frame) over pt_restir_di (row N10, DESIGN.md spec S16), a
 // stand-in for the RTXDI SDK, which the reference does not vendor.  The settings are the subset of ReSTIRDI_Parameters
 // (Source/MyAppData.h:190-250) the stand-in reads; resources are DEVICE pointers of RenderSize texels (the layouts of
-// PtRestirDiTextures) instead of D3D12 textures.
+// PtRestirDiTextures) instead of D3D12 textures.  With a local-light sampling mode other than Uniform the passes run through
+// pt_restir_di_sampled (row N16, spec S22: Power_RIS tiles and the ReGIR grid, MyAppData.h:194-218).
 #pragma once
 
 #include <array>
@@ -15,8 +16,16 @@ namespace dxrs {
 
 enum class ReSTIRDI_BiasCorrectionMode : uint32_t { Off = 0, Basic = 1, Pairwise = 2, Raytraced = 3 };
 
+enum class ReSTIRDI_LocalLightSamplingMode : uint32_t { Uniform = 0, Power_RIS = 1, ReGIR_RIS = 2 };
+
 struct ReSTIRDISettings {  // MyAppData.h:190-250 (IsEnabled = true is the reference's default frame)
-    struct { uint32_t LocalLightSamples = 8; } InitialSampling;
+    struct {  // MyAppData.h:194-208: Cell.Size in [0.1, 10], BuildSamples at most 32 (the cell visualisation is not built)
+        struct { float Size = 1; } Cell;
+        uint32_t BuildSamples = 8;
+    } ReGIR;
+    // LocalLightMode: the reference's default is ReGIR_RIS (MyAppData.h:212); this mirror's stays Uniform, so that a host written
+    // against row N10 keeps the frames it had
+    struct { ReSTIRDI_LocalLightSamplingMode LocalLightMode = ReSTIRDI_LocalLightSamplingMode::Uniform; uint32_t LocalLightSamples = 8; } InitialSampling;
     struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t MaxHistoryLength = 20; } TemporalResampling;
     struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t Samples = 1; float Radius = 32; } SpatialResampling;
 };
@@ -50,6 +59,10 @@ public:
         m_settings.SpatialBiasCorrection = static_cast<uint32_t>(settings.SpatialResampling.BiasCorrectionMode);
         m_settings.SpatialSamples = settings.SpatialResampling.Samples;
         m_settings.SpatialRadius = settings.SpatialResampling.Radius;
+        m_sampling = PtLightSamplingSettings{};  // (tile and grid sizes: the library's defaults)
+        m_sampling.Mode = static_cast<uint32_t>(settings.InitialSampling.LocalLightMode);
+        m_sampling.ReGIRBuildSamples = settings.ReGIR.BuildSamples;
+        m_sampling.ReGIRCellSize = settings.ReGIR.Cell.Size;
     }
 
     // RTXDI::Render: the DI passes of the frame the next render call renders, asynchronous
@@ -58,12 +71,14 @@ public:
         const PtRestirDiTextures t{ GPUBuffers.Position, GPUBuffers.GeometricNormal, GPUBuffers.LinearDepth, GPUBuffers.MotionVector,
                                     GPUBuffers.BaseColorMetalness, GPUBuffers.NormalRoughness, GPUBuffers.IOR, GPUBuffers.Transmission,
                                     GPUBuffers.Diffuse, GPUBuffers.Specular };
-        ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
+        if (m_sampling.Mode == PT_LIGHT_SAMPLING_UNIFORM) ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
+        else ThrowIfFailed(pt_restir_di_sampled(m_ctx, &m_settings, &m_sampling, &t), m_ctx, "pt_restir_di_sampled");
     }
 
 private:
     PtContext* m_ctx;
     PtRestirDiSettings m_settings{};
+    PtLightSamplingSettings m_sampling{};
 };
 
 }  // namespace dxrs

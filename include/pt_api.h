@@ -23,6 +23,7 @@
  *                            Source/App.cpp:1584-1638
  *   pt_restir_di             RTXDI::SetConstants / Render: the DI passes (a stand-in for RTXDI, spec S16)   Source/App.cpp:1187-1227,
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
+ *   pt_restir_di_sampled     the same with Power_RIS / ReGIR_RIS local-light presampling (spec S22)                 Source/RTXDI.ixx:209-226
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
@@ -372,7 +373,8 @@ PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, co
  * The context owns the history -- two alternating slots of a 68-byte surface record and a 32-byte reservoir per pixel -- allocated on
  * first use and freed by pt_destroy.  The history restarts on the first call, with ResetHistory, when RenderSize changes and after
  * pt_set_scene (emitter indices change); spheres moved by pt_update_spheres keep it.
- * Not built (spec S16): ReGIR and Power_RIS presampling, BRDF and environment candidates, the boiling filter, checkerboard rendering,
+ * The candidates are uniform over the emitter list; pt_restir_di_sampled below draws them from presampled structures (row N16).
+ * Not built (spec S16): BRDF and environment candidates, the boiling filter, checkerboard rendering,
  * visibility reuse, pairwise MIS, the DLSS-RR SpecularHitDistance write.
  * PT_ERR_INVALID_ARG: a null argument; a missing buffer; a float4 buffer not 16-byte aligned, GeometricNormal not 8-byte, another not
  * 4-byte; an output overlapping an input or the other output; a value outside the ranges of PtRestirDiSettings.  PT_ERR_UNSUPPORTED:
@@ -389,6 +391,34 @@ typedef struct PtRestirDiTextures {     /* DEVICE pointers; inputs are what RAB_
     void *Diffuse, *Specular;           /* float4: outputs */
 } PtRestirDiTextures;
 PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const PtRestirDiTextures *textures);
+
+/* Row N16 -- pt_restir_di with the reference's three local-light sampling modes (ReSTIRDI_LocalLightSamplingMode; DESIGN.md spec S22): a
+ * stand-in for the passes the reference runs in front of the DI passes (LightPreparation.hlsl, MipmapGeneration.hlsl,
+ * LocalLightPresampling.hlsl, ReGIRPresampling.hlsl; RTXDI::Render, Source/RTXDI.ixx:209-226).  Before launch 1 the call rebuilds, from the
+ * spheres the lane's frame sees (pt_update_spheres included), a power pyramid over the emitter list, a Power_RIS tile buffer
+ * (TileCount x TileSize entries) and, in ReGIR_RIS mode, a grid of ReGIRGridSize^3 cells of ReGIRCellSize around Camera.Position with
+ * ReGIRLightsPerCell entries each; launch 1 then draws its InitialSamples candidates from the pixel block's tile (Power_RIS) or from the
+ * cell of the jittered surface point (ReGIR_RIS; outside the grid: the tile).  Everything after initial sampling is pt_restir_di's.
+ * `sampling` NULL or Mode 0 (Uniform): the call IS pt_restir_di -- the same history slots, restart rules and bits; calls of the two
+ * entry points may alternate on one context and share the history.  Errors, lane, ordering, buffer rotation, profiling slots (plus
+ * the presampling launches, as one interval, under ms_tail) and the "no emitters: success, nothing written" rule: as pt_restir_di.
+ * Not built: ReGIR's onion mode, the cell visualisation, BRDF and environment candidates, the compact-light-info path.
+ * PT_ERR_INVALID_ARG also: a Mode above 2, a size above its range, a cell size that is not finite or outside [0.1, 10], a nonzero _pad,
+ * more than 2^24 entries in the two segments together. */
+PtStatus pt_restir_di_sampled(PtContext *ctx, const PtRestirDiSettings *settings, const PtLightSamplingSettings *sampling, const PtRestirDiTextures *textures);
+
+/* Test hook: a slot of the history pt_restir_di / pt_restir_di_sampled keep, after waiting for the last call: which = 0 the slot the
+ * last call wrote, 1 the slot the call before it wrote.  planes: six planes of RenderSize float4 (the surface record's four, then the
+ * reservoir's two: {emitter bits, u1, u2, W}, {M, p_hat, age bits, 0}); transmission: RenderSize floats.  A pixel without a surface
+ * holds only plane 3 (its depth is +inf); its other words are whatever the slot held before.  PT_ERR_STATE: no call has left a history. */
+PtStatus pt_restir_di_history(PtContext *ctx, uint32_t which, void *planes, void *transmission);
+
+/* Test hook: what the last pt_restir_di_sampled call with a presampling mode built, after waiting for it.  On entry *n_pyramid and
+ * *n_entries hold the capacities of `pyramid` (floats) and `ris` (entries of two uint32: emitter index or 0xFFFFFFFF, bits of
+ * 1 / source pdf); on return the counts.  pyramid: every level, leaves first (4^Lv, ..., 4, 1 floats, each level in Z-curve order);
+ * ris: the Power_RIS segment, then the ReGIR segment (ReGIR_RIS mode only).  A null array is not filled (its count still is).
+ * PT_ERR_STATE: no such call has been made; PT_ERR_INVALID_ARG: a null count or a capacity below the count. */
+PtStatus pt_light_ris_download(PtContext *ctx, float *pyramid, uint32_t *n_pyramid, uint32_t *ris, uint32_t *n_entries);
 
 /* Row N14 -- the frame through the radiance cache (Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings), Source/Raytracing.ixx:114-148;
  * DESIGN.md spec S20): a stand-in for the SHARC library, which the reference does not vendor.  Three stages on the lane of the next render

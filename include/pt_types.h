@@ -14,6 +14,7 @@
  *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
+ *   PtLightSamplingSettings (row N16) the local-light sampling mode and the ReGIR settings (Source/MyAppData.h:194-218), 32 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
@@ -194,6 +195,21 @@ typedef struct PtRestirDiSettings {
     float SpatialRadius;             /* 44: pixels; 0 -> 32; finite and >= 0 (radii above 16384 act as 16384) */
 } PtRestirDiSettings;
 
+/* Row N16 (pt_restir_di_sampled, DESIGN.md spec S22): the local-light sampling mode of ReSTIRDI_LocalLightSamplingMode and the sizes of
+ * the presampled structures (Source/MyAppData.h:194-218; defaults of the RTXDI SDK as recollected).  0 = the default. */
+typedef struct PtLightSamplingSettings {
+    uint32_t Mode;                /*  0: PT_LIGHT_SAMPLING_UNIFORM / _POWER_RIS / _REGIR_RIS (the reference's default is ReGIR_RIS) */
+    uint32_t TileSize;            /*  4: entries of a Power_RIS tile; 0 -> 1024, at most 8192 */
+    uint32_t TileCount;           /*  8: Power_RIS tiles; 0 -> 128, at most 1024 */
+    uint32_t ReGIRGridSize;       /* 12: cells per axis of the cube around the camera; 0 -> 16, at most 32 */
+    uint32_t ReGIRLightsPerCell;  /* 16: 0 -> 512, at most 1024 */
+    uint32_t ReGIRBuildSamples;   /* 20: 0 -> 8, at most 32 */
+    float ReGIRCellSize;          /* 24: 0 -> 1; otherwise finite, 0.1 .. 10 */
+    uint32_t _pad;                /* 28: must be 0 */
+} PtLightSamplingSettings;
+
+enum { PT_LIGHT_SAMPLING_UNIFORM = 0, PT_LIGHT_SAMPLING_POWER_RIS = 1, PT_LIGHT_SAMPLING_REGIR_RIS = 2 };
+
 /* Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in of DESIGN.md spec S17): XeSSSettings as App::ProcessXeSSSuperResolution fills it
  * (Source/App.cpp:1685-1690; InputSize, Jitter, Reset), the output size XeSS is created with, and the stand-in's history cap. */
 typedef struct PtUpscaleSettings {
@@ -280,6 +296,10 @@ static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSetting
               && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
               && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
+static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingSettings, TileSize) == 4 && offsetof(PtLightSamplingSettings, TileCount) == 8
+              && offsetof(PtLightSamplingSettings, ReGIRGridSize) == 12 && offsetof(PtLightSamplingSettings, ReGIRLightsPerCell) == 16
+              && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
+              && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
@@ -304,6 +324,10 @@ _Static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettin
                && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
 _Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
                && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
+_Static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingSettings, TileSize) == 4 && offsetof(PtLightSamplingSettings, TileCount) == 8
+               && offsetof(PtLightSamplingSettings, ReGIRGridSize) == 12 && offsetof(PtLightSamplingSettings, ReGIRLightsPerCell) == 16
+               && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
+               && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
