@@ -133,6 +133,17 @@ def light_sampling_settings(mode=0, tile_size=0, tile_count=0, grid_size=0, ligh
                                    ReGIRBuildSamples=build_samples, ReGIRCellSize=cell_size)
 
 
+# Row N17 (pt_restir_di_ex): the BRDF candidates of initial sampling and the boiling filter; all zero = both off
+class PtRestirDiCandidates(C.Structure):
+    _fields_ = [("BrdfSamples", C.c_uint32), ("EnableBoilingFilter", C.c_uint32), ("BoilingFilterStrength", C.c_float), ("_pad", C.c_uint32)]
+
+
+def restir_di_candidates(brdf_samples=0, boiling_filter=None):
+    """boiling_filter: None / False = off, otherwise the filter's strength (the reference's defaults: brdf_samples 1, strength 0.2)"""
+    on = boiling_filter is not None and boiling_filter is not False
+    return PtRestirDiCandidates(BrdfSamples=brdf_samples, EnableBoilingFilter=int(on), BoilingFilterStrength=float(boiling_filter) if on else 0.0)
+
+
 # Row N14 (pt_render_sharc, the SHARC stand-in): SHARCSettings plus the cache's accumulation constants and the stages of a call
 SHARC_UPDATE, SHARC_RESOLVE, SHARC_QUERY = 1, 2, 4
 SHARC_VOXEL_DTYPE = np.dtype([("sum", "<u4", (3,)), ("w", "<u4")])  # w = samples | frames << 16 | stale << 24

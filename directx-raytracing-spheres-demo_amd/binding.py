@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
                         ray_reconstruction_settings)
 
@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -104,6 +104,8 @@ class HipLib:
         lib.pt_restir_di.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtRestirDiTextures)]
         lib.pt_restir_di_sampled.restype = C.c_int
         lib.pt_restir_di_sampled.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtLightSamplingSettings), C.POINTER(PtRestirDiTextures)]
+        lib.pt_restir_di_ex.restype = C.c_int
+        lib.pt_restir_di_ex.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtLightSamplingSettings), C.POINTER(PtRestirDiCandidates), C.POINTER(PtRestirDiTextures)]
         lib.pt_restir_di_history.restype = C.c_int
         lib.pt_restir_di_history.argtypes = [vp, u32, vp, vp]
         lib.pt_light_ris_download.restype = C.c_int
@@ -543,7 +545,8 @@ class Renderer:
         self._check(self._lib.pt_nrd_denoise(self._ctx, C.byref(s), C.byref(t)))
 
     def restir_di_device(self, width, height, buffers, frame_index=0, reset_history=False, initial_samples=0, temporal=True, temporal_bias=1,
-                         max_history=0, spatial=True, spatial_bias=1, spatial_samples=0, spatial_radius=0.0, light_sampling=None):
+                         max_history=0, spatial=True, spatial_bias=1, spatial_samples=0, spatial_radius=0.0, light_sampling=None,
+                         candidates=None):
         """The reservoir pass that makes the DI render_with_di_device takes (row N10, DESIGN.md spec S16) over width x height pixels, for
         the frame the next render call renders: buffers = {RESTIR_DI_TEXTURES name: device pointer}, the G-buffer channels of
         render_gbuffer_device and the Diffuse / Specular outputs (float4; the caller clears them: pixels without DI are not written).
@@ -551,7 +554,9 @@ class Renderer:
         calls.  Asynchronous, ordered like render_gbuffer_device; what is queued on the context's stream later sees the outputs.
         light_sampling: None = pt_restir_di (uniform candidates); a PtLightSamplingSettings or a dict of light_sampling_settings'
         arguments (mode = abi_types.LIGHT_SAMPLING_*, tile_size, tile_count, grid_size, lights_per_cell, build_samples, cell_size) =
-        pt_restir_di_sampled (row N16, DESIGN.md spec S22)."""
+        pt_restir_di_sampled (row N16, DESIGN.md spec S22).
+        candidates: None = neither; a PtRestirDiCandidates or a dict of restir_di_candidates' arguments (brdf_samples, boiling_filter =
+        the filter's strength) = pt_restir_di_ex (row N17, DESIGN.md spec S23)."""
         unknown = set(buffers) - set(RESTIR_DI_TEXTURES)
         if unknown:
             raise ValueError(f"unknown ReSTIR DI buffers {sorted(unknown)}")
@@ -560,11 +565,16 @@ class Renderer:
                                MaxHistoryLength=max_history, EnableSpatial=int(spatial), SpatialBiasCorrection=spatial_bias,
                                SpatialSamples=spatial_samples, SpatialRadius=spatial_radius)
         t = PtRestirDiTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
-        if light_sampling is None:
+        ls = None
+        if light_sampling is not None:
+            ls = light_sampling if isinstance(light_sampling, PtLightSamplingSettings) else light_sampling_settings(**light_sampling)
+        if candidates is not None:
+            cd = candidates if isinstance(candidates, PtRestirDiCandidates) else restir_di_candidates(**candidates)
+            self._check(self._lib.pt_restir_di_ex(self._ctx, C.byref(s), C.byref(ls) if ls is not None else None, C.byref(cd), C.byref(t)))
+        elif ls is None:
             self._check(self._lib.pt_restir_di(self._ctx, C.byref(s), C.byref(t)))
-            return
-        ls = light_sampling if isinstance(light_sampling, PtLightSamplingSettings) else light_sampling_settings(**light_sampling)
-        self._check(self._lib.pt_restir_di_sampled(self._ctx, C.byref(s), C.byref(ls), C.byref(t)))
+        else:
+            self._check(self._lib.pt_restir_di_sampled(self._ctx, C.byref(s), C.byref(ls), C.byref(t)))
 
     def restir_di_history(self, width, height, which=0):
         """A slot of the reservoir pass's history (pt_restir_di_history; synchronous): which = 0 the slot the last restir_di_device call

@@ -1282,7 +1282,7 @@ void pt_destroy(PtContext* c)
         if (L.ev_done) (void)hipEventDestroy(L.ev_done);
         if (L.stream && L.stream != c->stream) (void)hipStreamDestroy(L.stream);
     }
-    free_dev(c->d_sph); free_dev(c->d_mats); free_dev(c->d_nodes); free_dev(c->d_wide); free_dev(c->d_sph_sorted); free_dev(c->d_sorted_id); free_dev(c->d_lights); free_dev(c->d_alpha_class); free_dev(c->d_leaf_ids);
+    free_dev(c->d_sph); free_dev(c->d_mats); free_dev(c->d_nodes); free_dev(c->d_wide); free_dev(c->d_sph_sorted); free_dev(c->d_sorted_id); free_dev(c->d_lights); free_dev(c->d_light_of); free_dev(c->d_alpha_class); free_dev(c->d_leaf_ids);
     for (auto& b : c->beam.buf) {
         free_dev(b.d_lists);
         free_dev(b.d_regions);
@@ -1337,11 +1337,14 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
         if (m.EmissiveStrength * m.EmissiveColor[0] > 0.0f || m.EmissiveStrength * m.EmissiveColor[1] > 0.0f || m.EmissiveStrength * m.EmissiveColor[2] > 0.0f)
             lights.push_back(i);
     }
+    std::vector<uint32_t> light_of(n, kRiNoHit);  // the inverse of `lights` (row N17: the emitter a BRDF candidate's ray found)
+    for (uint32_t j = 0; j < (uint32_t)lights.size(); j++) light_of[lights[j]] = j;
     // Every allocation that can fail comes first, into temporaries: a call that runs out of memory leaves the previous scene intact
     // (nothing of the context has been touched yet).
     float4* new_sph = nullptr;
     float4* new_mats = nullptr;
     uint32_t* new_lights = nullptr;
+    uint32_t* new_light_of = nullptr;
     if (n != c->n || !c->d_sph || !c->d_mats) {
         if (hipMalloc(&new_sph, (size_t)n * sizeof(float4)) != hipSuccess || hipMalloc(&new_mats, (size_t)n * sizeof(PtMaterial)) != hipSuccess) {
             (void)hipGetLastError();
@@ -1349,9 +1352,9 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
             return fail(c, PT_ERR_OOM, "pt_set_scene: out of device memory (the previous scene is unchanged)");
         }
     }
-    if (!lights.empty() && hipMalloc(&new_lights, lights.size() * sizeof(uint32_t)) != hipSuccess) {
+    if (!lights.empty() && (hipMalloc(&new_lights, lights.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc(&new_light_of, (size_t)n * sizeof(uint32_t)) != hipSuccess)) {
         (void)hipGetLastError();
-        free_dev(new_sph); free_dev(new_mats);
+        free_dev(new_sph); free_dev(new_mats); free_dev(new_lights);
         return fail(c, PT_ERR_OOM, "pt_set_scene: out of device memory (the previous scene is unchanged)");
     }
     c->empty_scene = empty;  // (after every check that can reject the call)
@@ -1359,6 +1362,8 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
     if (new_sph) { free_dev(c->d_sph); free_dev(c->d_mats); c->d_sph = new_sph; c->d_mats = new_mats; }
     free_dev(c->d_lights);
     c->d_lights = new_lights;
+    free_dev(c->d_light_of);
+    c->d_light_of = new_light_of;
     c->n_lights = (uint32_t)lights.size();
     c->n = n;
     c->h_sph.assign(spheres, spheres + n);
@@ -1374,6 +1379,7 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
     }
     PT_HIP(c, hipMemcpyAsync(c->d_mats, mats.data(), (size_t)n * sizeof(PtMaterial), hipMemcpyHostToDevice, c->stream));
     if (c->n_lights) PT_HIP(c, hipMemcpyAsync(c->d_lights, lights.data(), lights.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (c->n_lights) PT_HIP(c, hipMemcpyAsync(c->d_light_of, light_of.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     PT_HIP(c, hipStreamSynchronize(c->stream));  // caller-owned host memory may be released on return
     c->sd = *sd;
     c->scene_set = true;
@@ -1961,8 +1967,10 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
 // the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
 constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
 
-// The body of pt_restir_di and pt_restir_di_sampled (row N16, spec S22); ls null or Mode 0 = Uniform: nothing is presampled.
-static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t)
+// The body of pt_restir_di, pt_restir_di_sampled (row N16, spec S22) and pt_restir_di_ex (row N17, spec S23); ls null or Mode 0 = Uniform:
+// nothing is presampled; cd null, or no BRDF candidates and the filter off: launch 1 is the one of rows N10 / N16.
+static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd,
+                                 const PtRestirDiTextures* t)
 {
     if (!c) return PT_ERR_INVALID_ARG;
     if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null pointer");
@@ -1976,6 +1984,13 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
         if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
     }
     if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialRadius must be finite and >= 0");
+    if (cd) {
+        if (cd->BrdfSamples > kRiMaxBrdfSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": BrdfSamples must be at most 8");
+        if (cd->EnableBoilingFilter > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": EnableBoilingFilter must be 0 or 1");
+        if (cd->EnableBoilingFilter && (!std::isfinite(cd->BoilingFilterStrength) || !(cd->BoilingFilterStrength >= 0.0f && cd->BoilingFilterStrength <= 1.0f)))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": BoilingFilterStrength must be finite and in [0, 1]");
+        if (cd->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": PtRestirDiCandidates._pad must be 0");
+    }
     // the candidates' source (spec S22): defaults applied, ranges checked
     const uint32_t mode = ls ? ls->Mode : kLrUniform;
     LrGrid lg{};
@@ -2065,7 +2080,7 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     b.prev_rec_t = tplanes + (uint64_t)prev * n;
     b.out_diffuse = static_cast<float4*>(t->Diffuse);
     b.out_specular = static_cast<float4*>(t->Specular);
-    RiParams P{};
+    RiParamsEx P{};
     P.frame_index = s->FrameIndex;
     P.initial_samples = s->InitialSamples ? s->InitialSamples : kRiDefaultInitialSamples;
     P.temporal = s->EnableTemporal; P.temporal_bias = s->TemporalBiasCorrection;
@@ -2076,6 +2091,11 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     P.history_valid = restart ? 0u : 1u;
     P.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
     P.prev_cam_pos = make_f3(c->cam.PreviousPosition[0], c->cam.PreviousPosition[1], c->cam.PreviousPosition[2]);
+    if (cd) {
+        P.brdf_samples = cd->BrdfSamples;
+        P.boiling_filter = cd->EnableBoilingFilter;
+        P.boiling_strength = cd->EnableBoilingFilter ? cd->BoilingFilterStrength : 0.0f;
+    }
     const PixelMap pm = make_pixel_map(w, h, PtRect{ 0, 0, w, h });  // (at most 2048^2 * 64 = 2^28 slots)
     const SceneView sv = make_scene_view(c, &L);
     const uint32_t grid = side_pass_grid(c, pm.n_slots);
@@ -2125,7 +2145,9 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
         EventPair* ev = c->profiling ? next_events(c, pass == 0 ? 1 : 2) : nullptr;  // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
         if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream); e != hipSuccess)
+        const RiExtra rx{ c->d_light_of, mode != kLrUniform ? c->d_lr_pyramid : nullptr, lr_levels(c->n_lights) };
+        if (const hipError_t e = pass == 0 ? launch_restir_pass1_ex(sv, pm, b, P, mode, lr, rx, grid, L.stream) : launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream);
+            e != hipSuccess)
             st = fail(c, PT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(e));
         if (ev) (void)hipEventRecord(ev->b, L.stream);
     }
@@ -2142,11 +2164,16 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     return st;
 }
 
-PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, t); }
+PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, nullptr, t); }
 
 PtStatus pt_restir_di_sampled(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t)
 {
-    return restir_di_common(c, "pt_restir_di_sampled", s, ls, t);
+    return restir_di_common(c, "pt_restir_di_sampled", s, ls, nullptr, t);
+}
+
+PtStatus pt_restir_di_ex(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd, const PtRestirDiTextures* t)
+{
+    return restir_di_common(c, "pt_restir_di_ex", s, ls, cd, t);
 }
 
 PtStatus pt_restir_di_history(PtContext* c, uint32_t which, void* planes, void* transmission)

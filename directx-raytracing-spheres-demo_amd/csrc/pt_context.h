@@ -133,6 +133,7 @@ struct PtContext {
 
     // emissive spheres (row N4)
     uint32_t* d_lights = nullptr;
+    uint32_t* d_light_of = nullptr;  // per sphere: its index in d_lights or 0xFFFFFFFF (pt_restir_di_ex's BRDF candidates, spec S23)
     uint32_t n_lights = 0;
 
     // alpha-tested hits (spec S10): the spheres whose AlphaMode is not Opaque, their class per sphere on the device (null while

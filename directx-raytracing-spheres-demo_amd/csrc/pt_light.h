@@ -62,6 +62,18 @@ PT_HD void bsdf_eval_reflective_lobes(const Bsdf& b, const Surf& s, f3 L, f3 V, 
     f_s = bsdf_eval(b, s, L, V, w, kLobeSpecular);
 }
 
+// Row N17 (spec S23): EvaluatePDF without a lobe argument (BxDF.hlsli:247-264), the pdf of bsdf_sample's direction over its three
+// lobes: the transmission term where its weight is > 0, the two reflective terms where that weight is < 1 and L lies above the
+// geometric horizon.  Each term is bsdf_pdf's, bit for bit.
+PT_HD float bsdf_pdf_all(const Bsdf& b, const Surf& s, f3 L, f3 V, const float w[3])
+{
+    const float wt = w[kLobeTransmission];
+    float pdf = 0.0f;
+    if (wt > 0.0f) pdf = bsdf_pdf(b, s, L, V, w, kLobeTransmission);
+    if (wt < 1.0f && dot(s.FrontNg, L) > 0.0f) pdf += bsdf_pdf(b, s, L, V, w, kLobeDiffuse) + bsdf_pdf(b, s, L, V, w, kLobeSpecular);
+    return pdf;
+}
+
 constexpr float kDiNegligible = 1e-7f;  // upper bound of an estimate below which no shadow ray is cast (di_estimate)
 constexpr uint32_t kDiRngSalt = 0x44495F31u;  // the DI pass has its own per-pixel stream: rng_init(px, py, FrameIndex ^ salt)
 

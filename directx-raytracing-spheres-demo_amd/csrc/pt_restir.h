@@ -12,9 +12,12 @@
 // The initial candidates come from one of three sources (row N16, spec S22, pt_lightris.h): uniformly from the emitter list (S16 as
 // it was; pt_restir_di), from a Power_RIS tile, or from a ReGIR cell with the Power_RIS tile as its fallback (pt_restir_di_sampled).
 //
-// Out of scope: ReGIR's onion mode; BRDF and environment candidates; the boiling filter; checkerboard rendering;
-// visibility reuse; pairwise MIS (bias mode 2); the DLSS-RR SpecularHitDistance write; dropping pt_render_with_di's whole-stream
-// wait for buffers this pass produced.
+// Row N17 (spec S23, pt_restir_di_ex): BRDF candidates mixed into initial sampling by the balance heuristic (ri_initial_mis) and the
+// boiling filter over launch 1's temporal result (ri_boiling_*); both off: the code of rows N10 / N16, untouched.
+//
+// Out of scope: ReGIR's onion mode; environment candidates (the reference's bridge stubs them to 0, RTXDIAppBridge.hlsli:503-511);
+// checkerboard rendering; visibility reuse; pairwise MIS (bias mode 2); the DLSS-RR SpecularHitDistance write; dropping
+// pt_render_with_di's whole-stream wait for buffers this pass produced.
 #pragma once
 
 #include "pt_light.h"
@@ -34,6 +37,8 @@ constexpr float kRiOwnSphere = 1e-3f;          // |d^2 - r^2| <= this * r^2: the
 constexpr uint32_t kRiDefaultInitialSamples = 8, kRiMaxInitialSamples = 32, kRiDefaultHistory = 20, kRiDefaultSpatialSamples = 1,
                    kRiMaxSpatialSamples = 32, kRiNeighbourTable = 32;
 constexpr float kRiDefaultRadius = 32.0f, kRiMaxRadius = 16384.0f;
+constexpr uint32_t kRiMaxBrdfSamples = 8;
+constexpr float kRiMinU = 5.9604644775390625e-08f;  // 2^-24: the lower clamp of an inverted cone sample (u1, u2 lie in (0, 1])
 enum : uint32_t { kRiBiasOff = 0, kRiBiasBasic = 1, kRiBiasPairwise = 2, kRiBiasRaytraced = 3 };
 
 // The compact surface record the first launch writes per pixel (four float4 planes and one float plane): later passes and the next
@@ -83,6 +88,10 @@ struct RiScene {
     const uint32_t* lights;   // ids of the emissive spheres
     uint32_t n_lights;
     LrView lr;                // the presampled candidates of spec S22 (read by ri_initial<kLrPowerRis / kLrRegirRis> only; all zero: none)
+    // row N17 (read by ri_initial_mis only; null / 0: BRDF candidates are off)
+    const uint32_t* light_of; // per sphere: its index in `lights`, or kRiNoHit
+    const float* pyramid;     // S22's power pyramid, every level (the presampled modes: the source pdf of an emitter a BRDF ray found)
+    uint32_t pyramid_levels;
 };
 
 struct RiParams {
@@ -90,6 +99,13 @@ struct RiParams {
     float radius;
     uint32_t history_valid;   // 0: the history restarts with this call
     f3 cam_pos, prev_cam_pos;
+};
+
+// ... with what row N17 adds (launch 1 of pt_restir_di_ex; the launches of rows N10 / N16 keep RiParams as their argument); all zero: off
+struct RiParamsEx : RiParams {
+    uint32_t brdf_samples;    // BRDF candidates of initial sampling
+    uint32_t boiling_filter;
+    float boiling_strength;
 };
 
 PT_HD float4 ri_float4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
@@ -315,6 +331,166 @@ PT_HD RiReservoir ri_initial(const RiScene& sc, const RiParams& p, const RiSurfa
     return r;
 }
 
+// ---- row N17 (spec S23): BRDF candidates and the boiling filter
+// The inverse of sample_sphere_cone: the (u1, u2) whose direction from P towards the sphere (C, r) is L.  1 - cos(theta) is formed
+// as (lx^2 + ly^2) / (1 + lz) in the basis of the cone's axis -- the forward function's cancellation-free form.  P inside the sphere: (1, 1).
+PT_HD void invert_sphere_cone(f3 P, f3 C, float r, f3 L, float& u1, float& u2)
+{
+    u1 = u2 = 1.0f;
+    const f3 w = C - P;
+    const float d2 = dot(w, w), r2 = r * r;
+    if (!(d2 > r2)) return;
+    const f3 wn = w * pt_rcp(pt_sqrt(d2));
+    const float sin2 = r2 / d2;
+    const float cos_max = sqrt01(1.0f - sin2);
+    const float omc = sin2 / (1.0f + cos_max);
+    const f3 l = rotate_vector(get_basis(wn), L);
+    const float k = (l.x * l.x + l.y * l.y) / (1.0f + l.z);
+    const float a = k / omc;
+    u1 = !(a > kRiMinU) ? kRiMinU : (a > 1.0f ? 1.0f : a);
+    float t = atan2_spec(l.y, l.x) * 0.15915494309189533577f;
+    if (!(t > 0.0f)) t += 1.0f;
+    u2 = !(t > kRiMinU) ? kRiMinU : (t > 1.0f ? 1.0f : t);
+}
+
+// the pdf with which the light technique proposes emitter j, as the BRDF side prices it: 1 / n_lights, or in the presampled modes
+// power_j / sum of powers from S22's pyramid (leaf over top; the top is the mean of 4^levels leaves) -- RAB_EvaluateLocalLightSourcePdf
+template <uint32_t kMode>
+PT_HD float ri_source_pdf(const RiScene& sc, uint32_t j)
+{
+    if (kMode == kLrUniform) return 1.0f / (float)sc.n_lights;
+    const float top = sc.pyramid[lr_level_offset(sc.pyramid_levels, sc.pyramid_levels)] * (float)lr_level_size(sc.pyramid_levels, 0u);
+    return top > 0.0f ? sc.pyramid[j] / top : 0.0f;
+}
+
+// the balance-heuristic RIS weight of a candidate: p_hat over the mixture density of its (emitter, u1, u2); 0 where it carries nothing
+PT_HD float ri_mis_weight(float p_hat, float w_l, float p_src, float w_b, float p_brdf, float inv_pdf)
+{
+    if (!(p_hat > 0.0f)) return 0.0f;
+    const float w = p_hat / (w_l * p_src + w_b * (p_brdf * inv_pdf));
+    return w > 0.0f && is_finite(w) ? w : 0.0f;
+}
+
+// Initial sampling with p.brdf_samples BRDF candidates behind the p.initial_samples local ones.  The local candidates' draws and source
+// are ri_initial's; a BRDF candidate draws (r0, r1, r2, r3, rnd), and where bsdf_sample's direction leaves above the geometric horizon
+// a closest-hit ray looks for an emitter: the candidate is then (emitter, invert_sphere_cone), shaded like any other.  One loop casts
+// the BRDF rays and, as its last turn, the selected sample's visibility ray: one walker call site.
+template <uint32_t kMode, typename TraceFn>
+PT_HD RiReservoir ri_initial_mis(const RiScene& sc, const RiParamsEx& p, const RiSurface& s, uint32_t px, uint32_t py, TraceFn&& trace)
+{
+    RiReservoir r = ri_empty_reservoir();
+    float w_sum = 0.0f;
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiInitialRngSalt);
+    const float n_all = (float)(p.initial_samples + p.brdf_samples);
+    const float w_l = (float)p.initial_samples / n_all, w_b = (float)p.brdf_samples / n_all;
+    const LrEntry* src = nullptr;
+    uint32_t src_n = 0u;
+    if (kMode != kLrUniform) {
+        bool in_cell = false;
+        if (kMode == kLrRegirRis) {
+            const float x0 = rng_float(rng), x1 = rng_float(rng), x2 = rng_float(rng);
+            uint32_t cell = 0u;
+            in_cell = lr_cell_of(s.P, make_f3(x0, x1, x2), p.cam_pos, sc.lr.grid, sc.lr.cell_size, cell);
+            if (in_cell) {
+                src = sc.lr.ris + ((size_t)sc.lr.tile_size * sc.lr.tile_count + (size_t)cell * sc.lr.lights_per_cell);
+                src_n = sc.lr.lights_per_cell;
+            }
+        }
+        if (!in_cell) {
+            src = sc.lr.ris + (size_t)lr_pixel_tile(px, py, p.frame_index, sc.lr.tile_count) * sc.lr.tile_size;
+            src_n = sc.lr.tile_size;
+        }
+    }
+    for (uint32_t i = 0; i < p.initial_samples; i++) {
+        const float u0 = rng_float(rng), u1 = rng_float(rng), u2 = rng_float(rng), rnd = rng_float(rng);
+        uint32_t j = kLrInvalid;
+        float p_sel = 0.0f;
+        if (kMode == kLrUniform) {
+            j = pick_light(u0, sc.n_lights);
+            p_sel = 1.0f / (float)sc.n_lights;
+        } else {
+            const LrEntry c = src[pick_light(u0, src_n)];
+            j = c.light;
+            p_sel = 1.0f / c.inv_pdf;
+        }
+        float w = 0.0f, p_hat = 0.0f;
+        if (j != kLrInvalid) {
+            const RiShade e = ri_shade(sc, s, j, u1, u2);
+            p_hat = e.p_hat;
+            if (p_hat > 0.0f) w = ri_mis_weight(p_hat, w_l, p_sel, w_b, bsdf_pdf_all(s.bsdf, s.surf, e.L, s.V, s.w), e.inv_pdf);
+        }
+        if (ri_stream(w_sum, w, rnd)) { r.light = j; r.u1 = u1; r.u2 = u2; r.p_hat = p_hat; }
+    }
+    for (uint32_t k = 0; k <= p.brdf_samples; k++) {
+        const bool last = k == p.brdf_samples;
+        f3 L = make_f3(0.0f, 0.0f, 1.0f);
+        float rnd = 1.0f;
+        uint32_t want = kRiNoHit;
+        bool cast = false;
+        if (!last) {
+            float q[4];
+            q[0] = rng_float(rng); q[1] = rng_float(rng); q[2] = rng_float(rng); q[3] = rng_float(rng);
+            rnd = rng_float(rng);
+            int lobe;
+            cast = bsdf_sample(s.bsdf, s.surf, s.V, s.w, q, L, lobe) && dot(s.surf.FrontNg, L) > 0.0f;
+        } else {
+            r.M = n_all;
+            r.W = r.p_hat > 0.0f ? w_sum / (r.M * r.p_hat) : 0.0f;
+            if (r.W > 0.0f) {  // enableInitialVisibility, whichever technique produced the sample
+                const RiShade e = ri_shade(sc, s, r.light, r.u1, r.u2);
+                L = e.L;
+                want = e.sphere;
+                cast = true;
+            }
+        }
+        uint32_t id = kRiNoHit;
+        float t = kInf;
+        if (cast) trace(spawn_origin(s.P, s.Ng, s.offset, L), L, t, id);
+        if (last) {
+            if (cast && id != want) r.W = 0.0f;
+        } else {
+            float w = 0.0f, p_hat = 0.0f, u1 = 1.0f, u2 = 1.0f;
+            uint32_t j = kRiNoHit;
+            if (cast && id != kRiNoHit) j = sc.light_of[id];
+            if (j != kRiNoHit) {
+                const float4 ls = sc.sph[id];
+                invert_sphere_cone(s.P, make_f3(ls.x, ls.y, ls.z), ls.w, L, u1, u2);
+                const RiShade e = ri_shade(sc, s, j, u1, u2);
+                p_hat = e.p_hat;
+                if (p_hat > 0.0f) w = ri_mis_weight(p_hat, w_l, ri_source_pdf<kMode>(sc, j), w_b, bsdf_pdf_all(s.bsdf, s.surf, e.L, s.V, s.w), e.inv_pdf);
+            }
+            if (ri_stream(w_sum, w, rnd)) { r.light = j; r.u1 = u1; r.u2 = u2; r.p_hat = p_hat; }
+        }
+    }
+    return r;
+}
+
+// The boiling filter (DITemporalResampling.hlsl:41-46) over one 8x8 pixel block = one wave64: a reservoir whose W exceeds the mean
+// of the block's nonzero W times the multiplier is emptied.
+PT_HD float ri_boiling_multiplier(float strength)
+{
+    const float s = !(strength > 1e-6f) ? 1e-6f : (strength > 1.0f ? 1.0f : strength);
+    return 10.0f / s - 9.0f;
+}
+PT_HD bool ri_boiled(float W, float sum, uint32_t n, float mult)
+{
+    const float avg = n ? sum / (float)n : 0.0f;
+    return W > avg * mult;
+}
+// the host form of the wave's reduction: six butterfly levels, level k adding the partial sums of lanes that differ in bit k of the
+// block's row-major lane index (what __shfl_xor(v, 1 << k) does); every lane ends with the same bits, lane 0's are returned
+inline float ri_boiling_sum64(const float w[64], uint32_t& n)
+{
+    float v[64], t[64];
+    n = 0u;
+    for (uint32_t l = 0; l < 64u; l++) { v[l] = w[l]; n += w[l] > 0.0f ? 1u : 0u; }
+    for (uint32_t k = 0; k < 6u; k++) {
+        for (uint32_t l = 0; l < 64u; l++) t[l] = v[l] + v[l ^ (1u << k)];
+        for (uint32_t l = 0; l < 64u; l++) v[l] = t[l];
+    }
+    return v[0];
+}
+
 // ---- temporal resampling (DITemporalResampling.hlsl): the reservoir of the reprojected pixel of the previous call
 template <typename TraceFn>
 PT_HD RiReservoir ri_temporal(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& cur, uint32_t px,
@@ -487,6 +663,49 @@ PT_HD void ri_pass1_px(const RiBuffers& b, const RiScene& sc, const RiParams& p,
     ri_store_reservoir(b.res, i, r);
 }
 
+// launch 1 of pt_restir_di_ex (row N17): as ri_pass1_px up to the store of the reservoir, which the caller does behind the boiling
+// filter; false: no surface (nothing but the record's validity plane is written, r is empty).  kBrdf: initial sampling is ri_initial_mis.
+template <uint32_t kMode, bool kBrdf, typename TraceFn>
+PT_HD bool ri_pass1_reservoir(const RiBuffers& b, const RiScene& sc, const RiParamsEx& p, uint32_t px, uint32_t py, TraceFn&& trace, RiReservoir& r)
+{
+    const uint32_t i = py * b.w + px;
+    r = ri_empty_reservoir();
+    const RiRecord rec = ri_record_from_gbuffer(b, i);
+    if (!is_finite(rec.r3.z)) {
+        b.rec[3][i] = rec.r3;
+        return false;
+    }
+    ri_store_record(b.rec, b.rec_t, i, rec);
+    const RiSurface s = ri_surface(rec, p.cam_pos);
+    if (kBrdf) r = ri_initial_mis<kMode>(sc, p, s, px, py, trace);
+    else r = ri_initial<kMode>(sc, p, s, px, py, trace);
+    const f3 mv = make_f3(b.motion_vector[3u * i], b.motion_vector[3u * i + 1u], b.motion_vector[3u * i + 2u]);
+    r = ri_temporal(b, sc, p, s, r, px, py, mv, trace);
+    return true;
+}
+
+// ... and the host form of one 8x8 block of it, (bx, by) in blocks: the 64 lanes in row-major order, the filter, the stores
+template <uint32_t kMode, bool kBrdf, typename TraceFn>
+inline void ri_pass1_block(const RiBuffers& b, const RiScene& sc, const RiParamsEx& p, uint32_t bx, uint32_t by, TraceFn&& trace)
+{
+    RiReservoir res[64];
+    bool has[64];
+    float w[64];
+    for (uint32_t l = 0; l < 64u; l++) {
+        const uint32_t px = bx * 8u + (l & 7u), py = by * 8u + (l >> 3);
+        has[l] = px < b.w && py < b.h && ri_pass1_reservoir<kMode, kBrdf>(b, sc, p, px, py, trace, res[l]);
+        w[l] = has[l] ? res[l].W : 0.0f;
+    }
+    uint32_t n = 0u;
+    const float sum = p.boiling_filter ? ri_boiling_sum64(w, n) : 0.0f;
+    const float mult = ri_boiling_multiplier(p.boiling_strength);
+    for (uint32_t l = 0; l < 64u; l++) {
+        if (!has[l]) continue;
+        if (p.boiling_filter && ri_boiled(w[l], sum, n, mult)) res[l] = ri_empty_reservoir();
+        ri_store_reservoir(b.res, (by * 8u + (l >> 3)) * b.w + bx * 8u + (l & 7u), res[l]);
+    }
+}
+
 // launch 2: spatial resampling over launch 1's results, final shading
 template <typename TraceFn, typename EmitFn>
 PT_HD void ri_pass2_px(const RiBuffers& b, const RiScene& sc, const RiParams& p, uint32_t px, uint32_t py, TraceFn&& trace, EmitFn&& emit)
@@ -507,6 +726,15 @@ struct PixelMap;
 // mode, lr: the source of launch 1's candidates (kLrUniform: lr is not read)
 hipError_t launch_restir_pass(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, uint32_t mode, const LrView& lr,
                               uint32_t grid, hipStream_t stream);
+// what launch 1 of pt_restir_di_ex reads besides (row N17): the emitter index of every sphere, S22's pyramid (null in Uniform mode)
+struct RiExtra {
+    const uint32_t* light_of;
+    const float* pyramid;
+    uint32_t pyramid_levels;
+};
+// launch 1 with p.brdf_samples > 0 and / or p.boiling_filter (both off: launch_restir_pass)
+hipError_t launch_restir_pass1_ex(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParamsEx& p, uint32_t mode, const LrView& lr,
+                                  const RiExtra& x, uint32_t grid, hipStream_t stream);
 #endif
 
 }  // namespace pt

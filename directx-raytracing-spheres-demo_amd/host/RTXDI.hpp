@@ -3,7 +3,8 @@
 // stand-in for the RTXDI SDK, which the reference does not vendor.  The settings are the subset of ReSTIRDI_Parameters
 // (Source/MyAppData.h:190-250) the stand-in reads; resources are DEVICE pointers of RenderSize texels (the layouts of
 // PtRestirDiTextures) instead of D3D12 textures.  With a local-light sampling mode other than Uniform the passes run through
-// pt_restir_di_sampled (row N16, spec S22: Power_RIS tiles and the ReGIR grid, MyAppData.h:194-218).
+// pt_restir_di_sampled (row N16, spec S22: Power_RIS tiles and the ReGIR grid, MyAppData.h:194-218); with BRDF candidates or the boiling
+// filter through pt_restir_di_ex (row N17, spec S23: MyAppData.h:220-221, 229-235).
 #pragma once
 
 #include <array>
@@ -25,9 +26,25 @@ struct ReSTIRDISettings {  // MyAppData.h:190-250 (IsEnabled = true is the refer
     } ReGIR;
     // LocalLightMode: the reference's default is ReGIR_RIS (MyAppData.h:212); this mirror's stays Uniform, so that a host written
     // against row N10 keeps the frames it had
-    struct { ReSTIRDI_LocalLightSamplingMode LocalLightMode = ReSTIRDI_LocalLightSamplingMode::Uniform; uint32_t LocalLightSamples = 8; } InitialSampling;
-    struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t MaxHistoryLength = 20; } TemporalResampling;
+    // BRDFSamples (at most 8) and BoilingFilter: the reference's defaults are 1 and {true, 0.2} (MyAppData.h:220-221, 229-235); this
+    // mirror's stay off for the same reason -- ReferenceDefaults() below is the reference's whole block
+    struct { ReSTIRDI_LocalLightSamplingMode LocalLightMode = ReSTIRDI_LocalLightSamplingMode::Uniform; uint32_t LocalLightSamples = 8; uint32_t BRDFSamples = 0; } InitialSampling;
+    struct {
+        bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t MaxHistoryLength = 20;
+        struct { bool IsEnabled = false; float Strength = 0.2f; } BoilingFilter;
+    } TemporalResampling;
     struct { bool IsEnabled = true; ReSTIRDI_BiasCorrectionMode BiasCorrectionMode = ReSTIRDI_BiasCorrectionMode::Basic; uint32_t Samples = 1; float Radius = 32; } SpatialResampling;
+
+    // the reference's default ReSTIRDI block: ReGIR_RIS candidates, 8 local + 1 BRDF candidate, the boiling filter at strength 0.2
+    static ReSTIRDISettings ReferenceDefaults()
+    {
+        ReSTIRDISettings s;
+        s.InitialSampling.LocalLightMode = ReSTIRDI_LocalLightSamplingMode::ReGIR_RIS;
+        s.InitialSampling.BRDFSamples = 1;
+        s.TemporalResampling.BoilingFilter.IsEnabled = true;
+        s.TemporalResampling.BoilingFilter.Strength = 0.2f;
+        return s;
+    }
 };
 
 class RTXDI {
@@ -63,6 +80,10 @@ public:
         m_sampling.Mode = static_cast<uint32_t>(settings.InitialSampling.LocalLightMode);
         m_sampling.ReGIRBuildSamples = settings.ReGIR.BuildSamples;
         m_sampling.ReGIRCellSize = settings.ReGIR.Cell.Size;
+        m_candidates = PtRestirDiCandidates{};
+        m_candidates.BrdfSamples = settings.InitialSampling.BRDFSamples;
+        m_candidates.EnableBoilingFilter = settings.TemporalResampling.BoilingFilter.IsEnabled ? 1u : 0u;
+        m_candidates.BoilingFilterStrength = settings.TemporalResampling.BoilingFilter.Strength;
     }
 
     // RTXDI::Render: the DI passes of the frame the next render call renders, asynchronous
@@ -71,7 +92,9 @@ public:
         const PtRestirDiTextures t{ GPUBuffers.Position, GPUBuffers.GeometricNormal, GPUBuffers.LinearDepth, GPUBuffers.MotionVector,
                                     GPUBuffers.BaseColorMetalness, GPUBuffers.NormalRoughness, GPUBuffers.IOR, GPUBuffers.Transmission,
                                     GPUBuffers.Diffuse, GPUBuffers.Specular };
-        if (m_sampling.Mode == PT_LIGHT_SAMPLING_UNIFORM) ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
+        if (m_candidates.BrdfSamples || m_candidates.EnableBoilingFilter)
+            ThrowIfFailed(pt_restir_di_ex(m_ctx, &m_settings, &m_sampling, &m_candidates, &t), m_ctx, "pt_restir_di_ex");
+        else if (m_sampling.Mode == PT_LIGHT_SAMPLING_UNIFORM) ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
         else ThrowIfFailed(pt_restir_di_sampled(m_ctx, &m_settings, &m_sampling, &t), m_ctx, "pt_restir_di_sampled");
     }
 
@@ -79,6 +102,7 @@ private:
     PtContext* m_ctx;
     PtRestirDiSettings m_settings{};
     PtLightSamplingSettings m_sampling{};
+    PtRestirDiCandidates m_candidates{};
 };
 
 }  // namespace dxrs

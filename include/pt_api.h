@@ -24,6 +24,7 @@
  *   pt_restir_di             RTXDI::SetConstants / Render: the DI passes (a stand-in for RTXDI, spec S16)   Source/App.cpp:1187-1227,
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_restir_di_sampled     the same with Power_RIS / ReGIR_RIS local-light presampling (spec S22)                 Source/RTXDI.ixx:209-226
+ *   pt_restir_di_ex          ... and with BRDF candidates and the boiling filter (spec S23)                         Source/App.cpp:1092-1101
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
@@ -374,7 +375,8 @@ PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, co
  * first use and freed by pt_destroy.  The history restarts on the first call, with ResetHistory, when RenderSize changes and after
  * pt_set_scene (emitter indices change); spheres moved by pt_update_spheres keep it.
  * The candidates are uniform over the emitter list; pt_restir_di_sampled below draws them from presampled structures (row N16).
- * Not built (spec S16): BRDF and environment candidates, the boiling filter, checkerboard rendering,
+ * BRDF candidates and the boiling filter: pt_restir_di_ex below (row N17).
+ * Not built (spec S16): environment candidates (the reference's bridge stubs them to 0), checkerboard rendering,
  * visibility reuse, pairwise MIS, the DLSS-RR SpecularHitDistance write.
  * PT_ERR_INVALID_ARG: a null argument; a missing buffer; a float4 buffer not 16-byte aligned, GeometricNormal not 8-byte, another not
  * 4-byte; an output overlapping an input or the other output; a value outside the ranges of PtRestirDiSettings.  PT_ERR_UNSUPPORTED:
@@ -402,12 +404,24 @@ PtStatus pt_restir_di(PtContext *ctx, const PtRestirDiSettings *settings, const 
  * `sampling` NULL or Mode 0 (Uniform): the call IS pt_restir_di -- the same history slots, restart rules and bits; calls of the two
  * entry points may alternate on one context and share the history.  Errors, lane, ordering, buffer rotation, profiling slots (plus
  * the presampling launches, as one interval, under ms_tail) and the "no emitters: success, nothing written" rule: as pt_restir_di.
- * Not built: ReGIR's onion mode, the cell visualisation, BRDF and environment candidates, the compact-light-info path.
+ * Not built: ReGIR's onion mode, the cell visualisation, environment candidates, the compact-light-info path.
  * PT_ERR_INVALID_ARG also: a Mode above 2, a size above its range, a cell size that is not finite or outside [0.1, 10], a nonzero _pad,
  * more than 2^24 entries in the two segments together. */
 PtStatus pt_restir_di_sampled(PtContext *ctx, const PtRestirDiSettings *settings, const PtLightSamplingSettings *sampling, const PtRestirDiTextures *textures);
 
-/* Test hook: a slot of the history pt_restir_di / pt_restir_di_sampled keep, after waiting for the last call: which = 0 the slot the
+/* Row N17 -- pt_restir_di_sampled with the two remaining defaults of the reference's ReSTIRDI settings block (DESIGN.md spec S23): BrdfSamples
+ * BSDF-sampled candidates mixed into initial sampling by the balance heuristic (InitialSampling.BRDFSamples; App.cpp:1092-1095 with
+ * brdfCutoff = 0; the callbacks of RTXDIAppBridge.hlsli:394-402, 468-501) -- each costs launch 1 one closest-hit ray -- and the boiling
+ * filter over launch 1's temporal result (TemporalResampling.BoilingFilter; DITemporalResampling.hlsl:41-46), per 8x8 pixel block.
+ * `candidates` NULL, or BrdfSamples 0 and the filter off: the call IS pt_restir_di_sampled -- the same history slots, restart rules and
+ * bits; calls of the three entry points may alternate on one context.  Errors, lane, ordering, buffer rotation, profiling slots: as
+ * pt_restir_di_sampled.  The arithmetic is this library's own (the RTXDI SDK is not vendored): no parity with the SDK is claimed.
+ * PT_ERR_INVALID_ARG also: BrdfSamples above 8, EnableBoilingFilter above 1, with the filter enabled a strength that is not finite or
+ * outside [0, 1], a nonzero _pad. */
+PtStatus pt_restir_di_ex(PtContext *ctx, const PtRestirDiSettings *settings, const PtLightSamplingSettings *sampling, const PtRestirDiCandidates *candidates,
+                         const PtRestirDiTextures *textures);
+
+/* Test hook: a slot of the history pt_restir_di / pt_restir_di_sampled / pt_restir_di_ex keep, after waiting for the last call: which = 0 the slot the
  * last call wrote, 1 the slot the call before it wrote.  planes: six planes of RenderSize float4 (the surface record's four, then the
  * reservoir's two: {emitter bits, u1, u2, W}, {M, p_hat, age bits, 0}); transmission: RenderSize floats.  A pixel without a surface
  * holds only plane 3 (its depth is +inf); its other words are whatever the slot held before.  PT_ERR_STATE: no call has left a history. */

@@ -15,6 +15,7 @@
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
  *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
  *   PtLightSamplingSettings (row N16) the local-light sampling mode and the ReGIR settings (Source/MyAppData.h:194-218), 32 B
+ *   PtRestirDiCandidates  (row N17) InitialSampling.BRDFSamples and TemporalResampling.BoilingFilter (Source/MyAppData.h:220-235), 16 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
@@ -210,6 +211,15 @@ typedef struct PtLightSamplingSettings {
 
 enum { PT_LIGHT_SAMPLING_UNIFORM = 0, PT_LIGHT_SAMPLING_POWER_RIS = 1, PT_LIGHT_SAMPLING_REGIR_RIS = 2 };
 
+/* Row N17 (pt_restir_di_ex, DESIGN.md spec S23): the BRDF candidates of initial sampling and the boiling filter of temporal resampling
+ * (Source/MyAppData.h:220-221, 229-235).  All zero = both off. */
+typedef struct PtRestirDiCandidates {
+    uint32_t BrdfSamples;           /*  0: 0 .. 8; 0 = none; the reference's default is 1 (InitialSampling.BRDFSamples) */
+    uint32_t EnableBoilingFilter;   /*  4: 0 / 1; the reference's default is 1 */
+    float    BoilingFilterStrength; /*  8: finite, 0 .. 1; the reference's default is 0.2; read only when the filter is enabled */
+    uint32_t _pad;                  /* 12: must be 0 */
+} PtRestirDiCandidates;
+
 /* Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in of DESIGN.md spec S17): XeSSSettings as App::ProcessXeSSSuperResolution fills it
  * (Source/App.cpp:1685-1690; InputSize, Jitter, Reset), the output size XeSS is created with, and the stand-in's history cap. */
 typedef struct PtUpscaleSettings {
@@ -300,6 +310,7 @@ static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingS
               && offsetof(PtLightSamplingSettings, ReGIRGridSize) == 12 && offsetof(PtLightSamplingSettings, ReGIRLightsPerCell) == 16
               && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
               && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
+static_assert(sizeof(PtRestirDiCandidates) == 16 && offsetof(PtRestirDiCandidates, BoilingFilterStrength) == 8, "PtRestirDiCandidates layout");
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
@@ -328,6 +339,7 @@ _Static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSampling
                && offsetof(PtLightSamplingSettings, ReGIRGridSize) == 12 && offsetof(PtLightSamplingSettings, ReGIRLightsPerCell) == 16
                && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
                && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
+_Static_assert(sizeof(PtRestirDiCandidates) == 16 && offsetof(PtRestirDiCandidates, BoilingFilterStrength) == 8, "PtRestirDiCandidates layout");
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");

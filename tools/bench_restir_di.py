@@ -8,6 +8,9 @@ Per size, the median (and the 10-90 % spread) of --frames one-call-at-a-time mea
     ms_shade; event pairs around each launch, so no launch gap), their sum, and the host's wall time from the call to the end of a wait;
   * wall time, call to end of wait, of the chain pt_render_gbuffer + pt_restir_di + pt_render_with_di against pt_render with row N4's
     DI and without DI, back to back in this script.
+  * row N17 (pt_restir_di_ex): in each local-light sampling mode (the library's default sizes), the pass with {1 BRDF candidate}, {the
+    boiling filter at 0.2}, {both}, and the same call with the extras off, per launch and per call as above (keys restir_ex_<mode>_<config>_...;
+    the presampling launches are under ms_tail and not in these figures);
 Also the share of pixels that have a surface for the pass (finite depth, roughness >= 0.05) and the bytes the two launches must move
 (launch 1: 20 B read per pixel (depth, NormalRoughness), without a surface 16 B written, with one 56 B more read, 100 B of record and
 reservoir written and 100 B of history read; launch 2: 16 B read per pixel, with a surface 84 B more and 100 B for a neighbour, 32 B
@@ -80,6 +83,23 @@ def main():
                 summary(res, f"restir_{kind}_{size}_launch2", l2)
                 summary(res, f"restir_{kind}_{size}_launches", [a + b for a, b in zip(l1, l2)])
                 summary(res, f"restir_{kind}_{size}_wall", wall)
+            # row N17: the extras in each sampling mode, next to the same call without them
+            t = dxrs_amd.types
+            for mode, ls in (("uniform", None), ("power", dict(mode=t.LIGHT_SAMPLING_POWER_RIS)), ("regir", dict(mode=t.LIGHT_SAMPLING_REGIR_RIS))):
+                for config, cd in (("off", dict()), ("brdf1", dict(brdf_samples=1)), ("filter", dict(boiling_filter=0.2)), ("both", dict(brdf_samples=1, boiling_filter=0.2))):
+                    l1, l2, wall = [], [], []
+                    for k in range(args.warmup + args.frames):
+                        r.profile(reset=True)
+                        t0 = time.perf_counter()
+                        r.restir_di_device(w, h, bufs, frame_index=k, reset_history=k == 0, light_sampling=ls, candidates=cd)
+                        r.synchronize()
+                        t1 = time.perf_counter()
+                        p = r.profile(reset=True)
+                        if k >= args.warmup:
+                            l1.append(p.ms_traverse); l2.append(p.ms_shade); wall.append((t1 - t0) * 1e3)
+                    summary(res, f"restir_ex_{mode}_{config}_{size}_launch1", l1)
+                    summary(res, f"restir_ex_{mode}_{config}_{size}_launch2", l2)
+                    summary(res, f"restir_ex_{mode}_{config}_{size}_wall", wall)
             r.set_profiling(False)
             res[f"lit_share_{size}"] = round(float((dd[..., :3].sum(-1) + ds[..., :3].sum(-1) > 0).float().mean()), 4)
             # the chain against pt_render with and without row N4's DI

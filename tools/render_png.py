@@ -11,7 +11,7 @@ mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendere
 pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]
                                         [--ray-reconstruction [performance]]"""
 import argparse
 import os
@@ -78,6 +78,10 @@ def main():
                     help="with --restir-di: where the reservoir pass draws its initial candidates (row N16): uniformly from the emitter list "
                          "(pt_restir_di), from Power_RIS tiles or from the ReGIR grid (pt_restir_di_sampled at its defaults; the reference's "
                          "default is regir)")
+    ap.add_argument("--brdf-samples", type=int, default=0, metavar="N",
+                    help="with --restir-di: N BSDF-sampled candidates mixed into initial sampling (row N17, pt_restir_di_ex; 0 .. 8, the reference's default is 1)")
+    ap.add_argument("--boiling-filter", type=float, default=None, metavar="STRENGTH",
+                    help="with --restir-di: the boiling filter over the temporal result at this strength in [0, 1] (row N17; the reference's default is 0.2)")
     ap.add_argument("--upscale", default=None, metavar="MODE", choices=list(dxrs_amd.types.UPSCALE_MODES),
                     help="--frames frames of a resting camera rendered at the mode's input size (pt_upscale_input_size) with Halton jitter (row "
                          "N11): pt_render_gbuffer (LinearDepth, MotionVector) -> pt_render -> pt_upscale to --width x --height [-> pt_bloom with "
@@ -107,6 +111,8 @@ def main():
         ap.error("--ray-reconstruction is a path of its own: it takes --nis and --bloom only")
     if args.light_sampling != "uniform" and not args.restir_di:
         ap.error("--light-sampling applies to --restir-di")
+    if (args.brdf_samples or args.boiling_filter is not None) and not args.restir_di:
+        ap.error("--brdf-samples and --boiling-filter apply to --restir-di")
     if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
@@ -264,10 +270,11 @@ def main():
     if args.restir_di:
         r.set_camera(host.camera_matrices(w, h, jitter=False))
         ls = {"uniform": None, "power": dict(mode=t.LIGHT_SAMPLING_POWER_RIS), "regir": dict(mode=t.LIGHT_SAMPLING_REGIR_RIS)}[args.light_sampling]
+        cd = dict(brdf_samples=args.brdf_samples, boiling_filter=args.boiling_filter) if args.brdf_samples or args.boiling_filter is not None else None
         for k in range(args.frames):
             gs.FrameIndex = k
             r.set_constants(gs)
-            dd, ds, _ = r.restir_di(fill=0.0, reset_history=k == 0, light_sampling=ls)  # (cleared outputs: a pixel without DI keeps 0)
+            dd, ds, _ = r.restir_di(fill=0.0, reset_history=k == 0, light_sampling=ls, candidates=cd)  # (cleared outputs: a pixel without DI keeps 0)
             r.render_with_di_device(frame.data_ptr(), dd.data_ptr(), ds.data_ptr())
             r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
             r.synchronize()
@@ -275,7 +282,8 @@ def main():
         r.tonemap(accum.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
         r.synchronize()
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
-        print(f"ReSTIR DI ({'pt_restir_di' if ls is None else 'pt_restir_di_sampled, ' + args.light_sampling}, {args.frames} frames) {w}x{h} -> {args.out}")
+        entry = "pt_restir_di_ex, " + args.light_sampling if cd else ("pt_restir_di" if ls is None else "pt_restir_di_sampled, " + args.light_sampling)
+        print(f"ReSTIR DI ({entry}, {args.frames} frames) {w}x{h} -> {args.out}")
         r.close()
         return
     if args.nrd_denoise:
