@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -112,6 +112,9 @@ class HipLib:
         lib.pt_light_ris_download.argtypes = [vp, vp, C.POINTER(u32), vp, C.POINTER(u32)]
         lib.pt_render_sharc.restype = C.c_int
         lib.pt_render_sharc.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtSharcSettings), C.POINTER(PtStats)]
+        lib.pt_render_sharc_ex.restype = C.c_int
+        lib.pt_render_sharc_ex.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtSharcSettings), C.POINTER(PtDirectLighting), C.POINTER(PtDenoiserOutputs),
+                                           C.POINTER(PtStats)]
         lib.pt_sharc_download.restype = C.c_int
         lib.pt_sharc_download.argtypes = [vp, vp, vp, u32]
         lib.pt_sharc_upload.restype = C.c_int
@@ -636,6 +639,46 @@ class Renderer:
         if not want_stats:
             self.synchronize()
         return out, stats
+
+    def render_sharc_ex_device(self, out_ptr, diffuse_ptr=None, specular_ptr=None, rect=None, mode=0, buffers=None, want_stats=False, **settings):
+        """render_sharc_device with the frame's direct illumination and denoiser outputs (row N18, DESIGN.md spec S24; pt_render_sharc_ex).
+        diffuse_ptr / specular_ptr: the DI as for render_with_di_device (None: no DI); mode 0 = Denoiser::None, else abi_types.DENOISER_*
+        with `buffers` as for render_denoiser_device.  Without DI and mode the call is render_sharc_device.  Asynchronous unless want_stats."""
+        r = PtRect(*rect) if rect is not None else None
+        s = sharc_settings(**settings)
+        di = PtDirectLighting(Diffuse=C.c_void_p(int(diffuse_ptr or 0)), Specular=C.c_void_p(int(specular_ptr or 0))) if diffuse_ptr or specular_ptr else None
+        o = PtDenoiserOutputs(Denoiser=mode, **{name: C.c_void_p(int(ptr)) for name, ptr in (buffers or {}).items() if ptr}) if mode else None
+        stats = PtStats()
+        self._check(self._lib.pt_render_sharc_ex(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr or 0), 1, C.byref(s),
+                                                 C.byref(di) if di is not None else None, C.byref(o) if o is not None else None,
+                                                 C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_sharc_ex(self, diffuse=None, specular=None, rect=None, mode=0, fill=float("nan"), device=None, alias=False, **settings):
+        """render_sharc_ex_device with the DI given as numpy float32 (h, w, 4) arrays or torch CUDA tensors (None: no DI), into torch
+        buffers filled with `fill` -> (out (h, w, 4) numpy or None without the query stage, {output name: numpy}, stats).  alias (NRD
+        modes): the DI is placed in the frame's own Diffuse / Specular outputs, as the reference uses them.  Synchronous."""
+        import torch
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+
+        def on_device(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+            return t.to(dev).reshape(h, w, 4).contiguous().clone()
+        dd, ds = (on_device(diffuse), on_device(specular)) if diffuse is not None else (None, None)
+        out = torch.from_numpy(np.full((h, w, 4), fill, dtype=np.float32)).to(dev)
+        bufs = {name: torch.from_numpy(np.full((h, w, width), fill, dtype=np.float32)).to(dev) for name, width in DENOISER_OUTPUTS.get(mode, ())}
+        if alias and mode in (2, 3) and dd is not None:
+            bufs = {"Diffuse": dd, "Specular": ds}
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        stats = self.render_sharc_ex_device(out.data_ptr(), dd.data_ptr() if dd is not None else None, ds.data_ptr() if ds is not None else None, rect, mode,
+                                            {name: b.data_ptr() for name, b in bufs.items()}, want_stats=True, **settings)
+        self.synchronize()
+        s = sharc_settings(**settings)
+        query = s.Stages == 0 or bool(s.Stages & 4)
+        return (out.cpu().numpy() if query else None), {name: b.cpu().numpy() for name, b in bufs.items()}, stats
 
     def sharc_download(self, capacity):
         """The cache as the last render_sharc call left it (pt_sharc_download) -> (keys uint64[capacity], voxels uint32[capacity, 4])"""

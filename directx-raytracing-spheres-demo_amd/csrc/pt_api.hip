@@ -2229,31 +2229,37 @@ static PtStatus sharc_allocate(PtContext* c, uint32_t capacity)
 
 static bool sharc_capacity_ok(uint32_t capacity) { return capacity >= kShBucket && capacity <= (1u << 28) && (capacity & (capacity - 1u)) == 0u; }
 
-PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, PtStats* stats)
+// pt_render_sharc (ex = false: di and outputs null) and pt_render_sharc_ex (row N18, DESIGN.md spec S24): one body.  `who` names the entry
+// point in messages.
+static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di,
+                           const PtDenoiserOutputs* outputs, PtStats* stats, bool ex, const std::string& who)
 {
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: null settings");
+    if (!s) return fail(c, PT_ERR_INVALID_ARG, who + ": null settings");
     const uint32_t stages = s->Stages ? s->Stages : (uint32_t)(PT_SHARC_UPDATE | PT_SHARC_RESOLVE | PT_SHARC_QUERY);
-    if (stages & ~7u) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: Stages must be a mask of PT_SHARC_UPDATE, PT_SHARC_RESOLVE and PT_SHARC_QUERY");
-    if ((stages & PT_SHARC_QUERY) && !out) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: null output");
-    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: the padding words must be 0");
+    if (stages & ~7u) return fail(c, PT_ERR_INVALID_ARG, who + ": Stages must be a mask of PT_SHARC_UPDATE, PT_SHARC_RESOLVE and PT_SHARC_QUERY");
+    if ((stages & PT_SHARC_QUERY) && !out) return fail(c, PT_ERR_INVALID_ARG, who + ": null output");
+    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, who + ": the padding words must be 0");
     const uint32_t capacity = s->Capacity ? s->Capacity : kShDefaultCapacity, downscale = s->DownscaleFactor ? s->DownscaleFactor : kShDefaultDownscale;
     const float scene_scale = s->SceneScale == 0.0f ? kShDefaultSceneScale : s->SceneScale;
     const uint32_t acc_frames = s->AccumulationFrames ? s->AccumulationFrames : kShDefaultAccumulationFrames;
     const uint32_t max_stale = s->MaxStaleFrames ? s->MaxStaleFrames : kShDefaultMaxStaleFrames;
-    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: Capacity must be a power of two in [16, 1 << 28]");
-    if (downscale > 4u) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: DownscaleFactor must be in [1, 4]");
-    if (!(scene_scale >= 5.0f && scene_scale <= 100.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: SceneScale must be in [5, 100]");
-    if (!(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: RoughnessThreshold must be in [0, 1]");
-    if (acc_frames > kShMaxFrames) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: AccumulationFrames must be at most 255");
-    if (max_stale > kShMaxStale) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: MaxStaleFrames must be at most 254");
-    if (s->IsAntiFireflyEnabled) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_sharc: the anti-firefly filter is not built");
+    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, who + ": Capacity must be a power of two in [16, 1 << 28]");
+    if (downscale > 4u) return fail(c, PT_ERR_INVALID_ARG, who + ": DownscaleFactor must be in [1, 4]");
+    if (!(scene_scale >= 5.0f && scene_scale <= 100.0f)) return fail(c, PT_ERR_INVALID_ARG, who + ": SceneScale must be in [5, 100]");
+    if (!(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, who + ": RoughnessThreshold must be in [0, 1]");
+    if (acc_frames > kShMaxFrames) return fail(c, PT_ERR_INVALID_ARG, who + ": AccumulationFrames must be at most 255");
+    if (max_stale > kShMaxStale) return fail(c, PT_ERR_INVALID_ARG, who + ": MaxStaleFrames must be at most 254");
+    if (s->IsAntiFireflyEnabled) return fail(c, PT_ERR_UNSUPPORTED, who + ": the anti-firefly filter is not built");
     PtStatus st = validate_frame(c);
     if (st != PT_OK) return st;
-    if (c->gs.IsDIEnabled || c->gs.Denoiser) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_sharc: IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs through the cache are not built)");
+    if (!ex && (c->gs.IsDIEnabled || c->gs.Denoiser)) return fail(c, PT_ERR_UNSUPPORTED, who + ": IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs through the cache are not built)");
     PtRect r;
     PixelMap pm{};
-    if ((st = rect_pixel_map(c, rect, "pt_render_sharc", r, pm)) != PT_OK) return st;
+    if ((st = rect_pixel_map(c, rect, who.c_str(), r, pm)) != PT_OK) return st;
+    DenoiseOut dn{};
+    if (outputs && (st = denoise_out(c, outputs, who.c_str(), dn)) != PT_OK) return st;
+    if (di && (stages & PT_SHARC_UPDATE) && (r.x || r.y || r.w != c->gs.RenderSize[0] || r.h != c->gs.RenderSize[1]))
+        return fail(c, PT_ERR_INVALID_ARG, who + ": with di and the UPDATE stage rect must be NULL or the whole frame (the update reads the whole frame's DI)");
     if ((st = check_environment(c)) != PT_OK) return st;
     if ((st = check_tree_lds(c)) != PT_OK) return st;
     PT_HIP(c, hipSetDevice(c->device));
@@ -2270,12 +2276,40 @@ PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is
         }
         dev_out = c->d_out;
     }
-    if (query && (reinterpret_cast<uintptr_t>(dev_out) & 15u)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_sharc: the output must be 16-byte aligned");
+    if (query && (reinterpret_cast<uintptr_t>(dev_out) & 15u)) return fail(c, PT_ERR_INVALID_ARG, who + ": the output must be 16-byte aligned");
+    if (di || outputs) {
+        // the buffer rule of pt_args.h: presence and alignment of all, nothing the call writes sharing a byte with another buffer of the
+        // call.  One exception: a DI buffer may BE the NRD modes' Diffuse or Specular (the same pointer: the update has read it before the
+        // query writes, and that query reads no DI); such a DI buffer leaves the overlap table once its presence and alignment are checked.
+        const uint64_t px = out_px;
+        const BufferUse in[2] = { { di ? di->Diffuse : nullptr, px * 16u, 16u, false, di != nullptr, "di->Diffuse" },
+                                  { di ? di->Specular : nullptr, px * 16u, 16u, false, di != nullptr, "di->Specular" } };
+        std::string msg = check_buffers(who.c_str(), in, 2);
+        if (msg.empty()) {
+            auto is_nrd_output = [&](const void* p) { return p && (p == dn.diffuse || p == dn.specular); };
+            const BufferUse all[6] = { { query ? dev_out : nullptr, px * 16u, 16u, true, false, "out" },
+                                       { dn.spec_hit_dist, px * 4u, 4u, true, false, "SpecularHitDistance" },
+                                       { dn.diffuse, px * 16u, 16u, true, false, "Diffuse" },
+                                       { dn.specular, px * 16u, 16u, true, false, "Specular" },
+                                       { is_nrd_output(in[0].p) ? nullptr : in[0].p, px * 16u, 16u, false, false, "di->Diffuse" },
+                                       { is_nrd_output(in[1].p) ? nullptr : in[1].p, px * 16u, 16u, false, false, "di->Specular" } };
+            msg = check_buffers(who.c_str(), all, 6);
+        }
+        if (!msg.empty()) return fail(c, PT_ERR_INVALID_ARG, msg);
+    }
 
     Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
     if ((st = side_pass_begin(c, L)) != PT_OK) return st;
     if (L.stream != c->stream) {
-        const bool shared = c->calls == 0 || (query && other_lane_uses(c, L, dev_out, true));
+        // (a supplied DI may have been written on the caller's stream right before this call: the lane waits for everything queued there;
+        // the denoiser outputs are held to the rule of `out`)
+        bool shared = c->calls == 0 || di != nullptr || (query && other_lane_uses(c, L, dev_out, true));
+        const void* extra[5] = { dn.spec_hit_dist, dn.diffuse, dn.specular, di ? di->Diffuse : nullptr, di ? di->Specular : nullptr };
+        for (int k = 0; k < 3 && query && !shared; k++) shared = extra[k] && other_lane_uses(c, L, extra[k], true);
+        if (di || outputs) {  // the rotation rule's record (render_common): a frame on another lane that writes one of them waits
+            for (int k = 0; k < 3; k++) L.last_dn[k] = query ? extra[k] : nullptr;
+            L.last_di[0] = extra[3]; L.last_di[1] = extra[4];
+        }
         if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
     }
     // the cache: the previous call (on whichever lane it ran) has finished with it before this one touches it
@@ -2300,6 +2334,15 @@ PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is
     fr.inv_spp = 1.0f / (float)c->gs.SamplesPerPixel;
     fr.roughness_threshold = s->RoughnessThreshold;
     fr.visualize = s->IsHashGridVisualizationEnabled ? 1u : 0u;
+    if (di) {  // (the query reads them indexed like `out`: rect-sized; the update, which demands the whole frame, as RenderSize texels)
+        fr.di_diffuse = static_cast<const float4*>(di->Diffuse);
+        fr.di_specular = static_cast<const float4*>(di->Specular);
+        fr.di_w = w; fr.di_h = h;
+    }
+    fr.dn_mode = dn.mode;
+    fr.spec_hit_dist = dn.spec_hit_dist;
+    fr.dn_diffuse = dn.diffuse;
+    fr.dn_specular = dn.specular;
     ShGrid g{};
     g.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
     g.scene_scale = scene_scale;
@@ -2312,27 +2355,28 @@ PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is
         const PixelMap pu = make_pixel_map(gw, gh, PtRect{ 0, 0, gw, gh });
         EventPair* ev = c->profiling ? next_events(c, 1) : nullptr;  // pt_get_profile: the update under ms_traverse
         if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = launch_sharc_update(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: update launch: ") + hipGetErrorString(e));
+        if (const hipError_t e = (di ? launch_sharc_update_ex : launch_sharc_update)(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, who + ": update launch: " + hipGetErrorString(e));
         if (ev) (void)hipEventRecord(ev->b, L.stream);
     }
     if (st == PT_OK && (stages & PT_SHARC_RESOLVE)) {
         EventPair* ev = c->profiling ? next_events(c, 3) : nullptr;  // ... the resolve under ms_tail
         if (ev) (void)hipEventRecord(ev->a, L.stream);
         if (const hipError_t e = launch_sharc_resolve(map(), acc_frames, max_stale, L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: resolve launch: ") + hipGetErrorString(e));
+            st = fail(c, PT_ERR_HIP, who + ": resolve launch: " + hipGetErrorString(e));
         else std::swap(c->sh_accum, c->sh_resolved);  // Raytracing.ixx:147
         if (ev) (void)hipEventRecord(ev->b, L.stream);
     }
     if (st == PT_OK && query) {
         EventPair* ev = c->profiling ? next_events(c, 2) : nullptr;  // ... the query under ms_shade
         if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = launch_sharc_query(sv, pm, fr, g, map(), dev_out, c->d_sh_counters, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: query launch: ") + hipGetErrorString(e));
+        if (const hipError_t e = (di || outputs ? launch_sharc_query_ex : launch_sharc_query)(sv, pm, fr, g, map(), dev_out, c->d_sh_counters, side_pass_grid(c, pm.n_slots), L.stream);
+            e != hipSuccess)
+            st = fail(c, PT_ERR_HIP, who + ": query launch: " + hipGetErrorString(e));
         if (ev) (void)hipEventRecord(ev->b, L.stream);
     }
     const hipError_t e0 = hipEventRecord(c->ev_sh, L.stream);
-    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string("pt_render_sharc: cache event: ") + hipGetErrorString(e0));
+    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": cache event: " + hipGetErrorString(e0));
     if (st == PT_OK && timed) {
         unsigned long long counters[2] = { 0, 0 };
         PT_HIP(c, hipEventRecord(c->ev1, L.stream));
@@ -2346,7 +2390,7 @@ PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is
         stats->pixels = query ? out_px : 0;
         stats->paths = (query ? out_px * c->gs.SamplesPerPixel : 0) + ((stages & PT_SHARC_UPDATE) ? (uint64_t)gw * gh : 0);
     }
-    st = publish_lane_to_caller(c, L, "pt_render_sharc", st);
+    st = publish_lane_to_caller(c, L, who.c_str(), st);
     if (st != PT_OK) return st;
     c->sh_valid = true;
     c->sh_scene = c->set_scene_calls;
@@ -2355,6 +2399,19 @@ PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is
         PT_HIP(c, hipStreamSynchronize(c->stream));
     }
     return PT_OK;
+}
+
+PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    return sharc_call(c, rect, out, out_is_device, s, nullptr, nullptr, stats, false, "pt_render_sharc");
+}
+
+PtStatus pt_render_sharc_ex(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di,
+                            const PtDenoiserOutputs* outputs, PtStats* stats)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    return sharc_call(c, rect, out, out_is_device, s, di, outputs, stats, true, "pt_render_sharc_ex");
 }
 
 PtStatus pt_sharc_download(PtContext* c, void* keys, void* voxels, uint32_t capacity)

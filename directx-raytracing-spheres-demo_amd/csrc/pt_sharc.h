@@ -8,12 +8,14 @@
 //   sh_add / sh_resolve_slot                 the voxel: 32-bit integer sums (order-independent), the per-frame resolve
 //   sh_update_path                           one path of the sparse update pass
 //   sh_query_pixel                           one pixel of the frame: pt_render's loop with the cache look-up in it
+//   sh_update_path_ex / sh_query_pixel_ex    the same two with the extras of pt_render_sharc_ex (row N18, spec S24): the frame's direct
+//                                            illumination read from the caller's buffers, the denoiser outputs of spec S13 written
 // The closest-hit query is a functor trace(o, d, tmin, tmax, t, id), the surface a functor material(id, o, d, t, primary) -> HitMaterial,
-// the radiance of a ray that left the scene a functor env(d).
+// the radiance of a ray that left the scene a functor env(d).  A trace that misses returns id = 0xFFFFFFFF and t = tmax.
 //
 // Out of scope: the anti-firefly filter; the compaction pass and its HashCopyOffset buffer (SHARC.hlsl:58-61: a hole an eviction
-// leaves is reused by the next insert instead); DI and denoiser outputs through the cache; re-loading the update path's first vertex
-// from a G-buffer (the path traces its own primary ray).
+// leaves is reused by the next insert instead); re-loading the update path's first vertex from a G-buffer (the path traces its own
+// primary ray).
 #pragma once
 
 #include "pt_surface.h"
@@ -57,6 +59,14 @@ struct ShFrame {
     float throughput_threshold, inv_spp;
     float roughness_threshold;  // update
     uint32_t visualize;         // query: IsHashGridVisualizationEnabled
+    // pt_render_sharc_ex (spec S24), read by the _ex functions only; all zero = off
+    const float4* di_diffuse;   // the frame's direct illumination, DI = Diffuse.rgb + Specular.rgb; null = none.  Update: one texel per
+    const float4* di_specular;  // pixel of the di_w x di_h frame, row-major; query: indexed like `out`
+    uint32_t di_w, di_h;        // update: RenderSize
+    uint32_t dn_mode;           // query: 0 Denoiser::None, 1 DLSSRayReconstruction, 2 NRDReBLUR, 3 NRDReLAX
+    float* spec_hit_dist;       // query, mode 1; indexed like `out`, as the next two
+    float4* dn_diffuse;         // query, modes 2 / 3
+    float4* dn_specular;
 };
 
 // ---------------------------------------------------------------------------------------------------- hash grid
@@ -277,10 +287,27 @@ PT_HD void sh_set_throughput(ShState& st, f3 T)
     st.weight[0] = st.skipped ? st.weight[0] * T : T;
 }
 
+// clamp(uint(u * n), 0, n - 1) of the update's LOAD (Raytracing.hlsl:69); a product that is NaN or below 1 is texel 0
+PT_HD uint32_t sh_texel(float u, uint32_t n)
+{
+    const float f = u * (float)n;
+    return !(f >= 1.0f) ? 0u : (f >= (float)n ? n - 1u : (uint32_t)f);
+}
+
+// DI = Diffuse.rgb + Specular.rgb of one texel (one addition per channel, .w is not read); true = any(DI > 0), the reference's isDIValid (:161)
+PT_HD bool sh_load_di(const ShFrame& fr, size_t index, f3& DI)
+{
+    const float4 a = fr.di_diffuse[index], b = fr.di_specular[index];
+    DI = load3(a) + load3(b);
+    return DI.x > 0.0f || DI.y > 0.0f || DI.z > 0.0f;
+}
+
 // One path of the update pass: path (x, y) of the grid fr.cam was made for (InvW, InvH = 1 / grid size).
-template <typename TraceFn, typename MaterialFn, typename EnvFn>
-PT_HD void sh_update_path(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
-                          uint32_t& rays, uint32_t& failed)
+// kEx (spec S24) with fr.di_diffuse: the first vertex takes the DI of the texel the path's UV falls in, and the second vertex's emission
+// is dropped where that DI is valid, unless the path left the first one through the transmission lobe (:302, :311).
+template <bool kEx, typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_path_t(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                            uint32_t& rays, uint32_t& failed)
 {
     uint32_t rng = rng_init(x, y, fr.frame_index);
     CameraParams cam = fr.cam;
@@ -288,6 +315,13 @@ PT_HD void sh_update_path(const ShFrame& fr, const ShGrid& g, const ShMap& m, ui
     f3 o, d;
     float tmin, tmax;
     primary_ray(cam, x, y, o, d, tmin, tmax);
+    const bool with_di = kEx && fr.di_diffuse != nullptr;
+    uint32_t texel = 0u;
+    bool drop_emission = false;  // kEx: the next vertex is the second one and the first one's DI covers its emission
+    if (with_di) {  // u, v as primary_ray forms them
+        const float u = ((float)x + 0.5f + cam.JitterX) * cam.InvW, v = ((float)y + 0.5f + cam.JitterY) * cam.InvH;
+        texel = sh_texel(v, fr.di_h) * fr.di_w + sh_texel(u, fr.di_w);
+    }
     ShState st;
     st.length = 0u;
     st.skipped = false;
@@ -305,7 +339,15 @@ PT_SH_UNROLL
         HitMaterial hm = material(id, o, d, t, bounce == 0u);
         hm.bsdf.Roughness = pt_max(hm.bsdf.Roughness, fr.roughness_threshold);  // :307
         const f3 front_normal = hm.hf.front ? hm.hf.N : -hm.hf.N;
-        if (!sh_update_hit(g, m, st, hm.hf.P, front_normal, hm.emission, rng_float(rng), failed)) return;
+        f3 radiance = hm.emission;
+        bool di_valid = false;
+        if (with_di && bounce == 0u) {
+            f3 DI;
+            di_valid = sh_load_di(fr, texel, DI);
+            if (di_valid) radiance = DI + radiance;
+        }
+        if (kEx && bounce == 1u && drop_emission) radiance = make_f3(0.0f, 0.0f, 0.0f);
+        if (!sh_update_hit(g, m, st, hm.hf.P, front_normal, radiance, rng_float(rng), failed)) return;
         if (bounce == fr.bounces) return;
         const Surf surf = surf_init(hm.hf.front, hm.hf.N, hm.Ns);
         const f3 V = -d;
@@ -316,6 +358,7 @@ PT_SH_UNROLL
         f3 L;
         int lobe;
         if (!bsdf_sample(hm.bsdf, surf, V, w, rnd, L, lobe)) return;
+        if (kEx && bounce == 0u) drop_emission = di_valid && lobe != kLobeTransmission;
         float pdf;
         f3 f;
         if (!bsdf_pdf_eval(hm.bsdf, surf, L, V, w, lobe, pdf, f)) return;
@@ -331,6 +374,20 @@ PT_SH_UNROLL
         d = L;
         tmin = 0.0f; tmax = kInf;
     }
+}
+
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_path(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                          uint32_t& rays, uint32_t& failed)
+{
+    sh_update_path_t<false>(fr, g, m, x, y, trace, material, env, rays, failed);
+}
+
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_path_ex(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                             uint32_t& rays, uint32_t& failed)
+{
+    sh_update_path_t<true>(fr, g, m, x, y, trace, material, env, rays, failed);
 }
 
 // ---------------------------------------------------------------------------------------------------- query (SHARC_QUERY)
@@ -353,9 +410,19 @@ PT_HD f3 sh_debug_colour(uint64_t key)
 
 // One pixel of the frame: pt_render's loop (one primary hit shared by the samples, the RNG running on across them) with the cache
 // look-up at every hit; m.keys = null: the cache is off.  With no voxel found the arithmetic is pt_render's, operation for operation.
-template <typename TraceFn, typename MaterialFn, typename EnvFn>
-PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t px, uint32_t py, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
-                        uint32_t& rays)
+// kEx (spec S24; what the pixel's finish needs beside the radiance returned): px_flags, hd = sample 0's bounce-1 hit distance (+inf
+// without one), prim = the primary hit's emission (the NRD modes only).  In modes 0 / 1 with fr.di_diffuse the sample takes the pixel's
+// DI (at out_index) at bounce 0 where it is valid, and drops its bounce-1 emission unless it left through the transmission lobe.
+enum : uint32_t {
+    kShPxHit = 1u,         // the primary ray hit
+    kShPxDiffuse = 2u,     // isDiffuse of spec S13 (sample 0's lobe at bounce 0; true where it spawned no bounce-1 ray)
+    kShPxVisualised = 4u,  // the radiance is the hash-grid visualisation's colour
+    kShPxDrop = 8u,        // (within a sample) the bounce-1 emission is covered by the DI
+};
+
+template <bool kEx, typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD f3 sh_query_pixel_t(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t px, uint32_t py, uint32_t out_index, TraceFn&& trace, MaterialFn&& material,
+                          EnvFn&& env, uint32_t& rays, uint32_t& px_flags, float& hd, f3& prim)
 {
     f3 o0, d0;
     float tmin, tmax, t0;
@@ -366,16 +433,23 @@ PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint
     if (id0 == 0xFFFFFFFFu) return env(d0);
     uint32_t rng = rng_init(px, py, fr.frame_index);
     f3 acc = make_f3(0.0f, 0.0f, 0.0f);
+    const bool with_di = kEx && fr.di_diffuse != nullptr && fr.dn_mode < 2u;  // (the NRD modes' query does not read it: :155-158)
+    if (kEx) { px_flags = kShPxHit | kShPxDiffuse; hd = kInf; }
+    // INVARIANT (kEx): iterations with sample < spp are the samples.  In the NRD modes one more follows with sample == spp, the
+    // material-only pass: it fetches the primary hit's material into prim and leaves the bounce loop at once.  Nothing else of the body
+    // may run in it -- no RNG draw, no ray, no write of hd or of a flag the finish reads -- and it adds srad = 0 to acc before the pixel returns.
     for (uint32_t sample = 0;;) {
         f3 o = o0, d = d0, T = make_f3(1.0f, 1.0f, 1.0f), srad = make_f3(0.0f, 0.0f, 0.0f);
         float t = t0, previous_roughness = 0.0f;
         uint32_t id = id0;
+        if (kEx) px_flags &= ~kShPxDrop;
         for (uint32_t bounce = 0;; bounce++) {
             if (id == 0xFFFFFFFFu) {
                 srad = srad + T * env(d);  // :254
                 break;
             }
             const HitMaterial hm = material(id, o, d, t, bounce == 0u);
+            if (kEx && sample == fr.spp) { prim = hm.emission; break; }  // the finish's pass (below)
             if (m.keys) {
                 float voxel;
                 const uint64_t key = sh_key_at(g, hm.hf.P, hm.hf.front ? hm.hf.N : -hm.hf.N, voxel);
@@ -387,6 +461,7 @@ PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint
                             if (fr.visualize) {  // :279-284: the primary hit's cell
                                 const HitMaterial h0 = material(id0, o0, d0, t0, true);
                                 float v0;
+                                if (kEx) px_flags |= kShPxVisualised;
                                 return sh_debug_colour(sh_key_at(g, h0.hf.P, h0.hf.front ? h0.hf.N : -h0.hf.N, v0));
                             }
                             srad = srad + T * sh_radiance(v);  // :286
@@ -396,7 +471,15 @@ PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint
                 }
             }
             const bool t_finite = is_finite(T.x) && is_finite(T.y) && is_finite(T.z);
-            if (hm.emission.x != 0.0f || hm.emission.y != 0.0f || hm.emission.z != 0.0f || !t_finite) srad = srad + T * hm.emission;  // :320
+            f3 emission = hm.emission;
+            bool di_valid = false;
+            if (kEx && bounce == 1u && (px_flags & kShPxDrop)) emission = make_f3(0.0f, 0.0f, 0.0f);  // :302
+            if (with_di && bounce == 0u) {
+                f3 DI;
+                di_valid = sh_load_di(fr, out_index, DI);
+                if (di_valid) srad = srad + (DI + T * emission);  // :318, unconditional
+            }
+            if (!di_valid && (emission.x != 0.0f || emission.y != 0.0f || emission.z != 0.0f || !t_finite)) srad = srad + T * emission;  // :320
             const bool last = bounce == fr.bounces;
             if (last && sample + 1u == fr.spp) break;  // the sample drawn on the final iteration is never used
             const Surf surf = surf_init(hm.hf.front, hm.hf.N, hm.Ns);
@@ -408,6 +491,7 @@ PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint
             f3 L;
             int lobe;
             if (!bsdf_sample(hm.bsdf, surf, V, w, rnd, L, lobe)) break;
+            if (kEx && di_valid && lobe != kLobeTransmission) px_flags |= kShPxDrop;
             float pdf;
             f3 f;
             if (!bsdf_pdf_eval(hm.bsdf, surf, L, V, w, lobe, pdf, f)) break;
@@ -425,15 +509,65 @@ PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint
             d = L;
             trace(o, d, 0.0f, kInf, t, id);
             rays++;
+            if (kEx && sample == 0u && bounce == 0u) {  // :235-239, before the cache look-up
+                if (lobe != kLobeDiffuse) px_flags &= ~kShPxDiffuse;  // (transmission counts as specular)
+                hd = t;  // (a miss returns its tmax: +inf)
+            }
         }
-        const f3 total = acc + srad;  // :373
-        sample++;
-        if (sample == fr.spp) {
+        const f3 total = acc + srad;  // :373 (the finish's pass adds 0 to a sum that is finite or not returned)
+        // kEx, the NRD modes: prim is re-derived at the finish, not carried through the samples, by one more pass that enters the bounce
+        // loop only as far as the primary hit's material -- the loop's own call, not another inlined copy of it (9 VGPRs in the
+        // textured instances)
+        const bool finish_pass = kEx && fr.dn_mode >= 2u && sample + 1u == fr.spp;
+        if (!(kEx && sample == fr.spp)) sample++;
+        if (sample == fr.spp && !finish_pass) {
             if (is_finite(total.x) && is_finite(total.y) && is_finite(total.z)) return total * fr.inv_spp;
             return make_f3(0.0f, 0.0f, 0.0f);
         }
         acc = total;
     }
+}
+
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD f3 sh_query_pixel(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t px, uint32_t py, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                        uint32_t& rays)
+{
+    uint32_t px_flags = 0u;
+    float hd = 0.0f;
+    f3 prim = make_f3(0.0f, 0.0f, 0.0f);
+    return sh_query_pixel_t<false>(fr, g, m, px, py, 0u, trace, material, env, rays, px_flags, hd, prim);
+}
+
+PT_HD float4 sh_f4(f3 v, float w)
+{
+    float4 r;  // (member-wise: the host build's float4 is a plain struct)
+    r.x = v.x; r.y = v.y; r.z = v.z; r.w = w;
+    return r;
+}
+
+// One pixel of pt_render_sharc_ex's frame, stored: `out` and the outputs of fr.dn_mode at out_index, as spec S13 writes them with
+// res = the query's radiance.  A primary miss and a visualised pixel write only `out`.
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_query_pixel_ex(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t px, uint32_t py, uint32_t out_index, TraceFn&& trace, MaterialFn&& material,
+                             EnvFn&& env, uint32_t& rays, float4* out)
+{
+    uint32_t px_flags = 0u;
+    float hd = kInf;
+    f3 prim = make_f3(0.0f, 0.0f, 0.0f);
+    const f3 res = sh_query_pixel_t<true>(fr, g, m, px, py, out_index, trace, material, env, rays, px_flags, hd, prim);
+    const bool plain = !(px_flags & kShPxHit) || (px_flags & kShPxVisualised) != 0u;  // a primary miss (res = the environment), a visualised pixel
+    const bool diffuse = (px_flags & kShPxDiffuse) != 0u;
+    if (plain || fr.dn_mode < 2u) {
+        out[out_index] = sh_f4(res, 1.0f);
+        if (!plain && fr.dn_mode == 1u && !diffuse && is_finite(hd)) fr.spec_hit_dist[out_index] = hd;
+        return;
+    }
+    const f3 ind = make_f3(pt_max(res.x - prim.x, 0.0f), pt_max(res.y - prim.y, 0.0f), pt_max(res.z - prim.z, 0.0f));
+    const f3 zero = make_f3(0.0f, 0.0f, 0.0f);
+    const f3 dif = zero + (diffuse ? ind : zero), spe = zero + (diffuse ? zero : ind);  // (S13's sums with direct halves of 0: :403-405)
+    fr.dn_diffuse[out_index] = sh_f4(dif, diffuse ? hd : 0.0f);
+    fr.dn_specular[out_index] = sh_f4(spe, diffuse ? 0.0f : hd);
+    out[out_index] = sh_f4(prim, 1.0f);
 }
 
 #if defined(__HIPCC__)
@@ -446,6 +580,11 @@ hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const Sh
 hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream);
 hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                               uint32_t grid, hipStream_t stream);
+// pt_render_sharc_ex (spec S24): the instances that read fr's DI (update, query) and write its denoiser outputs (query)
+hipError_t launch_sharc_update_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
+                                  hipStream_t stream);
+hipError_t launch_sharc_query_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                                 uint32_t grid, hipStream_t stream);
 #endif
 
 }  // namespace pt

@@ -1,7 +1,8 @@
-// pt_sharc.hip -- the three kernels of row N14 (pt_render_sharc, DESIGN.md spec S20) over pt_sharc.h:
+// pt_sharc.hip -- the three kernels of rows N14 and N18 (pt_render_sharc, pt_render_sharc_ex; DESIGN.md specs S20 and S24) over pt_sharc.h:
 //   update   one lane per path of the downscaled grid, one 8x8 block of paths per wave64 (PixelMap): sh_update_path
 //   resolve  one lane per slot of the hash map, streaming: sh_resolve_slot, 128-bit loads and stores
 //   query    one lane per pixel, one 8x8 pixel block per wave64: sh_query_pixel
+// kEx: the instances of pt_render_sharc_ex with a DI or denoiser outputs (sh_update_path_ex, sh_query_pixel_ex, which stores the pixel itself)
 // Rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory), chosen as
 // pt_restir.hip chooses it.
 #include "pt_trace.h"
@@ -11,7 +12,7 @@ namespace pt {
 
 namespace {
 
-template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha>
+template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha, bool kEx>
 __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, PixelMap pm, ShFrame fr, ShGrid g, ShMap m, float4* __restrict__ out,
                                                                  unsigned long long* __restrict__ counters)
 {
@@ -44,9 +45,13 @@ __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, P
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
         if (!pr.valid) continue;
-        if (kQuery) {
+        if (kQuery && kEx) {
+            sh_query_pixel_ex(fr, g, m, pr.px, pr.py, pr.out_index, trace, material, env, rays, out);
+        } else if (kQuery) {
             const f3 c = sh_query_pixel(fr, g, m, pr.px, pr.py, trace, material, env, rays);
             out[pr.out_index] = make_float4(c.x, c.y, c.z, 1.0f);
+        } else if (kEx) {
+            sh_update_path_ex(fr, g, m, pr.px, pr.py, trace, material, env, rays, failed);
         } else {
             sh_update_path(fr, g, m, pr.px, pr.py, trace, material, env, rays, failed);
         }
@@ -55,34 +60,34 @@ __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, P
     if (!kQuery) block_atomic_add(counters + 1, failed);
 }
 
-template <bool kQuery, bool kTex, bool kAlpha>
+template <bool kQuery, bool kEx, bool kTex, bool kAlpha>
 hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                     uint32_t grid, hipStream_t stream)
 {
     const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
     const uint32_t threads = traverse_threads(lds_scene);
     const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha>)
-                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha>);
+    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx>)
+                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx>);
     if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (lds_scene) {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
     } else {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
     }
     return hipGetLastError();
 }
 
-template <bool kQuery>
+template <bool kQuery, bool kEx>
 hipError_t launch_any(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                       uint32_t grid, hipStream_t stream)
 {
     // the textured variants only where textures exist; the alpha-tested walk only where some sphere's hits are tested against a map
-    if (!sv.tex_maps) return launch_t<kQuery, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
-    if (sv.alpha_tested) return launch_t<kQuery, true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
-    return launch_t<kQuery, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    if (!sv.tex_maps) return launch_t<kQuery, kEx, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    if (sv.alpha_tested) return launch_t<kQuery, kEx, true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_t<kQuery, kEx, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
 }
 
 constexpr uint32_t kResolveThreads = 256;
@@ -105,13 +110,25 @@ __global__ __launch_bounds__(kResolveThreads) void sharc_resolve_kernel(ShMap m,
 hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
                                hipStream_t stream)
 {
-    return launch_any<false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+    return launch_any<false, false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+}
+
+hipError_t launch_sharc_update_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
+                                  hipStream_t stream)
+{
+    return launch_any<false, true>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
 }
 
 hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                               uint32_t grid, hipStream_t stream)
 {
-    return launch_any<true>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_any<true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+}
+
+hipError_t launch_sharc_query_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
+                                 uint32_t grid, hipStream_t stream)
+{
+    return launch_any<true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
 }
 
 hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream)

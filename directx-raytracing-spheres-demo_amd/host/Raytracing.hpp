@@ -206,6 +206,45 @@ struct Raytracing {
         return stats;
     }
 
+    // The same with IsDIEnabled = isReSTIRDIEnabled and GraphicsSettings.Denoiser (App.cpp:1255-1268; row N18, pt_render_sharc_ex): the
+    // reference's default frame.  di: null = no DI; buffers: the denoiser outputs when GraphicsSettings.Denoiser names one (required
+    // then).  The constants go up with Denoiser = None, the mode travels with the call.
+    PtStats Render(std::vector<Float4>& radiance, SHARC& sharc, const SHARCSettings& settings, const DirectLighting* di, DenoiserBuffers* buffers)
+    {
+        PtGraphicsSettings constants = m_graphicsSettings;
+        constants.Denoiser = 0;
+        ThrowIfFailed(pt_set_constants(m_ctx, &constants), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtSharcSettings s{};
+        s.Capacity = sharc.GetCapacity();
+        s.DownscaleFactor = settings.DownscaleFactor;
+        s.SceneScale = settings.SceneScale;
+        s.RoughnessThreshold = settings.RoughnessThreshold;
+        s.AccumulationFrames = settings.AccumulationFrames;
+        s.MaxStaleFrames = settings.MaxStaleFrames;
+        s.IsAntiFireflyEnabled = settings.IsAntiFireflyEnabled ? 1u : 0u;
+        s.IsHashGridVisualizationEnabled = settings.IsHashGridVisualizationEnabled;
+        s.ResetHistory = sharc.NeedsReset() ? 1u : 0u;
+        PtDirectLighting lighting{};
+        if (di) {
+            lighting.Diffuse = di->Diffuse;
+            lighting.Specular = di->Specular;
+        }
+        PtDenoiserOutputs outputs{};
+        if (m_graphicsSettings.Denoiser != 0) {
+            if (!buffers) throw std::invalid_argument("Raytracing::Render: GraphicsSettings.Denoiser needs its DenoiserBuffers");
+            outputs.Denoiser = m_graphicsSettings.Denoiser;
+            outputs.Diffuse = buffers->Diffuse;
+            outputs.Specular = buffers->Specular;
+            outputs.SpecularHitDistance = buffers->SpecularHitDistance;
+        }
+        PtStats stats{};
+        ThrowIfFailed(pt_render_sharc_ex(m_ctx, nullptr, radiance.data(), 0, &s, di ? &lighting : nullptr, m_graphicsSettings.Denoiser != 0 ? &outputs : nullptr, &stats),
+                      m_ctx, "pt_render_sharc_ex");
+        sharc.ClearReset();
+        return stats;
+    }
+
 private:
     PtContext* m_ctx;
     PtGraphicsSettings m_graphicsSettings{};

@@ -25,6 +25,9 @@
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_restir_di_sampled     the same with Power_RIS / ReGIR_RIS local-light presampling (spec S22)                 Source/RTXDI.ixx:209-226
  *   pt_restir_di_ex          ... and with BRDF candidates and the boiling filter (spec S23)                         Source/App.cpp:1092-1101
+ *   pt_render_sharc          Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings) (a stand-in for SHARC, spec S20)   Source/Raytracing.ixx:114-148
+ *   pt_render_sharc_ex       ... with IsDIEnabled and a denoiser, the reference's default frame (spec S24)   Source/App.cpp:1255-1268,
+ *                            Shaders/Raytracing.hlsl:150-163, 302-318, 376-414
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
@@ -452,6 +455,33 @@ PtStatus pt_light_ris_download(PtContext *ctx, float *pyramid, uint32_t *n_pyram
  * PT_ERR_INVALID_ARG: a null argument; a value outside the ranges of PtSharcSettings; a rect outside RenderSize.  PT_ERR_UNSUPPORTED:
  * IsAntiFireflyEnabled; IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as pt_render. */
 PtStatus pt_render_sharc(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtSharcSettings *settings, PtStats *stats);
+
+/* Row N18 -- pt_render_sharc with the frame's direct illumination and the denoiser outputs (the SHARC permutations of
+ * Shaders/Raytracing.hlsl with IsDIEnabled and Denoiser != None: :150-163, 302, 311, 318, 376-414; DESIGN.md spec S24), the middle of the
+ * reference's default frame GBufferGeneration -> RTXDI -> Raytracing::Render(SHARC) -> DLSS-RR.  di == NULL and outputs == NULL: the call
+ * IS pt_render_sharc -- the same cache, restart rules, stages, stats, profiling slots and bits; calls of the two entry points may
+ * alternate on one context.  PtGraphicsSettings.IsDIEnabled is ignored (as for pt_render_with_di); the constants' Denoiser stays 0, the
+ * mode arrives in `outputs`.
+ *   di       DI = Diffuse.rgb + Specular.rgb, e.g. what pt_restir_di* wrote.  A pixel's DI counts where the primary ray hit and
+ *            any(DI > 0) (the reference's rule; pt_render_with_di counts every primary surface).  UPDATE: the path's first vertex takes
+ *            the DI of the texel its jittered UV falls in, and the second vertex's emission is dropped where that DI counts (unless the
+ *            path left through the transmission lobe): the buffers are RenderSize, so with di and UPDATE rect must be NULL or the whole
+ *            frame.  QUERY, outputs NULL or Denoiser 1: every sample adds DI at bounce 0 and drops its bounce-1 emission likewise; nothing
+ *            is added after the sample average, so a non-finite DI zeroes the pixel.  QUERY, Denoiser 2 / 3: DI is not read, Diffuse /
+ *            Specular carry no direct halves, the kept bounce-1 emission is the direct light (the reference's rule).  A QUERY-only call
+ *            takes rect-sized buffers, as pt_render_with_di.
+ *   outputs  as pt_render_denoiser (spec S13) with res = the query's radiance: Denoiser 1 writes SpecularHitDistance where the primary
+ *            ray hit, sample 0 left through a non-diffuse lobe and its bounce-1 ray hit; Denoiser 2 / 3 write out = (primary emission, 1),
+ *            Diffuse / Specular on hits.  isDiffuse and the hit distance do not depend on the cache.  A pixel of the hash-grid
+ *            visualisation writes only `out`.  outputs->Diffuse / Specular may be di->Diffuse / Specular: the update reads them before
+ *            the query writes.
+ * Ordering: as pt_render_sharc; with di the lane also waits for everything queued on the context's stream (DI made by pt_restir_di* just
+ * before is ordered by the lane's own stream); the DI and output buffers are held to the buffer rotation rule with the lane's frame buffers.
+ * PT_ERR_INVALID_ARG also: a null or misaligned DI or output buffer, an output that overlaps another or `out`, a DI buffer that overlaps
+ * `out` or an output (other than being Denoiser 2 / 3's Diffuse or Specular itself, as above), Denoiser outside 1..3, di with UPDATE and
+ * a partial rect.  On any error nothing is written. */
+PtStatus pt_render_sharc_ex(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtSharcSettings *settings,
+                            const PtDirectLighting *di, const PtDenoiserOutputs *outputs, PtStats *stats);
 
 /* Test hooks of row N14: the cache as the last pt_render_sharc call left it -- `capacity` keys (uint64, 0 = empty) and resolved voxels
  * (4 x uint32: fixed-point RGB sums, samples | frames << 16 | stale << 24) to HOST memory -- and the reverse, which installs a cache made

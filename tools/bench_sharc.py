@@ -18,11 +18,18 @@ bytes per second against a device-to-device copy that moves the same number of b
 Then the image quality on the same scene at --quality-size: the RMSE of a 1-spp pt_render_sharc frame and of a 1-spp pt_render frame
 against --reference-frames accumulated pt_render frames.
 
+pt_render_sharc_ex (row N18) per size, with the DI one pt_render_gbuffer + pt_restir_di_ex pair made for the view and DLSS-RR's output
+(mode 1): the whole call and UPDATE | RESOLVE over the warm cache as above (ex_query_in_call = their difference), its surcharge over
+pt_render_sharc, and beside it pt_render_with_di's surcharge over pt_render (a gather launch of 32 B per pixel); then the default
+frame's chain pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex -> pt_ray_reconstruction (to 2x the size), the median wall
+time from the first call to the end of the wait, next to the same chain with pt_render_with_di in the cache's place.
+
     python tools/bench_sharc.py [--calls 100 --warmup 10 --fill 12 --sizes 1920x1080,3840x2160 --quality-size 480x270 --reference-frames 2048]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -30,6 +37,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402  (device buffers and events only)
 import dxrs_amd_loader  # noqa: E402,F401
 import dxrs_amd  # noqa: E402
+from dxrs_amd.abi_types import GBUFFER_CHANNELS, RESTIR_DI_INPUTS  # noqa: E402
 
 UPDATE, RESOLVE, QUERY = 1, 2, 4
 RESOLVE_BYTES_PER_SLOT, RESOLVE_BYTES_PER_OCCUPIED_SLOT = 8, 48
@@ -118,6 +126,60 @@ def main():
         rays_call = r.render_sharc_device(out.data_ptr(), want_stats=True, **st).rays
         rays_query = r.render_sharc_device(out.data_ptr(), want_stats=True, stages=QUERY, **st).rays
         rays_plain = r.render_device(out.data_ptr(), want_stats=True).rays
+        # ---- row N18: the same frame with the DI of pt_restir_di_ex and DLSS-RR's SpecularHitDistance
+        width = dict(GBUFFER_CHANNELS)
+        gb = {n: torch.zeros((H * W, width[n]), dtype=torch.float32, device="cuda") for n in set(RESTIR_DI_INPUTS) | {"DiffuseAlbedo", "SpecularAlbedo"}}
+        dd, ds = (torch.zeros((H * W, 4), dtype=torch.float32, device="cuda") for _ in range(2))
+        shd = torch.zeros(H * W, dtype=torch.float32, device="cuda")
+        up = torch.zeros((4 * H * W, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        cam = host.camera_matrices(W, H, jitter=False)
+        ptrs = {n: b.data_ptr() for n, b in gb.items()}
+
+        def make_di(reset=False):
+            r.render_gbuffer_device(ptrs)
+            r.restir_di_device(W, H, dict({n: ptrs[n] for n in RESTIR_DI_INPUTS}, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), frame_index=frame[0], reset_history=reset,
+                               candidates=dict(brdf_samples=1, boiling_filter=0.2))
+
+        next_frame(W, H)
+        make_di(True)
+        r.synchronize()
+
+        def stage_ex(stages):
+            next_frame(W, H)
+            r.render_sharc_ex_device(out.data_ptr() if stages & QUERY else 0, dd.data_ptr(), ds.data_ptr(), None, 1, dict(SpecularHitDistance=shd.data_ptr()), stages=stages, **st)
+
+        def with_di():
+            next_frame(W, H)
+            r.render_with_di_device(out.data_ptr(), dd.data_ptr(), ds.data_ptr(), None, 1, dict(SpecularHitDistance=shd.data_ptr()))
+
+        ms["ex_call"] = warm(lambda: stage_ex(7))
+        ms["ex_update_resolve"] = warm(lambda: stage_ex(UPDATE | RESOLVE))
+        ms["ex_query_in_call"] = ms["ex_call"] - ms["ex_update_resolve"]
+        ms["ex_update_resolve_surcharge"] = ms["ex_update_resolve"] - ms["update_resolve"]
+        ms["ex_query_surcharge"] = ms["ex_query_in_call"] - ms["query_in_call"]
+        ms["pt_render_with_di"] = median_ms(stream, with_di, args.calls, args.warmup)
+        ms["with_di_surcharge"] = ms["pt_render_with_di"] - ms["pt_render"]
+
+        def chain(middle):
+            wall = []
+            for k in range(args.warmup + args.calls // 2):
+                next_frame(W, H)
+                t0 = time.perf_counter()
+                make_di()
+                middle()
+                r.ray_reconstruction_device((W, H), (2 * W, 2 * H), dict(Color=out.data_ptr(), Depth=ptrs["LinearDepth"], MotionVector=ptrs["MotionVector"],
+                                                                         NormalRoughness=ptrs["NormalRoughness"], DiffuseAlbedo=ptrs["DiffuseAlbedo"],
+                                                                         SpecularAlbedo=ptrs["SpecularAlbedo"], SpecularHitDistance=shd.data_ptr(), Output=up.data_ptr()),
+                                            cam, reset=k == 0)
+                r.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
+            return float(np.median(wall[args.warmup:]))
+
+        r.sharc_upload(keys, voxels)
+        ms["chain_default_frame"] = chain(lambda: r.render_sharc_ex_device(out.data_ptr(), dd.data_ptr(), ds.data_ptr(), None, 1, dict(SpecularHitDistance=shd.data_ptr()), **st))
+        ms["chain_with_di_no_cache"] = chain(lambda: r.render_with_di_device(out.data_ptr(), dd.data_ptr(), ds.data_ptr(), None, 1, dict(SpecularHitDistance=shd.data_ptr())))
+        del gb, dd, ds, shd, up
         res["sizes"][f"{W}x{H}"] = dict({k + "_ms": round(v, 5) for k, v in ms.items()}, call_over_pt_render=round(ms["call"] / ms["pt_render"], 3),
                                         rays_call=int(rays_call), rays_query=int(rays_query), rays_pt_render=int(rays_plain), occupied_slots=occupied, resolve_bytes=model,
                                         resolve_TBps=round(model / (ms["resolve"] * 1e-3) / 1e12, 3), copy_TBps=round(model / (ms["copy"] * 1e-3) / 1e12, 3),

@@ -8,10 +8,11 @@ upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_s
 upscaler when there is one and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
 pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting camera through pt_render_sharc, row N14, the last one tone
 mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendered at the mode's input size through pt_render_gbuffer ->
-pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height; --sharc --restir-di --ray-reconstruction together: the
+reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc]
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc] | --sharc --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
                                         [--ray-reconstruction [performance]]"""
 import argparse
 import os
@@ -105,15 +106,20 @@ def main():
     args = ap.parse_args()
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--frame-gen applies to the plain path-traced frame")
-    if args.sharc and (args.frame_gen or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
+    default_frame = bool(args.sharc and args.restir_di and args.ray_reconstruction)  # the reference's default frame, rows N6 / N17 / N18 / N15
+    if default_frame and (args.frame_gen or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.upscale):
+        ap.error("--sharc --restir-di --ray-reconstruction is the default frame: it takes --light-sampling, --brdf-samples, --boiling-filter, --nis and --bloom only")
+    if default_frame:
+        pass
+    elif args.sharc and (args.frame_gen or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--sharc applies to the plain path-traced frame")
-    if args.ray_reconstruction and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale):
+    if not default_frame and args.ray_reconstruction and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale):
         ap.error("--ray-reconstruction is a path of its own: it takes --nis and --bloom only")
     if args.light_sampling != "uniform" and not args.restir_di:
         ap.error("--light-sampling applies to --restir-di")
     if (args.brdf_samples or args.boiling_filter is not None) and not args.restir_di:
         ap.error("--brdf-samples and --boiling-filter apply to --restir-di")
-    if args.nis is not None and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
+    if args.nis is not None and not default_frame and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
 
@@ -187,6 +193,51 @@ def main():
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
         Image.fromarray(mid.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.frame_gen)
         print(f"frame generation (pt_frame_gen) {w}x{h}: time {args.time} -> {args.out}, time {args.time - args.dt / 2} -> {args.frame_gen}")
+        r.close()
+        return
+    if default_frame:
+        # GBufferGeneration -> RTXDI -> Raytracing::Render(SHARC) -> DLSS-RR (App.cpp:1255-1268): pt_render_gbuffer -> pt_restir_di_ex ->
+        # pt_render_sharc_ex with that DI and mode 1 -> pt_ray_reconstruction, every pass queued on the frame's lane or the context's stream
+        iw, ih = dxrs_amd.load_hip().upscale_input_size(t.UPSCALE_MODES[args.ray_reconstruction], w, h)
+        b = {name: torch.zeros((ih, iw, width), dtype=torch.float32, device="cuda") for name, width in t.RAY_RECONSTRUCTION_INPUTS}
+        b["Output"] = accum
+        gwidth = dict(t.GBUFFER_CHANNELS)
+        gbuf = {name: torch.zeros((ih, iw, gwidth[name]), dtype=torch.float32, device="cuda") for name in t.RESTIR_DI_INPUTS if name not in ("LinearDepth", "MotionVector", "NormalRoughness")}
+        dd, ds = (torch.zeros((ih, iw, 4), dtype=torch.float32, device="cuda") for _ in range(2))
+        torch.cuda.synchronize()
+        gs = t.graphics_settings(iw, ih, bounces=args.bounces, spp=args.spp)
+        ls = {"uniform": None, "power": dict(mode=t.LIGHT_SAMPLING_POWER_RIS), "regir": dict(mode=t.LIGHT_SAMPLING_REGIR_RIS)}[args.light_sampling]
+        cd = dict(brdf_samples=args.brdf_samples, boiling_filter=args.boiling_filter)
+        prev_cam, rays = None, 0
+        for k in range(args.frames):
+            gs.FrameIndex = k
+            cam = host.camera_matrices(iw, ih, jitter_index=k, jitter_count=32, previous=prev_cam)
+            prev_cam = cam
+            r.set_camera(cam)
+            r.set_constants(gs)
+            ptrs = dict({name: v.data_ptr() for name, v in gbuf.items()}, LinearDepth=b["Depth"].data_ptr(), MotionVector=b["MotionVector"].data_ptr(),
+                        NormalRoughness=b["NormalRoughness"].data_ptr())
+            r.render_gbuffer_device(dict(ptrs, DiffuseAlbedo=b["DiffuseAlbedo"].data_ptr(), SpecularAlbedo=b["SpecularAlbedo"].data_ptr()))
+            r.restir_di_device(iw, ih, dict(ptrs, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), frame_index=k, reset_history=k == 0, light_sampling=ls, candidates=cd)
+            rays = r.render_sharc_ex_device(b["Color"].data_ptr(), dd.data_ptr(), ds.data_ptr(), None, t.DENOISER_DLSS_RR,
+                                            dict(SpecularHitDistance=b["SpecularHitDistance"].data_ptr()), want_stats=True, roughness_threshold=0.4, reset_history=k == 0).rays
+            r.ray_reconstruction_device((iw, ih), (w, h), {name: v.data_ptr() for name, v in b.items()}, cam, reset=k == 0)
+            r.synchronize()
+            for buf in (b["SpecularHitDistance"], dd, ds):  # cleared by the caller, after the calls that read them
+                buf.zero_()
+            torch.cuda.synchronize()
+        hdr = accum
+        if args.nis is not None:
+            r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
+            hdr = frame
+        if args.bloom is not None:
+            r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
+        op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
+        r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
+        r.synchronize()
+        Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
+        print(f"default frame (pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex -> pt_ray_reconstruction {args.ray_reconstruction}, {args.frames} frames, "
+              f"{rays} rays in the last) {iw}x{ih} -> {w}x{h} -> {args.out}")
         r.close()
         return
     if args.sharc:
