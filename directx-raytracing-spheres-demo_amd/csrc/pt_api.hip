@@ -1,6 +1,7 @@
 // pt_api.hip -- implementation of the C-ABI (include/pt_api.h) on the HIP runtime: context, device
 // memory, LBVH upload, and the per-frame launch sequence of the wavefront kernel set.  (The passes that only use the context's stream
-// -- tone mapping to frame interpolation -- are in pt_api_post.hip; the context itself is pt_context.h.)
+// -- tone mapping to frame interpolation -- are in pt_api_post.hip, the side passes of a frame -- G-buffer, reservoir pass, radiance cache --
+// in pt_api_side.hip; the context itself is pt_context.h.)
 // There is no CPU fallback here by design: without a HIP device pt_create fails.
 #include <dlfcn.h>
 #include <link.h>
@@ -19,8 +20,6 @@
 #include "pt_context.h"
 #include "pt_beam_cache.h"
 #include "pt_restir.h"
-#include "pt_lightris.h"
-#include "pt_sharc.h"
 
 namespace {
 
@@ -246,52 +245,12 @@ PtStatus update_alpha_classes(PtContext* c)
     return refresh_leaf_ids(c);
 }
 
-PtStatus validate_frame(PtContext* c)
-{
-    if (!c->scene_set) return fail(c, PT_ERR_STATE, "pt_set_scene has not been called");
-    if (!c->accel_valid) return fail(c, PT_ERR_STATE, "pt_build_accel has not been called for the current scene");
-    if (!c->cam_set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    if (!c->gs_set) return fail(c, PT_ERR_STATE, "pt_set_constants has not been called");
-    return PT_OK;
-}
-
 inline uint32_t knob_or(int v, uint32_t dflt) { return v < 0 ? dflt : (uint32_t)v; }
 
 // per-lane traversal-stack entries: one per level for the binary walk; the wide walk pushes up to three per wide level
 uint32_t stack_entries(const PtContext* c, bool wide)
 {
     return wide ? std::max(1u, c->depth) + (c->depth + 1u) / 2u + 2u : std::max(1u, c->depth);
-}
-
-SceneView make_scene_view(const PtContext* c, const Lane* L = nullptr)
-{
-    SceneView sv{};
-    const bool priv = L && L->scene_private;
-    sv.nodes = priv ? L->d_nodes : c->d_nodes;
-    sv.wide = priv ? nullptr : c->d_wide;  // (a lane's refitted private tree is walked through its binary records)
-    sv.sph_sorted = priv ? L->d_sph_sorted : c->d_sph_sorted;
-    sv.sorted_id = c->d_leaf_ids ? c->d_leaf_ids : c->d_sorted_id;
-    sv.alpha_class = c->d_alpha_class;
-    sv.alpha_tested = c->alpha_tested ? 1u : 0u;
-    sv.sph = priv ? L->d_sph : c->d_sph;
-    sv.mats = c->d_mats;
-    sv.n = c->n;
-    sv.n_nodes = c->n_nodes;
-    sv.stack_depth = stack_entries(c, sv.wide != nullptr);
-    // Global-memory scenes: a lane makes at most this many node visits before its wave turns to the sphere tests.  Unbounded, the
-    // lanes that already hold a leaf idle until the longest descent of the wave ends (hundreds of visits in the 2^20-sphere scene's
-    // heavy tail): 3.99 -> 2.54 ms per frame there with any bound from 2 to 24; LDS-resident scenes (coherent, shallow) gain nothing.
-    sv.descent_cap = c->lds_scene ? 0u : knob_or(c->knobs.descent, 8u);
-    sv.lds_scene = c->lds_scene ? 1u : 0u;
-    sv.slab_tiny = c->slab_tiny;  // (of the tree pt_build_accel made: a lane's refitted private tree keeps it, pt_update_spheres does not look at coordinates)
-    for (int i = 0; i < 4; i++) sv.env[i] = c->sd.EnvironmentLightColor[i];
-    if (c->has_textures) { sv.tex = c->d_tex; sv.tex_maps = c->d_tex_maps; sv.rot = (c->rot_gen != c->rot_master_gen && L && L->d_rot && L->rot_gen == c->rot_gen) ? L->d_rot : c->d_rot; }
-    sv.env_tex = c->sd.EnvironmentLightTextureDescriptor;  // ~0u == kNoTexture; render_common has checked it against the table
-    sv.env_cube = c->sd.IsEnvironmentLightTextureCubeMap ? 1u : 0u;
-    for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++) sv.env_xf[3 * r + k] = c->sd.EnvironmentLightTransform[4 * r + k];
-    sv.lights = c->d_lights; sv.n_lights = c->n_lights;
-    return sv;
 }
 
 FrameParams make_frame_params(const PtContext* c)
@@ -327,19 +286,6 @@ Knobs read_knobs()
     k.sah_max_spheres = env_knob("PT_SAH_MAX_SPHERES"); k.beams = env_knob("PT_BEAMS"); k.refl_beams = env_knob("PT_REFL_BEAMS"); k.coop_walk = env_knob("PT_COOP_WALK"); k.wide = env_knob("PT_WIDE"); k.descent = env_knob("PT_DESCENT"); k.roctx = env_knob("PT_ROCTX");
     k.tile_order = env_knob("PT_TILE_ORDER"); k.sky_fast = env_knob("PT_SKY_FAST"); k.tile_table = env_knob("PT_TILE_TABLE");
     return k;
-}
-
-EventPair* next_events(PtContext* c, int kind)
-{
-    if (c->ev_used >= (1u << 20)) return nullptr;  // bounded pool: profiling left on for a long run simply stops recording
-    if (c->ev_used == c->ev_pool.size()) {
-        EventPair p{};
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(p);
-    }
-    EventPair* p = &c->ev_pool[c->ev_used++];
-    p->kind = kind;
-    return p;
 }
 
 // DESIGN.md byte model (what the wavefront formulation must move through HBM).
@@ -393,6 +339,20 @@ void sum_events(PtContext* c, size_t begin, size_t end, PtStats* stats)
     }
 }
 
+// room for n_blocks records of `words` dwords in one of dst's buffers: grown with nothing in flight (frames may read the old lists); the new buffer has no reader yet
+static PtStatus beam_reserve(PtContext* c, PtContext::BeamLists* dst, uint32_t*& buf, size_t& cap, size_t n_blocks, size_t words)
+{
+    if (n_blocks <= cap) return PT_OK;
+    PT_HIP(c, sync_all(c));
+    if (c->beam.stream) PT_HIP(c, hipStreamSynchronize(c->beam.stream));
+    free_dev(buf);
+    cap = 0;
+    PT_HIP(c, hipMalloc(&buf, n_blocks * words * sizeof(uint32_t)));
+    cap = n_blocks;
+    dst->used = false;
+    return PT_OK;
+}
+
 // Launches the build of primary-beam lists into `dst` (centre, slack: Beam), on stream `on` or, if null, on the cache's side stream.
 // regions: also the blocks' reflection-beam records (exact lists of a resting view only: slack 0).
 static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamLists* dst, const float centre[3], float slack, std::vector<uint32_t> key, hipStream_t on, bool regions)
@@ -405,24 +365,8 @@ static PtStatus beam_build(PtContext* c, const PixelMap& pm, PtContext::BeamList
     }
     if (!dst->ev_ready) PT_HIP(c, hipEventCreateWithFlags(&dst->ev_ready, hipEventDisableTiming));
     const size_t n_blocks = pm.n_slots >> 6;
-    if (n_blocks > dst->cap_blocks) {
-        PT_HIP(c, sync_all(c));  // frames in flight may read the old lists
-        if (B.stream) PT_HIP(c, hipStreamSynchronize(B.stream));
-        free_dev(dst->d_lists);
-        dst->cap_blocks = 0;
-        PT_HIP(c, hipMalloc(&dst->d_lists, n_blocks * 16u * sizeof(uint32_t)));
-        dst->cap_blocks = n_blocks;
-        dst->used = false;
-    }
-    if (regions && n_blocks > dst->cap_regions) {
-        PT_HIP(c, sync_all(c));
-        if (B.stream) PT_HIP(c, hipStreamSynchronize(B.stream));
-        free_dev(dst->d_regions);
-        dst->cap_regions = 0;
-        PT_HIP(c, hipMalloc(&dst->d_regions, n_blocks * kReflRecord * sizeof(uint32_t)));
-        dst->cap_regions = n_blocks;
-        dst->used = false;
-    }
+    if (const PtStatus st = beam_reserve(c, dst, dst->d_lists, dst->cap_blocks, n_blocks, 16u); st != PT_OK) return st;
+    if (const PtStatus st = regions ? beam_reserve(c, dst, dst->d_regions, dst->cap_regions, n_blocks, kReflRecord) : PT_OK; st != PT_OK) return st;
     // an earlier build into this buffer may still run (on another lane's stream), and the frames in flight may still read the buffer's
     // previous lists: the build waits for both (device-side waits only)
     if (dst->building) PT_HIP(c, hipStreamWaitEvent(on, dst->ev_ready, 0));
@@ -598,14 +542,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
     for (float x : mid) ok = ok && std::isfinite(x);
     for (float x : mid_basis) ok = ok && std::isfinite(x);
     if (!ok) return PT_OK;
-    if (n_blocks > dst->cap_blocks) {
-        PT_HIP(c, sync_all(c));  // frames in flight may read the old lists
-        if (B.stream) PT_HIP(c, hipStreamSynchronize(B.stream));
-        free_dev(dst->d_lists);
-        dst->cap_blocks = 0;
-        PT_HIP(c, hipMalloc(&dst->d_lists, n_blocks * 16u * sizeof(uint32_t)));
-        dst->cap_blocks = n_blocks;
-    }
+    if (const PtStatus st = beam_reserve(c, dst, dst->d_lists, dst->cap_blocks, n_blocks, 16u); st != PT_OK) return st;  // (used: set below)
     dst->key.clear();  // (nothing may take the buffer's old lists from here on)
     dst->regions = false;
     dst->used = true;   // (written by frames in flight from now on)
@@ -686,28 +623,6 @@ static PtStatus sync_lane_spheres(PtContext* c, Lane& L)
     return refit_lane(c, L);
 }
 
-// the environment map SceneData names must be in the texture table (render_common, pt_render_gbuffer)
-static PtStatus check_environment(PtContext* c)
-{
-    if (const uint32_t env = c->sd.EnvironmentLightTextureDescriptor; env != ~0u) {
-        const size_t n_faces = c->sd.IsEnvironmentLightTextureCubeMap ? 6 : 1;
-        if (!c->has_textures || (size_t)env + n_faces > c->tex_dims.size())
-            return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor names a texture the table of pt_set_textures does not hold (call pt_set_textures after pt_set_scene; a cube map takes six consecutive entries)");
-        for (size_t f = 0; f < n_faces; f++)
-            if (n_faces == 6 && (c->tex_dims[env + f].first != c->tex_dims[env].first || c->tex_dims[env + f].second != c->tex_dims[env].first))
-                return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor: the six faces of a cube map must be square and of one size");
-    }
-    return PT_OK;
-}
-
-// the tree walk's traversal stack must fit a workgroup's LDS (render_common, pt_render_gbuffer, pt_restir_di)
-static PtStatus check_tree_lds(PtContext* c)
-{
-    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)  // (the kernels' static LDS comes on top)
-        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
-    return PT_OK;
-}
-
 // The lane side of a frame and of its side passes (pt_render_gbuffer, pt_restir_di: work for the frame the NEXT render call renders,
 // queued on the lane that frame will take; the lane rotation is not advanced, the render call finds the lane up to date).
 //
@@ -724,92 +639,32 @@ static bool lanes_idle_for_next_frame(PtContext* c)
 }
 
 // the lane's copies of what moves: rotations, spheres, and the boxes of spheres updated without pt_refit_accel (the frame refits by itself)
-static PtStatus lane_catch_up(PtContext* c, Lane& L)
+PtStatus lane_catch_up(PtContext* c, Lane& L)
 {
     if (const PtStatus st = sync_lane_rotations(c, L); st != PT_OK) return st;
     if (const PtStatus st = sync_lane_spheres(c, L); st != PT_OK) return st;
     return L.needs_refit ? refit_lane(c, L) : PT_OK;
 }
 
-// a side pass starts: the idle test made for the frame it belongs to (render_common must not mistake the pass for a frame in flight;
-// a second pass for the same frame finds its own lane busy with the first one), then the lane brought up to date
-static PtStatus side_pass_begin(PtContext* c, Lane& L)
+// Orders lane L after the caller's stream (pt_lane_order.h; one lane: the stream is the caller's).  A marker recorded NOW stands for everything
+// the caller has queued so far.  frame: records this render call's own marker (ev_in), waits for the window marker, if shared also for its own,
+// and counts the call; side pass: if shared a marker of the lane's (ev_gb_in) INSTEAD of the window marker; calls is the render calls' alone.
+PtStatus order_lane_after_caller(PtContext* c, Lane& L, bool shared, bool frame)
 {
-    const bool idle = lanes_idle_for_next_frame(c);
-    c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
-    return lane_catch_up(c, L);
-}
-
-// is p a buffer that the latest frame, G-buffer call or (with_ri) DI pass of a lane other than L wrote, or that its frame read as DI?
-static bool other_lane_uses(const PtContext* c, const Lane& L, const void* p, bool with_ri)
-{
-    for (uint32_t i = 0; i < c->n_lanes; i++) {
-        const Lane& o = c->lanes[i];
-        if (&o == &L) continue;
-        bool hit = p == o.last_out;
-        for (const void* q : o.last_gb) hit = hit || p == q;
-        for (const void* q : o.last_dn) hit = hit || p == q;
-        for (const void* q : o.last_di) hit = hit || p == q;
-        for (const void* q : o.last_ri) hit = hit || (with_ri && p == q);
-        if (hit) return true;
-    }
-    return false;
-}
-
-// A side pass is ordered as the frame it belongs to (render_common): the caller rotates over n_lanes sets of buffers, so the pass waits
-// for the marker recorded on the caller's stream at the start of the render call n_lanes - 1 calls ago (after the consumer of this
-// lane's previous buffers), not for the frames in between.  shared (before the first render call, or a buffer that was touched elsewhere
-// within that window): it waits for everything the caller has queued so far instead.
-static PtStatus order_lane_after_caller(PtContext* c, Lane& L, bool shared)
-{
-    if (shared) {
-        if (!L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
-        PT_HIP(c, hipEventRecord(L.ev_gb_in, c->stream));
-        PT_HIP(c, hipStreamWaitEvent(L.stream, L.ev_gb_in, 0));
-        return PT_OK;
-    }
+    if (L.stream == c->stream) return PT_OK;
     const uint64_t nl = c->n_lanes;
-    const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
-    if (hipEventQuery(marker) != hipSuccess) {
+    if (!frame && shared && !L.ev_gb_in) PT_HIP(c, hipEventCreateWithFlags(&L.ev_gb_in, hipEventDisableTiming));
+    const hipEvent_t now = frame ? c->ev_in[c->calls % nl] : L.ev_gb_in;
+    if (frame || shared) PT_HIP(c, hipEventRecord(now, c->stream));
+    // (a stream wait costs the host ~8 us, a query ~1: when the GPU is ahead of the host -- small frames -- the window marker has
+    // usually completed already and the wait is skipped)
+    if (const hipEvent_t marker = c->ev_in[window_marker_slot(c->calls, nl)]; (frame || !shared) && hipEventQuery(marker) != hipSuccess) {
         (void)hipGetLastError();  // hipErrorNotReady is not an error here
         PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
     }
+    if (shared) PT_HIP(c, hipStreamWaitEvent(L.stream, now, 0));
+    if (frame) c->calls++;
     return PT_OK;
-}
-
-// whatever the caller queues next on its stream (a gather, a copy, pt_download, the next use of the buffers) sees what the lane has
-// finished -- also after a failed launch: the caller's stream must stay ordered behind the kernels that did run.  Returns st, or the
-// event's failure if st was PT_OK.
-static PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus st)
-{
-    if (L.stream == c->stream) return st;
-    const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
-    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
-    if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": completion event: " + hipGetErrorString(e2));
-    return st;
-}
-
-// the slot map of the primary pass over a rect of the image: 8x8-pixel blocks of the rect, one per wave
-static uint64_t rect_slots(const PtRect& r) { return (uint64_t)((r.w + 7) / 8) * ((r.h + 7) / 8) * 64ull; }
-static PixelMap make_pixel_map(uint32_t img_w, uint32_t img_h, const PtRect& r)
-{
-    PixelMap pm{};
-    pm.mode = 0;
-    pm.img_w = img_w; pm.img_h = img_h;
-    pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
-    pm.blocks_x = (r.w + 7) / 8;
-    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
-    const uint64_t slots = rect_slots(r);
-    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
-    pm.n_slots = (uint32_t)slots;
-    return pm;
-}
-
-// the launch grid of a side pass: LDS-resident scenes stage the tree once per workgroup, so a few workgroups per CU walk the whole frame
-static uint32_t side_pass_grid(const PtContext* c, uint32_t n_slots)
-{
-    const uint32_t threads = traverse_threads(c->lds_scene);
-    return std::max(1u, std::min((n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
 }
 
 // The per-frame launch sequence.  out: device float4 buffer addressed by PixelRef::out_index.
@@ -897,47 +752,10 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         c->beam.last_key.clear();
         c->beam.inc.active = false;  // (a share build in progress was planned for a view this frame does not continue)
     }
-    if (L.stream != c->stream) {
-        // N frames in flight.  The caller rotates over N output buffers, so this frame may start as soon as the consumer of
-        // ITS buffer (queued on the caller's stream right after the render call N calls ago, i.e. before the call N-1 calls
-        // ago) has run: wait for the marker recorded at the start of that call -- not for the frames in between, whose
-        // completion waits were queued on the caller's stream after that marker.
-        const uint64_t nl = c->n_lanes;
-        PT_HIP(c, hipEventRecord(c->ev_in[c->calls % nl], c->stream));
-        // (a stream wait costs the host ~8 us, a query ~1: when the GPU is ahead of the host -- small frames -- the marker has
-        // usually completed already and the wait is skipped)
-        const hipEvent_t marker = c->ev_in[c->calls >= nl - 1 ? (c->calls - (nl - 1)) % nl : 0];
-        if (hipEventQuery(marker) != hipSuccess) {
-            (void)hipGetLastError();  // hipErrorNotReady is not an error here
-            PT_HIP(c, hipStreamWaitEvent(L.stream, marker, 0));
-        }
-        // The rotation rule above is the caller's side of the contract; it is also enforced: when `out` is a buffer one of the
-        // other lanes wrote within the window, this frame waits for the marker recorded at the start of THIS call -- i.e. for
-        // everything the caller has queued so far, which includes the wait for that earlier frame and whatever consumed it.
-        // (Costs the overlap of the frames, never correctness.)
-        // (a denoiser frame's Diffuse / Specular / SpecularHitDistance are held to the same rule as `out`)
-        // (and so are the buffers a pt_render_with_di frame READS as its DI: a later frame on another lane that writes one of them waits,
-        // so it cannot overwrite them before that frame's gather has read them)
-        const void* mine[4] = { out, dn ? dn->diffuse : nullptr, dn ? dn->specular : nullptr, dn ? dn->spec_hit_dist : nullptr };
-        bool reused = false;
-        for (uint32_t i = 0; i < c->n_lanes && !reused; i++) {
-            if (&c->lanes[i] == &L) continue;
-            const Lane& o = c->lanes[i];
-            const void* theirs[6] = { o.last_out, o.last_dn[0], o.last_dn[1], o.last_dn[2], o.last_di[0], o.last_di[1] };
-            for (int a = 0; a < 4 && !reused; a++)
-                for (int b = 0; b < 6 && !reused; b++) reused = mine[a] && mine[a] == theirs[b];
-        }
-        // A supplied DI is an input that may have been written on the caller's stream right before this call, after the marker above:
-        // the frame waits for everything the caller has queued so far, which includes whatever wrote it.  (With frames in flight this
-        // costs their overlap; a producer queued on this frame's own lane would be ordered without it.)
-        if (ext) reused = true;
-        if (reused) PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_in[c->calls % nl], 0));
-        L.last_out = out;
-        for (int a = 0; a < 3; a++) L.last_dn[a] = mine[a + 1];
-        L.last_di[0] = ext ? ext->diffuse : nullptr;
-        L.last_di[1] = ext ? ext->specular : nullptr;
-        c->calls++;
-    }
+    // (pt_lane_order.h; the supplied DI forces this frame's own wait: a producer queued on this frame's own lane would be ordered without it)
+    const bool shared = ledger_frame({ c->ledgers, c->n_lanes, c->last_lane }, out, dn ? dn->diffuse : nullptr, dn ? dn->specular : nullptr, dn ? dn->spec_hit_dist : nullptr,
+                                     ext != nullptr, ext ? ext->diffuse : nullptr, ext ? ext->specular : nullptr);
+    if ((st = order_lane_after_caller(c, L, shared, true)) != PT_OK) return st;
 
     const SceneView sv = make_scene_view(c, &L);
     // the lane's scratch as this frame's kernels see it: a denoiser frame names its mode and outputs (the kDn kernel instances), an
@@ -997,13 +815,6 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     const size_t ev_begin = c->ev_used;  // this frame's slice of the per-launch event pool
     if (timed) PT_HIP(c, hipEventRecord(c->ev0, L.stream));
 
-    auto bracket = [&](int kind, auto&& launch) -> hipError_t {
-        EventPair* ev = c->profiling ? next_events(c, kind) : nullptr;
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        hipError_t e = launch();
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-        return e;
-    };
     // decide, after pass k has filled queue k+1, whether the looping kernel takes over (and whether anything is left)
     auto poll = [&](size_t k, bool& empty, bool& go_loop) -> PtStatus {
         empty = false;
@@ -1037,12 +848,12 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         if (ext) {
             // pt_render_with_di: the caller's estimate into the per-slot scratch the passes read (before the first one: the buffers may be the frame's
             // own denoiser outputs, which it overwrites)
-            PT_HIP(c, bracket(1, [&] { return launch_di_gather(pm, ext->diffuse, ext->specular, L.scratch.di, scr.dn.mode > 1 ? scr.dn.di_s : nullptr, L.stream); }));
+            PT_HIP(c, profiled_launch(c, L.stream, 1, [&] { return launch_di_gather(pm, ext->diffuse, ext->specular, L.scratch.di, scr.dn.mode > 1 ? scr.dn.di_s : nullptr, L.stream); }));
         } else if (fp.di_enabled && split) {
             // row N4, split schedule: the direct-illumination estimate of every primary surface, before the shade passes read it
             // (the fused schedule's primary pass makes the estimate itself, at the first shading of the primary surface)
             const uint32_t di_grid = grid_for(pm.n_slots, trav_threads, trav_cap_wide);
-            PT_HIP(c, bracket(1, [&] { return launch_di(sv, pm, fp, L.scratch.di, L.scratch.primary_hit, fc.tail_rays, di_grid, L.stream, scr.dn.mode > 1 ? scr.dn.di_s : nullptr); }));
+            PT_HIP(c, profiled_launch(c, L.stream, 1, [&] { return launch_di(sv, pm, fp, L.scratch.di, L.scratch.primary_hit, fc.tail_rays, di_grid, L.stream, scr.dn.mode > 1 ? scr.dn.di_s : nullptr); }));
         }
         if (!split) {
             // The looping pass follows the primary pass directly (1 spp with the in-register second bounce; spp > 1): the hand-over
@@ -1084,7 +895,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
                     PT_HIP(c, launch_tail(sv, pm, fp, qin, scr, out, counts + k, fc.tail_rays, fc.totals, grid_for(items, kTailThreads, tail_cap), L.stream));
                     break;
                 }
-                PT_HIP(c, bracket(loop ? 3 : (primary ? 0 : 1), [&] {
+                PT_HIP(c, profiled_launch(c, L.stream, loop ? 3 : (primary ? 0 : 1), [&] {
                     return launch_bounce(sv, pm, fp, qin, qout, scratch, out, counts + k, counts + k + 1, k <= 1 ? fc_seg : fc, primary, loop, inline2, threads,
                                          primary ? primary_grid : grid_for(items, threads, cap), L.stream);
                 }));
@@ -1092,27 +903,27 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
             }
         } else {
             const uint32_t trav_grid = grid_for(pm.n_slots, trav_threads, trav_cap);
-            PT_HIP(c, bracket(0, [&] { return launch_primary(sv, pm, fp, L.q[0], scr, out, fc, trav_grid, L.stream); }));
+            PT_HIP(c, profiled_launch(c, L.stream, 0, [&] { return launch_primary(sv, pm, fp, L.q[0], scr, out, fc, trav_grid, L.stream); }));
             // shade pass k consumes queue k (counts[k]) and appends to queue k+1; queue k+1 is then traversed, or handed to the tail
             for (size_t k = 0;; k++) {
                 const RayQueue& qin = L.q[k & 1];
                 const RayQueue& qout = L.q[(k + 1) & 1];
-                PT_HIP(c, bracket(2, [&] { return launch_shade(sv, pm, fp, qin, qout, scr, out, counts + k, counts + k + 1, grid_for(estimate(k), kShadeThreads, shade_cap), L.stream); }));
+                PT_HIP(c, profiled_launch(c, L.stream, 2, [&] { return launch_shade(sv, pm, fp, qin, qout, scr, out, counts + k, counts + k + 1, grid_for(estimate(k), kShadeThreads, shade_cap), L.stream); }));
                 if (k + 1 == max_iters) break;  // no path can have another ray
                 bool go_loop = false, empty = false;
                 if ((st = poll(k, empty, go_loop)) != PT_OK) return st;
                 if (empty) break;
                 if (go_loop) {
-                    PT_HIP(c, bracket(3, [&] { return launch_tail(sv, pm, fp, qout, scr, out, counts + k + 1, fc.tail_rays, fc.totals, grid_for(estimate(k + 1), kTailThreads, tail_cap), L.stream); }));
+                    PT_HIP(c, profiled_launch(c, L.stream, 3, [&] { return launch_tail(sv, pm, fp, qout, scr, out, counts + k + 1, fc.tail_rays, fc.totals, grid_for(estimate(k + 1), kTailThreads, tail_cap), L.stream); }));
                     break;
                 }
                 if (!c->lds_scene && sv.n > 1 && knob_or(c->knobs.ray_replacement, 1)) {
                     // persistent waves with ray replacement (heavy-tailed visit counts of large scenes)
                     uint32_t* cursor = counts + L.cap_counts + k + 1;
                     const uint32_t grid = std::min(grid_for(estimate(k + 1), 256u, c->num_cus * 8u), c->num_cus * knob_or(c->knobs.dyn_blocks_per_cu, 4));
-                    PT_HIP(c, bracket(1, [&] { return launch_traverse_dyn(sv, qout, counts + k + 1, cursor, fc.totals, grid, L.stream); }));
+                    PT_HIP(c, profiled_launch(c, L.stream, 1, [&] { return launch_traverse_dyn(sv, qout, counts + k + 1, cursor, fc.totals, grid, L.stream); }));
                 } else {
-                    PT_HIP(c, bracket(1, [&] { return launch_traverse(sv, qout, counts + k + 1, grid_for(estimate(k + 1), trav_threads, trav_cap), L.stream); }));
+                    PT_HIP(c, profiled_launch(c, L.stream, 1, [&] { return launch_traverse(sv, qout, counts + k + 1, grid_for(estimate(k + 1), trav_threads, trav_cap), L.stream); }));
                 }
             }
         }
@@ -1193,6 +1004,181 @@ uint32_t frame_tiles(const PtContext* c)
 
 }  // namespace
 
+// ---- the helpers pt_api_side.hip uses too (declared at the end of pt_context.h)
+PtStatus validate_frame(PtContext* c)
+{
+    if (!c->scene_set) return fail(c, PT_ERR_STATE, "pt_set_scene has not been called");
+    if (!c->accel_valid) return fail(c, PT_ERR_STATE, "pt_build_accel has not been called for the current scene");
+    if (!c->cam_set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    if (!c->gs_set) return fail(c, PT_ERR_STATE, "pt_set_constants has not been called");
+    return PT_OK;
+}
+
+SceneView make_scene_view(const PtContext* c, const Lane* L)
+{
+    SceneView sv{};
+    const bool priv = L && L->scene_private;
+    sv.nodes = priv ? L->d_nodes : c->d_nodes;
+    sv.wide = priv ? nullptr : c->d_wide;  // (a lane's refitted private tree is walked through its binary records)
+    sv.sph_sorted = priv ? L->d_sph_sorted : c->d_sph_sorted;
+    sv.sorted_id = c->d_leaf_ids ? c->d_leaf_ids : c->d_sorted_id;
+    sv.alpha_class = c->d_alpha_class;
+    sv.alpha_tested = c->alpha_tested ? 1u : 0u;
+    sv.sph = priv ? L->d_sph : c->d_sph;
+    sv.mats = c->d_mats;
+    sv.n = c->n;
+    sv.n_nodes = c->n_nodes;
+    sv.stack_depth = stack_entries(c, sv.wide != nullptr);
+    // Global-memory scenes: a lane makes at most this many node visits before its wave turns to the sphere tests.  Unbounded, the
+    // lanes that already hold a leaf idle until the longest descent of the wave ends (hundreds of visits in the 2^20-sphere scene's
+    // heavy tail): 3.99 -> 2.54 ms per frame there with any bound from 2 to 24; LDS-resident scenes (coherent, shallow) gain nothing.
+    sv.descent_cap = c->lds_scene ? 0u : knob_or(c->knobs.descent, 8u);
+    sv.lds_scene = c->lds_scene ? 1u : 0u;
+    sv.slab_tiny = c->slab_tiny;  // (of the tree pt_build_accel made: a lane's refitted private tree keeps it, pt_update_spheres does not look at coordinates)
+    for (int i = 0; i < 4; i++) sv.env[i] = c->sd.EnvironmentLightColor[i];
+    if (c->has_textures) { sv.tex = c->d_tex; sv.tex_maps = c->d_tex_maps; sv.rot = (c->rot_gen != c->rot_master_gen && L && L->d_rot && L->rot_gen == c->rot_gen) ? L->d_rot : c->d_rot; }
+    sv.env_tex = c->sd.EnvironmentLightTextureDescriptor;  // ~0u == kNoTexture; render_common has checked it against the table
+    sv.env_cube = c->sd.IsEnvironmentLightTextureCubeMap ? 1u : 0u;
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++) sv.env_xf[3 * r + k] = c->sd.EnvironmentLightTransform[4 * r + k];
+    sv.lights = c->d_lights; sv.n_lights = c->n_lights;
+    return sv;
+}
+
+EventPair* next_events(PtContext* c, int kind)
+{
+    if (c->ev_used >= (1u << 20)) return nullptr;  // bounded pool: profiling left on for a long run simply stops recording
+    if (c->ev_used == c->ev_pool.size()) {
+        EventPair p{};
+        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
+        c->ev_pool.push_back(p);
+    }
+    EventPair* p = &c->ev_pool[c->ev_used++];
+    p->kind = kind;
+    return p;
+}
+
+// the environment map SceneData names must be in the texture table (render_common, pt_render_gbuffer)
+PtStatus check_environment(PtContext* c)
+{
+    if (const uint32_t env = c->sd.EnvironmentLightTextureDescriptor; env != ~0u) {
+        const size_t n_faces = c->sd.IsEnvironmentLightTextureCubeMap ? 6 : 1;
+        if (!c->has_textures || (size_t)env + n_faces > c->tex_dims.size())
+            return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor names a texture the table of pt_set_textures does not hold (call pt_set_textures after pt_set_scene; a cube map takes six consecutive entries)");
+        for (size_t f = 0; f < n_faces; f++)
+            if (n_faces == 6 && (c->tex_dims[env + f].first != c->tex_dims[env].first || c->tex_dims[env + f].second != c->tex_dims[env].first))
+                return fail(c, PT_ERR_STATE, "SceneData.EnvironmentLightTextureDescriptor: the six faces of a cube map must be square and of one size");
+    }
+    return PT_OK;
+}
+
+// the tree walk's traversal stack must fit a workgroup's LDS (render_common, pt_render_gbuffer, pt_restir_di)
+PtStatus check_tree_lds(PtContext* c)
+{
+    if (traverse_lds_bytes_for(c->n_nodes, c->n, stack_entries(c, c->d_wide != nullptr), c->lds_scene) > kMaxLdsBytes - 9u * 1024u)  // (the kernels' static LDS comes on top)
+        return fail(c, PT_ERR_UNSUPPORTED, "BVH depth needs more traversal-stack LDS than a workgroup can have");
+    return PT_OK;
+}
+
+// a side pass starts: the idle test made for the frame it belongs to (render_common must not mistake the pass for a frame in flight;
+// a second pass for the same frame finds its own lane busy with the first one), then the lane brought up to date and ordered
+PtStatus side_pass_begin(PtContext* c, Lane& L, bool shared)
+{
+    const bool idle = lanes_idle_for_next_frame(c);
+    c->gb_frame = c->frames; c->gb_lane = c->next_lane; c->gb_lanes_idle = idle;
+    if (const PtStatus st = lane_catch_up(c, L); st != PT_OK) return st;
+    return order_lane_after_caller(c, L, shared, false);
+}
+
+// whatever the caller queues next on its stream (a gather, a copy, pt_download, the next use of the buffers) sees what the lane has
+// finished -- also after a failed launch: the caller's stream must stay ordered behind the kernels that did run.  Returns st, or the
+// event's failure if st was PT_OK.
+PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus st)
+{
+    if (L.stream == c->stream) return st;
+    const hipError_t e1 = hipEventRecord(L.ev_done, L.stream);
+    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, L.ev_done, 0) : e1;
+    if (st == PT_OK && e2 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": completion event: " + hipGetErrorString(e2));
+    return st;
+}
+
+// the slot map of the primary pass over a rect of the image: 8x8-pixel blocks of the rect, one per wave
+static uint64_t rect_slots(const PtRect& r) { return (uint64_t)((r.w + 7) / 8) * ((r.h + 7) / 8) * 64ull; }
+PixelMap make_pixel_map(uint32_t img_w, uint32_t img_h, const PtRect& r)
+{
+    PixelMap pm{};
+    pm.mode = 0;
+    pm.img_w = img_w; pm.img_h = img_h;
+    pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
+    pm.blocks_x = (r.w + 7) / 8;
+    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
+    const uint64_t slots = rect_slots(r);
+    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
+    pm.n_slots = (uint32_t)slots;
+    return pm;
+}
+
+// the launch grid of a side pass: LDS-resident scenes stage the tree once per workgroup, so a few workgroups per CU walk the whole frame
+uint32_t side_pass_grid(const PtContext* c, uint32_t n_slots)
+{
+    const uint32_t threads = traverse_threads(c->lds_scene);
+    return std::max(1u, std::min((n_slots + threads - 1) / threads, c->num_cus * (c->lds_scene ? 2u : 8u)));
+}
+
+// rect (NULL = the whole RenderSize), validated -> the slot map of the primary pass (make_pixel_map)
+PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who, PtRect& r, PixelMap& pm)
+{
+    r = rect ? *rect : PtRect{ 0, 0, c->gs.RenderSize[0], c->gs.RenderSize[1] };
+    if (r.w == 0 || r.h == 0 || r.x >= c->gs.RenderSize[0] || r.w > c->gs.RenderSize[0] - r.x || r.y >= c->gs.RenderSize[1] || r.h > c->gs.RenderSize[1] - r.y)
+        return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect is empty or outside RenderSize");
+    if (rect_slots(r) > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect too large");
+    pm = make_pixel_map(c->gs.RenderSize[0], c->gs.RenderSize[1], r);
+    return PT_OK;
+}
+
+// the DenoiseOut of a PtDenoiserOutputs (pt_render_denoiser, pt_render_with_di), validated
+PtStatus denoise_out(PtContext* c, const PtDenoiserOutputs* outputs, const char* who, DenoiseOut& dn)
+{
+    const uint32_t mode = outputs->Denoiser;
+    if (mode < 1 || mode > 3) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": Denoiser must be 1 (DLSSRayReconstruction), 2 (NRDReBLUR) or 3 (NRDReLAX)");
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
+    dn = DenoiseOut{};
+    dn.mode = mode;
+    if (mode == 1) {
+        if (!outputs->SpecularHitDistance || misaligned(outputs->SpecularHitDistance, 4))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": DLSSRayReconstruction needs a 4-byte aligned SpecularHitDistance");
+        dn.spec_hit_dist = static_cast<float*>(outputs->SpecularHitDistance);
+    } else {
+        if (!outputs->Diffuse || !outputs->Specular || misaligned(outputs->Diffuse, 16) || misaligned(outputs->Specular, 16))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": the NRD modes need 16-byte aligned Diffuse and Specular");
+        dn.diffuse = static_cast<float4*>(outputs->Diffuse);
+        dn.specular = static_cast<float4*>(outputs->Specular);
+    }
+    return PT_OK;
+}
+
+// A call's output: the caller's device buffer or, staged (a host buffer), the context's, grown with nothing in flight and copied back by
+// staged_out_finish.  (cap_out is zero while there is no buffer: after a failed allocation the next call allocates again, not launches on null.)
+PtStatus staged_out_begin(PtContext* c, void* out, bool staged, size_t out_px, float4*& dev_out)
+{
+    if (staged && out_px > c->cap_out) {
+        PT_HIP(c, sync_all(c));
+        free_dev(c->d_out);
+        c->cap_out = 0;
+        PT_HIP(c, hipMalloc(&c->d_out, out_px * sizeof(float4)));
+        c->cap_out = out_px;
+    }
+    dev_out = staged ? c->d_out : static_cast<float4*>(out);
+    return PT_OK;
+}
+
+PtStatus staged_out_finish(PtContext* c, void* out, bool staged, size_t out_px)
+{
+    if (staged) PT_HIP(c, hipMemcpyAsync(out, c->d_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (staged) PT_HIP(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 // ==================================================================================================== C-ABI
 extern "C" {
 
@@ -1223,6 +1209,7 @@ PtStatus pt_create(const PtConfig* config, PtContext** out_ctx)
     }
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess
         ) { pt_destroy(c); return PT_ERR_HIP; }
+    for (uint32_t i = 0; i < kMaxLanes; i++) c->ledgers[i] = &c->lanes[i].ledger;
     c->n_lanes = config->frames_in_flight > 1 ? std::min(config->frames_in_flight, kMaxLanes) : ((config->flags & PT_FLAG_TWO_FRAMES_IN_FLIGHT) ? 2u : 1u);
     for (uint32_t i = 0; i < c->n_lanes; i++)
         if (hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming) != hipSuccess) { pt_destroy(c); return PT_ERR_HIP; }
@@ -1587,17 +1574,6 @@ uint32_t pt_tiles_count_ex(PtContext* c, uint32_t first, uint32_t run, uint32_t 
     return count_tiles(frame_tiles(c), first, run, stride);
 }
 
-// rect (NULL = the whole RenderSize), validated -> the slot map of the primary pass (make_pixel_map)
-static PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who, PtRect& r, PixelMap& pm)
-{
-    r = rect ? *rect : PtRect{ 0, 0, c->gs.RenderSize[0], c->gs.RenderSize[1] };
-    if (r.w == 0 || r.h == 0 || r.x >= c->gs.RenderSize[0] || r.w > c->gs.RenderSize[0] - r.x || r.y >= c->gs.RenderSize[1] || r.h > c->gs.RenderSize[1] - r.y)
-        return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect is empty or outside RenderSize");
-    if (rect_slots(r) > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": rect too large");
-    pm = make_pixel_map(c->gs.RenderSize[0], c->gs.RenderSize[1], r);
-    return PT_OK;
-}
-
 // pt_render, pt_render_denoiser and pt_render_with_di: a frame of the rect into `out` (a host buffer is staged through the context's device
 // buffer and copied back); dn = the denoiser outputs of a denoiser frame, null for Denoiser::None; di = the supplied DI (pt_render_with_di)
 static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats, const DenoiseOut* dn, const char* who,
@@ -1610,56 +1586,18 @@ static PtStatus render_rect(PtContext* c, const PtRect* rect, void* out, int out
     PtRect r;
     PixelMap pm{};
     if ((st = rect_pixel_map(c, rect, who, r, pm)) != PT_OK) return st;
-    float4* dev_out = static_cast<float4*>(out);
+    float4* dev_out = nullptr;
     const size_t out_px = (size_t)r.w * r.h;
-    if (!out_is_device) {
-        if (out_px > c->cap_out) {
-            PT_HIP(c, sync_all(c));
-            free_dev(c->d_out);
-            PT_HIP(c, hipMalloc(&c->d_out, out_px * sizeof(float4)));
-            c->cap_out = out_px;
-        }
-        dev_out = c->d_out;
-    }
-    SuppliedDI ext{};
-    if (di) {
-        ext.diffuse = static_cast<const float4*>(di->Diffuse);
-        ext.specular = static_cast<const float4*>(di->Specular);
-    }
+    if ((st = staged_out_begin(c, out, !out_is_device, out_px, dev_out)) != PT_OK) return st;
+    const SuppliedDI ext{ static_cast<const float4*>(di ? di->Diffuse : nullptr), static_cast<const float4*>(di ? di->Specular : nullptr) };
     st = render_common(c, pm, (uint64_t)r.w * r.h, dev_out, stats, dn, di ? &ext : nullptr);
-    if (st != PT_OK) return st;
-    if (!out_is_device) {
-        PT_HIP(c, hipMemcpyAsync(out, dev_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        PT_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return PT_OK;
+    return st != PT_OK ? st : staged_out_finish(c, out, !out_is_device, out_px);
 }
 
 PtStatus pt_render(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
 {
     if (!c) return PT_ERR_INVALID_ARG;
     return render_rect(c, rect, out, out_is_device, stats, nullptr, "pt_render");
-}
-
-// the DenoiseOut of a PtDenoiserOutputs (pt_render_denoiser, pt_render_with_di), validated
-static PtStatus denoise_out(PtContext* c, const PtDenoiserOutputs* outputs, const char* who, DenoiseOut& dn)
-{
-    const uint32_t mode = outputs->Denoiser;
-    if (mode < 1 || mode > 3) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": Denoiser must be 1 (DLSSRayReconstruction), 2 (NRDReBLUR) or 3 (NRDReLAX)");
-    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; };
-    dn = DenoiseOut{};
-    dn.mode = mode;
-    if (mode == 1) {
-        if (!outputs->SpecularHitDistance || misaligned(outputs->SpecularHitDistance, 4))
-            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": DLSSRayReconstruction needs a 4-byte aligned SpecularHitDistance");
-        dn.spec_hit_dist = static_cast<float*>(outputs->SpecularHitDistance);
-    } else {
-        if (!outputs->Diffuse || !outputs->Specular || misaligned(outputs->Diffuse, 16) || misaligned(outputs->Specular, 16))
-            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": the NRD modes need 16-byte aligned Diffuse and Specular");
-        dn.diffuse = static_cast<float4*>(outputs->Diffuse);
-        dn.specular = static_cast<float4*>(outputs->Specular);
-    }
-    return PT_OK;
 }
 
 // Row N7 -- a frame that writes the denoiser outputs of its mode (DESIGN.md spec S13): render_common with the kDn kernel instances
@@ -1686,106 +1624,6 @@ PtStatus pt_render_with_di(PtContext* c, const PtRect* rect, void* out, int out_
         if (const PtStatus st = denoise_out(c, outputs, "pt_render_with_di", dn); st != PT_OK) return st;
     }
     return render_rect(c, rect, out, out_is_device, stats, outputs ? &dn : nullptr, "pt_render_with_di", di);
-}
-
-// Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12)
-PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!gb) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: null PtGBuffer");
-    // the requested channels; every buffer must be aligned to its channel's vector width (float4: 16 B, float2: 8 B, else 4 B)
-    void* const ptrs[13] = { gb->Position, gb->FlatNormal, gb->GeometricNormal, gb->LinearDepth, gb->NormalizedDepth, gb->MotionVector,
-                             gb->BaseColorMetalness, gb->DiffuseAlbedo, gb->SpecularAlbedo, gb->NormalRoughness, gb->IOR, gb->Transmission, gb->Radiance };
-    const uint32_t align[13] = { 16, 8, 8, 4, 4, 4, 16, 4, 4, 16, 4, 4, 4 };
-    uint32_t want = 0;
-    for (uint32_t k = 0; k < 13; k++) {
-        if (!ptrs[k]) continue;
-        if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: a buffer is not aligned to its channel's width");
-        want |= 1u << k;
-    }
-    if (!want) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: no output requested (all 13 pointers are NULL)");
-    PtStatus st = validate_frame(c);
-    if (st != PT_OK) return st;
-    PtRect r;
-    PixelMap pm{};
-    if ((st = rect_pixel_map(c, rect, "pt_render_gbuffer", r, pm)) != PT_OK) return st;
-    if ((st = check_environment(c)) != PT_OK) return st;
-    if ((st = check_tree_lds(c)) != PT_OK) return st;
-    // previous poses (PreviousObjectToWorld): only while the scene is not static; the empty scene has none
-    const uint32_t n = c->empty_scene ? 0u : c->n;
-    const bool use_prev_sph = previous_spheres && !c->sd.IsStatic && n > 0, use_prev_rot = previous_rotations && !c->sd.IsStatic && n > 0;
-    for (uint32_t i = 0; use_prev_sph && i < n; i++) {
-        const PtSphere& p = previous_spheres[i];
-        if (!std::isfinite(p.cx) || !std::isfinite(p.cy) || !std::isfinite(p.cz) || !std::isfinite(p.r) || !(p.r > 0.0f))
-            return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous sphere " + std::to_string(i) + " is not finite or has radius <= 0");
-    }
-    for (uint32_t i = 0; use_prev_rot && i < 4u * n; i++)
-        if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous rotation " + std::to_string(i / 4) + " is not finite");
-    PT_HIP(c, hipSetDevice(c->device));
-
-    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
-    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
-    if (L.stream != c->stream) {
-        // shared: a buffer is one that another lane's G-buffer or frame wrote within the window
-        bool shared = c->calls == 0;
-        for (uint32_t k = 0; k < 13 && !shared; k++) shared = ptrs[k] && other_lane_uses(c, L, ptrs[k], false);
-        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
-        for (uint32_t k = 0; k < 13; k++) L.last_gb[k] = ptrs[k];
-    }
-    const SceneView sv = make_scene_view(c, &L);
-    GBufferScene sc{};
-    sc.sph = sv.sph; sc.mats = sv.mats; sc.tex = sv.tex; sc.tex_maps = sv.tex_maps; sc.rot = sv.rot;
-    sc.is_static = c->sd.IsStatic ? 1u : 0u;
-    sc.env_tex = sv.env_tex; sc.env_cube = sv.env_cube;
-    for (int k = 0; k < 4; k++) sc.env[k] = sv.env[k];
-    for (int k = 0; k < 9; k++) sc.env_xf[k] = sv.env_xf[k];
-    if (use_prev_sph || use_prev_rot) {
-        // one set per lane: a call on another lane may still be reading its own
-        if (L.prev_cap < n) {
-            PT_HIP(c, hipStreamSynchronize(L.stream));
-            free_dev(L.d_prev_pose);
-            if (L.h_prev_stage) { (void)hipHostFree(L.h_prev_stage); L.h_prev_stage = nullptr; }
-            L.prev_cap = 0;
-            PT_HIP(c, hipMalloc(&L.d_prev_pose, 2u * (size_t)n * sizeof(float4)));
-            PT_HIP(c, hipHostMalloc(&L.h_prev_stage, 2u * (size_t)n * sizeof(float4)));
-            if (!L.ev_prev) PT_HIP(c, hipEventCreateWithFlags(&L.ev_prev, hipEventDisableTiming));
-            L.prev_cap = n;
-        } else {
-            PT_HIP(c, hipEventSynchronize(L.ev_prev));  // the previous upload from the staging buffer has been consumed
-        }
-        if (use_prev_sph) std::memcpy(L.h_prev_stage, previous_spheres, (size_t)n * sizeof(float4));
-        if (use_prev_rot) std::memcpy(L.h_prev_stage + n, previous_rotations, (size_t)n * sizeof(float4));
-        PT_HIP(c, hipMemcpyAsync(L.d_prev_pose, L.h_prev_stage, 2u * (size_t)n * sizeof(float4), hipMemcpyHostToDevice, L.stream));
-        PT_HIP(c, hipEventRecord(L.ev_prev, L.stream));
-        sc.prev_sph = use_prev_sph ? L.d_prev_pose : nullptr;
-        sc.prev_rot = use_prev_rot ? L.d_prev_pose + n : nullptr;
-    }
-    GBufferFrame fr{};
-    fr.cam = camera_params(c->cam, c->gs.RenderSize[0], c->gs.RenderSize[1]);
-    fr.width = (float)c->gs.RenderSize[0];
-    fr.height = (float)c->gs.RenderSize[1];
-    fr.reversed = c->cam.IsNormalizedDepthReversed ? 1u : 0u;
-    std::memcpy(fr.world_to_projection, c->cam.Matrices[5], sizeof fr.world_to_projection);
-    std::memcpy(fr.prev_world_to_projection, c->cam.Matrices[2], sizeof fr.prev_world_to_projection);
-    std::memcpy(fr.prev_world_to_view, c->cam.Matrices[0], sizeof fr.prev_world_to_view);
-    GBufferOut out{};
-    out.Position = static_cast<float4*>(gb->Position);
-    out.FlatNormal = static_cast<float2*>(gb->FlatNormal);
-    out.GeometricNormal = static_cast<float2*>(gb->GeometricNormal);
-    out.LinearDepth = static_cast<float*>(gb->LinearDepth);
-    out.NormalizedDepth = static_cast<float*>(gb->NormalizedDepth);
-    out.MotionVector = static_cast<f3*>(gb->MotionVector);
-    out.BaseColorMetalness = static_cast<float4*>(gb->BaseColorMetalness);
-    out.DiffuseAlbedo = static_cast<f3*>(gb->DiffuseAlbedo);
-    out.SpecularAlbedo = static_cast<f3*>(gb->SpecularAlbedo);
-    out.NormalRoughness = static_cast<float4*>(gb->NormalRoughness);
-    out.IOR = static_cast<float*>(gb->IOR);
-    out.Transmission = static_cast<float*>(gb->Transmission);
-    out.Radiance = static_cast<f3*>(gb->Radiance);
-    st = PT_OK;
-    if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
-        st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: launch: ") + hipGetErrorString(e));
-    return publish_lane_to_caller(c, L, "pt_render_gbuffer", st);
 }
 
 PtStatus pt_render_tiles(PtContext* c, void* out_device_packed, PtStats* stats)
@@ -1830,7 +1668,21 @@ PtStatus pt_unpack_tiles(PtContext* c, const void* gathered, uint32_t max_tiles_
 }
 
 static PtStatus unpack_ex(PtContext* c, const void* packed, uint64_t part_stride_px, uint32_t n_parts, uint32_t first0, uint32_t run,
-                          uint32_t stride, void* frame, bool rgb);
+                          uint32_t stride, void* frame, bool rgb)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!packed || !frame || !c->gs_set) return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: null pointer or no constants");
+    if (stride == 0 || run == 0 || n_parts == 0 || (uint64_t)first0 + (uint64_t)n_parts * run > stride)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: need run, n_parts > 0 and first0 + n_parts * run <= stride");
+    const uint32_t ts = c->tile_size, w = c->gs.RenderSize[0], h = c->gs.RenderSize[1];
+    // the first part owns at least as many tiles as any later one
+    if (n_parts > 1 && part_stride_px < (uint64_t)count_tiles(frame_tiles(c), first0, run, stride) * ts * ts)
+        return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: part_stride_px smaller than one part's tiles");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, launch_unpack_tiles(static_cast<const float4*>(packed), static_cast<float4*>(frame), w, h, ts, (w + ts - 1) / ts, first0, run, stride,
+                                  n_parts, part_stride_px, rgb, c->stream));
+    return PT_OK;
+}
 
 PtStatus pt_unpack_tiles_ex(PtContext* c, const void* packed, uint64_t part_stride_px, uint32_t n_parts, uint32_t first0, uint32_t run,
                             uint32_t stride, void* frame)
@@ -1851,23 +1703,6 @@ PtStatus pt_pack_rgb(PtContext* c, const void* src, uint64_t n_pixels, void* dst
     if (n_pixels == 0) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, launch_pack_rgb(static_cast<const float4*>(src), static_cast<float*>(dst), n_pixels, c->stream));
-    return PT_OK;
-}
-
-static PtStatus unpack_ex(PtContext* c, const void* packed, uint64_t part_stride_px, uint32_t n_parts, uint32_t first0, uint32_t run,
-                          uint32_t stride, void* frame, bool rgb)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!packed || !frame || !c->gs_set) return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: null pointer or no constants");
-    if (stride == 0 || run == 0 || n_parts == 0 || (uint64_t)first0 + (uint64_t)n_parts * run > stride)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: need run, n_parts > 0 and first0 + n_parts * run <= stride");
-    const uint32_t ts = c->tile_size, w = c->gs.RenderSize[0], h = c->gs.RenderSize[1];
-    // the first part owns at least as many tiles as any later one
-    if (n_parts > 1 && part_stride_px < (uint64_t)count_tiles(frame_tiles(c), first0, run, stride) * ts * ts)
-        return fail(c, PT_ERR_INVALID_ARG, "pt_unpack_tiles_ex: part_stride_px smaller than one part's tiles");
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, launch_unpack_tiles(static_cast<const float4*>(packed), static_cast<float4*>(frame), w, h, ts, (w + ts - 1) / ts, first0, run, stride,
-                                  n_parts, part_stride_px, rgb, c->stream));
     return PT_OK;
 }
 
@@ -1960,487 +1795,6 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
     for (uint32_t i = 0; i < n; i++)
         c->h_rot[i] = rotations ? make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]) : make_float4(0.f, 0.f, 0.f, 1.f);
     c->rot_gen++;
-    return PT_OK;
-}
-
-// Row N10 -- the reservoir pass (DESIGN.md spec S16): two launches on the lane of the next render call, ordered like pt_render_gbuffer;
-// the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
-constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
-
-// The body of pt_restir_di, pt_restir_di_sampled (row N16, spec S22) and pt_restir_di_ex (row N17, spec S23); ls null or Mode 0 = Uniform:
-// nothing is presampled; cd null, or no BRDF candidates and the filter off: launch 1 is the one of rows N10 / N16.
-static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd,
-                                 const PtRestirDiTextures* t)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null pointer");
-    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
-    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": RenderSize must be in [1, 16384]");
-    if (s->InitialSamples > kRiMaxInitialSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": InitialSamples must be at most 32");
-    if (s->SpatialSamples > kRiMaxSpatialSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialSamples must be at most 32");
-    if (s->EnableTemporal > 1 || s->EnableSpatial > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": EnableTemporal and EnableSpatial must be 0 or 1");
-    for (const uint32_t mode : { s->TemporalBiasCorrection, s->SpatialBiasCorrection }) {
-        if (mode == kRiBiasPairwise) return fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": pairwise bias correction (2) is not built");
-        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
-    }
-    if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialRadius must be finite and >= 0");
-    if (cd) {
-        if (cd->BrdfSamples > kRiMaxBrdfSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": BrdfSamples must be at most 8");
-        if (cd->EnableBoilingFilter > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": EnableBoilingFilter must be 0 or 1");
-        if (cd->EnableBoilingFilter && (!std::isfinite(cd->BoilingFilterStrength) || !(cd->BoilingFilterStrength >= 0.0f && cd->BoilingFilterStrength <= 1.0f)))
-            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": BoilingFilterStrength must be finite and in [0, 1]");
-        if (cd->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": PtRestirDiCandidates._pad must be 0");
-    }
-    // the candidates' source (spec S22): defaults applied, ranges checked
-    const uint32_t mode = ls ? ls->Mode : kLrUniform;
-    LrGrid lg{};
-    if (mode != kLrUniform) {
-        if (mode > kLrRegirRis) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": Mode must be 0 (Uniform), 1 (Power_RIS) or 2 (ReGIR_RIS)");
-        if (ls->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": PtLightSamplingSettings._pad must be 0");
-        if (ls->TileSize > kLrMaxTileSize) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": TileSize must be at most 8192");
-        if (ls->TileCount > kLrMaxTileCount) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": TileCount must be at most 1024");
-        if (ls->ReGIRGridSize > kLrMaxGrid) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRGridSize must be at most 32");
-        if (ls->ReGIRLightsPerCell > kLrMaxLightsPerCell) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRLightsPerCell must be at most 1024");
-        if (ls->ReGIRBuildSamples > kLrMaxBuildSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRBuildSamples must be at most 32");
-        if (ls->ReGIRCellSize != 0.0f && !(std::isfinite(ls->ReGIRCellSize) && ls->ReGIRCellSize >= kLrMinCellSize && ls->ReGIRCellSize <= kLrMaxCellSize))
-            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReGIRCellSize must be 0 or finite and in [0.1, 10]");
-        lg.tile_size = ls->TileSize ? ls->TileSize : kLrDefaultTileSize;
-        lg.tile_count = ls->TileCount ? ls->TileCount : kLrDefaultTileCount;
-        lg.grid = ls->ReGIRGridSize ? ls->ReGIRGridSize : kLrDefaultGrid;
-        lg.lights_per_cell = ls->ReGIRLightsPerCell ? ls->ReGIRLightsPerCell : kLrDefaultLightsPerCell;
-        lg.build_samples = ls->ReGIRBuildSamples ? ls->ReGIRBuildSamples : kLrDefaultBuildSamples;
-        lg.cell_size = ls->ReGIRCellSize != 0.0f ? ls->ReGIRCellSize : kLrDefaultCellSize;
-        if ((uint64_t)lg.tile_size * lg.tile_count + (uint64_t)lg.grid * lg.grid * lg.grid * lg.lights_per_cell > kLrMaxEntries)
-            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": the Power_RIS and ReGIR segments together hold more than 2^24 entries");
-    }
-    const uint64_t n = (uint64_t)w * h;
-    // the eight inputs, then the two outputs
-    const BufferUse use[10] = {
-        {t->Position, n * 16, 16, false, true, "Position"}, {t->GeometricNormal, n * 8, 8, false, true, "GeometricNormal"},
-        {t->LinearDepth, n * 4, 4, false, true, "LinearDepth"}, {t->MotionVector, n * 12, 4, false, true, "MotionVector"},
-        {t->BaseColorMetalness, n * 16, 16, false, true, "BaseColorMetalness"}, {t->NormalRoughness, n * 16, 16, false, true, "NormalRoughness"},
-        {t->IOR, n * 4, 4, false, true, "IOR"}, {t->Transmission, n * 4, 4, false, true, "Transmission"},
-        {t->Diffuse, n * 16, 16, true, true, "Diffuse"}, {t->Specular, n * 16, 16, true, true, "Specular"},
-    };
-    PtStatus st = buffers_ok(c, who, use, 10);
-    if (st != PT_OK) return st;
-    if ((st = validate_frame(c)) != PT_OK) return st;
-    if ((st = check_environment(c)) != PT_OK) return st;
-    if ((st = check_tree_lds(c)) != PT_OK) return st;
-    PT_HIP(c, hipSetDevice(c->device));
-    if (c->n_lights == 0 || c->empty_scene) {  // no emitters: nothing is written, and there is no history to keep
-        c->ri_valid = false;
-        return PT_OK;
-    }
-
-    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
-    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
-    if (L.stream != c->stream) {
-        // pt_render_gbuffer's rule, and shared also when an input is not a buffer this lane's own G-buffer call wrote (it was made
-        // elsewhere: on the caller's stream), or when a buffer is one another lane's DI pass wrote within the window.
-        // (One-sided for last_ri: only this entry point looks at the outputs of other lanes' DI passes.  pt_render_gbuffer and the
-        // frames do not, so a caller that hands a DI buffer of one lane to them inside the window relies on the rotation rule.)
-        bool shared = c->calls == 0;
-        for (uint32_t k = 0; k < 8 && !shared; k++) shared = std::find(L.last_gb, L.last_gb + 13, use[k].p) == L.last_gb + 13;
-        for (uint32_t k = 0; k < 10 && !shared; k++) shared = other_lane_uses(c, L, use[k].p, true);
-        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
-        L.last_ri[0] = t->Diffuse; L.last_ri[1] = t->Specular;
-    }
-    // the history: the previous call (on whichever lane it ran) wrote the slot this one reads and read the slot this one writes
-    bool restart = s->ResetHistory != 0 || !c->ri_valid || c->ri_scene != c->set_scene_calls;
-    if (!c->ev_ri) PT_HIP(c, hipEventCreateWithFlags(&c->ev_ri, hipEventDisableTiming));
-    if (!c->d_ri || c->ri_w != w || c->ri_h != h) {
-        if (c->d_ri) PT_HIP(c, hipEventSynchronize(c->ev_ri));  // (the previous call may still use the old buffers)
-        free_dev(c->d_ri);
-        c->ri_valid = false;
-        void* mem = nullptr;
-        if (hipMalloc(&mem, 2u * n * kRiSlotBytesPerPixel) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": history allocation failed"); }
-        c->d_ri = static_cast<float4*>(mem);
-        c->ri_w = w; c->ri_h = h;
-        restart = true;
-    } else if (L.stream != c->stream || c->n_lanes > 1) {
-        PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_ri, 0));
-    }
-    const uint32_t cur = c->ri_slot ^ 1u, prev = c->ri_slot;
-    RiBuffers b{};
-    b.w = w; b.h = h;
-    b.position = static_cast<const float4*>(t->Position);
-    b.geometric_normal = static_cast<const float*>(t->GeometricNormal);
-    b.linear_depth = static_cast<const float*>(t->LinearDepth);
-    b.motion_vector = static_cast<const float*>(t->MotionVector);
-    b.base_color_metalness = static_cast<const float4*>(t->BaseColorMetalness);
-    b.normal_roughness = static_cast<const float4*>(t->NormalRoughness);
-    b.ior = static_cast<const float*>(t->IOR);
-    b.transmission = static_cast<const float*>(t->Transmission);
-    float4* planes = c->d_ri;                                              // [slot][6 planes][n] float4, then [slot][n] float
-    float* tplanes = reinterpret_cast<float*>(c->d_ri + 12u * n);
-    for (uint32_t k = 0; k < 4; k++) { b.rec[k] = planes + ((uint64_t)cur * 6u + k) * n; b.prev_rec[k] = planes + ((uint64_t)prev * 6u + k) * n; }
-    for (uint32_t k = 0; k < 2; k++) { b.res[k] = planes + ((uint64_t)cur * 6u + 4u + k) * n; b.prev_res[k] = planes + ((uint64_t)prev * 6u + 4u + k) * n; }
-    b.rec_t = tplanes + (uint64_t)cur * n;
-    b.prev_rec_t = tplanes + (uint64_t)prev * n;
-    b.out_diffuse = static_cast<float4*>(t->Diffuse);
-    b.out_specular = static_cast<float4*>(t->Specular);
-    RiParamsEx P{};
-    P.frame_index = s->FrameIndex;
-    P.initial_samples = s->InitialSamples ? s->InitialSamples : kRiDefaultInitialSamples;
-    P.temporal = s->EnableTemporal; P.temporal_bias = s->TemporalBiasCorrection;
-    P.max_history = s->MaxHistoryLength ? s->MaxHistoryLength : kRiDefaultHistory;
-    P.spatial = s->EnableSpatial; P.spatial_bias = s->SpatialBiasCorrection;
-    P.spatial_samples = s->SpatialSamples ? s->SpatialSamples : kRiDefaultSpatialSamples;
-    P.radius = std::min(s->SpatialRadius == 0.0f ? kRiDefaultRadius : s->SpatialRadius, kRiMaxRadius);
-    P.history_valid = restart ? 0u : 1u;
-    P.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
-    P.prev_cam_pos = make_f3(c->cam.PreviousPosition[0], c->cam.PreviousPosition[1], c->cam.PreviousPosition[2]);
-    if (cd) {
-        P.brdf_samples = cd->BrdfSamples;
-        P.boiling_filter = cd->EnableBoilingFilter;
-        P.boiling_strength = cd->EnableBoilingFilter ? cd->BoilingFilterStrength : 0.0f;
-    }
-    const PixelMap pm = make_pixel_map(w, h, PtRect{ 0, 0, w, h });  // (at most 2048^2 * 64 = 2^28 slots)
-    const SceneView sv = make_scene_view(c, &L);
-    const uint32_t grid = side_pass_grid(c, pm.n_slots);
-    st = PT_OK;
-    // Presampling (spec S22): pyramid -> Power_RIS -> ReGIR on the lane's stream, in front of launch 1.  The previous call's launch 1 read
-    // the two buffers: this call is ordered after it by what orders the history above -- the stream itself on a one-lane context, the
-    // ev_ri wait otherwise, and a host-side wait where the history was reallocated (a first call has no predecessor) -- so the existing
-    // condition suffices.  The kernels read the lane's own spheres (sv.sph): an emitter moved by pt_update_spheres is seen.
-    LrView lr{};
-    if (mode != kLrUniform) {
-        const uint32_t lv = lr_levels(c->n_lights), n_pyr = lr_pyramid_floats(lv);
-        const uint32_t n_power = lg.tile_size * lg.tile_count;
-        const uint32_t n_ris = n_power + (mode == kLrRegirRis ? lg.grid * lg.grid * lg.grid * lg.lights_per_cell : 0u);
-        if (n_pyr > c->lr_cap_pyramid || n_ris > c->lr_cap_ris) {
-            PT_HIP(c, hipEventSynchronize(c->ev_ri));  // (the previous call, on whichever lane, may still read the old buffers; a no-op before the first record)
-            if (n_pyr > c->lr_cap_pyramid) {
-                free_dev(c->d_lr_pyramid);
-                c->lr_cap_pyramid = 0; c->lr_n_pyramid = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&c->d_lr_pyramid), (size_t)n_pyr * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": pyramid allocation failed"); }
-                c->lr_cap_pyramid = n_pyr;
-            }
-            if (n_ris > c->lr_cap_ris) {
-                free_dev(c->d_lr_ris);
-                c->lr_cap_ris = 0; c->lr_n_ris = 0;
-                if (hipMalloc(&c->d_lr_ris, (size_t)n_ris * sizeof(LrEntry)) != hipSuccess) { (void)hipGetLastError(); return fail(c, PT_ERR_OOM, std::string(who) + ": RIS buffer allocation failed"); }
-                c->lr_cap_ris = n_ris;
-            }
-        }
-        lg.cam = P.cam_pos;
-        LrBuild lb{};
-        lb.sph = sv.sph; lb.mats = sv.mats; lb.lights = sv.lights; lb.n_lights = sv.n_lights; lb.frame_index = s->FrameIndex;
-        lb.pyramid = c->d_lr_pyramid;
-        lb.ris = static_cast<LrEntry*>(c->d_lr_ris);
-        lb.grid = lg;
-        EventPair* ev = c->profiling ? next_events(c, 3) : nullptr;  // pt_get_profile: the presampling launches, as one interval, under ms_tail
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        hipError_t e = launch_lr_pyramid(lb, L.stream);
-        if (e == hipSuccess) e = launch_lr_power(lb, L.stream);
-        if (e == hipSuccess && mode == kLrRegirRis) e = launch_lr_regir(lb, L.stream);
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-        if (e != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": presampling launch: " + hipGetErrorString(e));
-        c->lr_n_pyramid = e == hipSuccess ? n_pyr : 0u;  // (pt_light_ris_download returns only what was built whole)
-        c->lr_n_ris = e == hipSuccess ? n_ris : 0u;
-        lr.ris = lb.ris;
-        lr.tile_size = lg.tile_size; lr.tile_count = lg.tile_count; lr.grid = lg.grid; lr.lights_per_cell = lg.lights_per_cell; lr.cell_size = lg.cell_size;
-    }
-    for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
-        EventPair* ev = c->profiling ? next_events(c, pass == 0 ? 1 : 2) : nullptr;  // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        const RiExtra rx{ c->d_light_of, mode != kLrUniform ? c->d_lr_pyramid : nullptr, lr_levels(c->n_lights) };
-        if (const hipError_t e = pass == 0 ? launch_restir_pass1_ex(sv, pm, b, P, mode, lr, rx, grid, L.stream) : launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream);
-            e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(e));
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-    }
-    const hipError_t e0 = hipEventRecord(c->ev_ri, L.stream);
-    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": history event: " + hipGetErrorString(e0));
-    st = publish_lane_to_caller(c, L, who, st);
-    if (st == PT_OK) {
-        c->ri_slot = cur;
-        c->ri_scene = c->set_scene_calls;
-        c->ri_valid = true;
-    } else {
-        c->ri_valid = false;
-    }
-    return st;
-}
-
-PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, nullptr, t); }
-
-PtStatus pt_restir_di_sampled(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t)
-{
-    return restir_di_common(c, "pt_restir_di_sampled", s, ls, nullptr, t);
-}
-
-PtStatus pt_restir_di_ex(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd, const PtRestirDiTextures* t)
-{
-    return restir_di_common(c, "pt_restir_di_ex", s, ls, cd, t);
-}
-
-PtStatus pt_restir_di_history(PtContext* c, uint32_t which, void* planes, void* transmission)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (which > 1u || !planes || !transmission) return fail(c, PT_ERR_INVALID_ARG, "pt_restir_di_history: which must be 0 or 1 and the arrays non-null");
-    if (!c->ri_valid || !c->d_ri) return fail(c, PT_ERR_STATE, "pt_restir_di_history: no pt_restir_di call has left a history");
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipEventSynchronize(c->ev_ri));
-    const uint64_t n = (uint64_t)c->ri_w * c->ri_h;
-    const uint32_t slot = c->ri_slot ^ which;
-    PT_HIP(c, hipMemcpy(planes, c->d_ri + (uint64_t)slot * 6u * n, 6u * n * sizeof(float4), hipMemcpyDeviceToHost));
-    PT_HIP(c, hipMemcpy(transmission, reinterpret_cast<const float*>(c->d_ri + 12u * n) + (uint64_t)slot * n, n * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-PtStatus pt_light_ris_download(PtContext* c, float* pyramid, uint32_t* n_pyramid, uint32_t* ris, uint32_t* n_entries)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!n_pyramid || !n_entries) return fail(c, PT_ERR_INVALID_ARG, "pt_light_ris_download: null count");
-    if (!c->lr_n_pyramid || !c->d_lr_pyramid || !c->d_lr_ris) return fail(c, PT_ERR_STATE, "pt_light_ris_download: no pt_restir_di_sampled call with a presampling mode has been made");
-    const uint32_t cap_p = *n_pyramid, cap_r = *n_entries;
-    *n_pyramid = c->lr_n_pyramid;
-    *n_entries = c->lr_n_ris;
-    if ((pyramid && cap_p < c->lr_n_pyramid) || (ris && cap_r < c->lr_n_ris)) return fail(c, PT_ERR_INVALID_ARG, "pt_light_ris_download: capacity below the count");
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipEventSynchronize(c->ev_ri));
-    if (pyramid) PT_HIP(c, hipMemcpy(pyramid, c->d_lr_pyramid, (size_t)c->lr_n_pyramid * sizeof(float), hipMemcpyDeviceToHost));
-    if (ris) PT_HIP(c, hipMemcpy(ris, c->d_lr_ris, (size_t)c->lr_n_ris * sizeof(LrEntry), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// Row N14 -- the frame through the radiance cache (DESIGN.md spec S20): up to three stages on the lane of the next render call, ordered
-// like pt_restir_di; the cache (keys, two voxel arrays that swap at every resolve, two counters) lives in the context.
-static PtStatus sharc_allocate(PtContext* c, uint32_t capacity)
-{
-    if (!c->ev_sh) PT_HIP(c, hipEventCreateWithFlags(&c->ev_sh, hipEventDisableTiming));
-    if (c->d_sh && c->sh_capacity == capacity) return PT_OK;
-    if (c->d_sh) PT_HIP(c, hipEventSynchronize(c->ev_sh));  // (the previous call may still use the old arrays)
-    free_dev(c->d_sh);
-    c->sh_valid = false;
-    c->sh_capacity = 0;
-    const size_t bytes = (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)) + 2u * sizeof(unsigned long long);
-    if (hipMalloc(&c->d_sh, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_sh = nullptr; return fail(c, PT_ERR_OOM, "pt_render_sharc: cache allocation failed"); }
-    char* base = static_cast<char*>(c->d_sh);
-    c->sh_accum = reinterpret_cast<uint4*>(base);
-    c->sh_resolved = reinterpret_cast<uint4*>(base + (size_t)capacity * sizeof(uint4));
-    c->sh_keys = reinterpret_cast<uint64_t*>(base + 2u * (size_t)capacity * sizeof(uint4));
-    c->d_sh_counters = reinterpret_cast<unsigned long long*>(base + (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)));
-    c->sh_capacity = capacity;
-    return PT_OK;
-}
-
-static bool sharc_capacity_ok(uint32_t capacity) { return capacity >= kShBucket && capacity <= (1u << 28) && (capacity & (capacity - 1u)) == 0u; }
-
-// pt_render_sharc (ex = false: di and outputs null) and pt_render_sharc_ex (row N18, DESIGN.md spec S24): one body.  `who` names the entry
-// point in messages.
-static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di,
-                           const PtDenoiserOutputs* outputs, PtStats* stats, bool ex, const std::string& who)
-{
-    if (!s) return fail(c, PT_ERR_INVALID_ARG, who + ": null settings");
-    const uint32_t stages = s->Stages ? s->Stages : (uint32_t)(PT_SHARC_UPDATE | PT_SHARC_RESOLVE | PT_SHARC_QUERY);
-    if (stages & ~7u) return fail(c, PT_ERR_INVALID_ARG, who + ": Stages must be a mask of PT_SHARC_UPDATE, PT_SHARC_RESOLVE and PT_SHARC_QUERY");
-    if ((stages & PT_SHARC_QUERY) && !out) return fail(c, PT_ERR_INVALID_ARG, who + ": null output");
-    if (s->_pad[0] || s->_pad[1]) return fail(c, PT_ERR_INVALID_ARG, who + ": the padding words must be 0");
-    const uint32_t capacity = s->Capacity ? s->Capacity : kShDefaultCapacity, downscale = s->DownscaleFactor ? s->DownscaleFactor : kShDefaultDownscale;
-    const float scene_scale = s->SceneScale == 0.0f ? kShDefaultSceneScale : s->SceneScale;
-    const uint32_t acc_frames = s->AccumulationFrames ? s->AccumulationFrames : kShDefaultAccumulationFrames;
-    const uint32_t max_stale = s->MaxStaleFrames ? s->MaxStaleFrames : kShDefaultMaxStaleFrames;
-    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, who + ": Capacity must be a power of two in [16, 1 << 28]");
-    if (downscale > 4u) return fail(c, PT_ERR_INVALID_ARG, who + ": DownscaleFactor must be in [1, 4]");
-    if (!(scene_scale >= 5.0f && scene_scale <= 100.0f)) return fail(c, PT_ERR_INVALID_ARG, who + ": SceneScale must be in [5, 100]");
-    if (!(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, who + ": RoughnessThreshold must be in [0, 1]");
-    if (acc_frames > kShMaxFrames) return fail(c, PT_ERR_INVALID_ARG, who + ": AccumulationFrames must be at most 255");
-    if (max_stale > kShMaxStale) return fail(c, PT_ERR_INVALID_ARG, who + ": MaxStaleFrames must be at most 254");
-    if (s->IsAntiFireflyEnabled) return fail(c, PT_ERR_UNSUPPORTED, who + ": the anti-firefly filter is not built");
-    PtStatus st = validate_frame(c);
-    if (st != PT_OK) return st;
-    if (!ex && (c->gs.IsDIEnabled || c->gs.Denoiser)) return fail(c, PT_ERR_UNSUPPORTED, who + ": IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs through the cache are not built)");
-    PtRect r;
-    PixelMap pm{};
-    if ((st = rect_pixel_map(c, rect, who.c_str(), r, pm)) != PT_OK) return st;
-    DenoiseOut dn{};
-    if (outputs && (st = denoise_out(c, outputs, who.c_str(), dn)) != PT_OK) return st;
-    if (di && (stages & PT_SHARC_UPDATE) && (r.x || r.y || r.w != c->gs.RenderSize[0] || r.h != c->gs.RenderSize[1]))
-        return fail(c, PT_ERR_INVALID_ARG, who + ": with di and the UPDATE stage rect must be NULL or the whole frame (the update reads the whole frame's DI)");
-    if ((st = check_environment(c)) != PT_OK) return st;
-    if ((st = check_tree_lds(c)) != PT_OK) return st;
-    PT_HIP(c, hipSetDevice(c->device));
-    const bool query = (stages & PT_SHARC_QUERY) != 0;
-    float4* dev_out = static_cast<float4*>(out);
-    const size_t out_px = (size_t)r.w * r.h;
-    if (query && !out_is_device) {
-        if (out_px > c->cap_out) {
-            PT_HIP(c, sync_all(c));
-            free_dev(c->d_out);
-            c->cap_out = 0;
-            PT_HIP(c, hipMalloc(&c->d_out, out_px * sizeof(float4)));
-            c->cap_out = out_px;
-        }
-        dev_out = c->d_out;
-    }
-    if (query && (reinterpret_cast<uintptr_t>(dev_out) & 15u)) return fail(c, PT_ERR_INVALID_ARG, who + ": the output must be 16-byte aligned");
-    if (di || outputs) {
-        // the buffer rule of pt_args.h: presence and alignment of all, nothing the call writes sharing a byte with another buffer of the
-        // call.  One exception: a DI buffer may BE the NRD modes' Diffuse or Specular (the same pointer: the update has read it before the
-        // query writes, and that query reads no DI); such a DI buffer leaves the overlap table once its presence and alignment are checked.
-        const uint64_t px = out_px;
-        const BufferUse in[2] = { { di ? di->Diffuse : nullptr, px * 16u, 16u, false, di != nullptr, "di->Diffuse" },
-                                  { di ? di->Specular : nullptr, px * 16u, 16u, false, di != nullptr, "di->Specular" } };
-        std::string msg = check_buffers(who.c_str(), in, 2);
-        if (msg.empty()) {
-            auto is_nrd_output = [&](const void* p) { return p && (p == dn.diffuse || p == dn.specular); };
-            const BufferUse all[6] = { { query ? dev_out : nullptr, px * 16u, 16u, true, false, "out" },
-                                       { dn.spec_hit_dist, px * 4u, 4u, true, false, "SpecularHitDistance" },
-                                       { dn.diffuse, px * 16u, 16u, true, false, "Diffuse" },
-                                       { dn.specular, px * 16u, 16u, true, false, "Specular" },
-                                       { is_nrd_output(in[0].p) ? nullptr : in[0].p, px * 16u, 16u, false, false, "di->Diffuse" },
-                                       { is_nrd_output(in[1].p) ? nullptr : in[1].p, px * 16u, 16u, false, false, "di->Specular" } };
-            msg = check_buffers(who.c_str(), all, 6);
-        }
-        if (!msg.empty()) return fail(c, PT_ERR_INVALID_ARG, msg);
-    }
-
-    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
-    if ((st = side_pass_begin(c, L)) != PT_OK) return st;
-    if (L.stream != c->stream) {
-        // (a supplied DI may have been written on the caller's stream right before this call: the lane waits for everything queued there;
-        // the denoiser outputs are held to the rule of `out`)
-        bool shared = c->calls == 0 || di != nullptr || (query && other_lane_uses(c, L, dev_out, true));
-        const void* extra[5] = { dn.spec_hit_dist, dn.diffuse, dn.specular, di ? di->Diffuse : nullptr, di ? di->Specular : nullptr };
-        for (int k = 0; k < 3 && query && !shared; k++) shared = extra[k] && other_lane_uses(c, L, extra[k], true);
-        if (di || outputs) {  // the rotation rule's record (render_common): a frame on another lane that writes one of them waits
-            for (int k = 0; k < 3; k++) L.last_dn[k] = query ? extra[k] : nullptr;
-            L.last_di[0] = extra[3]; L.last_di[1] = extra[4];
-        }
-        if ((st = order_lane_after_caller(c, L, shared)) != PT_OK) return st;
-    }
-    // the cache: the previous call (on whichever lane it ran) has finished with it before this one touches it
-    const bool had = c->d_sh && c->sh_capacity == capacity;
-    if ((st = sharc_allocate(c, capacity)) != PT_OK) return st;
-    if (had) PT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_sh, 0));
-    const bool restart = s->ResetHistory != 0 || !c->sh_valid || c->sh_scene != c->set_scene_calls;
-    c->sh_valid = false;  // (until the call has been queued whole)
-    const bool timed = stats != nullptr;
-    if (timed) PT_HIP(c, hipEventRecord(c->ev0, L.stream));
-    if (restart) PT_HIP(c, hipMemsetAsync(c->d_sh, 0, (size_t)capacity * (sizeof(uint64_t) + 2u * sizeof(uint4)), L.stream));
-    else if (stages & (PT_SHARC_UPDATE | PT_SHARC_RESOLVE)) PT_HIP(c, hipMemsetAsync(c->sh_accum, 0, (size_t)capacity * sizeof(uint4), L.stream));  // Raytracing.ixx:124
-    PT_HIP(c, hipMemsetAsync(c->d_sh_counters, 0, 2u * sizeof(unsigned long long), L.stream));
-
-    const SceneView sv = make_scene_view(c, &L);
-    const uint32_t w = c->gs.RenderSize[0], h = c->gs.RenderSize[1];
-    ShFrame fr{};
-    fr.cam = camera_params(c->cam, w, h);
-    fr.frame_index = c->gs.FrameIndex; fr.bounces = c->gs.Bounces; fr.spp = c->gs.SamplesPerPixel;
-    fr.rr_enabled = c->gs.IsRussianRouletteEnabled ? 1u : 0u;
-    fr.throughput_threshold = c->gs.ThroughputThreshold;
-    fr.inv_spp = 1.0f / (float)c->gs.SamplesPerPixel;
-    fr.roughness_threshold = s->RoughnessThreshold;
-    fr.visualize = s->IsHashGridVisualizationEnabled ? 1u : 0u;
-    if (di) {  // (the query reads them indexed like `out`: rect-sized; the update, which demands the whole frame, as RenderSize texels)
-        fr.di_diffuse = static_cast<const float4*>(di->Diffuse);
-        fr.di_specular = static_cast<const float4*>(di->Specular);
-        fr.di_w = w; fr.di_h = h;
-    }
-    fr.dn_mode = dn.mode;
-    fr.spec_hit_dist = dn.spec_hit_dist;
-    fr.dn_diffuse = dn.diffuse;
-    fr.dn_specular = dn.specular;
-    ShGrid g{};
-    g.cam_pos = make_f3(c->cam.Position[0], c->cam.Position[1], c->cam.Position[2]);
-    g.scene_scale = scene_scale;
-    auto map = [&] { ShMap m{}; m.keys = c->sh_keys; m.accum = c->sh_accum; m.resolved = c->sh_resolved; m.capacity = capacity; return m; };
-    st = PT_OK;
-    const uint32_t gw = w / downscale, gh = h / downscale;
-    if ((stages & PT_SHARC_UPDATE) && gw && gh) {
-        ShFrame fu = fr;
-        fu.cam = camera_params(c->cam, gw, gh);  // (InvW, InvH of the update grid; the jitter is the path's own)
-        const PixelMap pu = make_pixel_map(gw, gh, PtRect{ 0, 0, gw, gh });
-        EventPair* ev = c->profiling ? next_events(c, 1) : nullptr;  // pt_get_profile: the update under ms_traverse
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = (di ? launch_sharc_update_ex : launch_sharc_update)(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, who + ": update launch: " + hipGetErrorString(e));
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-    }
-    if (st == PT_OK && (stages & PT_SHARC_RESOLVE)) {
-        EventPair* ev = c->profiling ? next_events(c, 3) : nullptr;  // ... the resolve under ms_tail
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = launch_sharc_resolve(map(), acc_frames, max_stale, L.stream); e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, who + ": resolve launch: " + hipGetErrorString(e));
-        else std::swap(c->sh_accum, c->sh_resolved);  // Raytracing.ixx:147
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-    }
-    if (st == PT_OK && query) {
-        EventPair* ev = c->profiling ? next_events(c, 2) : nullptr;  // ... the query under ms_shade
-        if (ev) (void)hipEventRecord(ev->a, L.stream);
-        if (const hipError_t e = (di || outputs ? launch_sharc_query_ex : launch_sharc_query)(sv, pm, fr, g, map(), dev_out, c->d_sh_counters, side_pass_grid(c, pm.n_slots), L.stream);
-            e != hipSuccess)
-            st = fail(c, PT_ERR_HIP, who + ": query launch: " + hipGetErrorString(e));
-        if (ev) (void)hipEventRecord(ev->b, L.stream);
-    }
-    const hipError_t e0 = hipEventRecord(c->ev_sh, L.stream);
-    if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": cache event: " + hipGetErrorString(e0));
-    if (st == PT_OK && timed) {
-        unsigned long long counters[2] = { 0, 0 };
-        PT_HIP(c, hipEventRecord(c->ev1, L.stream));
-        PT_HIP(c, hipMemcpyAsync(counters, c->d_sh_counters, sizeof counters, hipMemcpyDeviceToHost, L.stream));
-        PT_HIP(c, hipStreamSynchronize(L.stream));
-        std::memset(stats, 0, sizeof *stats);
-        float ms = 0;
-        PT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        stats->ms_total = ms;
-        stats->rays = counters[0];
-        stats->pixels = query ? out_px : 0;
-        stats->paths = (query ? out_px * c->gs.SamplesPerPixel : 0) + ((stages & PT_SHARC_UPDATE) ? (uint64_t)gw * gh : 0);
-    }
-    st = publish_lane_to_caller(c, L, who.c_str(), st);
-    if (st != PT_OK) return st;
-    c->sh_valid = true;
-    c->sh_scene = c->set_scene_calls;
-    if (query && !out_is_device) {
-        PT_HIP(c, hipMemcpyAsync(out, dev_out, out_px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        PT_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return PT_OK;
-}
-
-PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, PtStats* stats)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    return sharc_call(c, rect, out, out_is_device, s, nullptr, nullptr, stats, false, "pt_render_sharc");
-}
-
-PtStatus pt_render_sharc_ex(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di,
-                            const PtDenoiserOutputs* outputs, PtStats* stats)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    return sharc_call(c, rect, out, out_is_device, s, di, outputs, stats, true, "pt_render_sharc_ex");
-}
-
-PtStatus pt_sharc_download(PtContext* c, void* keys, void* voxels, uint32_t capacity)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!keys || !voxels) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_download: null pointer");
-    if (!c->d_sh || !c->sh_valid) return fail(c, PT_ERR_STATE, "pt_sharc_download: there is no cache (no pt_render_sharc call has completed)");
-    if (capacity != c->sh_capacity) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_download: capacity differs from the cache's");
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipEventSynchronize(c->ev_sh));
-    PT_HIP(c, hipMemcpy(keys, c->sh_keys, (size_t)capacity * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    PT_HIP(c, hipMemcpy(voxels, c->sh_resolved, (size_t)capacity * sizeof(uint4), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-PtStatus pt_sharc_upload(PtContext* c, const void* keys, const void* voxels, uint32_t capacity)
-{
-    if (!c) return PT_ERR_INVALID_ARG;
-    if (!keys || !voxels) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_upload: null pointer");
-    if (!sharc_capacity_ok(capacity)) return fail(c, PT_ERR_INVALID_ARG, "pt_sharc_upload: capacity must be a power of two in [16, 1 << 28]");
-    PT_HIP(c, hipSetDevice(c->device));
-    if (const PtStatus st = sharc_allocate(c, capacity); st != PT_OK) return st;
-    PT_HIP(c, hipEventSynchronize(c->ev_sh));
-    PT_HIP(c, hipMemcpy(c->sh_keys, keys, (size_t)capacity * sizeof(uint64_t), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->sh_resolved, voxels, (size_t)capacity * sizeof(uint4), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemset(c->sh_accum, 0, (size_t)capacity * sizeof(uint4)));
-    PT_HIP(c, hipDeviceSynchronize());  // (a memset may return before the device has finished it: the lanes' streams do not wait for the null stream)
-    c->sh_valid = true;
-    c->sh_scene = c->set_scene_calls;
     return PT_OK;
 }
 

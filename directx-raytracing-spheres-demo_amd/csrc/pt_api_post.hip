@@ -1,7 +1,7 @@
 // pt_api_post.hip -- the entry points of the C-ABI (include/pt_api.h) that touch nothing but the context's stream and their own state:
 // tone mapping, accumulation, bloom, the NRD composition and stand-in, super-resolution, sharpening, frame interpolation and ray
 // reconstruction.
-// Everything that knows lanes, the scene, the tree or the beam cache is in pt_api.hip.
+// Everything that knows lanes, the scene, the tree or the beam cache is in pt_api.hip and pt_api_side.hip (the side passes of a frame).
 #include <algorithm>
 #include <string>
 

@@ -1,6 +1,7 @@
 // pt_context.h -- the context behind the C-ABI's opaque PtContext and the helpers every entry point uses (fail, PT_HIP, free_dev).
-// Internal to the two translation units that implement include/pt_api.h: pt_api.hip (everything that knows lanes, the scene, the tree
-// or the beam cache) and pt_api_post.hip (the passes that touch nothing but the context's stream and their own state).
+// Internal to the three translation units that implement include/pt_api.h: pt_api.hip (the context, the scene, the tree, the beam cache
+// and the frames), pt_api_side.hip (the side passes of a frame: G-buffer, reservoir pass, radiance cache; they share the helpers declared
+// at the end of this file) and pt_api_post.hip (the passes that touch nothing but the context's stream and their own state).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,10 +14,11 @@
 #include "../../include/pt_api.h"
 #include "pt_args.h"
 #include "pt_kernels.h"
+#include "pt_lane_order.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
 
-using namespace pt;  // (an internal header: the two units it serves are written in pt's names throughout)
+using namespace pt;  // (an internal header: the units it serves are written in pt's names throughout)
 
 struct EventPair {
     hipEvent_t a, b;
@@ -71,9 +73,7 @@ struct Lane {
     uint64_t sph_gen = 0;         // the pt_update_spheres generation this lane's private scene holds (PtContext::sph_gen)
     bool needs_refit = false;     // spheres were staged on this lane and its boxes / Morton-ordered copy have not been redone yet
     bool upload_pending = false;  // h_stage holds spheres that have not been copied to d_sph yet (pt_update_spheres of a small scene: pt_refit_accel's kernel reads them)
-    const void* last_out = nullptr;   // output buffer of the lane's latest frame (render_common: repeated buffers inside the window)
-    const void* last_dn[3] = {};      // ... and its denoiser buffers (Diffuse, Specular, SpecularHitDistance; null for other frames)
-    const void* last_di[2] = {};      // ... and the DI buffers it read (pt_render_with_di: Diffuse, Specular; null for other frames)
+    LaneLedger ledger;  // the caller buffers of the lane's latest frame, G-buffer call and reservoir pass (pt_lane_order.h: repeated buffers inside the window)
     // object rotations (textured scenes): the lane's own copy, refreshed from PtContext::h_rot when its generation is behind
     float4* d_rot = nullptr;
     float4* h_rot_stage = nullptr;    // pinned
@@ -87,8 +87,6 @@ struct Lane {
     hipEvent_t ev_prev = nullptr;     // the last upload from h_prev_stage has been consumed
     uint32_t prev_cap = 0;            // spheres the two buffers hold room for
     hipEvent_t ev_gb_in = nullptr;
-    void* last_gb[13] = {};           // the buffers of the lane's latest G-buffer call (its ordering against the caller's stream)
-    const void* last_ri[2] = {};      // the outputs of the lane's latest pt_restir_di call
 };
 constexpr uint32_t kMaxLanes = 8;
 
@@ -165,6 +163,7 @@ struct PtContext {
     // work buffers: one set per frame in flight.  Frame f runs on lane f % n_lanes, on that lane's own stream, so the
     // latency-bound looping pass of one frame overlaps the throughput-bound first passes of the next.
     Lane lanes[kMaxLanes];
+    LaneLedger* ledgers[kMaxLanes];  // &lanes[i].ledger (pt_create): the form pt_lane_order.h takes them in
     uint32_t n_lanes = 1;
     uint32_t next_lane = 0;
     uint32_t last_lane = 0;
@@ -302,4 +301,29 @@ template <typename T>
 inline void free_dev(T*& p)
 {
     if (p) { (void)hipFree(p); p = nullptr; }
+}
+
+// ---- the lane side of a frame and of its side passes: defined in pt_api.hip (each with its comment), used by pt_api_side.hip too; hidden: not part of the library's interface
+#pragma GCC visibility push(hidden)
+PtStatus validate_frame(PtContext* c), check_environment(PtContext* c), check_tree_lds(PtContext* c);
+PtStatus rect_pixel_map(PtContext* c, const PtRect* rect, const char* who, PtRect& r, PixelMap& pm);
+PixelMap make_pixel_map(uint32_t img_w, uint32_t img_h, const PtRect& r);
+PtStatus denoise_out(PtContext* c, const PtDenoiserOutputs* outputs, const char* who, DenoiseOut& dn);
+SceneView make_scene_view(const PtContext* c, const Lane* L = nullptr);
+uint32_t side_pass_grid(const PtContext* c, uint32_t n_slots);
+PtStatus side_pass_begin(PtContext* c, Lane& L, bool shared);
+PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus st);
+EventPair* next_events(PtContext* c, int kind);
+PtStatus staged_out_begin(PtContext* c, void* out, bool staged, size_t out_px, float4*& dev_out), staged_out_finish(PtContext* c, void* out, bool staged, size_t out_px);
+#pragma GCC visibility pop
+
+// launch() with its interval booked under `kind` while profiling is on (pt_get_profile: EventPair::kind); the second event is recorded after a failed launch too
+template <typename F>
+inline hipError_t profiled_launch(PtContext* c, hipStream_t stream, int kind, F&& launch)
+{
+    EventPair* ev = c->profiling ? next_events(c, kind) : nullptr;
+    if (ev) (void)hipEventRecord(ev->a, stream);
+    const hipError_t e = launch();
+    if (ev) (void)hipEventRecord(ev->b, stream);
+    return e;
 }
