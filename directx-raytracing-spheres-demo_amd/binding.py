@@ -643,7 +643,8 @@ class Renderer:
     def render_sharc_ex_device(self, out_ptr, diffuse_ptr=None, specular_ptr=None, rect=None, mode=0, buffers=None, want_stats=False, **settings):
         """render_sharc_device with the frame's direct illumination and denoiser outputs (row N18, DESIGN.md spec S24; pt_render_sharc_ex).
         diffuse_ptr / specular_ptr: the DI as for render_with_di_device (None: no DI); mode 0 = Denoiser::None, else abi_types.DENOISER_*
-        with `buffers` as for render_denoiser_device.  Without DI and mode the call is render_sharc_device.  Asynchronous unless want_stats."""
+        with `buffers` as for render_denoiser_device.  Without DI and mode the call is render_sharc_device.  anti_firefly=True (row N19,
+        spec S25) is accepted here, with or without DI and mode; render_sharc_device refuses it.  Asynchronous unless want_stats."""
         r = PtRect(*rect) if rect is not None else None
         s = sharc_settings(**settings)
         di = PtDirectLighting(Diffuse=C.c_void_p(int(diffuse_ptr or 0)), Specular=C.c_void_p(int(specular_ptr or 0))) if diffuse_ptr or specular_ptr else None

@@ -343,7 +343,7 @@ static PtStatus sharc_allocate(PtContext* c, uint32_t capacity)
 static bool sharc_capacity_ok(uint32_t capacity) { return capacity >= kShBucket && capacity <= (1u << 28) && (capacity & (capacity - 1u)) == 0u; }
 
 // pt_render_sharc (ex = false: di and outputs null) and pt_render_sharc_ex (row N18, DESIGN.md spec S24): one body.  `who` names the entry
-// point in messages.
+// point in messages.  IsAntiFireflyEnabled (row N19, spec S25) is accepted by the _ex entry point only.
 static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di,
                            const PtDenoiserOutputs* outputs, PtStats* stats, bool ex, const std::string& who)
 {
@@ -363,7 +363,8 @@ static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_
     if (!(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, who + ": RoughnessThreshold must be in [0, 1]");
     if (acc_frames > kShMaxFrames) return fail(c, PT_ERR_INVALID_ARG, who + ": AccumulationFrames must be at most 255");
     if (max_stale > kShMaxStale) return fail(c, PT_ERR_INVALID_ARG, who + ": MaxStaleFrames must be at most 254");
-    if (s->IsAntiFireflyEnabled) return fail(c, PT_ERR_UNSUPPORTED, who + ": the anti-firefly filter is not built");
+    const bool ff = s->IsAntiFireflyEnabled != 0;  // (row N19, spec S25: the _ex update and the resolve; no state of its own)
+    if (ff && !ex) return fail(c, PT_ERR_UNSUPPORTED, who + ": IsAntiFireflyEnabled must be 0 (the anti-firefly filter runs through pt_render_sharc_ex)");
     PtStatus st = validate_frame(c);
     if (st != PT_OK) return st;
     if (!ex && (c->gs.IsDIEnabled || c->gs.Denoiser)) return fail(c, PT_ERR_UNSUPPORTED, who + ": IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs through the cache are not built)");
@@ -450,11 +451,12 @@ static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_
         fu.cam = camera_params(c->cam, gw, gh);  // (InvW, InvH of the update grid; the jitter is the path's own)
         const PixelMap pu = make_pixel_map(gw, gh, PtRect{ 0, 0, gw, gh });
         // pt_get_profile: the update under ms_traverse
-        const hipError_t e = profiled_launch(c, L.stream, 1, [&] { return (di ? launch_sharc_update_ex : launch_sharc_update)(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); });
+        const hipError_t e = profiled_launch(c, L.stream, 1, [&] { return di || ff ? launch_sharc_update_ex(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), ff, L.stream)
+                                                                              : launch_sharc_update(sv, pu, fu, g, map(), c->d_sh_counters, side_pass_grid(c, pu.n_slots), L.stream); });
         if (e != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": update launch: " + hipGetErrorString(e));
     }
     if (st == PT_OK && (stages & PT_SHARC_RESOLVE)) {
-        const hipError_t e = profiled_launch(c, L.stream, 3, [&] { return launch_sharc_resolve(map(), acc_frames, max_stale, L.stream); });  // ... the resolve under ms_tail
+        const hipError_t e = profiled_launch(c, L.stream, 3, [&] { return launch_sharc_resolve(map(), acc_frames, max_stale, ff, L.stream); });  // ... the resolve under ms_tail
         if (e != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": resolve launch: " + hipGetErrorString(e));
         else std::swap(c->sh_accum, c->sh_resolved);  // Raytracing.ixx:147
     }

@@ -10,12 +10,15 @@
 //   sh_query_pixel                           one pixel of the frame: pt_render's loop with the cache look-up in it
 //   sh_update_path_ex / sh_query_pixel_ex    the same two with the extras of pt_render_sharc_ex (row N18, spec S24): the frame's direct
 //                                            illumination read from the caller's buffers, the denoiser outputs of spec S13 written
+//   sh_resolve_slot_ff / sh_propagate_ff     the anti-firefly filter (row N19, spec S25; IsAntiFireflyEnabled through pt_render_sharc_ex): a
+//                                            luminance clamp of the frame's sums against the voxel's history in front of the resolve's
+//                                            join, and a weight threshold that stops the update's back-propagation.  The library's
+//                                            structure as far as recollection goes; the arithmetic and the constants are this project's
 // The closest-hit query is a functor trace(o, d, tmin, tmax, t, id), the surface a functor material(id, o, d, t, primary) -> HitMaterial,
 // the radiance of a ray that left the scene a functor env(d).  A trace that misses returns id = 0xFFFFFFFF and t = tmax.
 //
-// Out of scope: the anti-firefly filter; the compaction pass and its HashCopyOffset buffer (SHARC.hlsl:58-61: a hole an eviction
-// leaves is reused by the next insert instead); re-loading the update path's first vertex from a G-buffer (the path traces its own
-// primary ray).
+// Out of scope: the compaction pass and its HashCopyOffset buffer (SHARC.hlsl:58-61: a hole an eviction leaves is reused by the next
+// insert instead); re-loading the update path's first vertex from a G-buffer (the path traces its own primary ray).
 #pragma once
 
 #include "pt_surface.h"
@@ -38,6 +41,11 @@ constexpr uint32_t kShSampleBits = 16, kShFrameBits = 8;  // voxel.w = samples |
 constexpr uint32_t kShMaxSamples = (1u << kShSampleBits) - 1u, kShMaxFrames = 255u, kShMaxStale = 254u;
 constexpr uint32_t kShDefaultCapacity = 1u << 22, kShDefaultDownscale = 4, kShDefaultAccumulationFrames = 10, kShDefaultMaxStaleFrames = 64;
 constexpr float kShDefaultSceneScale = 50.0f;
+// the anti-firefly filter (spec S25; this project's constants)
+constexpr uint32_t kShFfMinSamples = 8, kShFfMinFrames = 2;  // the history the resolve's clamp needs: resolved samples, resolved frames
+constexpr float kShFfFloor = 1.0f;                           // the history's luminance counts at least this
+constexpr float kShFfClampBase = 5.0f, kShFfClampSlope = 5.0f;  // K = base + slope / samples: 5 for a long history, at most 5.625
+constexpr float kShFfWeightThreshold = 2.0f;                 // the back-propagation stops where the running weight's luminance exceeds this
 
 struct alignas(16) ShKeyPair { uint64_t k[2]; };  // two keys per 128-bit load
 
@@ -230,12 +238,62 @@ PT_HD uint4 sh_resolve_slot(const uint4& acc, const uint4& prev, uint32_t accumu
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------- anti-firefly filter (spec S25)
+// Y(c), left to right, no fma
+PT_HD float sh_luminance(f3 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z; }
+
+// sum / (n kRadianceScale) of this frame's accumulators, whose count is the whole word (sh_radiance masks a resolved voxel's to 16 bits)
+PT_HD f3 sh_accum_mean(const uint4& acc)
+{
+    const float d = (float)acc.w * kShRadianceScale;
+    return make_f3((float)acc.x / d, (float)acc.y / d, (float)acc.z / d);
+}
+
+// trunc(float(sum) * s) for s in (0, 1], never above sum: float(sum) rounds to nearest and may lie above sum (at 2^32 for the largest
+// sums, which no uint32_t holds), and s may have rounded to 1
+PT_HD uint32_t sh_ff_scale(uint32_t sum, float s)
+{
+    const float t = (float)sum * s;
+    if (!(t < 4294967296.0f)) return sum;
+    const uint32_t r = (uint32_t)t;
+    return r < sum ? r : sum;
+}
+
+// The resolve's clamp: where the voxel has a history of kShFfMinSamples samples over kShFfMinFrames frames and this frame brought
+// samples whose mean luminance Y_a exceeds K max(Y(history), kShFfFloor), the three sums are scaled by K Y_p / Y_a (one division, one
+// multiplication per sum, truncation); the count stays.  true = clamped.  Every value is finite: the history has samples, Y_a > 0 where
+// it is divided by.
+PT_HD bool sh_ff_clamp(uint4& acc, const uint4& prev)
+{
+    const uint32_t n_p = sh_samples(prev);
+    if (!(acc.w > 0u && n_p >= kShFfMinSamples && sh_frames(prev) >= kShFfMinFrames)) return false;
+    const float y_p = pt_max(sh_luminance(sh_radiance(prev)), kShFfFloor);
+    const float y_a = sh_luminance(sh_accum_mean(acc));
+    const float k = kShFfClampBase + kShFfClampSlope / (float)n_p;
+    const float limit = k * y_p;
+    if (!(y_a > limit)) return false;
+    const float s = limit / y_a;
+    acc.x = sh_ff_scale(acc.x, s);
+    acc.y = sh_ff_scale(acc.y, s);
+    acc.z = sh_ff_scale(acc.z, s);
+    return true;
+}
+
+// sh_resolve_slot with the clamp in front of the join
+PT_HD uint4 sh_resolve_slot_ff(const uint4& acc, const uint4& prev, uint32_t accumulation_frames, uint32_t max_stale_frames, bool& clear)
+{
+    uint4 a = acc;
+    (void)sh_ff_clamp(a, prev);
+    return sh_resolve_slot(a, prev, accumulation_frames, max_stale_frames, clear);
+}
+
 // ---------------------------------------------------------------------------------------------------- update (SHARC_UPDATE)
 struct ShState {
     uint32_t slot[kShPropagationDepth - 1u];
     f3 weight[kShPropagationDepth - 1u];
     uint32_t length;   // stored vertices
     bool skipped;      // the last vertex found no slot: its segment's throughput joins the stored one
+    uint32_t stopped;  // kFf: walks the weight threshold stopped (a statistic the host-side tests read; the kernels never do)
 };
 
 // SharcUpdateMiss, and the tail of SharcUpdateHit: the radiance through the stored weights into every stored vertex, without samples
@@ -250,15 +308,42 @@ PT_SH_UNROLL
     }
 }
 
-// SharcUpdateHit: false = the path ends here (it took the previous frame's radiance of the voxel)
-PT_HD bool sh_update_hit(const ShGrid& g, const ShMap& m, ShState& st, f3 P, f3 front_normal, f3 emission, float rnd, uint32_t& failed)
+// sh_propagate with the anti-firefly filter's weight threshold (spec S25): W, the running product of the stored weights, is multiplied
+// as the radiance is, and the walk stops in front of the first vertex where Y(W) exceeds kShFfWeightThreshold: that vertex and every
+// one behind it receive nothing of this radiance.  (A NaN luminance compares false and stops nothing: sh_quantise counts a NaN as 0.)
+PT_HD void sh_propagate_ff(const ShMap& m, ShState& st, f3 radiance)
+{
+    f3 W = make_f3(1.0f, 1.0f, 1.0f);
+    bool open = true;
+PT_SH_UNROLL
+    for (uint32_t i = 0; i < kShPropagationDepth - 1u; i++) {
+        if (i < st.length && open) {
+            radiance = radiance * st.weight[i];
+            W = W * st.weight[i];
+            if (sh_luminance(W) > kShFfWeightThreshold) { open = false; st.stopped++; }
+            else sh_add(m.accum, st.slot[i], radiance, 0u);
+        }
+    }
+}
+
+template <bool kFf>
+PT_HD void sh_propagate_t(const ShMap& m, ShState& st, f3 radiance)
+{
+    if constexpr (kFf) sh_propagate_ff(m, st, radiance);
+    else sh_propagate(m, st, radiance);
+}
+
+// SharcUpdateHit: false = the path ends here (it took the previous frame's radiance of the voxel).  kFf: the radiance goes back
+// through sh_propagate_ff; the vertex's own (emission, 1 sample) is added as without the filter.
+template <bool kFf>
+PT_HD bool sh_update_hit_t(const ShGrid& g, const ShMap& m, ShState& st, f3 P, f3 front_normal, f3 emission, float rnd, uint32_t& failed)
 {
     float voxel;
     const uint64_t key = sh_key_at(g, P, front_normal, voxel);
     const uint32_t slot = sh_insert(m.keys, m.capacity, key);
     if (slot == kShNoSlot) {  // the bucket is full: the path goes on without this vertex
         failed++;
-        sh_propagate(m, st, emission);
+        sh_propagate_t<kFf>(m, st, emission);
         st.skipped = true;
         return true;
     }
@@ -270,7 +355,7 @@ PT_HD bool sh_update_hit(const ShGrid& g, const ShMap& m, ShState& st, f3 P, f3 
         if (sh_samples(v) > 0u) { radiance = sh_radiance(v); go_on = false; }
     }
     if (go_on) sh_add(m.accum, slot, emission, 1u);
-    sh_propagate(m, st, radiance);
+    sh_propagate_t<kFf>(m, st, radiance);
 PT_SH_UNROLL
     for (uint32_t i = kShPropagationDepth - 2u; i > 0u; i--) { st.slot[i] = st.slot[i - 1u]; st.weight[i] = st.weight[i - 1u]; }
     st.slot[0] = slot;
@@ -278,6 +363,11 @@ PT_SH_UNROLL
     st.length = st.length + 1u < kShPropagationDepth - 1u ? st.length + 1u : kShPropagationDepth - 1u;
     st.skipped = false;
     return go_on;
+}
+
+PT_HD bool sh_update_hit(const ShGrid& g, const ShMap& m, ShState& st, f3 P, f3 front_normal, f3 emission, float rnd, uint32_t& failed)
+{
+    return sh_update_hit_t<false>(g, m, st, P, front_normal, emission, rnd, failed);
 }
 
 // SharcSetThroughput
@@ -305,9 +395,11 @@ PT_HD bool sh_load_di(const ShFrame& fr, size_t index, f3& DI)
 // One path of the update pass: path (x, y) of the grid fr.cam was made for (InvW, InvH = 1 / grid size).
 // kEx (spec S24) with fr.di_diffuse: the first vertex takes the DI of the texel the path's UV falls in, and the second vertex's emission
 // is dropped where that DI is valid, unless the path left the first one through the transmission lobe (:302, :311).
-template <bool kEx, typename TraceFn, typename MaterialFn, typename EnvFn>
-PT_HD void sh_update_path_t(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
-                            uint32_t& rays, uint32_t& failed)
+// kFf (spec S25): the radiance goes back through sh_propagate_ff.  st: the path's state, the caller's, so that a host-side test can read
+// st.stopped afterwards.
+template <bool kEx, bool kFf, typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_walk(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                          ShState& st, uint32_t& rays, uint32_t& failed)
 {
     uint32_t rng = rng_init(x, y, fr.frame_index);
     CameraParams cam = fr.cam;
@@ -322,9 +414,9 @@ PT_HD void sh_update_path_t(const ShFrame& fr, const ShGrid& g, const ShMap& m, 
         const float u = ((float)x + 0.5f + cam.JitterX) * cam.InvW, v = ((float)y + 0.5f + cam.JitterY) * cam.InvH;
         texel = sh_texel(v, fr.di_h) * fr.di_w + sh_texel(u, fr.di_w);
     }
-    ShState st;
     st.length = 0u;
     st.skipped = false;
+    st.stopped = 0u;
 PT_SH_UNROLL
     for (uint32_t i = 0; i < kShPropagationDepth - 1u; i++) { st.slot[i] = 0u; st.weight[i] = make_f3(1.0f, 1.0f, 1.0f); }
     for (uint32_t bounce = 0;; bounce++) {
@@ -333,7 +425,7 @@ PT_SH_UNROLL
         trace(o, d, tmin, tmax, t, id);
         rays++;
         if (id == 0xFFFFFFFFu) {
-            sh_propagate(m, st, env(d));
+            sh_propagate_t<kFf>(m, st, env(d));
             return;
         }
         HitMaterial hm = material(id, o, d, t, bounce == 0u);
@@ -347,7 +439,7 @@ PT_SH_UNROLL
             if (di_valid) radiance = DI + radiance;
         }
         if (kEx && bounce == 1u && drop_emission) radiance = make_f3(0.0f, 0.0f, 0.0f);
-        if (!sh_update_hit(g, m, st, hm.hf.P, front_normal, radiance, rng_float(rng), failed)) return;
+        if (!sh_update_hit_t<kFf>(g, m, st, hm.hf.P, front_normal, radiance, rng_float(rng), failed)) return;
         if (bounce == fr.bounces) return;
         const Surf surf = surf_init(hm.hf.front, hm.hf.N, hm.Ns);
         const f3 V = -d;
@@ -376,6 +468,14 @@ PT_SH_UNROLL
     }
 }
 
+template <bool kEx, typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD void sh_update_path_t(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                            uint32_t& rays, uint32_t& failed)
+{
+    ShState st;
+    sh_update_walk<kEx, false>(fr, g, m, x, y, trace, material, env, st, rays, failed);
+}
+
 template <typename TraceFn, typename MaterialFn, typename EnvFn>
 PT_HD void sh_update_path(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
                           uint32_t& rays, uint32_t& failed)
@@ -388,6 +488,16 @@ PT_HD void sh_update_path_ex(const ShFrame& fr, const ShGrid& g, const ShMap& m,
                              uint32_t& rays, uint32_t& failed)
 {
     sh_update_path_t<true>(fr, g, m, x, y, trace, material, env, rays, failed);
+}
+
+// sh_update_path_ex with the anti-firefly filter (spec S25); returns the walks the weight threshold stopped
+template <typename TraceFn, typename MaterialFn, typename EnvFn>
+PT_HD uint32_t sh_update_path_ff(const ShFrame& fr, const ShGrid& g, const ShMap& m, uint32_t x, uint32_t y, TraceFn&& trace, MaterialFn&& material, EnvFn&& env,
+                                 uint32_t& rays, uint32_t& failed)
+{
+    ShState st;
+    sh_update_walk<true, true>(fr, g, m, x, y, trace, material, env, st, rays, failed);
+    return st.stopped;
 }
 
 // ---------------------------------------------------------------------------------------------------- query (SHARC_QUERY)
@@ -577,12 +687,13 @@ struct PixelMap;
 // counters: [0] rays traced, [1] inserts that found their bucket full
 hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
                                hipStream_t stream);
-hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream);
+// ff: the anti-firefly filter (spec S25), in the resolve and in the _ex update
+hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, bool ff, hipStream_t stream);
 hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                               uint32_t grid, hipStream_t stream);
 // pt_render_sharc_ex (spec S24): the instances that read fr's DI (update, query) and write its denoiser outputs (query)
 hipError_t launch_sharc_update_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
-                                  hipStream_t stream);
+                                  bool ff, hipStream_t stream);
 hipError_t launch_sharc_query_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                                  uint32_t grid, hipStream_t stream);
 #endif

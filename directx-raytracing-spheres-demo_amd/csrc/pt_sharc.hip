@@ -1,8 +1,9 @@
-// pt_sharc.hip -- the three kernels of rows N14 and N18 (pt_render_sharc, pt_render_sharc_ex; DESIGN.md specs S20 and S24) over pt_sharc.h:
+// pt_sharc.hip -- the three kernels of rows N14, N18 and N19 (pt_render_sharc, pt_render_sharc_ex; DESIGN.md specs S20, S24 and S25) over pt_sharc.h:
 //   update   one lane per path of the downscaled grid, one 8x8 block of paths per wave64 (PixelMap): sh_update_path
 //   resolve  one lane per slot of the hash map, streaming: sh_resolve_slot, 128-bit loads and stores
 //   query    one lane per pixel, one 8x8 pixel block per wave64: sh_query_pixel
 // kEx: the instances of pt_render_sharc_ex with a DI or denoiser outputs (sh_update_path_ex, sh_query_pixel_ex, which stores the pixel itself)
+// kFf: the anti-firefly filter of row N19 (spec S25): the kEx update (sh_update_path_ff) and the resolve (sh_resolve_slot_ff); the query does not read the flag
 // Rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory), chosen as
 // pt_restir.hip chooses it.
 #include "pt_trace.h"
@@ -12,7 +13,7 @@ namespace pt {
 
 namespace {
 
-template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha, bool kEx>
+template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha, bool kEx, bool kFf>
 __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, PixelMap pm, ShFrame fr, ShGrid g, ShMap m, float4* __restrict__ out,
                                                                  unsigned long long* __restrict__ counters)
 {
@@ -50,6 +51,8 @@ __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, P
         } else if (kQuery) {
             const f3 c = sh_query_pixel(fr, g, m, pr.px, pr.py, trace, material, env, rays);
             out[pr.out_index] = make_float4(c.x, c.y, c.z, 1.0f);
+        } else if (kEx && kFf) {
+            (void)sh_update_path_ff(fr, g, m, pr.px, pr.py, trace, material, env, rays, failed);
         } else if (kEx) {
             sh_update_path_ex(fr, g, m, pr.px, pr.py, trace, material, env, rays, failed);
         } else {
@@ -60,46 +63,48 @@ __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, P
     if (!kQuery) block_atomic_add(counters + 1, failed);
 }
 
-template <bool kQuery, bool kEx, bool kTex, bool kAlpha>
+template <bool kQuery, bool kEx, bool kFf, bool kTex, bool kAlpha>
 hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                     uint32_t grid, hipStream_t stream)
 {
     const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
     const uint32_t threads = traverse_threads(lds_scene);
     const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx>)
-                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx>);
+    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx, kFf> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx, kFf>)
+                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx, kFf> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx, kFf>);
     if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (lds_scene) {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
     } else {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
+        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
     }
     return hipGetLastError();
 }
 
-template <bool kQuery, bool kEx>
+template <bool kQuery, bool kEx, bool kFf>
 hipError_t launch_any(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                       uint32_t grid, hipStream_t stream)
 {
     // the textured variants only where textures exist; the alpha-tested walk only where some sphere's hits are tested against a map
-    if (!sv.tex_maps) return launch_t<kQuery, kEx, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
-    if (sv.alpha_tested) return launch_t<kQuery, kEx, true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
-    return launch_t<kQuery, kEx, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    if (!sv.tex_maps) return launch_t<kQuery, kEx, kFf, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    if (sv.alpha_tested) return launch_t<kQuery, kEx, kFf, true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_t<kQuery, kEx, kFf, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
 }
 
 constexpr uint32_t kResolveThreads = 256;
 
-// one lane per slot: key (8 B) and two voxels (16 B each) in, one voxel out, the key only where the slot is evicted
+// one lane per slot: key (8 B) and two voxels (16 B each) in, one voxel out, the key only where the slot is evicted.  kFf: the
+// anti-firefly clamp in front of the join (sh_resolve_slot_ff, spec S25)
+template <bool kFf>
 __global__ __launch_bounds__(kResolveThreads) void sharc_resolve_kernel(ShMap m, uint32_t accumulation_frames, uint32_t max_stale_frames)
 {
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < m.capacity; slot += gridDim.x * blockDim.x) {
         if (m.keys[slot] == 0u) continue;  // (an empty slot's accumulators were cleared with the array and nothing adds to them)
         const uint4 acc = m.accum[slot], prev = m.resolved[slot];
         bool clear;
-        const uint4 r = sh_resolve_slot(acc, prev, accumulation_frames, max_stale_frames, clear);
+        const uint4 r = kFf ? sh_resolve_slot_ff(acc, prev, accumulation_frames, max_stale_frames, clear) : sh_resolve_slot(acc, prev, accumulation_frames, max_stale_frames, clear);
         m.accum[slot] = r;
         if (clear) m.keys[slot] = 0u;
     }
@@ -110,31 +115,33 @@ __global__ __launch_bounds__(kResolveThreads) void sharc_resolve_kernel(ShMap m,
 hipError_t launch_sharc_update(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
                                hipStream_t stream)
 {
-    return launch_any<false, false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+    return launch_any<false, false, false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
 }
 
 hipError_t launch_sharc_update_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, unsigned long long* counters, uint32_t grid,
-                                  hipStream_t stream)
+                                  bool ff, hipStream_t stream)
 {
-    return launch_any<false, true>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+    if (ff) return launch_any<false, true, true>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
+    return launch_any<false, true, false>(sv, pm, fr, g, m, nullptr, counters, grid, stream);
 }
 
 hipError_t launch_sharc_query(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                               uint32_t grid, hipStream_t stream)
 {
-    return launch_any<true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_any<true, false, false>(sv, pm, fr, g, m, out, counters, grid, stream);
 }
 
 hipError_t launch_sharc_query_ex(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                                  uint32_t grid, hipStream_t stream)
 {
-    return launch_any<true, true>(sv, pm, fr, g, m, out, counters, grid, stream);
+    return launch_any<true, true, false>(sv, pm, fr, g, m, out, counters, grid, stream);
 }
 
-hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, hipStream_t stream)
+hipError_t launch_sharc_resolve(const ShMap& m, uint32_t accumulation_frames, uint32_t max_stale_frames, bool ff, hipStream_t stream)
 {
     const uint32_t grid = std::min((m.capacity + kResolveThreads - 1u) / kResolveThreads, 4096u);
-    hipLaunchKernelGGL(sharc_resolve_kernel, dim3(grid), dim3(kResolveThreads), 0, stream, m, accumulation_frames, max_stale_frames);
+    if (ff) hipLaunchKernelGGL(sharc_resolve_kernel<true>, dim3(grid), dim3(kResolveThreads), 0, stream, m, accumulation_frames, max_stale_frames);
+    else hipLaunchKernelGGL(sharc_resolve_kernel<false>, dim3(grid), dim3(kResolveThreads), 0, stream, m, accumulation_frames, max_stale_frames);
     return hipGetLastError();
 }
 

@@ -186,8 +186,12 @@ struct Raytracing {
 
     // Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings) (Raytracing.ixx:114-148; row N14, pt_render_sharc): the sparse update
     // pass, the resolve and the frame through the cache.  The context owns the cache the reference's SHARC object owns.
+    // settings.IsAntiFireflyEnabled (App.cpp:1278 sets it; row N19, spec S25): pt_render_sharc refuses the filter, so such a frame goes
+    // through pt_render_sharc_ex, without DI or denoiser outputs unless GraphicsSettings.Denoiser names one (which then needs the
+    // five-argument form and its buffers).
     PtStats Render(std::vector<Float4>& radiance, SHARC& sharc, const SHARCSettings& settings)
     {
+        if (settings.IsAntiFireflyEnabled) return Render(radiance, sharc, settings, nullptr, nullptr);
         ThrowIfFailed(pt_set_constants(m_ctx, &m_graphicsSettings), m_ctx, "pt_set_constants");
         radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
         PtSharcSettings s{};
@@ -208,7 +212,8 @@ struct Raytracing {
 
     // The same with IsDIEnabled = isReSTIRDIEnabled and GraphicsSettings.Denoiser (App.cpp:1255-1268; row N18, pt_render_sharc_ex): the
     // reference's default frame.  di: null = no DI; buffers: the denoiser outputs when GraphicsSettings.Denoiser names one (required
-    // then).  The constants go up with Denoiser = None, the mode travels with the call.
+    // then).  The constants go up with Denoiser = None, the mode travels with the call.  settings.IsAntiFireflyEnabled reaches the
+    // filter (row N19, spec S25) here.
     PtStats Render(std::vector<Float4>& radiance, SHARC& sharc, const SHARCSettings& settings, const DirectLighting* di, DenoiserBuffers* buffers)
     {
         PtGraphicsSettings constants = m_graphicsSettings;

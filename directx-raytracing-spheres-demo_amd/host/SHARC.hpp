@@ -12,7 +12,7 @@ struct SHARC {
     struct Constants {  // SHARC.ixx:23-27
         uint32_t AccumulationFrames = 10, MaxStaleFrames = 64;
         float SceneScale = 50;
-        bool IsAntiFireflyEnabled{};
+        bool IsAntiFireflyEnabled{};  // the filter of row N19 (DESIGN.md spec S25): Raytracing::Render routes such a frame to pt_render_sharc_ex
     };
 
     // SHARC::Configure: the cache is made for `capacity` slots (a power of two) and starts empty

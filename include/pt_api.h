@@ -453,7 +453,8 @@ PtStatus pt_light_ris_download(PtContext *ctx, float *pyramid, uint32_t *n_pyram
  * keys of 8 bytes and two voxels of 16 bytes each -- allocated on first use and again when Capacity changes.  The cache restarts empty on
  * the first call, with ResetHistory, after pt_set_scene and when Capacity changes.
  * PT_ERR_INVALID_ARG: a null argument; a value outside the ranges of PtSharcSettings; a rect outside RenderSize.  PT_ERR_UNSUPPORTED:
- * IsAntiFireflyEnabled; IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as pt_render. */
+ * IsAntiFireflyEnabled (the filter runs through pt_render_sharc_ex); IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as
+ * pt_render. */
 PtStatus pt_render_sharc(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtSharcSettings *settings, PtStats *stats);
 
 /* Row N18 -- pt_render_sharc with the frame's direct illumination and the denoiser outputs (the SHARC permutations of
@@ -475,6 +476,12 @@ PtStatus pt_render_sharc(PtContext *ctx, const PtRect *rect, void *out, int out_
  *            Diffuse / Specular on hits.  isDiffuse and the hit distance do not depend on the cache.  A pixel of the hash-grid
  *            visualisation writes only `out`.  outputs->Diffuse / Specular may be di->Diffuse / Specular: the update reads them before
  *            the query writes.
+ *   settings->IsAntiFireflyEnabled (row N19, DESIGN.md spec S25; the reference's application sets it, App.cpp:1278): accepted here, with or
+ *            without di and outputs, with every Stages mask.  UPDATE: a path's radiance stops going back to earlier vertices where the
+ *            luminance of the running segment weight exceeds 2.  RESOLVE: a voxel with a history of 8 samples over 2 frames has this
+ *            frame's sums scaled down where their mean luminance exceeds (5 + 5 / samples) max(history luminance, 1).  QUERY does not
+ *            read the flag.  The flag has no state: calls with and without it may alternate on one cache.  The arithmetic is this
+ *            project's (the SHARC library is not in the reference tree): no parity with the SDK is claimed.
  * Ordering: as pt_render_sharc; with di the lane also waits for everything queued on the context's stream (DI made by pt_restir_di* just
  * before is ordered by the lane's own stream); the DI and output buffers are held to the buffer rotation rule with the lane's frame buffers.
  * PT_ERR_INVALID_ARG also: a null or misaligned DI or output buffer, an output that overlaps another or `out`, a DI buffer that overlaps

@@ -273,7 +273,8 @@ typedef struct PtSharcSettings {
     float RoughnessThreshold;                 /* 12: 0 .. 1: the update pass's surfaces are at least this rough */
     uint32_t AccumulationFrames;              /* 16: 0 -> 10; 1 .. 255 */
     uint32_t MaxStaleFrames;                  /* 20: 0 -> 64; 1 .. 254 */
-    uint32_t IsAntiFireflyEnabled;            /* 24: nonzero -> PT_ERR_UNSUPPORTED (not built) */
+    uint32_t IsAntiFireflyEnabled;            /* 24: nonzero = the anti-firefly filter of spec S25 in the update and the resolve
+                                               *     (pt_render_sharc_ex; pt_render_sharc -> PT_ERR_UNSUPPORTED) */
     uint32_t IsHashGridVisualizationEnabled;  /* 28: a pixel whose path met the cache shows a colour of its primary hit's cell */
     uint32_t ResetHistory;                    /* 32: nonzero = the cache restarts empty with this call */
     uint32_t Stages;                          /* 36: PT_SHARC_UPDATE | PT_SHARC_RESOLVE | PT_SHARC_QUERY; 0 -> all three */

@@ -24,6 +24,10 @@ pt_render_sharc, and beside it pt_render_with_di's surcharge over pt_render (a g
 frame's chain pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex -> pt_ray_reconstruction (to 2x the size), the median wall
 time from the first call to the end of the wait, next to the same chain with pt_render_with_di in the cache's place.
 
+The anti-firefly filter (row N19, IsAntiFireflyEnabled through pt_render_sharc_ex without DI or outputs) per size, over the warm cache
+as above: the whole call, UPDATE | RESOLVE and the update alone with the filter on (ff_*), the resolve as their difference and against the
+same device copy, next to the filter-off figures of the same run; and the 1-spp RMSE with the filter on beside the existing pair.
+
     python tools/bench_sharc.py [--calls 100 --warmup 10 --fill 12 --sizes 1920x1080,3840x2160 --quality-size 480x270 --reference-frames 2048]"""
 import argparse
 import json
@@ -114,6 +118,15 @@ def main():
                                               ("query_alone", lambda: stage(QUERY)))}
         ms["pt_render"] = median_ms(stream, plain, args.calls, args.warmup)
         ms["resolve"] = ms["update_resolve"] - ms["update_alone"]
+
+        def stage_ff(stages):
+            next_frame(W, H)
+            r.render_sharc_ex_device(out.data_ptr() if stages & QUERY else 0, None, None, None, 0, None, stages=stages, anti_firefly=True, **st)
+
+        ms["ff_call"] = warm(lambda: stage_ff(7))
+        ms["ff_update_resolve"] = warm(lambda: stage_ff(UPDATE | RESOLVE))
+        ms["ff_update_alone"] = warm(lambda: stage_ff(UPDATE))
+        ms["ff_resolve"] = ms["ff_update_resolve"] - ms["ff_update_alone"]
         ms["query_in_call"] = ms["call"] - ms["update_resolve"]
         clear = torch.zeros(args.capacity * 4, dtype=torch.int32, device="cuda")
         ms["clear"] = median_ms(stream, lambda: clear.zero_(), args.calls, args.warmup)
@@ -183,7 +196,7 @@ def main():
         res["sizes"][f"{W}x{H}"] = dict({k + "_ms": round(v, 5) for k, v in ms.items()}, call_over_pt_render=round(ms["call"] / ms["pt_render"], 3),
                                         rays_call=int(rays_call), rays_query=int(rays_query), rays_pt_render=int(rays_plain), occupied_slots=occupied, resolve_bytes=model,
                                         resolve_TBps=round(model / (ms["resolve"] * 1e-3) / 1e12, 3), copy_TBps=round(model / (ms["copy"] * 1e-3) / 1e12, 3),
-                                        resolve_fraction_of_copy=round(ms["copy"] / ms["resolve"], 3))
+                                        resolve_fraction_of_copy=round(ms["copy"] / ms["resolve"], 3), ff_resolve_fraction_of_copy=round(ms["copy"] / ms["ff_resolve"], 3))
         del out, clear, src, dst
     # image quality: 1 spp through the cache and without it against a converged pt_render accumulation
     W, H = map(int, args.quality_size.split("x"))
@@ -206,7 +219,13 @@ def main():
     r.render_device(out.data_ptr())
     r.synchronize()
     plain_img = out.cpu().numpy()[:, :3].astype(np.float64)
+    for k in range(args.fill):
+        r.set_constants(t.graphics_settings(W, H, frame_index=k, bounces=8, spp=1))
+        r.render_sharc_ex_device(out.data_ptr(), None, None, None, 0, None, reset_history=k == 0, anti_firefly=True, **st)
+    r.synchronize()
+    filtered = out.cpu().numpy()[:, :3].astype(np.float64)
     res["quality"] = {"size": f"{W}x{H}", "reference_frames": args.reference_frames, "rmse_pt_render_sharc_1spp": round(float(np.sqrt(((cached - truth) ** 2).mean())), 5),
+                      "rmse_pt_render_sharc_ff_1spp": round(float(np.sqrt(((filtered - truth) ** 2).mean())), 5),
                       "rmse_pt_render_1spp": round(float(np.sqrt(((plain_img - truth) ** 2).mean())), 5), "mean_radiance": round(float(truth.mean()), 5)}
     r.close()
     print(json.dumps(res))

@@ -12,7 +12,7 @@ pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --heig
 reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc] | --sharc --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
                                         [--ray-reconstruction [performance]]"""
 import argparse
 import os
@@ -97,6 +97,9 @@ def main():
     ap.add_argument("--sharc", action="store_true",
                     help="--frames frames of a resting camera through the radiance cache (row N14): pt_render_sharc with the reference's "
                          "SHARC settings (update at a quarter of the size, resolve, query); the last frame, tone mapped (no accumulation)")
+    ap.add_argument("--sharc-anti-firefly", action="store_true",
+                    help="--sharc with the cache's anti-firefly filter (row N19, IsAntiFireflyEnabled, which the reference's application sets): "
+                         "the frame goes through pt_render_sharc_ex")
     ap.add_argument("--ray-reconstruction", nargs="?", const="native", default=None, metavar="MODE", choices=list(dxrs_amd.types.UPSCALE_MODES),
                     help="--frames frames of a resting camera through the reference's default denoiser path (row N15): rendered at the "
                          "mode's input size (pt_upscale_input_size; native without a mode) with Halton jitter: pt_render_gbuffer -> "
@@ -115,6 +118,8 @@ def main():
         ap.error("--sharc applies to the plain path-traced frame")
     if not default_frame and args.ray_reconstruction and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale):
         ap.error("--ray-reconstruction is a path of its own: it takes --nis and --bloom only")
+    if args.sharc_anti_firefly and not args.sharc:
+        ap.error("--sharc-anti-firefly applies to --sharc")
     if args.light_sampling != "uniform" and not args.restir_di:
         ap.error("--light-sampling applies to --restir-di")
     if (args.brdf_samples or args.boiling_filter is not None) and not args.restir_di:
@@ -220,7 +225,8 @@ def main():
             r.render_gbuffer_device(dict(ptrs, DiffuseAlbedo=b["DiffuseAlbedo"].data_ptr(), SpecularAlbedo=b["SpecularAlbedo"].data_ptr()))
             r.restir_di_device(iw, ih, dict(ptrs, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), frame_index=k, reset_history=k == 0, light_sampling=ls, candidates=cd)
             rays = r.render_sharc_ex_device(b["Color"].data_ptr(), dd.data_ptr(), ds.data_ptr(), None, t.DENOISER_DLSS_RR,
-                                            dict(SpecularHitDistance=b["SpecularHitDistance"].data_ptr()), want_stats=True, roughness_threshold=0.4, reset_history=k == 0).rays
+                                            dict(SpecularHitDistance=b["SpecularHitDistance"].data_ptr()), want_stats=True, roughness_threshold=0.4, reset_history=k == 0,
+                                            anti_firefly=args.sharc_anti_firefly).rays
             r.ray_reconstruction_device((iw, ih), (w, h), {name: v.data_ptr() for name, v in b.items()}, cam, reset=k == 0)
             r.synchronize()
             for buf in (b["SpecularHitDistance"], dd, ds):  # cleared by the caller, after the calls that read them
@@ -246,7 +252,10 @@ def main():
         for k in range(args.frames):
             gs.FrameIndex = k
             r.set_constants(gs)
-            rays = r.render_sharc_device(frame.data_ptr(), want_stats=True, roughness_threshold=0.4, reset_history=k == 0).rays
+            if args.sharc_anti_firefly:
+                rays = r.render_sharc_ex_device(frame.data_ptr(), want_stats=True, roughness_threshold=0.4, reset_history=k == 0, anti_firefly=True).rays
+            else:
+                rays = r.render_sharc_device(frame.data_ptr(), want_stats=True, roughness_threshold=0.4, reset_history=k == 0).rays
         hdr = frame
         if args.bloom is not None:
             r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
@@ -254,7 +263,7 @@ def main():
         r.tonemap(hdr.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
         r.synchronize()
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
-        print(f"SHARC (pt_render_sharc, {args.frames} frames, {rays} rays in the last) {w}x{h} -> {args.out}")
+        print(f"SHARC ({'pt_render_sharc_ex, anti-firefly filter' if args.sharc_anti_firefly else 'pt_render_sharc'}, {args.frames} frames, {rays} rays in the last) {w}x{h} -> {args.out}")
         r.close()
         return
     if args.ray_reconstruction:
