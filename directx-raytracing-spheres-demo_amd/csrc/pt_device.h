@@ -207,6 +207,8 @@ constexpr uint32_t kTileTable = 256;  // entries of the tile order table: a work
 
 constexpr uint32_t kMaxSegs = 2048;
 
+constexpr uint32_t kCutSlots = 16;  // entries of the cooperative walk's table of tree cuts (pt_trace.h build_cut)
+
 // Row N7 (DESIGN.md spec S13): the outputs of a denoiser frame (pt_render_denoiser); mode 0 = an ordinary frame, and every other field is
 // then unused.  The kernels of such frames are the kDn instances; the None kernels never read this.
 //   rec[slot]  = {primary emission (prim), hit distance of sample 0's bounce-1 ray (hd; +inf by default)}: written by the first shading of

@@ -1,6 +1,7 @@
 // pt_gbuffer.hip -- the G-buffer pass (row N6, DESIGN.md spec S12): one lane per pixel, one 8x8 pixel block per wave (the
 // PixelMap of the primary pass, so that traversal stays coherent), the closest hit of the pixel's primary ray through the
-// tree the context has (LDS copy or the wide global walk), then gbuffer_pixel (pt_gbuffer.h) and the requested stores.
+// tree the context has (LDS copy or the wide global walk: with_tree_walk, pt_launch.h), then gbuffer_pixel (pt_gbuffer.h) and the
+// requested stores.
 // No beam lists: the pass neither reads nor touches the primary-beam cache.
 #include "pt_trace.h"
 
@@ -13,21 +14,9 @@ namespace {
 template <bool kLds, typename StackT, bool kTex, bool kAlpha>
 __global__ __launch_bounds__(kTraverseThreads) void gbuffer_kernel(SceneView sv, PixelMap pm, GBufferFrame fr, GBufferScene sc, GBufferOut out, uint32_t want)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
         if (!pr.valid) continue;
@@ -59,20 +48,10 @@ template <bool kTex, bool kAlpha>
 hipError_t launch_gbuffer_t(const SceneView& sv, const PixelMap& pm, const GBufferFrame& fr, const GBufferScene& sc, const GBufferOut& out,
                             uint32_t want, uint32_t grid, hipStream_t stream)
 {
-    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
-    const uint32_t threads = traverse_threads(lds_scene);
-    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)gbuffer_kernel<true, uint16_t, kTex, kAlpha> : (const void*)gbuffer_kernel<true, uint32_t, kTex, kAlpha>)
-                               : (small ? (const void*)gbuffer_kernel<false, uint16_t, kTex, kAlpha> : (const void*)gbuffer_kernel<false, uint32_t, kTex, kAlpha>);
-    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (lds_scene) {
-        if (small) hipLaunchKernelGGL((gbuffer_kernel<true, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
-        else hipLaunchKernelGGL((gbuffer_kernel<true, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
-    } else {
-        if (small) hipLaunchKernelGGL((gbuffer_kernel<false, uint16_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
-        else hipLaunchKernelGGL((gbuffer_kernel<false, uint32_t, kTex, kAlpha>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, sc, out, want);
-    }
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(gbuffer_kernel<kLds, StackT, kTex, kAlpha>, grid, traverse_threads(kLds), traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream,
+                             sv, pm, fr, sc, out, want);
+    });
 }
 
 }  // namespace

@@ -16,7 +16,8 @@ constexpr uint32_t kShadeThreads = 256;
 constexpr uint32_t kTailThreads = 256;
 constexpr uint32_t kFusedThreads = 512;  // launch bound of the fused trace+shade kernel (launched with 512 or 256 threads)
 
-// dynamic LDS a traverse-type launch needs (scene copy if lds_scene, plus the per-lane stacks)
+// dynamic LDS a launch of a kernel that walks the tree needs: the scene copy if lds_scene, plus `depth` stack entries for each of
+// `threads` lanes (0: traverse_threads(lds_scene))
 uint32_t traverse_lds_bytes_for(uint32_t n_nodes, uint32_t n, uint32_t depth, bool lds_scene, uint32_t threads = 0);
 
 hipError_t launch_primary(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const RayQueue& q, const Scratch& scratch,

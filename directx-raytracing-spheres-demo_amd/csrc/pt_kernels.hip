@@ -8,6 +8,8 @@
 //                    BSDFSample, lobe select + sample, PDF, BSDF, Russian roulette, throughput cutoff, sample
 //                    regeneration; wave64 ballot + prefix compaction of the surviving rays into the next queue
 //   trace_kernel / brute_kernel   test hooks (pt_trace_rays)
+// Every kernel that walks the tree opens with tree_walk_setup (pt_trace.h); its launch wrapper picks the instance with with_tree_walk /
+// with_flag and launches it with launch_kernel (pt_launch.h).
 //
 // Everything is compiled with -ffp-contract=off; arithmetic that decides a branch follows pt_math.h /
 // pt_bsdf.h (bit-exact with the CPU oracle).  The AABB slab test is traversal-only arithmetic: it must be
@@ -24,21 +26,9 @@ __global__ __launch_bounds__(kTraverseThreads) void primary_kernel(SceneView sv,
     // Counter housekeeping rides on the first block (everything later in the frame is stream-ordered after this kernel):
     // fold the previous frame's ray counts into the running total, then reset the per-frame counters.
     if (blockIdx.x == 0) frame_counters_begin(fc, pm.n_slots);
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     uint32_t visits[2] = { 0u, 0u };
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
@@ -70,23 +60,11 @@ __global__ __launch_bounds__(kTraverseThreads) void primary_kernel(SceneView sv,
 template <bool kLds, typename StackT, bool kAlphaTex>
 __global__ __launch_bounds__(kTraverseThreads) void traverse_kernel(SceneView sv, RayQueue q, const uint32_t* __restrict__ count_ptr)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
     const uint32_t count = *count_ptr;
     if (blockIdx.x * blockDim.x >= count) return;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
         const float4 a = q.q0[i];
         const float4 b = q.q1[i];
@@ -253,24 +231,12 @@ __global__ __launch_bounds__(kTailThreads) void tail_kernel(SceneView sv, PixelM
                                                             float4* __restrict__ out, const uint32_t* __restrict__ count_ptr,
                                                             unsigned long long* __restrict__ tail_rays, unsigned long long* __restrict__ totals)
 {
-    extern __shared__ float4 smem[];
     const uint32_t count = *count_ptr;
     if (blockIdx.x * blockDim.x >= count) return;
     uint32_t visits[2] = { 0u, 0u };
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     uint32_t my_rays = 0;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
         PathState ps = load_path<kDn>(qin, i);
@@ -298,21 +264,9 @@ template <bool kLds, typename StackT, bool kTex, bool kSplit>
 __global__ __launch_bounds__(kTraverseThreads) void di_kernel(SceneView sv, PixelMap pm, FrameParams fp, float4* __restrict__ di, uint2* __restrict__ primary_hit,
                                                               unsigned long long* __restrict__ ray_counter, float4* __restrict__ di_s)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     uint32_t my_rays = 0;
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < pm.n_slots; slot += gridDim.x * blockDim.x) {
         const PixelRef pr = slot_to_pixel(pm, slot);
@@ -369,21 +323,9 @@ __global__ __launch_bounds__(kTraverseThreads) void trace_kernel(SceneView sv, c
                                                                  uint32_t n_rays, float tmin, float* __restrict__ out_t, uint32_t* __restrict__ out_id,
                                                                  uint2* __restrict__ out_visits)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rays; i += gridDim.x * blockDim.x) {
         float t;
         uint32_t id;
@@ -512,12 +454,6 @@ __global__ void leaf_ids_kernel(const uint32_t* __restrict__ sorted_id, const ui
 }
 
 // ------------------------------------------------------------------------------------------------ launch wrappers
-static uint32_t traverse_lds_bytes(const SceneView& sv, uint32_t stack_elem)
-{
-    const uint32_t stack = traverse_threads(sv.lds_scene != 0) * sv.stack_depth * stack_elem;
-    return (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + stack;
-}
-
 uint32_t traverse_lds_bytes_for(uint32_t n_nodes, uint32_t n, uint32_t depth, bool lds_scene, uint32_t threads)
 {
     const uint32_t elem = n_nodes < 32767u ? 2u : 4u;
@@ -525,99 +461,61 @@ uint32_t traverse_lds_bytes_for(uint32_t n_nodes, uint32_t n, uint32_t depth, bo
     return (lds_scene ? scene_lds_bytes(n_nodes, n) : 0u) + threads * depth * elem;
 }
 
-// KERNEL<kLds, StackT, ...>: EXTRA = further template arguments (with their leading comma) or nothing
-#define PT_DISPATCH_TRAVERSE(KERNEL, EXTRA, GRID, STREAM, ...)                                                 \
-    do {                                                                                                        \
-        const bool small = sv.n_nodes < 32767u;                                                                 \
-        const uint32_t lds = traverse_lds_bytes(sv, small ? 2u : 4u);                                           \
-        if (lds + kStaticLdsMargin > 65536u) {                                                                                     \
-            const void* fn = sv.lds_scene ? (small ? (const void*)KERNEL<true, uint16_t EXTRA> : (const void*)KERNEL<true, uint32_t EXTRA>)   \
-                                          : (small ? (const void*)KERNEL<false, uint16_t EXTRA> : (const void*)KERNEL<false, uint32_t EXTRA>); \
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-        }                                                                                                       \
-        if (sv.lds_scene) {                                                                                     \
-            if (small) hipLaunchKernelGGL((KERNEL<true, uint16_t EXTRA>), dim3(GRID), dim3(traverse_threads(true)), lds, STREAM, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<true, uint32_t EXTRA>), dim3(GRID), dim3(traverse_threads(true)), lds, STREAM, __VA_ARGS__);       \
-        } else {                                                                                                \
-            if (small) hipLaunchKernelGGL((KERNEL<false, uint16_t EXTRA>), dim3(GRID), dim3(traverse_threads(false)), lds, STREAM, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<false, uint32_t EXTRA>), dim3(GRID), dim3(traverse_threads(false)), lds, STREAM, __VA_ARGS__);       \
-        }                                                                                                       \
-    } while (0)
-#define PT_COMMA_TRUE , true
-#define PT_COMMA_FALSE , false
-
 hipError_t launch_primary(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const RayQueue& q, const Scratch& scratch,
                           float4* out, const FrameCounters& fc, uint32_t grid, hipStream_t stream)
 {
     // (the kAlphaTex form only when some sphere's hits are alpha-tested against a map)
-    if (sv.alpha_tested) PT_DISPATCH_TRAVERSE(primary_kernel, PT_COMMA_TRUE, grid, stream, sv, pm, fp, q, scratch, out, fc);
-    else PT_DISPATCH_TRAVERSE(primary_kernel, PT_COMMA_FALSE, grid, stream, sv, pm, fp, q, scratch, out, fc);
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return with_flag(sv.alpha_tested != 0u, [&]<bool kAlphaTex>() {
+            return launch_kernel(primary_kernel<kLds, StackT, kAlphaTex>, grid, traverse_threads(kLds), traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, pm, fp, q, scratch, out, fc);
+        });
+    });
 }
 
 hipError_t launch_traverse(const SceneView& sv, const RayQueue& q, const uint32_t* count_ptr, uint32_t grid, hipStream_t stream)
 {
-    if (sv.alpha_tested) PT_DISPATCH_TRAVERSE(traverse_kernel, PT_COMMA_TRUE, grid, stream, sv, q, count_ptr);
-    else PT_DISPATCH_TRAVERSE(traverse_kernel, PT_COMMA_FALSE, grid, stream, sv, q, count_ptr);
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return with_flag(sv.alpha_tested != 0u, [&]<bool kAlphaTex>() {
+            return launch_kernel(traverse_kernel<kLds, StackT, kAlphaTex>, grid, traverse_threads(kLds), traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, q, count_ptr);
+        });
+    });
 }
 
 hipError_t launch_traverse_dyn(const SceneView& sv, const RayQueue& q, const uint32_t* count_ptr, uint32_t* cursor, unsigned long long* totals, uint32_t grid,
                                hipStream_t stream)
 {
-    const bool small = sv.n_nodes < 32767u;
-    const uint32_t lds = 256u * sv.stack_depth * (small ? 2u : 4u);
-#define PT_DYN(T, W, A)                                                                                                          \
-    do {                                                                                                                          \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)traverse_dyn_kernel<T, W, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((traverse_dyn_kernel<T, W, A>), dim3(grid), dim3(256), lds, stream, sv, q, count_ptr, cursor, totals);  \
-    } while (0)
-#define PT_DYN2(T, W) do { if (sv.alpha_tested) PT_DYN(T, W, true); else PT_DYN(T, W, false); } while (0)
-    if (sv.wide) { if (small) PT_DYN2(uint16_t, true); else PT_DYN2(uint32_t, true); }
-    else { if (small) PT_DYN2(uint16_t, false); else PT_DYN2(uint32_t, false); }
-#undef PT_DYN2
-#undef PT_DYN
-    return hipGetLastError();
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, false, 256u);  // (no kLds form: the stacks only)
+    return with_tree_walk(sv, [&]<bool, typename StackT>() {
+        return with_flag(sv.wide != nullptr, [&]<bool kWide>() {
+            return with_flag(sv.alpha_tested != 0u, [&]<bool kAlphaTex>() {
+                return launch_kernel(traverse_dyn_kernel<StackT, kWide, kAlphaTex>, grid, 256u, lds, stream, sv, q, count_ptr, cursor, totals);
+            });
+        });
+    });
 }
 
 hipError_t launch_beams(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, float slack, uint32_t* lists, uint32_t* regions, hipStream_t stream)
 {
     const uint32_t n_blocks = pm.n_slots >> 6;
     if (n_blocks == 0) return hipSuccess;
-    const bool small = sv.n_nodes < 32767u;
-    const uint32_t stack_bytes = 256u * (sv.stack_depth + 1u) * (small ? 2u : 4u);
-    const uint32_t lds = (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + stack_bytes;
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth + 1u, sv.lds_scene != 0, 256u);
     const uint32_t grid = (n_blocks + 255u) / 256u;
-#define PT_BEAM(L, T)                                                                                                                            \
-    do {                                                                                                                                          \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)beam_kernel<L, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((beam_kernel<L, T>), dim3(grid), dim3(256), lds, stream, sv, pm, fp, slack, lists, regions);                                           \
-    } while (0)
-    if (sv.lds_scene) { if (small) PT_BEAM(true, uint16_t); else PT_BEAM(true, uint32_t); }
-    else { if (small) PT_BEAM(false, uint16_t); else PT_BEAM(false, uint32_t); }
-#undef PT_BEAM
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(beam_kernel<kLds, StackT>, grid, 256u, lds, stream, sv, pm, fp, slack, lists, regions);
+    });
 }
 
 hipError_t launch_tail(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const RayQueue& qin, const Scratch& scratch, float4* out,
                        const uint32_t* count_ptr, unsigned long long* tail_rays, unsigned long long* totals, uint32_t grid, hipStream_t stream)
 {
-    const bool small = sv.n_nodes < 32767u;
-    const uint32_t elem = small ? 2u : 4u;
-    const uint32_t lds = (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + kTailThreads * sv.stack_depth * elem;
-#define PT_TAIL3(L, T, X, N)                                                                                               \
-    do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)tail_kernel<L, T, X, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((tail_kernel<L, T, X, N>), dim3(grid), dim3(kTailThreads), lds, stream, sv, pm, fp, qin, scratch, out, count_ptr, tail_rays, totals); \
-    } while (0)
-#define PT_TAIL2(L, T, X) do { if (scratch.dn.mode) PT_TAIL3(L, T, X, true); else PT_TAIL3(L, T, X, false); } while (0)
-#define PT_TAIL(L, T) do { if (sv.tex_maps) PT_TAIL2(L, T, true); else PT_TAIL2(L, T, false); } while (0)
-    if (sv.lds_scene) { if (small) PT_TAIL(true, uint16_t); else PT_TAIL(true, uint32_t); }
-    else { if (small) PT_TAIL(false, uint16_t); else PT_TAIL(false, uint32_t); }
-#undef PT_TAIL
-#undef PT_TAIL2
-#undef PT_TAIL3
-    return hipGetLastError();
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, sv.lds_scene != 0, kTailThreads);
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return with_flag(sv.tex_maps != nullptr, [&]<bool kTex>() {
+            return with_flag(scratch.dn.mode != 0u, [&]<bool kDn>() {
+                return launch_kernel(tail_kernel<kLds, StackT, kTex, kDn>, grid, kTailThreads, lds, stream, sv, pm, fp, qin, scratch, out, count_ptr, tail_rays, totals);
+            });
+        });
+    });
 }
 
 hipError_t launch_bounce(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const RayQueue& qin, const RayQueue& qout,
@@ -649,12 +547,13 @@ hipError_t launch_trace(const SceneView& sv, const float* o, const float* d, uin
     const uint32_t tt = traverse_threads(sv.lds_scene != 0);
     const uint32_t grid = (n_rays + tt - 1) / tt < 2048u ? (n_rays + tt - 1) / tt : 2048u;
     if (grid == 0) return hipSuccess;
-    if (use_bvh) {
-        PT_DISPATCH_TRAVERSE(trace_kernel, , grid, stream, sv, o, d, n_rays, tmin, out_t, out_id, out_visits);
-    } else {
+    if (!use_bvh) {
         hipLaunchKernelGGL(brute_kernel, dim3(grid), dim3(kTraverseThreads), 0, stream, sv, o, d, n_rays, tmin, out_t, out_id);
+        return hipGetLastError();
     }
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(trace_kernel<kLds, StackT>, grid, tt, traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, o, d, n_rays, tmin, out_t, out_id, out_visits);
+    });
 }
 
 hipError_t launch_flush_counters(uint32_t* counts, uint32_t n_counts, unsigned long long* tail, unsigned long long* totals, uint32_t* host_counts,
@@ -678,22 +577,13 @@ hipError_t launch_unpack_tiles(const float4* packed, float4* frame, uint32_t w, 
 hipError_t launch_di(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, float4* di, uint2* primary_hit, unsigned long long* ray_counter, uint32_t grid,
                      hipStream_t stream, float4* di_s)
 {
-    const bool small = sv.n_nodes < 32767u;
-    const uint32_t threads = traverse_threads(sv.lds_scene != 0);
-    const uint32_t lds = traverse_lds_bytes(sv, small ? 2u : 4u);
-#define PT_DI3(L, T, X, S)                                                                                                  \
-    do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)di_kernel<L, T, X, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((di_kernel<L, T, X, S>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, di, primary_hit, ray_counter, di_s); \
-    } while (0)
-#define PT_DI2(L, T, X) do { if (di_s) PT_DI3(L, T, X, true); else PT_DI3(L, T, X, false); } while (0)
-#define PT_DI(L, T) do { if (sv.tex_maps) PT_DI2(L, T, true); else PT_DI2(L, T, false); } while (0)
-    if (sv.lds_scene) { if (small) PT_DI(true, uint16_t); else PT_DI(true, uint32_t); }
-    else { if (small) PT_DI(false, uint16_t); else PT_DI(false, uint32_t); }
-#undef PT_DI
-#undef PT_DI2
-#undef PT_DI3
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return with_flag(sv.tex_maps != nullptr, [&]<bool kTex>() {
+            return with_flag(di_s != nullptr, [&]<bool kSplit>() {
+                return launch_kernel(di_kernel<kLds, StackT, kTex, kSplit>, grid, traverse_threads(kLds), traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, pm, fp, di, primary_hit, ray_counter, di_s);
+            });
+        });
+    });
 }
 
 hipError_t launch_di_gather(const PixelMap& pm, const float4* dd, const float4* ds, float4* di, float4* di_s, hipStream_t stream)

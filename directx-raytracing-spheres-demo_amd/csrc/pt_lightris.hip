@@ -9,6 +9,7 @@
 // Every kernel calls the header's function for its element.  Cross-lane operations: __shfl_down and LDS with __syncthreads only.
 #include <hip/hip_runtime.h>
 
+#include "pt_launch.h"
 #include "pt_lightris.h"
 
 namespace pt {
@@ -114,9 +115,7 @@ hipError_t launch_lr_regir(const LrBuild& b, hipStream_t stream)
 {
     const uint32_t n = b.grid.grid * b.grid.grid * b.grid.grid * b.grid.lights_per_cell;
     const uint32_t lds = b.grid.tile_size * (uint32_t)sizeof(LrEntry);  // at most 64 KB
-    if (lds > 48u * 1024u) (void)hipFuncSetAttribute((const void*)lr_regir_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(lr_regir_kernel, dim3((n + kLrThreads - 1u) / kLrThreads), dim3(kLrThreads), lds, stream, b, n);
-    return hipGetLastError();
+    return launch_kernel(lr_regir_kernel, (n + kLrThreads - 1u) / kLrThreads, kLrThreads, lds, stream, b, n);
 }
 
 }  // namespace pt

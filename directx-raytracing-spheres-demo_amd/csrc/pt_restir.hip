@@ -3,7 +3,8 @@
 //   launch 1  ri_pass1_px: the pixel's surface record from the G-buffer, initial sampling, temporal resampling -- reads only the
 //             previous call's slot, writes this call's record and reservoir
 //   launch 2  ri_pass2_px: spatial resampling over every pixel's launch-1 result (hence the launch boundary), final shading
-// Visibility rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory).
+// Visibility rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory),
+// chosen by with_tree_walk (pt_launch.h).
 #include "pt_trace.h"
 #include "pt_restir.h"
 
@@ -16,21 +17,9 @@ namespace {
 template <bool kPass2, bool kLds, typename StackT, bool kTex, bool kAlpha, uint32_t kMode>
 __global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, PixelMap pm, RiBuffers b, RiParams p, LrView lr)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     RiScene sc;
     sc.sph = sv.sph; sc.mats = sv.mats; sc.lights = sv.lights; sc.n_lights = sv.n_lights;
     sc.lr = lr;
@@ -51,21 +40,9 @@ __global__ __launch_bounds__(kTraverseThreads) void restir_kernel(SceneView sv, 
 template <bool kLds, typename StackT, bool kAlpha, uint32_t kMode, bool kBrdf, bool kFilter>
 __global__ __launch_bounds__(kTraverseThreads) void restir_ex_kernel(SceneView sv, PixelMap pm, RiBuffers b, RiParamsEx p, LrView lr, RiExtra x)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     RiScene sc;
     sc.sph = sv.sph; sc.mats = sv.mats; sc.lights = sv.lights; sc.n_lights = sv.n_lights;
     sc.lr = lr;
@@ -98,20 +75,10 @@ __global__ __launch_bounds__(kTraverseThreads) void restir_ex_kernel(SceneView s
 template <bool kAlpha, uint32_t kMode, bool kBrdf, bool kFilter>
 hipError_t launch_ex_t(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParamsEx& p, const LrView& lr, const RiExtra& x, uint32_t grid, hipStream_t stream)
 {
-    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
-    const uint32_t threads = traverse_threads(lds_scene);
-    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)restir_ex_kernel<true, uint16_t, kAlpha, kMode, kBrdf, kFilter> : (const void*)restir_ex_kernel<true, uint32_t, kAlpha, kMode, kBrdf, kFilter>)
-                               : (small ? (const void*)restir_ex_kernel<false, uint16_t, kAlpha, kMode, kBrdf, kFilter> : (const void*)restir_ex_kernel<false, uint32_t, kAlpha, kMode, kBrdf, kFilter>);
-    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (lds_scene) {
-        if (small) hipLaunchKernelGGL((restir_ex_kernel<true, uint16_t, kAlpha, kMode, kBrdf, kFilter>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr, x);
-        else hipLaunchKernelGGL((restir_ex_kernel<true, uint32_t, kAlpha, kMode, kBrdf, kFilter>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr, x);
-    } else {
-        if (small) hipLaunchKernelGGL((restir_ex_kernel<false, uint16_t, kAlpha, kMode, kBrdf, kFilter>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr, x);
-        else hipLaunchKernelGGL((restir_ex_kernel<false, uint32_t, kAlpha, kMode, kBrdf, kFilter>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr, x);
-    }
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(restir_ex_kernel<kLds, StackT, kAlpha, kMode, kBrdf, kFilter>, grid, traverse_threads(kLds),
+                             traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, pm, b, p, lr, x);
+    });
 }
 
 template <bool kAlpha, uint32_t kMode>
@@ -134,20 +101,10 @@ hipError_t launch_ex_alpha(const SceneView& sv, const PixelMap& pm, const RiBuff
 template <bool kPass2, bool kTex, bool kAlpha, uint32_t kMode = kLrUniform>
 hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParams& p, const LrView& lr, uint32_t grid, hipStream_t stream)
 {
-    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
-    const uint32_t threads = traverse_threads(lds_scene);
-    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)restir_kernel<kPass2, true, uint16_t, kTex, kAlpha, kMode> : (const void*)restir_kernel<kPass2, true, uint32_t, kTex, kAlpha, kMode>)
-                               : (small ? (const void*)restir_kernel<kPass2, false, uint16_t, kTex, kAlpha, kMode> : (const void*)restir_kernel<kPass2, false, uint32_t, kTex, kAlpha, kMode>);
-    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (lds_scene) {
-        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, true, uint16_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
-        else hipLaunchKernelGGL((restir_kernel<kPass2, true, uint32_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
-    } else {
-        if (small) hipLaunchKernelGGL((restir_kernel<kPass2, false, uint16_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
-        else hipLaunchKernelGGL((restir_kernel<kPass2, false, uint32_t, kTex, kAlpha, kMode>), dim3(grid), dim3(threads), lds, stream, sv, pm, b, p, lr);
-    }
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(restir_kernel<kPass2, kLds, StackT, kTex, kAlpha, kMode>, grid, traverse_threads(kLds),
+                             traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, pm, b, p, lr);
+    });
 }
 
 template <bool kAlpha>

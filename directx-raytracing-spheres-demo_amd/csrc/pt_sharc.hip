@@ -4,8 +4,8 @@
 //   query    one lane per pixel, one 8x8 pixel block per wave64: sh_query_pixel
 // kEx: the instances of pt_render_sharc_ex with a DI or denoiser outputs (sh_update_path_ex, sh_query_pixel_ex, which stores the pixel itself)
 // kFf: the anti-firefly filter of row N19 (spec S25): the kEx update (sh_update_path_ff) and the resolve (sh_resolve_slot_ff); the query does not read the flag
-// Rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory), chosen as
-// pt_restir.hip chooses it.
+// Rays go through the closest-hit walker the context's tree has (LDS copy, or the wide / binary walk in global memory), chosen by
+// with_tree_walk (pt_launch.h).
 #include "pt_trace.h"
 #include "pt_sharc.h"
 
@@ -17,21 +17,9 @@ template <bool kQuery, bool kLds, typename StackT, bool kTex, bool kAlpha, bool 
 __global__ __launch_bounds__(kTraverseThreads) void sharc_kernel(SceneView sv, PixelMap pm, ShFrame fr, ShGrid g, ShMap m, float4* __restrict__ out,
                                                                  unsigned long long* __restrict__ counters)
 {
-    extern __shared__ float4 smem[];
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     const uint32_t stride = blockDim.x;
     auto trace = [&](f3 o, f3 d, float tmin, float tmax, float& t, uint32_t& id) {
         closest_hit_any<kLds, StackT, kAlpha>(sv, nodes, sph, ids, o, d, tmin, tmax, stack, stride, t, id);
@@ -67,20 +55,10 @@ template <bool kQuery, bool kEx, bool kFf, bool kTex, bool kAlpha>
 hipError_t launch_t(const SceneView& sv, const PixelMap& pm, const ShFrame& fr, const ShGrid& g, const ShMap& m, float4* out, unsigned long long* counters,
                     uint32_t grid, hipStream_t stream)
 {
-    const bool lds_scene = sv.lds_scene != 0, small = sv.n_nodes < 32767u;
-    const uint32_t threads = traverse_threads(lds_scene);
-    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, lds_scene, threads);
-    const void* fn = lds_scene ? (small ? (const void*)sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx, kFf> : (const void*)sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx, kFf>)
-                               : (small ? (const void*)sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx, kFf> : (const void*)sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx, kFf>);
-    if (lds > 48u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (lds_scene) {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint16_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, true, uint32_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-    } else {
-        if (small) hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint16_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-        else hipLaunchKernelGGL((sharc_kernel<kQuery, false, uint32_t, kTex, kAlpha, kEx, kFf>), dim3(grid), dim3(threads), lds, stream, sv, pm, fr, g, m, out, counters);
-    }
-    return hipGetLastError();
+    return with_tree_walk(sv, [&]<bool kLds, typename StackT>() {
+        return launch_kernel(sharc_kernel<kQuery, kLds, StackT, kTex, kAlpha, kEx, kFf>, grid, traverse_threads(kLds),
+                             traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, kLds), stream, sv, pm, fr, g, m, out, counters);
+    });
 }
 
 template <bool kQuery, bool kEx, bool kFf>

@@ -1,7 +1,8 @@
-// pt_trace.h -- device code shared by the kernel translation units: BVH traversal (closest_hit, wide_visit, primary-beam
-// helpers), the shading step of the bounce loop (shade_step: Raytracing.hlsl:213-364) and the fused trace + shade kernel
-// bounce_kernel with its launcher template.  pt_kernels.hip holds the other kernels; pt_bounce_*.hip instantiate bounce_kernel
-// for one (BVH residence, stack entry type) pair each, so that the ~100 instances compile in parallel.
+// pt_trace.h -- device code shared by the kernel translation units: the opening of every kernel that walks the tree (stage_scene,
+// tree_walk_setup), BVH traversal (closest_hit, wide_visit, primary-beam helpers), the shading step of the bounce loop (shade_step:
+// Raytracing.hlsl:213-364) and the fused trace + shade kernel bounce_kernel with its launcher template (over pt_launch.h).
+// pt_kernels.hip holds the other kernels; pt_bounce_*.hip instantiate bounce_kernel for one (BVH residence, stack entry type) pair
+// each, so that the ~100 instances compile in parallel.
 //
 // Everything is compiled with -ffp-contract=off; arithmetic that decides a branch follows pt_math.h /
 // pt_bsdf.h (bit-exact with the CPU oracle).  The AABB slab test is traversal-only arithmetic: it must be
@@ -9,6 +10,7 @@
 #pragma once
 
 #include "pt_kernels.h"
+#include "pt_launch.h"
 #include "pt_beam.h"
 
 namespace pt {
@@ -98,6 +100,45 @@ __device__ __forceinline__ void stage_scene(const SceneView& sv, float4* lds, bo
 }
 
 __host__ __device__ inline uint32_t scene_lds_bytes(uint32_t n_nodes, uint32_t n) { return (n_nodes * 4u + n) * 16u + ((n * 4u + 15u) & ~15u); }
+
+// What a lane walks the tree with: the tree as the walkers read it and the lane's stack (entry k at stack[k * blockDim.x]).
+template <typename StackT>
+struct TreeWalk {
+    const float4* nodes;
+    const float4* sph;
+    const uint32_t* ids;
+    StackT* stack;
+};
+
+// Fills `w`.  (By reference on purpose: with the struct returned by value the kernels' register allocation moves -- scratch bytes
+// of a bounce_kernel instance, SGPR spills of several side-pass instances; profiles/n20_isa_*.)  kLds: the copy stage_scene has made or is making at the start of the dynamic LDS (nothing is read here), the stacks
+// behind it; else the tree in global memory, the stacks at the start of the dynamic LDS.
+template <bool kLds, typename StackT>
+__device__ __forceinline__ void tree_walk_pointers(const SceneView& sv, TreeWalk<StackT>& w)
+{
+    extern __shared__ float4 smem[];
+    if (kLds) {
+        w.nodes = smem;
+        w.sph = smem + sv.n_nodes * 4u;
+        w.ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
+        w.stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
+    } else {
+        w.nodes = sv.nodes;
+        w.sph = sv.sph_sorted;
+        w.ids = sv.sorted_id;
+        w.stack = reinterpret_cast<StackT*>(smem);
+    }
+    w.stack += threadIdx.x;
+}
+
+// The opening of a kernel that walks the tree, called by every thread of the workgroup (kLds: staging ends with a barrier).
+template <bool kLds, typename StackT>
+__device__ __forceinline__ void tree_walk_setup(const SceneView& sv, TreeWalk<StackT>& w)
+{
+    extern __shared__ float4 smem[];
+    if (kLds) stage_scene(sv, smem);
+    tree_walk_pointers<kLds, StackT>(sv, w);
+}
 
 // Stack entries hold a child reference: internal node index i >= 0, or leaf (Morton-sorted sphere index k) as ~k.
 // The 16-bit stack (trees with < 32768 leaves) stores a leaf as 0x8000 | k.
@@ -332,8 +373,7 @@ __device__ __forceinline__ void closest_hit_any(const SceneView& sv, const float
 // tests, so the result is closest_hit's bit for bit.
 
 // The cuts of the binary tree at depths 1, 2 and 3: s_cut[k - 2 + j] = start of helper j of k (a child reference, or kTraversalDone where
-// a leaf above the cut has left the slot empty).  One thread builds it, after stage_scene (n >= 2: the root is an internal node).
-constexpr uint32_t kCutSlots = 16;
+// a leaf above the cut has left the slot empty; kCutSlots entries).  One thread builds it, after stage_scene (n >= 2: the root is an internal node).
 __device__ __forceinline__ void build_cut(const float4* __restrict__ nodes, int* s_cut)
 {
     auto expand = [&](int ref, int& a, int& b) {
@@ -637,21 +677,11 @@ __device__ __forceinline__ bool refl_contains(const uint32_t* rec, f3 o, f3 d)
 template <bool kLds, typename StackT>
 __global__ __launch_bounds__(256) void beam_kernel(SceneView sv, PixelMap pm, FrameParams fp, float slack, uint32_t* __restrict__ lists, uint32_t* __restrict__ regions)
 {
-    extern __shared__ float4 smem[];
     const uint32_t stride = blockDim.x;
     const uint32_t n_blocks = pm.n_slots >> 6;
-    const float4* nodes = sv.nodes;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
-    if (kLds) {
-        stage_scene(sv, smem);
-        nodes = smem;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
-    }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_setup<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;  // (the beams read no sphere record: sph is unused)
     for (uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x; tile < n_blocks; tile += gridDim.x * blockDim.x)
     {
         beam_walk_block<StackT>(sv, nodes, ids, stack, stride, pm, fp.cam, slack, 0.0f, tile, lists);
@@ -1049,10 +1079,6 @@ __device__ __forceinline__ void store_path(const RayQueue& q, uint32_t j, const 
     q.q2[j] = make_float4(ps.T.x, ps.T.y, ps.T.z, as_float(flags));
 }
 
-// static LDS of the kernels below (counters, the segment prefix table of the looping pass) on top of their dynamic LDS: the
-// 64 KB default limit counts both, so the opt-in for more is taken this much earlier
-constexpr uint32_t kStaticLdsMargin = (kMaxSegs + 64u + kCutSlots) * 4u;
-
 // Cold kernel arguments.  A by-value kernel argument is loaded into SGPRs at the kernel's entry and stays there: with ~120 dwords of
 // arguments and 100 SGPRs, the camera and the pixel map -- needed once per batch, to generate the primary rays -- lived in VGPR lanes
 // and came back through ~70 v_readlane per batch (VALU issue slots, in a VALU-bound kernel).  cold_arg re-reads such an argument from the
@@ -1215,26 +1241,18 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         if (tile_builder) build_tile_order();
         if (seg_out || kIters > 1u) __syncthreads();  // (with kLds the barrier after stage_scene orders the reset and the table)
     }
-    const float4* nodes = sv.nodes;
-    const float4* sph = sv.sph_sorted;
-    const uint32_t* ids = sv.sorted_id;
-    StackT* stack;
     if (kLds) {
         stage_scene(sv, smem, false);
         if (tile_builder) build_tile_order();
         __syncthreads();
-        nodes = smem;
-        sph = smem + sv.n_nodes * 4u;
-        ids = reinterpret_cast<const uint32_t*>(smem + sv.n_nodes * 4u + sv.n);
-        stack = reinterpret_cast<StackT*>(reinterpret_cast<char*>(smem) + scene_lds_bytes(sv.n_nodes, sv.n));
         if (kCoop && fc.coop_walk != 0u && sv.n > 1u) {
             if (threadIdx.x == 0) build_cut(smem, s_cut);
             __syncthreads();
         }
-    } else {
-        stack = reinterpret_cast<StackT*>(smem);
     }
-    stack += threadIdx.x;
+    TreeWalk<StackT> tw;
+    tree_walk_pointers<kLds, StackT>(sv, tw);
+    const auto [nodes, sph, ids, stack] = tw;
     const uint32_t lane = lane_id();
     const uint32_t wave = threadIdx.x >> 6;
     const bool coop = kCoop && fc.coop_walk != 0u && sv.n > 1u && (blockDim.x & 63u) == 0u;  // (whole waves only: every lane takes part in the exchanges)
@@ -1516,12 +1534,10 @@ hipError_t launch_bounce_for(const SceneView& sv, const PixelMap& pm, const Fram
                              const Scratch& scratch, float4* out, const uint32_t* count_in, uint32_t* count_out, const FrameCounters& fc,
                              bool primary, bool loop, bool inline2, uint32_t threads, uint32_t grid, hipStream_t stream)
 {
-    const uint32_t lds = (sv.lds_scene ? scene_lds_bytes(sv.n_nodes, sv.n) : 0u) + threads * sv.stack_depth * (uint32_t)sizeof(StackT);
-#define PT_BOUNCE9(P, LP, M, X, I, F, D, N)                                                                                \
-    do {                                                                                                                    \
-        if (lds + kStaticLdsMargin > 65536u) (void)hipFuncSetAttribute((const void*)bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D, N>), dim3(grid), dim3(threads), lds, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out, fc); \
-    } while (0)
+    const uint32_t lds = traverse_lds_bytes_for(sv.n_nodes, sv.n, sv.stack_depth, sv.lds_scene != 0, threads);
+    hipError_t err = hipSuccess;
+#define PT_BOUNCE9(P, LP, M, X, I, F, D, N) \
+    err = launch_kernel(bounce_kernel<kLds, StackT, P, LP, M, X, I, F, D, N>, grid, threads, lds, stream, sv, pm, fp, qin, qout, scratch, out, count_in, count_out, fc)
 /* row N7: a denoiser frame (scratch.dn.mode != 0) runs the kDn instance of the same schedule */
 #define PT_BOUNCE8(P, LP, M, X, I, F, D)                                                                                   \
     do { if (scratch.dn.mode) PT_BOUNCE9(P, LP, M, X, I, F, D, true); else PT_BOUNCE9(P, LP, M, X, I, F, D, false); } while (0)
@@ -1547,7 +1563,7 @@ hipError_t launch_bounce_for(const SceneView& sv, const PixelMap& pm, const Fram
 #undef PT_BOUNCE7
 #undef PT_BOUNCE8
 #undef PT_BOUNCE9
-    return hipGetLastError();
+    return err;
 }
 
 // the three instantiations (pt_bounce_lds16.hip, pt_bounce_g16.hip, pt_bounce_g32.hip).  An LDS-resident tree has fewer than

@@ -569,17 +569,18 @@ def test_gpu_zero_di_equals_pt_render_sharc(dxrs, host, renderer):
     assert same_bits(res[0][0], res[1][0]) and res[0][1] == res[1][1] and res[0][2] == res[1][2]
 
 
-def ex_frames_against_host(dxrs, r, hc, spheres, mats, sd, cams, modes=(0, 1, 2, 3), textures=None, bounces=8, zero_fraction=0.2, **kw):
+def ex_frames_against_host(dxrs, r, hc, spheres, mats, sd, cams, modes=(0, 1, 2, 3), textures=None, bounces=8, zero_fraction=0.2, size=(GW, GH), **kw):
     """consecutive pt_render_sharc_ex calls with a random DI (positive, a fifth of the texels 0) against the host header, per mode: the
     cache as a map after each call, the image, the outputs and the ray count"""
+    width, height = size
     for mode in modes:
         for f, cam in enumerate(cams):
-            gs = dxrs.types.graphics_settings(GW, GH, frame_index=f, bounces=bounces, spp=2 if f == 1 else 1)
+            gs = dxrs.types.graphics_settings(width, height, frame_index=f, bounces=bounces, spp=2 if f == 1 else 1)
             if f == 0:
                 setup(r, dxrs, spheres, mats, sd, cam, gs, textures)
             r.set_camera(cam)
             r.set_constants(gs)
-            di = random_di(GW, GH, 100 + 10 * mode + f, zero_fraction)
+            di = random_di(width, height, 100 + 10 * mode + f, zero_fraction)
             st = defaults(reset_history=f == 0, **kw)
             got, gb, rays = gpu_call(r, di=di, mode=mode, **st)
             want, wb, wrays, failed = hc.call_ex(cam, gs, di=di, mode=mode, **st)
