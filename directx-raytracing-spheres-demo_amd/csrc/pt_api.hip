@@ -748,6 +748,12 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
         // frame costs that frame 1 %)
         if ((st = beam_cache_lookup(c, pm, std::min(primary_grid, knob_or(c->knobs.beam_share_wgs, 128u)) * 64u, &beam_lists, &refl_lists, &beam_wait, &beam_job)) != PT_OK) return st;
         if (beam_wait) PT_HIP(c, hipStreamWaitEvent(L.stream, beam_wait, 0));
+        // The record rule.  The primary pass reads its beam and region records on the scalar path (pt_trace.h scalar_load), which sees no
+        // store made while the kernel runs: NO KERNEL WRITES A RECORD BUFFER WHILE A FRAME THAT READS IT IS IN FLIGHT.  beam_build's
+        // launch is ordered behind the buffer's readers and in front of its next ones by events; a share (beam_job) is written by this
+        // frame's own primary pass, into the buffer that no frame reads before every share's frame has finished -- never the one handed out here.
+        if (beam_job.n_blocks != 0u && (beam_job.lists == nullptr || beam_job.lists == beam_lists))
+            return fail(c, PT_ERR_STATE, "primary beams: a frame would build a share of the lists it reads");
     } else {
         c->beam.last_key.clear();
         c->beam.inc.active = false;  // (a share build in progress was planned for a view this frame does not continue)

@@ -657,14 +657,28 @@ __device__ __forceinline__ void refl_walk_block(const SceneView& sv, const float
     rec[0] = count;
 }
 
-// The run-time test of a lane's bounce-1 ray against its block's region record (scalar loads: the record is the wave's)
-__device__ __forceinline__ bool refl_contains(const uint32_t* rec, f3 o, f3 d)
+// Wave-uniform records on the scalar path.  A block's beam record, its region record and the sphere records they name belong to the whole
+// wave, and no kernel writes them while a frame that reads them is in flight (pt_api.hip render_common states the rule and checks it where
+// beam_cache_lookup hands the buffers out; sv.sph is written by earlier kernels of the frame's own stream only).  The kernel itself stores
+// to global memory, so the compiler takes a plain load of them for a vector load (global_load -> s_waitcnt vmcnt(0), which on gfx9 also
+// drains the wave's stores -> v_readfirstlane); read through the constant address space they are s_load_dword[xN]: SGPRs from the scalar
+// cache, waited for with lgkmcnt.  p must be wave-uniform and aligned to V.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+template <typename V>
+__device__ __forceinline__ V scalar_load(const void* p)
+{
+    return *(const __attribute__((address_space(4))) V*)p;
+}
+
+// The run-time test of a lane's bounce-1 ray against its block's region record: h0, h1 = the record's first sixteen words (scalar_load)
+__device__ __forceinline__ bool refl_contains(u32x8 h0, u32x8 h1, f3 o, f3 d)
 {
     ReflRegion g;
-    g.lo = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[1])), as_float(__builtin_amdgcn_readfirstlane(rec[2])), as_float(__builtin_amdgcn_readfirstlane(rec[3])));
-    g.hi = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[4])), as_float(__builtin_amdgcn_readfirstlane(rec[5])), as_float(__builtin_amdgcn_readfirstlane(rec[6])));
-    g.axis = make_f3(as_float(__builtin_amdgcn_readfirstlane(rec[7])), as_float(__builtin_amdgcn_readfirstlane(rec[8])), as_float(__builtin_amdgcn_readfirstlane(rec[9])));
-    g.cos_run = as_float(__builtin_amdgcn_readfirstlane(rec[10]));
+    g.lo = make_f3(as_float(h0[1]), as_float(h0[2]), as_float(h0[3]));
+    g.hi = make_f3(as_float(h0[4]), as_float(h0[5]), as_float(h0[6]));
+    g.axis = make_f3(as_float(h0[7]), as_float(h1[0]), as_float(h1[1]));
+    g.cos_run = as_float(h1[2]);
     g.theta = 0.0f;
     return region_contains(g, o, d);
 }
@@ -689,24 +703,52 @@ __global__ __launch_bounds__(256) void beam_kernel(SceneView sv, PixelMap pm, Fr
     }
 }
 
-// Closest hit of a primary ray over its block's candidate list (wave-uniform loop; sphere records come through the scalar
-// cache).  Same intersect_sphere, same tie rule as closest_hit's leaves.
+// A candidate list as its reader holds it: where the ids stand in the record, how many there are (walked when 1 .. cap), the first three of them
+// (they come with the record's first words: one scalar round trip) and the first one's sphere record (a second, begun as soon as the
+// first is back and long before the list is walked).  All wave-uniform.
+struct ListHead {
+    const uint32_t* ids;
+    uint32_t count, cap;
+    uint32_t id0, id1, id2;
+    u32x4 s0;
+};
+
+// the first candidate's sphere (the ids carry their alpha class); a list with no entry names none
+__device__ __forceinline__ u32x4 list_first_sphere(const SceneView& sv, uint32_t count, uint32_t cap, uint32_t id0)
+{
+    u32x4 s0 = { 0u, 0u, 0u, 0u };
+    if (count - 1u < cap) s0 = scalar_load<u32x4>(sv.sph + (id0 & kIdMask));
+    return s0;
+}
+
+// Closest hit of a ray over its block's candidate list (wave-uniform loop).  Same candidates, same order, same intersect_sphere, same
+// tie rule as closest_hit's leaves.  Nothing the loop reads comes through the vector memory path: while candidate j is intersected, the
+// sphere of candidate j + 1 and the id of candidate j + 3 are under way as scalar loads (the ids two entries ahead of the spheres, since
+// a sphere's address needs its id), so an iteration waits for neither.  The loads ahead stay inside the record (the id index is clamped
+// to the record's last word) and inside sv.sph (past the list's end the current candidate's sphere is fetched again).
 template <bool kAlphaTex = false>
-__device__ __forceinline__ void closest_hit_list(const SceneView& sv, const uint32_t* __restrict__ rec, uint32_t count, f3 o, f3 d, float tmin, float tmax,
-                                                 float& t_out, uint32_t& id_out)
+__device__ __forceinline__ void closest_hit_list(const SceneView& sv, const ListHead& L, f3 o, f3 d, float tmin, float tmax, float& t_out, uint32_t& id_out)
 {
     float best = tmax;
     uint32_t best_id = kMissId;
-    for (uint32_t j = 0; j < count; j++) {
-        const uint32_t idf = __builtin_amdgcn_readfirstlane(rec[1 + j]);  // (the list carries the leaf ids with their alpha class)
-        const uint32_t id = idf & kIdMask;
-        if ((idf >> kIdClassShift) == kAlphaInvisible) continue;  // wave-uniform
-        const float4 s = sv.sph[id];
-        float t;
-        if (intersect_sphere(o, d, tmin, kInf, make_f3(s.x, s.y, s.z), s.w, t)) {
-            if ((idf >> kIdClassShift) == 0u || alpha_candidate<kAlphaTex>(sv, idf, make_f3(s.x, s.y, s.z), s.w, o, d, t))
-                if (t < best || (t == best && best_id != kMissId && id < best_id)) { best = t; best_id = id; }
+    uint32_t idf = L.id0, idf1 = L.id1, idf2 = L.id2;  // (the list carries the leaf ids with their alpha class)
+    u32x4 sb = L.s0;
+    // (scalar loads return in any order, so a wait for one is a wait for all: L.s0 is waited for here, where nothing else is under way -- left
+    // to the loop's first use it would be a wait behind the loads ahead in every iteration.  gfx9 encoding: lgkmcnt(0), vmcnt and expcnt open.)
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    for (uint32_t j = 0; j < L.count; j++) {
+        const u32x4 sb1 = scalar_load<u32x4>(sv.sph + ((j + 1u < L.count ? idf1 : idf) & kIdMask));
+        const uint32_t idf3 = scalar_load<uint32_t>(L.ids + (j + 3u < L.cap ? j + 3u : L.cap - 1u));
+        if ((idf >> kIdClassShift) != kAlphaInvisible) {  // wave-uniform
+            const uint32_t id = idf & kIdMask;
+            const float4 s = make_float4(as_float(sb.x), as_float(sb.y), as_float(sb.z), as_float(sb.w));
+            float t;
+            if (intersect_sphere(o, d, tmin, kInf, make_f3(s.x, s.y, s.z), s.w, t)) {
+                if ((idf >> kIdClassShift) == 0u || alpha_candidate<kAlphaTex>(sv, idf, make_f3(s.x, s.y, s.z), s.w, o, d, t))
+                    if (t < best || (t == best && best_id != kMissId && id < best_id)) { best = t; best_id = id; }
+            }
         }
+        idf = idf1; idf1 = idf2; idf2 = idf3; sb = sb1;
     }
     t_out = best; id_out = best_id;
 }
@@ -1089,10 +1131,17 @@ struct BounceArgs { SceneView sv; PixelMap pm; FrameParams fp; RayQueue qin, qou
 template <typename T>
 __device__ __forceinline__ T cold_arg(uint32_t offset)
 {
+    // (read word by word through a dword pointer: the laundering hides the segment's alignment with its origin, and a load the compiler
+    // takes for byte-aligned cannot be a scalar one -- it became global_load -> s_waitcnt vmcnt -> v_readfirstlane, once per tile)
+    static_assert(sizeof(T) % 4u == 0u && alignof(T) >= 4u, "cold_arg: whole dwords");
     const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
+    const __attribute__((address_space(4))) uint32_t* q = (const __attribute__((address_space(4))) uint32_t*)(p + offset);
+    uint32_t w[sizeof(T) / 4u];
+#pragma unroll
+    for (uint32_t k = 0; k < sizeof(T) / 4u; k++) w[k] = q[k];
     T v;
-    __builtin_memcpy(&v, p + offset, sizeof(T));
+    __builtin_memcpy(&v, w, sizeof(T));
     return v;
 }
 
@@ -1339,12 +1388,16 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             continue;  // (a looping pass hands nothing on)
         }
         // primary beams: this wave's 64 slots are one 8x8-pixel block; its candidate list was made by beam_kernel
-        const uint32_t* beam_rec = nullptr;
-        uint32_t beam_count = ~0u;
+        // (its count and first three ids in one scalar load, the first candidate's sphere in the next: both are back before the rays are made)
+        ListHead beam{ nullptr, ~0u, kBeamListCap, 0u, 0u, 0u, { 0u, 0u, 0u, 0u } };
         if (kPrimary && fp.beam_lists) {
-            beam_rec = fp.beam_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kBeamRecord;
-            beam_count = __builtin_amdgcn_readfirstlane(beam_rec[0]);
+            const uint32_t* beam_rec = fp.beam_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kBeamRecord;
+            const u32x4 head = scalar_load<u32x4>(beam_rec);
+            beam.ids = beam_rec + 1;
+            beam.count = head[0]; beam.id0 = head[1]; beam.id1 = head[2]; beam.id2 = head[3];
+            beam.s0 = list_first_sphere(sv, beam.count, kBeamListCap, beam.id0);
         }
+        const uint32_t beam_count = beam.count;
         // Sky tiles: an empty list says that every ray of the block misses, and a primary miss of these instances ends the pixel with one
         // store (shade_step_ex, shade_miss).  The short path stores the environment's colour in the primary direction, as primary_ray makes
         // it, and is done: no tmin / tmax, no RNG stream, no list walk, no shade_step, no second slot -> pixel mapping.
@@ -1404,21 +1457,25 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                     float t;
                     uint32_t id;
                     if (kPrimary && primary_trace && fp.beam_lists && beam_count <= kBeamListCap) {
-                        closest_hit_list<kTex>(sv, beam_rec, beam_count, ps.o, ps.d, tmin, tmax, t, id);
+                        closest_hit_list<kTex>(sv, beam, ps.o, ps.d, tmin, tmax, t, id);
                         if (kMulti) scratch.primary_hit[i] = make_uint2(as_uint(t), id);
                     } else {
                         // reflection beams: the in-register first bounce of a block with a region record, when every active lane's ray lies in the region
                         // (the counts of pt_get_refl_stats are kept only while the records are in use: a frame without them runs nothing but the pointer test)
                         bool listed = false;
-                        const uint32_t* rrec = nullptr;
-                        uint32_t rcount = 0;
+                        ListHead refl{ nullptr, 0u, kReflListCap, 0u, 0u, 0u, { 0u, 0u, 0u, 0u } };
                         if (kIters > 1u && !primary_trace && fp.refl_lists) {
-                            rrec = fp.refl_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kReflRecord;
-                            rcount = __builtin_amdgcn_readfirstlane(rrec[0]);
-                            listed = rcount != 0u && __ballot(!refl_contains(rrec, ps.o, ps.d)) == 0ull;
+                            // the record's first sixteen words in one scalar round trip: the count, the region's ten words and the first five ids
+                            static_assert(kReflIds == 11u && kReflRecord == 32u, "the region record's layout");
+                            const uint32_t* rrec = fp.refl_lists + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kReflRecord;
+                            const u32x8 h0 = scalar_load<u32x8>(rrec), h1 = scalar_load<u32x8>(rrec + 8);
+                            refl.ids = rrec + kReflIds;
+                            refl.count = h0[0]; refl.id0 = h1[3]; refl.id1 = h1[4]; refl.id2 = h1[5];
+                            refl.s0 = list_first_sphere(sv, refl.count, kReflListCap, refl.id0);
+                            listed = refl.count != 0u && __ballot(!refl_contains(h0, h1, ps.o, ps.d)) == 0ull;
                             if (lane == (uint32_t)__builtin_amdgcn_readfirstlane(lane)) { atomicAdd(&s_refl[0], 1u); if (listed) atomicAdd(&s_refl[1], 1u); }
                         }
-                        if (listed) closest_hit_list<kTex>(sv, rrec + (kReflIds - 1u), rcount, ps.o, ps.d, tmin, tmax, t, id);
+                        if (listed) closest_hit_list<kTex>(sv, refl, ps.o, ps.d, tmin, tmax, t, id);
                         else closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, ps.o, ps.d, tmin, tmax, stack, blockDim.x, t, id);
                         if (kMulti && kPrimary && primary_trace) scratch.primary_hit[i] = make_uint2(as_uint(t), id);
                     }
