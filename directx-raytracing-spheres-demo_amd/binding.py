@@ -773,7 +773,9 @@ class Renderer:
         self._check(self._lib.pt_unpack_tiles_rgb(self._ctx, C.c_void_p(packed_ptr), part_stride_px, n_parts, first0, run, stride, C.c_void_p(frame_ptr)))
 
     def trace_rays(self, origins, directions, tmin=0.0, use_bvh=True):
-        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        """pt_trace_rays -> (t, ids): closest hits against the scene the next render call renders (after update_spheres: the moved spheres and
+        the refitted tree of that frame's lane); use_bvh=False runs the brute-force kernel.  Does not count as a frame."""
+        o =np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
         t = np.empty(n, dtype=np.float32)
@@ -782,7 +784,7 @@ class Renderer:
         return t, ids
 
     def trace_rays_stats(self, origins, directions, tmin=0.0):
-        """-> (t, ids, visits) with visits[:, 0] = internal nodes visited, visits[:, 1] = spheres tested per ray"""
+        """-> (t, ids, visits) with visits[:, 0] = internal nodes visited, visits[:, 1] = spheres tested per ray; the scene is trace_rays'"""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -793,6 +795,8 @@ class Renderer:
         return t, ids, visits
 
     def download_accel(self):
+        """-> (nodes, order): the binary tree the next render call walks (after update_spheres: the refitted tree of that frame's lane) and its
+        leaf order"""
         n = self.accel.node_count
         nodes = np.zeros(n, dtype=BVH_NODE_DTYPE)
         self._check(self._lib.pt_accel_download(self._ctx, nodes.ctypes.data, n))

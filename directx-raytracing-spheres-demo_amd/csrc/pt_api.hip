@@ -620,6 +620,7 @@ static PtStatus sync_lane_spheres(PtContext* c, Lane& L)
     const Lane& src = c->lanes[c->latest_lane];
     if (PtStatus st = stage_spheres_on_lane(c, L, reinterpret_cast<const PtSphere*>(src.h_stage)); st != PT_OK) return st;
     L.sph_gen = c->sph_gen;
+    L.slab_tiny = src.slab_tiny;
     return refit_lane(c, L);
 }
 
@@ -1040,7 +1041,7 @@ SceneView make_scene_view(const PtContext* c, const Lane* L)
     // heavy tail): 3.99 -> 2.54 ms per frame there with any bound from 2 to 24; LDS-resident scenes (coherent, shallow) gain nothing.
     sv.descent_cap = c->lds_scene ? 0u : knob_or(c->knobs.descent, 8u);
     sv.lds_scene = c->lds_scene ? 1u : 0u;
-    sv.slab_tiny = c->slab_tiny;  // (of the tree pt_build_accel made: a lane's refitted private tree keeps it, pt_update_spheres does not look at coordinates)
+    sv.slab_tiny = priv ? L->slab_tiny : c->slab_tiny;  // (pt_build_accel's for the master tree; a lane's private scene may have moved anywhere: pt_update_spheres chose its own)
     for (int i = 0; i < 4; i++) sv.env[i] = c->sd.EnvironmentLightColor[i];
     if (c->has_textures) { sv.tex = c->d_tex; sv.tex_maps = c->d_tex_maps; sv.rot = (c->rot_gen != c->rot_master_gen && L && L->d_rot && L->rot_gen == c->rot_gen) ? L->d_rot : c->d_rot; }
     sv.env_tex = c->sd.EnvironmentLightTextureDescriptor;  // ~0u == kNoTexture; render_common has checked it against the table
@@ -1391,11 +1392,16 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
             c->alpha_mats.push_back(am);
         }
     if (PtStatus st = update_alpha_classes(c); st != PT_OK) return st;
-    for (auto& L : c->lanes) { L.scene_private = false; L.upload_pending = false; L.needs_refit = false; L.sph_gen = 0; }  // every lane renders the new master scene
+    for (auto& L : c->lanes) { L.scene_private = false; L.upload_pending = false; L.needs_refit = false; L.sph_gen = 0; }  // every lane renders the new master scene (with the master slab_tiny: make_scene_view)
     c->sph_gen = 0;
     c->latest_lane = -1;
     return PT_OK;
 }
+
+// A zero ray-direction component is walked as +-1e-30 (slab_rcp, pt_trace.h), which needs |coordinate| * 1e30 and a node's extent * 1e30 to
+// stay finite.  Beyond that the component's axis takes no part in the slab tests: NaN ray parameters, which their min / max drop.
+// smax: max |c -+ r| of the spheres the tree holds -- the built ones (pt_build_accel) or the moved ones of a lane (pt_update_spheres).
+static float slab_tiny_for(float smax) { return smax < 1e8f ? 1e-30f : std::numeric_limits<float>::quiet_NaN(); }
 
 PtStatus pt_build_accel(PtContext* c, PtAccelInfo* info)
 {
@@ -1456,12 +1462,10 @@ PtStatus pt_build_accel(PtContext* c, PtAccelInfo* info)
         c->lbvh.pad = gi.pad;
         for (int a = 0; a < 3; a++) { c->lbvh.bounds_min[a] = gi.bounds_min[a]; c->lbvh.bounds_max[a] = gi.bounds_max[a]; }
     }
-    // A zero ray-direction component is walked as +-1e-30 (slab_rcp, pt_trace.h), which needs |coordinate| * 1e30 and a node's extent * 1e30 to
-    // stay finite.  Beyond that the component's axis takes no part in the slab tests: NaN ray parameters, which their min / max drop.
     {
         float smax = 0.0f;
         for (int a = 0; a < 3; a++) smax = std::max(smax, std::max(std::fabs(c->lbvh.bounds_min[a]), std::fabs(c->lbvh.bounds_max[a])));
-        c->slab_tiny = smax < 1e8f ? 1e-30f : std::numeric_limits<float>::quiet_NaN();
+        c->slab_tiny = slab_tiny_for(smax);
     }
     // stage the BVH in LDS when scene + stacks leave room for two workgroups per CU
     const uint32_t scene_bytes = traverse_lds_bytes_for(c->n_nodes, n, 0, true);
@@ -1502,14 +1506,18 @@ PtStatus pt_update_spheres(PtContext* c, const PtSphere* spheres, uint32_t n)
     if (!c->scene_set || !c->accel_valid) return fail(c, PT_ERR_STATE, "pt_update_spheres: pt_set_scene + pt_build_accel first");
     if (n != c->n) return fail(c, PT_ERR_INVALID_ARG, "pt_update_spheres: the sphere count must not change (use pt_set_scene)");
     if (!c->gpu_builder) return fail(c, PT_ERR_UNSUPPORTED, "pt_update_spheres needs the device LBVH builder (no PT_FLAG_HOST_LBVH)");
-    for (uint32_t i = 0; i < n; i++)
+    float smax = 0.0f;  // max |c -+ r|: the moved scene's bounds, whatever those of the build were
+    for (uint32_t i = 0; i < n; i++) {
         if (!(spheres[i].r > 0.0f) || !std::isfinite(spheres[i].r) || !std::isfinite(spheres[i].cx) || !std::isfinite(spheres[i].cy) || !std::isfinite(spheres[i].cz))
             return fail(c, PT_ERR_INVALID_ARG, "pt_update_spheres: sphere " + std::to_string(i) + " has a non-finite centre or non-positive radius");
+        for (const float x : { spheres[i].cx, spheres[i].cy, spheres[i].cz }) smax = std::max(smax, std::max(std::fabs(x - spheres[i].r), std::fabs(x + spheres[i].r)));
+    }
     PT_HIP(c, hipSetDevice(c->device));
     Lane& L = c->lanes[c->next_lane];  // the lane the next render call will use
     c->scene_gen++;
     if (PtStatus st = stage_spheres_on_lane(c, L, spheres); st != PT_OK) return st;
-    // the other lanes take these spheres over from this lane's staging buffer when they render next (sync_lane_spheres)
+    // the other lanes take these spheres, and their slab_tiny, over from this lane when they render next (sync_lane_spheres)
+    L.slab_tiny = slab_tiny_for(smax);
     L.sph_gen = ++c->sph_gen;
     c->latest_lane = (int)c->next_lane;
     return PT_OK;
@@ -1804,6 +1812,20 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
     return PT_OK;
 }
 
+// The test hooks answer for the scene the NEXT render call renders: its lane, brought up to date as that call would do it (spheres staged by
+// pt_update_spheres uploaded and refitted; the render call then finds nothing left to do).  A lane with a private scene is read on its own stream,
+// behind everything the caller has queued; the lane rotation, the frame count, the markers of order_lane_after_caller and the totals stay untouched.
+// Returns the stream to queue on and to wait for: the lane's if *lane is set to it, else the caller's (the master scene, *lane = nullptr).
+static PtStatus hook_lane(PtContext* c, const Lane** lane, hipStream_t* stream)
+{
+    Lane& L = c->lanes[c->next_lane];
+    if (const PtStatus st = lane_catch_up(c, L); st != PT_OK) return st;
+    *lane = L.scene_private ? &L : nullptr;
+    *stream = L.scene_private ? L.stream : c->stream;
+    if (L.scene_private && L.stream != c->stream) PT_HIP(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 static PtStatus trace_rays_impl(PtContext* c, const float* origins, const float* directions, uint32_t n, float tmin, int use_bvh, float* out_t,
                                 uint32_t* out_id, uint32_t* out_visits)
 {
@@ -1824,14 +1846,17 @@ static PtStatus trace_rays_impl(PtContext* c, const float* origins, const float*
         cleanup();
         return fail(c, PT_ERR_OOM, std::string("pt_trace_rays: ") + hipGetErrorString(e));
     }
-    const SceneView sv = make_scene_view(c);
-    if ((e = hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)) != hipSuccess
-        || (e = hipMemcpyAsync(d_d, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)) != hipSuccess
-        || (e = launch_trace(sv, d_o, d_d, n, tmin, use_bvh, d_t, d_id, d_v, c->stream)) != hipSuccess
-        || (e = hipMemcpyAsync(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess
-        || (e = hipMemcpyAsync(out_id, d_id, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess
-        || (d_v && (e = hipMemcpyAsync(out_visits, d_v, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        || (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+    const Lane* lane = nullptr;
+    hipStream_t stream = nullptr;
+    if ((st = hook_lane(c, &lane, &stream)) != PT_OK) { cleanup(); return st; }
+    const SceneView sv = make_scene_view(c, lane);
+    if ((e = hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, stream)) != hipSuccess
+        || (e = hipMemcpyAsync(d_d, directions, (size_t)n * 12, hipMemcpyHostToDevice, stream)) != hipSuccess
+        || (e = launch_trace(sv, d_o, d_d, n, tmin, use_bvh, d_t, d_id, d_v, stream)) != hipSuccess
+        || (e = hipMemcpyAsync(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess
+        || (e = hipMemcpyAsync(out_id, d_id, (size_t)n * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess
+        || (d_v && (e = hipMemcpyAsync(out_visits, d_v, (size_t)n * 8, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+        || (e = hipStreamSynchronize(stream)) != hipSuccess) {
         st = fail(c, PT_ERR_HIP, std::string("pt_trace_rays: ") + hipGetErrorString(e));
     }
     cleanup();
@@ -1857,8 +1882,11 @@ PtStatus pt_accel_download(PtContext* c, PtBvhNode* nodes, uint32_t capacity)
     if (!nodes || capacity < c->n_nodes) return fail(c, PT_ERR_INVALID_ARG, "pt_accel_download: buffer too small");
     if (c->n_nodes == 0) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipMemcpyAsync(nodes, c->d_nodes, (size_t)c->n_nodes * sizeof(PtBvhNode), hipMemcpyDeviceToHost, c->stream));
-    PT_HIP(c, hipStreamSynchronize(c->stream));
+    const Lane* lane = nullptr;
+    hipStream_t stream = nullptr;
+    if (const PtStatus st = hook_lane(c, &lane, &stream); st != PT_OK) return st;
+    PT_HIP(c, hipMemcpyAsync(nodes, lane ? lane->d_nodes : c->d_nodes, (size_t)c->n_nodes * sizeof(PtBvhNode), hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipStreamSynchronize(stream));
     return PT_OK;
 }
 

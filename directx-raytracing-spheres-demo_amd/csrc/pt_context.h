@@ -71,6 +71,7 @@ struct Lane {
     uint32_t scene_n = 0;             // sphere count the private copy was allocated for
     bool scene_private = false;
     uint64_t sph_gen = 0;         // the pt_update_spheres generation this lane's private scene holds (PtContext::sph_gen)
+    float slab_tiny = 1e-30f;     // SceneView::slab_tiny of the private scene: chosen by pt_update_spheres from the staged coordinates, travels with sph_gen
     bool needs_refit = false;     // spheres were staged on this lane and its boxes / Morton-ordered copy have not been redone yet
     bool upload_pending = false;  // h_stage holds spheres that have not been copied to d_sph yet (pt_update_spheres of a small scene: pt_refit_accel's kernel reads them)
     LaneLedger ledger;  // the caller buffers of the lane's latest frame, G-buffer call and reservoir pass (pt_lane_order.h: repeated buffers inside the window)
@@ -262,7 +263,7 @@ struct PtContext {
         bool have_vel = false;
     } beam;
     uint64_t scene_gen = 0;  // bumped by everything that changes what a ray can hit
-    float slab_tiny = 1e-30f;  // SceneView::slab_tiny of the tree pt_build_accel made
+    float slab_tiny = 1e-30f;  // SceneView::slab_tiny of the tree pt_build_accel made (a lane's private scene has its own: Lane::slab_tiny)
     float min_radius = 0.0f;  // smallest sphere of the scene set by pt_set_scene (bounds the slack of a moving camera's beam lists)
 
     // multi-GPU exchange (pt_comm_init / pt_gather): the RCCL communicator of this rank

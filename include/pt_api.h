@@ -613,8 +613,11 @@ PtStatus pt_ray_reconstruction(PtContext *ctx, const PtRayReconstructionSettings
 PtStatus pt_ray_reconstruction_history(PtContext *ctx, void *history, void *normal, void *depth);
 
 /* Test / tooling hooks. */
-/* Closest hit of n rays against the scene and accel of the last pt_set_scene / pt_build_accel (spheres moved by pt_update_spheres live in
- * the lanes' private copies and are not seen here): o,d = n*3 floats (d unit length), tmin per call.
+/* Closest hit of n rays against the scene and accel that the NEXT render call renders: o,d = n*3 floats (d unit length), tmin per call.
+ * Spheres moved by pt_update_spheres are seen: the lane of the next frame is brought up to date first, as the render call would do it
+ * (pending spheres uploaded, boxes refitted -- the render call then does neither again), and its private spheres and refitted tree are
+ * what is traced, on the lane's stream, after everything queued on the caller's.  Without an update since pt_set_scene: the master scene.
+ * The lane rotation, the frame count and pt_get_totals are not touched.
  * Outputs host arrays t[n], id[n] (id = 0xFFFFFFFF on miss).  use_bvh = 0 runs the device brute-force kernel. */
 PtStatus pt_trace_rays(PtContext *ctx, const float *origins, const float *directions, uint32_t n, float tmin,
                        int use_bvh, float *out_t, uint32_t *out_id);
@@ -623,13 +626,16 @@ PtStatus pt_trace_rays(PtContext *ctx, const float *origins, const float *direct
 PtStatus pt_trace_rays_stats(PtContext *ctx, const float *origins, const float *directions, uint32_t n, float tmin,
                              float *out_t, uint32_t *out_id, uint32_t *out_visits);
 /* Copy the device BVH to host: nodes[node_count]; leaf child c < 0 refers to Morton-sorted index ~c, whose
- * original sphere id is sorted_id[~c] (pt_accel_download_order: sorted_id[leaf_count]). */
+ * original sphere id is sorted_id[~c] (pt_accel_download_order: sorted_id[leaf_count]).  As pt_trace_rays, the tree is the one the
+ * next render call walks: after pt_update_spheres the refitted private tree of that frame's lane (same links, new boxes).  The leaf
+ * order belongs to the topology, which a refit keeps. */
 PtStatus pt_accel_download(PtContext *ctx, PtBvhNode *nodes, uint32_t capacity);
 PtStatus pt_accel_download_order(PtContext *ctx, uint32_t *sorted_id, uint32_t capacity);
 /* Copy the 4-wide, quantised view of the tree that scenes traversed in global memory are walked through:
  * words[node_count * 16], record i at words[16 * i] (the layout is the comment above collapse4_kernel, csrc/pt_lbvh_gpu.hip).  Only
  * the slots of binary nodes at even depth hold a record; the others are zero.  *has_wide = 0, and nothing is copied, when the
- * context has no wide view: an LDS-resident scene, node_count <= 1, or PT_WIDE=0.  Synchronises the context's stream.
+ * context has no wide view: an LDS-resident scene, node_count <= 1, or PT_WIDE=0.  Synchronises the context's stream.  Always the view
+ * of the tree pt_build_accel made: a lane's refitted private tree has none (it is walked through its binary records).
  * PT_ERR_STATE: no accel; PT_ERR_INVALID_ARG: has_wide null, or a wide view and words null or capacity_nodes < node_count. */
 PtStatus pt_accel_download_wide(PtContext *ctx, uint32_t *words, uint32_t capacity_nodes, uint32_t *has_wide);
 /* Host LBVH builder (the PT_FLAG_HOST_LBVH path), callable without a context or a GPU, for structural tests:

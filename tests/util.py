@@ -47,11 +47,15 @@ def assert_hits_match_oracle(lib, spheres, o, d, t_gpu, id_gpu, tmin=0.0):
     """every ray's closest hit (id, and t bit for bit) is the one the CPU oracle's oracle_intersect_sphere finds, sphere by sphere in id
     order; lib = the `oracle` fixture's .lib"""
     fp = C.POINTER(C.c_float)
+    spheres = np.ascontiguousarray(spheres)
+    base, tmin_c = spheres.ctypes.data, C.c_float(tmin)  # (pointers made once per ray, not per sphere: layouts with thousands of candidates per ray)
     for i in range(len(t_gpu)):
         best, best_id = np.float32(np.inf), 0xFFFFFFFF
         tt = C.c_float()
         oi, di = np.ascontiguousarray(o[i]), np.ascontiguousarray(d[i])
-        for sid in np.nonzero(candidates(spheres, oi, di))[0]:
-            if lib.oracle_intersect_sphere(oi.ctypes.data_as(fp), di.ctypes.data_as(fp), C.c_float(tmin), C.c_float(best), spheres[sid:sid + 1].ctypes.data, C.byref(tt)):
+        op, dp, best_c = oi.ctypes.data_as(fp), di.ctypes.data_as(fp), C.c_float(best)
+        for sid in np.nonzero(candidates(spheres, oi, di))[0].tolist():
+            if lib.oracle_intersect_sphere(op, dp, tmin_c, best_c, base + 16 * sid, C.byref(tt)):
                 best, best_id = np.float32(tt.value), sid
+                best_c = C.c_float(best)
         assert best_id == id_gpu[i] and (best_id == 0xFFFFFFFF or best == t_gpu[i]), (i, best_id, id_gpu[i], best, t_gpu[i])
