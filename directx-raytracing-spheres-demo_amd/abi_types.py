@@ -144,6 +144,16 @@ def restir_di_candidates(brdf_samples=0, boiling_filter=None):
     return PtRestirDiCandidates(BrdfSamples=brdf_samples, EnableBoilingFilter=int(on), BoilingFilterStrength=float(boiling_filter) if on else 0.0)
 
 
+# Row N22 (pt_restir_di_full): final shading's reuse of a sample's visibility; the limits are literal; all zero = off
+class PtRestirDiShading(C.Structure):
+    _fields_ = [("ReuseFinalVisibility", C.c_uint32), ("FinalVisibilityMaxAge", C.c_uint32), ("FinalVisibilityMaxDistance", C.c_float), ("_pad", C.c_uint32)]
+
+
+def restir_di_shading(reuse=False, max_age=0, max_distance=0.0):
+    """the RTXDI SDK's defaults, as recollected: reuse on, max_age 4, max_distance 16"""
+    return PtRestirDiShading(ReuseFinalVisibility=int(reuse), FinalVisibilityMaxAge=max_age, FinalVisibilityMaxDistance=float(max_distance))
+
+
 # Row N14 (pt_render_sharc, the SHARC stand-in): SHARCSettings plus the cache's accumulation constants and the stages of a call
 SHARC_UPDATE, SHARC_RESOLVE, SHARC_QUERY = 1, 2, 4
 SHARC_VOXEL_DTYPE = np.dtype([("sum", "<u4", (3,)), ("w", "<u4")])  # w = samples | frames << 16 | stale << 24

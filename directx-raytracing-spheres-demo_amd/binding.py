@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
                         ray_reconstruction_settings)
 
@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
 ]
@@ -106,6 +106,9 @@ class HipLib:
         lib.pt_restir_di_sampled.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtLightSamplingSettings), C.POINTER(PtRestirDiTextures)]
         lib.pt_restir_di_ex.restype = C.c_int
         lib.pt_restir_di_ex.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtLightSamplingSettings), C.POINTER(PtRestirDiCandidates), C.POINTER(PtRestirDiTextures)]
+        lib.pt_restir_di_full.restype = C.c_int
+        lib.pt_restir_di_full.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtLightSamplingSettings), C.POINTER(PtRestirDiCandidates), C.POINTER(PtRestirDiShading),
+                                          C.POINTER(PtRestirDiTextures)]
         lib.pt_restir_di_history.restype = C.c_int
         lib.pt_restir_di_history.argtypes = [vp, u32, vp, vp]
         lib.pt_light_ris_download.restype = C.c_int
@@ -549,7 +552,7 @@ class Renderer:
 
     def restir_di_device(self, width, height, buffers, frame_index=0, reset_history=False, initial_samples=0, temporal=True, temporal_bias=1,
                          max_history=0, spatial=True, spatial_bias=1, spatial_samples=0, spatial_radius=0.0, light_sampling=None,
-                         candidates=None):
+                         candidates=None, shading=None):
         """The reservoir pass that makes the DI render_with_di_device takes (row N10, DESIGN.md spec S16) over width x height pixels, for
         the frame the next render call renders: buffers = {RESTIR_DI_TEXTURES name: device pointer}, the G-buffer channels of
         render_gbuffer_device and the Diffuse / Specular outputs (float4; the caller clears them: pixels without DI are not written).
@@ -559,7 +562,9 @@ class Renderer:
         arguments (mode = abi_types.LIGHT_SAMPLING_*, tile_size, tile_count, grid_size, lights_per_cell, build_samples, cell_size) =
         pt_restir_di_sampled (row N16, DESIGN.md spec S22).
         candidates: None = neither; a PtRestirDiCandidates or a dict of restir_di_candidates' arguments (brdf_samples, boiling_filter =
-        the filter's strength) = pt_restir_di_ex (row N17, DESIGN.md spec S23)."""
+        the filter's strength) = pt_restir_di_ex (row N17, DESIGN.md spec S23).
+        shading: not None = pt_restir_di_full (row N22, DESIGN.md spec S26), which also accepts RESTIR_BIAS_PAIRWISE: a PtRestirDiShading or
+        a dict of restir_di_shading's arguments (reuse, max_age, max_distance; {} = reuse off)."""
         unknown = set(buffers) - set(RESTIR_DI_TEXTURES)
         if unknown:
             raise ValueError(f"unknown ReSTIR DI buffers {sorted(unknown)}")
@@ -571,8 +576,14 @@ class Renderer:
         ls = None
         if light_sampling is not None:
             ls = light_sampling if isinstance(light_sampling, PtLightSamplingSettings) else light_sampling_settings(**light_sampling)
+        cd = None
         if candidates is not None:
             cd = candidates if isinstance(candidates, PtRestirDiCandidates) else restir_di_candidates(**candidates)
+        if shading is not None:
+            sh = shading if isinstance(shading, PtRestirDiShading) else restir_di_shading(**shading)
+            self._check(self._lib.pt_restir_di_full(self._ctx, C.byref(s), C.byref(ls) if ls is not None else None, C.byref(cd) if cd is not None else None, C.byref(sh),
+                                                    C.byref(t)))
+        elif cd is not None:
             self._check(self._lib.pt_restir_di_ex(self._ctx, C.byref(s), C.byref(ls) if ls is not None else None, C.byref(cd), C.byref(t)))
         elif ls is None:
             self._check(self._lib.pt_restir_di(self._ctx, C.byref(s), C.byref(t)))
@@ -612,6 +623,11 @@ class Renderer:
         self.restir_di_device(w, h, dict({name: b.data_ptr() for name, b in gb.items()}, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), **settings)
         self.synchronize()
         return dd, ds, gb
+
+    def restir_di_full(self, shading=None, **kw):
+        """restir_di through pt_restir_di_full (row N22): shading as restir_di_device takes it (None = reuse off); temporal_bias /
+        spatial_bias may be RESTIR_BIAS_PAIRWISE"""
+        return self.restir_di(shading={} if shading is None else shading, **kw)
 
     def render_sharc_device(self, out_ptr, rect=None, want_stats=False, **settings):
         """The frame through the radiance cache (row N14, DESIGN.md spec S20; pt_render_sharc) into device memory: settings = the fields of

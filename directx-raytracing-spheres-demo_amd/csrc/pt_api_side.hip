@@ -99,10 +99,12 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
 // the history (per pixel and slot: a surface record of four float4 and a float, a reservoir of two float4) lives in the context.
 constexpr uint64_t kRiSlotBytesPerPixel = 6 * sizeof(float4) + sizeof(float);
 
-// The body of pt_restir_di, pt_restir_di_sampled (row N16, spec S22) and pt_restir_di_ex (row N17, spec S23); ls null or Mode 0 = Uniform:
-// nothing is presampled; cd null, or no BRDF candidates and the filter off: launch 1 is the one of rows N10 / N16.
+// The body of pt_restir_di, pt_restir_di_sampled (row N16, spec S22), pt_restir_di_ex (row N17, spec S23) and pt_restir_di_full (row N22,
+// spec S26); ls null or Mode 0 = Uniform: nothing is presampled; cd null, or no BRDF candidates and the filter off: launch 1 is the one of
+// rows N10 / N16.  full: the entry point accepts pairwise bias correction (2) and reads sh; sh null or ReuseFinalVisibility 0 and no mode
+// equal to 2: the launches are pt_restir_di_ex's.
 static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd,
-                                 const PtRestirDiTextures* t)
+                                 const PtRestirDiShading* sh, bool full, const PtRestirDiTextures* t)
 {
     if (!c) return PT_ERR_INVALID_ARG;
     if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": null pointer");
@@ -112,8 +114,15 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     if (s->SpatialSamples > kRiMaxSpatialSamples) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialSamples must be at most 32");
     if (s->EnableTemporal > 1 || s->EnableSpatial > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": EnableTemporal and EnableSpatial must be 0 or 1");
     for (const uint32_t mode : { s->TemporalBiasCorrection, s->SpatialBiasCorrection }) {
-        if (mode == kRiBiasPairwise) return fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": pairwise bias correction (2) is not built");
-        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": a bias correction mode must be 0 (Off), 1 (Basic) or 3 (Raytraced)");
+        if (mode == kRiBiasPairwise && !full) return fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": pairwise bias correction (2) runs through pt_restir_di_full");
+        if (mode > kRiBiasRaytraced) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": a bias correction mode must be 0 (Off), 1 (Basic), 2 (Pairwise: pt_restir_di_full) or 3 (Raytraced)");
+    }
+    if (sh) {
+        if (sh->ReuseFinalVisibility > 1) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": ReuseFinalVisibility must be 0 or 1");
+        if (sh->FinalVisibilityMaxAge > 255u) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": FinalVisibilityMaxAge must be at most 255");
+        if (!std::isfinite(sh->FinalVisibilityMaxDistance) || !(sh->FinalVisibilityMaxDistance >= 0.0f))
+            return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": FinalVisibilityMaxDistance must be finite and >= 0");
+        if (sh->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": PtRestirDiShading._pad must be 0");
     }
     if (!std::isfinite(s->SpatialRadius) || !(s->SpatialRadius >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, std::string(who) + ": SpatialRadius must be finite and >= 0");
     if (cd) {
@@ -203,7 +212,7 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     b.prev_rec_t = tplanes + (uint64_t)prev * n;
     b.out_diffuse = static_cast<float4*>(t->Diffuse);
     b.out_specular = static_cast<float4*>(t->Specular);
-    RiParamsEx P{};
+    RiParamsFull P{};
     P.frame_index = s->FrameIndex;
     P.initial_samples = s->InitialSamples ? s->InitialSamples : kRiDefaultInitialSamples;
     P.temporal = s->EnableTemporal; P.temporal_bias = s->TemporalBiasCorrection;
@@ -219,6 +228,15 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
         P.boiling_filter = cd->EnableBoilingFilter;
         P.boiling_strength = cd->EnableBoilingFilter ? cd->BoilingFilterStrength : 0.0f;
     }
+    if (sh && sh->ReuseFinalVisibility) {
+        P.sh.reuse = 1u;
+        P.sh.max_age = sh->FinalVisibilityMaxAge;
+        P.sh.max_dist2 = sh->FinalVisibilityMaxDistance * sh->FinalVisibilityMaxDistance;
+    }
+    // row N22: launch 1 writes the visibility word where something of this call reads it or temporal resampling is pairwise; launch 2 is
+    // the new one where the spatial pass is pairwise or final shading reuses the word.  Neither: the launches of rows N10 / N16 / N17.
+    const bool full2 = P.sh.reuse || (P.spatial && P.spatial_bias == kRiBiasPairwise);
+    const bool full1 = P.sh.reuse || (P.temporal && P.temporal_bias == kRiBiasPairwise);
     const PixelMap pm = make_pixel_map(w, h, PtRect{ 0, 0, w, h });  // (at most 2048^2 * 64 = 2^28 slots)
     const SceneView sv = make_scene_view(c, &L);
     const uint32_t grid = side_pass_grid(c, pm.n_slots);
@@ -267,7 +285,10 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     for (int pass = 0; pass < 2 && st == PT_OK; pass++) {
         const RiExtra rx{ c->d_light_of, mode != kLrUniform ? c->d_lr_pyramid : nullptr, lr_levels(c->n_lights) };
         // pt_get_profile: launch 1 under ms_traverse, launch 2 under ms_shade
-        const hipError_t e = profiled_launch(c, L.stream, pass == 0 ? 1 : 2, [&] { return pass == 0 ? launch_restir_pass1_ex(sv, pm, b, P, mode, lr, rx, grid, L.stream) : launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream); });
+        const hipError_t e = profiled_launch(c, L.stream, pass == 0 ? 1 : 2, [&] {
+            if (pass == 0 ? full1 : full2) return launch_restir_full(pass, sv, pm, b, P, mode, lr, rx, grid, L.stream);
+            return pass == 0 ? launch_restir_pass1_ex(sv, pm, b, P, mode, lr, rx, grid, L.stream) : launch_restir_pass(pass, sv, pm, b, P, mode, lr, grid, L.stream);
+        });
         if (e != hipSuccess) st = fail(c, PT_ERR_HIP, std::string(who) + ": launch: " + hipGetErrorString(e));
     }
     const hipError_t e0 = hipEventRecord(c->ev_ri, L.stream);
@@ -283,11 +304,17 @@ static PtStatus restir_di_common(PtContext* c, const char* who, const PtRestirDi
     return st;
 }
 
-PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, nullptr, t); }
+PtStatus pt_restir_di(PtContext* c, const PtRestirDiSettings* s, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di", s, nullptr, nullptr, nullptr, false, t); }
 
-PtStatus pt_restir_di_sampled(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di_sampled", s, ls, nullptr, t); }
+PtStatus pt_restir_di_sampled(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di_sampled", s, ls, nullptr, nullptr, false, t); }
 
-PtStatus pt_restir_di_ex(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di_ex", s, ls, cd, t); }
+PtStatus pt_restir_di_ex(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd, const PtRestirDiTextures* t) { return restir_di_common(c, "pt_restir_di_ex", s, ls, cd, nullptr, false, t); }
+
+PtStatus pt_restir_di_full(PtContext* c, const PtRestirDiSettings* s, const PtLightSamplingSettings* ls, const PtRestirDiCandidates* cd, const PtRestirDiShading* sh,
+                           const PtRestirDiTextures* t)
+{
+    return restir_di_common(c, "pt_restir_di_full", s, ls, cd, sh, true, t);
+}
 
 PtStatus pt_restir_di_history(PtContext* c, uint32_t which, void* planes, void* transmission)
 {

@@ -15,9 +15,14 @@
 // Row N17 (spec S23, pt_restir_di_ex): BRDF candidates mixed into initial sampling by the balance heuristic (ri_initial_mis) and the
 // boiling filter over launch 1's temporal result (ri_boiling_*); both off: the code of rows N10 / N16, untouched.
 //
+// Row N22 (spec S26, pt_restir_di_full): the visibility word a reservoir carries and final shading's reuse of it (ri_vis_*,
+// ri_final_reuse), and pairwise MIS (bias mode 2: ri_temporal_pairwise, ri_spatial_pairwise).  The arithmetic is this project's own,
+// written from the reference's shaders and from recollection of RTXDI (the SDK is not vendored): no parity with the SDK is claimed.
+// Both live in launches of their own (ri_pass1_full_*, ri_pass2_full_px); the functions of rows N10 / N16 / N17 compile as they did.
+//
 // Out of scope: ReGIR's onion mode; environment candidates (the reference's bridge stubs them to 0, RTXDIAppBridge.hlsli:503-511);
-// checkerboard rendering; visibility reuse; pairwise MIS (bias mode 2); the DLSS-RR SpecularHitDistance write; dropping
-// pt_render_with_di's whole-stream wait for buffers this pass produced.
+// checkerboard rendering; writing the final ray's result back into the history; discardInvisibleSamples; a ray-traced pairwise
+// variant; the DLSS-RR SpecularHitDistance write; dropping pt_render_with_di's whole-stream wait for buffers this pass produced.
 #pragma once
 
 #include "pt_light.h"
@@ -58,6 +63,7 @@ struct RiReservoir {
     float M;         // candidates seen
     float p_hat;     // target function of the sample at the surface that holds it
     uint32_t age;    // frames since the sample was drawn
+    uint32_t vis;    // row N22: what is known of the sample's visibility (ri_vis_*); 0: nothing -- all that rows N10 / N16 / N17 write
 };
 
 struct RiBuffers {
@@ -92,6 +98,8 @@ struct RiScene {
     const uint32_t* light_of; // per sphere: its index in `lights`, or kRiNoHit
     const float* pyramid;     // S22's power pyramid, every level (the presampled modes: the source pdf of an emitter a BRDF ray found)
     uint32_t pyramid_levels;
+    // row N22 (read by ri_final_reuse only): per sphere its alpha class (pt_device.h; 0: every crossing is accepted), or null: all 0
+    const uint32_t* alpha_class;
 };
 
 struct RiParams {
@@ -106,6 +114,16 @@ struct RiParamsEx : RiParams {
     uint32_t brdf_samples;    // BRDF candidates of initial sampling
     uint32_t boiling_filter;
     float boiling_strength;
+};
+
+// ... and with what row N22 adds (the launches of pt_restir_di_full): final shading's reuse of the visibility word
+struct RiShading {
+    uint32_t reuse;           // 0: every final ray is cast
+    uint32_t max_age;         // the sample's age at most this ...
+    float max_dist2;          // ... and the square of its pixel offset at most this (MaxDistance * MaxDistance in float32)
+};
+struct RiParamsFull : RiParamsEx {
+    RiShading sh;
 };
 
 PT_HD float4 ri_float4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
@@ -167,14 +185,14 @@ PT_HD RiRecord ri_load_record(P4 const rec[4], const float* rec_t, uint32_t i)
 PT_HD RiReservoir ri_empty_reservoir()
 {
     RiReservoir r;
-    r.light = 0u; r.u1 = r.u2 = 1.0f; r.W = 0.0f; r.M = 0.0f; r.p_hat = 0.0f; r.age = 0u;
+    r.light = 0u; r.u1 = r.u2 = 1.0f; r.W = 0.0f; r.M = 0.0f; r.p_hat = 0.0f; r.age = 0u; r.vis = 0u;
     return r;
 }
 
 PT_HD void ri_store_reservoir(float4* const res[2], uint32_t i, const RiReservoir& r)
 {
     res[0][i] = ri_float4(as_float(r.light), r.u1, r.u2, r.W);
-    res[1][i] = ri_float4(r.M, r.p_hat, as_float(r.age), 0.0f);
+    res[1][i] = ri_float4(r.M, r.p_hat, as_float(r.age), as_float(r.vis));
 }
 
 template <typename P4>
@@ -182,7 +200,7 @@ PT_HD RiReservoir ri_load_reservoir(P4 const res[2], uint32_t i)
 {
     const float4 a = res[0][i], c = res[1][i];
     RiReservoir r;
-    r.light = as_uint(a.x); r.u1 = a.y; r.u2 = a.z; r.W = a.w; r.M = c.x; r.p_hat = c.y; r.age = as_uint(c.z);
+    r.light = as_uint(a.x); r.u1 = a.y; r.u2 = a.z; r.W = a.w; r.M = c.x; r.p_hat = c.y; r.age = as_uint(c.z); r.vis = as_uint(c.w);
     return r;
 }
 
@@ -491,8 +509,37 @@ inline float ri_boiling_sum64(const float w[64], uint32_t& n)
     return v[0];
 }
 
-// ---- temporal resampling (DITemporalResampling.hlsl): the reservoir of the reprojected pixel of the previous call
-template <typename TraceFn>
+// ---- row N22 (spec S26, part 1): the visibility word.  Bit 0: the visibility ray cast from the surface that drew the sample reached
+// its emitter; bits 8-15 and 16-23: the pixel offset (dx, dy) the sample has travelled since, each a biased int8 (value + 128, |value|
+// <= 127) where 0 means saturated and stays so.  The word 0 therefore says nothing and moves to itself.
+constexpr uint32_t kRiVisSeen = 1u;
+constexpr uint32_t kRiVisFresh = kRiVisSeen | (128u << 8) | (128u << 16);  // seen by this pixel: offset (0, 0)
+
+PT_HD uint32_t ri_vis_axis(uint32_t byte, int d)
+{
+    if (byte == 0u) return 0u;
+    d = d < -256 ? -256 : (d > 256 ? 256 : d);
+    const int v = (int)byte - 128 + d;
+    return v < -127 || v > 127 ? 0u : (uint32_t)(v + 128);
+}
+// the word of a sample that pixel (x + dx, y + dy) takes from pixel (x, y)
+PT_HD uint32_t ri_vis_moved(uint32_t vis, int dx, int dy)
+{
+    return (vis & 0xFF0000FFu) | (ri_vis_axis((vis >> 8) & 0xFFu, dx) << 8) | (ri_vis_axis((vis >> 16) & 0xFFu, dy) << 16);
+}
+// final shading may take the sample's visibility as known (the emitter's alpha class is the caller's to check)
+PT_HD bool ri_vis_usable(const RiShading& sh, const RiReservoir& r)
+{
+    if (!sh.reuse || !(r.vis & kRiVisSeen) || r.age > sh.max_age) return false;
+    const uint32_t bx = (r.vis >> 8) & 0xFFu, by = (r.vis >> 16) & 0xFFu;
+    if (bx == 0u || by == 0u) return false;
+    const float dx = (float)((int)bx - 128), dy = (float)((int)by - 128);
+    return dx * dx + dy * dy <= sh.max_dist2;
+}
+
+// ---- temporal resampling (DITemporalResampling.hlsl): the reservoir of the reprojected pixel of the previous call.  kVis (row N22):
+// the selected sample's visibility word travels with it
+template <bool kVis = false, typename TraceFn>
 PT_HD RiReservoir ri_temporal(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& cur, uint32_t px,
                               uint32_t py, f3 mv, TraceFn&& trace)
 {
@@ -513,7 +560,10 @@ PT_HD RiReservoir ri_temporal(const RiBuffers& b, const RiScene& sc, const RiPar
     RiReservoir r = cur;
     float w_sum = cur.p_hat * cur.W * cur.M;
     const RiShade e = ri_shade(sc, s, prev.light, prev.u1, prev.u2);  // the history's sample, re-aimed from this surface
-    if (ri_stream(w_sum, e.p_hat * prev.W * prev.M, rnd)) { r.light = prev.light; r.u1 = prev.u1; r.u2 = prev.u2; r.p_hat = e.p_hat; r.age = prev.age + 1u; }
+    if (ri_stream(w_sum, e.p_hat * prev.W * prev.M, rnd)) {
+        r.light = prev.light; r.u1 = prev.u1; r.u2 = prev.u2; r.p_hat = e.p_hat; r.age = prev.age + 1u;
+        if (kVis) r.vis = ri_vis_moved(prev.vis, (int)px - (int)fx, (int)py - (int)fy);
+    }
     r.M = cur.M + prev.M;
     r.W = 0.0f;
     if (!(r.p_hat > 0.0f)) return r;
@@ -569,8 +619,8 @@ PT_HD bool ri_neighbour_surface(const RiBuffers& b, const RiParams& p, const RiS
         && ri_materials_similar(s.bsdf, ns.bsdf);
 }
 
-// ---- spatial resampling (DISpatialResampling.hlsl): SpatialSamples neighbours of this call's temporal result
-template <typename TraceFn>
+// ---- spatial resampling (DISpatialResampling.hlsl): SpatialSamples neighbours of this call's temporal result.  kVis: as ri_temporal's
+template <bool kVis = false, typename TraceFn>
 PT_HD RiReservoir ri_spatial(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& centre, uint32_t px,
                              uint32_t py, TraceFn&& trace)
 {
@@ -592,7 +642,10 @@ PT_HD RiReservoir ri_spatial(const RiBuffers& b, const RiScene& sc, const RiPara
         if (!(nr.M > 0.0f)) continue;
         accepted |= 1u << i;
         const RiShade e = ri_shade(sc, s, nr.light, nr.u1, nr.u2);
-        if (ri_stream(w_sum, e.p_hat * nr.W * nr.M, rnd)) { r.light = nr.light; r.u1 = nr.u1; r.u2 = nr.u2; r.p_hat = e.p_hat; r.age = nr.age; }
+        if (ri_stream(w_sum, e.p_hat * nr.W * nr.M, rnd)) {
+            r.light = nr.light; r.u1 = nr.u1; r.u2 = nr.u2; r.p_hat = e.p_hat; r.age = nr.age;
+            if (kVis) r.vis = ri_vis_moved(nr.vis, (int)px - (int)qx, (int)py - (int)qy);
+        }
         r.M += nr.M;
     }
     if (!accepted) return centre;
@@ -622,6 +675,125 @@ PT_HD RiReservoir ri_spatial(const RiBuffers& b, const RiScene& sc, const RiPara
     return r;
 }
 
+// ---- row N22 (spec S26, part 2): pairwise MIS, bias mode 2.  The canonical reservoir (M_c, sample y_c, on surface c) against k
+// accepted neighbours (M_i, y_i, on surface i), p_x(y) the target function of y re-aimed from x (no visibility):
+//   neighbour i streams with  p_c(y_i) W_i m_i / k,   m_i = M_i p_i(y_i) / (M_i p_i(y_i) + (M_c / k) p_c(y_i))       (0 where that sum is not > 0)
+//   the canonical streams last with  p_c(y_c) W_c m_c,   m_c = (1 / k) sum_i (M_c / k) p_c(y_c) / (M_i p_i(y_c) + (M_c / k) p_c(y_c))   (a term counts 1 there)
+//   W = w_sum / p_c(y_selected), M = M_c + sum_i M_i.  The k + 1 weights sum to 1 at every y.
+// p_i(y_i) and p_c(y_c) are the p_hat the reservoirs store.  Every product and sum is one float32 operation in the order written in
+// ri_pairwise_neighbour / ri_pairwise_canonical_term (DESIGN.md spec S26 freezes it).
+struct RiPairwise {
+    float kf, mc;      // k and M_c / k
+    float w_sum, m_c;  // the stream's weight so far; the canonical's terms so far
+};
+
+PT_HD RiPairwise ri_pairwise_begin(float M_c, uint32_t k)
+{
+    RiPairwise s;
+    s.kf = (float)k;
+    s.mc = M_c / s.kf;
+    s.w_sum = 0.0f;
+    s.m_c = 0.0f;
+    return s;
+}
+// the weight neighbour i's sample streams with: pc_yi = p_c(y_i), pi_yi = p_i(y_i)
+PT_HD float ri_pairwise_neighbour(const RiPairwise& s, float M_i, float W_i, float pi_yi, float pc_yi)
+{
+    const float a = M_i * pi_yi, b = s.mc * pc_yi, d = a + b;
+    const float m = d > 0.0f ? a / d : 0.0f;
+    return ((pc_yi * W_i) * m) / s.kf;
+}
+// pair i's term of the canonical weight: pc_yc = p_c(y_c), pi_yc = p_i(y_c)
+PT_HD float ri_pairwise_canonical_term(const RiPairwise& s, float M_i, float pc_yc, float pi_yc)
+{
+    const float c = s.mc * pc_yc, d = M_i * pi_yc + c;
+    return d > 0.0f ? c / d : 1.0f;
+}
+// the canonical sample streams last; `centre` is restored where it wins; then W of whatever was selected
+PT_HD void ri_pairwise_end(RiPairwise& s, const RiReservoir& centre, float rnd, RiReservoir& r)
+{
+    const float w_c = (centre.p_hat * centre.W) * (s.m_c / s.kf);
+    if (ri_stream(s.w_sum, w_c, rnd)) { r.light = centre.light; r.u1 = centre.u1; r.u2 = centre.u2; r.p_hat = centre.p_hat; r.age = centre.age; r.vis = centre.vis; }
+    r.W = r.p_hat > 0.0f ? s.w_sum / r.p_hat : 0.0f;
+    if (!is_finite(r.W)) r.W = 0.0f;
+}
+
+// ri_temporal under pairwise MIS: k = 1, the neighbour is the reprojected history reservoir (M capped as there) on the previous call's
+// surface seen from prev_cam_pos.  Draws ri_temporal's rnd, then one more for the canonical sample.  The visibility word travels.
+PT_HD RiReservoir ri_temporal_pairwise(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& cur, uint32_t px,
+                                       uint32_t py, f3 mv)
+{
+    if (!p.temporal || !p.history_valid) return cur;
+    const float fx = pt_floor((float)px + mv.x + 0.5f), fy = pt_floor((float)py + mv.y + 0.5f);
+    if (!(fx >= 0.0f && fx < (float)b.w && fy >= 0.0f && fy < (float)b.h)) return cur;
+    const uint32_t qi = (uint32_t)fy * b.w + (uint32_t)fx;
+    const RiSurface ps = ri_surface(ri_load_record(b.prev_rec, b.prev_rec_t, qi), p.prev_cam_pos);
+    if (!ps.valid) return cur;
+    const float expected = s.depth + mv.z;
+    if (!(pt_abs(ps.depth - expected) <= kRiDepthThreshold * expected)) return cur;
+    if (!(dot(s.surf.Ns, ps.surf.Ns) >= kRiNormalThreshold)) return cur;
+    RiReservoir prev = ri_load_reservoir(b.prev_res, qi);
+    if (!(prev.M > 0.0f)) return cur;
+    prev.M = pt_min(prev.M, (float)p.max_history * cur.M);
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiTemporalRngSalt);
+    const float rnd = rng_float(rng);
+    RiReservoir r = cur;
+    RiPairwise pw = ri_pairwise_begin(cur.M, 1u);
+    const RiShade e = ri_shade(sc, s, prev.light, prev.u1, prev.u2);  // the history's sample, re-aimed from this surface
+    if (ri_stream(pw.w_sum, ri_pairwise_neighbour(pw, prev.M, prev.W, prev.p_hat, e.p_hat), rnd)) {
+        r.light = prev.light; r.u1 = prev.u1; r.u2 = prev.u2; r.p_hat = e.p_hat; r.age = prev.age + 1u;
+        r.vis = ri_vis_moved(prev.vis, (int)px - (int)fx, (int)py - (int)fy);
+    }
+    pw.m_c += ri_pairwise_canonical_term(pw, prev.M, cur.p_hat, ri_shade(sc, ps, cur.light, cur.u1, cur.u2).p_hat);
+    ri_pairwise_end(pw, cur, rng_float(rng), r);
+    r.M = cur.M + prev.M;
+    return r;
+}
+
+// ri_spatial under pairwise MIS.  Every neighbour's weight depends on k, the number of accepted neighbours, so the acceptance tests run
+// first (records only: no sample is shaded); the second loop shades p_c(y_i) and p_i(y_c) while neighbour i's record is in registers,
+// which replaces both loops of the Basic form.  Draws ri_spatial's numbers, then one more for the canonical sample.
+PT_HD RiReservoir ri_spatial_pairwise(const RiBuffers& b, const RiScene& sc, const RiParams& p, const RiSurface& s, const RiReservoir& centre, uint32_t px,
+                                      uint32_t py)
+{
+    if (!p.spatial) return centre;
+    uint32_t rng = rng_init(px, py, p.frame_index ^ kRiSpatialRngSalt);
+    const uint32_t start = rng_next(rng) & (kRiNeighbourTable - 1u);
+    const float rot = rng_float(rng);
+    uint32_t accepted = 0u, k = 0u;
+    for (uint32_t i = 0; i < p.spatial_samples; i++) {
+        uint32_t qx, qy;
+        if (!ri_neighbour(b, p.radius, px, py, (start + i) & (kRiNeighbourTable - 1u), rot, qx, qy)) continue;
+        const uint32_t qi = qy * b.w + qx;
+        RiSurface ns;
+        if (!ri_neighbour_surface(b, p, s, qi, ns)) continue;
+        if (!(b.res[1][qi].x > 0.0f)) continue;
+        accepted |= 1u << i;
+        k++;
+    }
+    if (!accepted) return centre;
+    RiReservoir r = centre;
+    RiPairwise pw = ri_pairwise_begin(centre.M, k);
+    for (uint32_t i = 0; i < p.spatial_samples; i++) {
+        const float rnd = rng_float(rng);
+        if (!(accepted & (1u << i))) continue;
+        uint32_t qx, qy;
+        (void)ri_neighbour(b, p.radius, px, py, (start + i) & (kRiNeighbourTable - 1u), rot, qx, qy);
+        const uint32_t qi = qy * b.w + qx;
+        const RiSurface ns = ri_surface(ri_load_record(b.rec, b.rec_t, qi), p.cam_pos);
+        const RiReservoir nr = ri_load_reservoir(b.res, qi);
+        const RiShade e = ri_shade(sc, s, nr.light, nr.u1, nr.u2);
+        if (ri_stream(pw.w_sum, ri_pairwise_neighbour(pw, nr.M, nr.W, nr.p_hat, e.p_hat), rnd)) {
+            r.light = nr.light; r.u1 = nr.u1; r.u2 = nr.u2; r.p_hat = e.p_hat; r.age = nr.age;
+            r.vis = ri_vis_moved(nr.vis, (int)px - (int)qx, (int)py - (int)qy);
+        }
+        pw.m_c += ri_pairwise_canonical_term(pw, nr.M, centre.p_hat, ri_shade(sc, ns, centre.light, centre.u1, centre.u2).p_hat);
+        r.M += nr.M;
+    }
+    ri_pairwise_end(pw, centre, rng_float(rng), r);
+    return r;
+}
+
 // ---- final shading (DIFinalShading.hlsl:23-103, IsLastRenderPass false): false = the pixel is not written
 template <typename TraceFn, typename EmitFn>
 PT_HD bool ri_final(const RiScene& sc, const RiSurface& s, const RiReservoir& r, TraceFn&& trace, EmitFn&& emit, float4& diffuse, float4& specular)
@@ -640,6 +812,26 @@ PT_HD bool ri_final(const RiScene& sc, const RiSurface& s, const RiReservoir& r,
     diffuse = ri_float4(d.x, d.y, d.z, t2);
     specular = ri_float4(sp.x, sp.y, sp.z, t2);
     return true;
+}
+
+// ri_final with reuseFinalVisibility (DIFinalShading.hlsl:32-56; spec S26, part 1): a sample whose word says it was seen, young and
+// near enough, on an emitter whose every crossing counts, casts no ray -- the light distance is intersect_sphere's from the spawn
+// origin, the leaf function every tree walk calls, so the pixel holds the bits a traced one would.  Where that intersection fails (a
+// limb sample) the ray is cast.  The reservoir is never changed.
+template <typename TraceFn, typename EmitFn>
+PT_HD bool ri_final_reuse(const RiScene& sc, const RiShading& sh, const RiSurface& s, const RiReservoir& r, TraceFn&& trace, EmitFn&& emit, float4& diffuse,
+                          float4& specular)
+{
+    const uint32_t sphere = sc.lights[r.light < sc.n_lights ? r.light : sc.n_lights - 1u];
+    const bool known = ri_vis_usable(sh, r) && !(sc.alpha_class && sc.alpha_class[sphere] != 0u);
+    auto query = [&](f3 o, f3 d, float& t, uint32_t& id) {
+        if (known) {
+            const float4 ls = sc.sph[sphere];
+            if (intersect_sphere(o, d, 0.0f, kInf, make_f3(ls.x, ls.y, ls.z), ls.w, t)) { id = sphere; return; }
+        }
+        trace(o, d, t, id);
+    };
+    return ri_final(sc, s, r, query, emit, diffuse, specular);
 }
 
 // ---- what one lane of each launch does
@@ -719,6 +911,67 @@ PT_HD void ri_pass2_px(const RiBuffers& b, const RiScene& sc, const RiParams& p,
     if (ri_final(sc, s, r, trace, emit, d, sp)) { b.out_diffuse[i] = d; b.out_specular[i] = sp; }
 }
 
+// ---- the launches of pt_restir_di_full (row N22)
+// launch 1: as ri_pass1_reservoir, and a sample whose initial visibility ray reached its emitter says so in its word (W > 0 behind
+// ri_initial / ri_initial_mis means exactly that); kPairwise: temporal resampling under bias mode 2
+template <uint32_t kMode, bool kBrdf, bool kPairwise, typename TraceFn>
+PT_HD bool ri_pass1_full_reservoir(const RiBuffers& b, const RiScene& sc, const RiParamsFull& p, uint32_t px, uint32_t py, TraceFn&& trace, RiReservoir& r)
+{
+    const uint32_t i = py * b.w + px;
+    r = ri_empty_reservoir();
+    const RiRecord rec = ri_record_from_gbuffer(b, i);
+    if (!is_finite(rec.r3.z)) {
+        b.rec[3][i] = rec.r3;
+        return false;
+    }
+    ri_store_record(b.rec, b.rec_t, i, rec);
+    const RiSurface s = ri_surface(rec, p.cam_pos);
+    if (kBrdf) r = ri_initial_mis<kMode>(sc, p, s, px, py, trace);
+    else r = ri_initial<kMode>(sc, p, s, px, py, trace);
+    if (r.W > 0.0f) r.vis = kRiVisFresh;
+    const f3 mv = make_f3(b.motion_vector[3u * i], b.motion_vector[3u * i + 1u], b.motion_vector[3u * i + 2u]);
+    if (kPairwise) r = ri_temporal_pairwise(b, sc, p, s, r, px, py, mv);
+    else r = ri_temporal<true>(b, sc, p, s, r, px, py, mv, trace);
+    return true;
+}
+
+// ... and the host form of one 8x8 block of it, as ri_pass1_block
+template <uint32_t kMode, bool kBrdf, bool kPairwise, typename TraceFn>
+inline void ri_pass1_full_block(const RiBuffers& b, const RiScene& sc, const RiParamsFull& p, uint32_t bx, uint32_t by, TraceFn&& trace)
+{
+    RiReservoir res[64];
+    bool has[64];
+    float w[64];
+    for (uint32_t l = 0; l < 64u; l++) {
+        const uint32_t px = bx * 8u + (l & 7u), py = by * 8u + (l >> 3);
+        has[l] = px < b.w && py < b.h && ri_pass1_full_reservoir<kMode, kBrdf, kPairwise>(b, sc, p, px, py, trace, res[l]);
+        w[l] = has[l] ? res[l].W : 0.0f;
+    }
+    uint32_t n = 0u;
+    const float sum = p.boiling_filter ? ri_boiling_sum64(w, n) : 0.0f;
+    const float mult = ri_boiling_multiplier(p.boiling_strength);
+    for (uint32_t l = 0; l < 64u; l++) {
+        if (!has[l]) continue;
+        if (p.boiling_filter && ri_boiled(w[l], sum, n, mult)) res[l] = ri_empty_reservoir();
+        ri_store_reservoir(b.res, (by * 8u + (l >> 3)) * b.w + bx * 8u + (l & 7u), res[l]);
+    }
+}
+
+// launch 2: kPairwise -- spatial resampling under bias mode 2; kReuse -- final shading through ri_final_reuse (the spatial pass then
+// carries the word).  Read-only on the slot, like ri_pass2_px.
+template <bool kPairwise, bool kReuse, typename TraceFn, typename EmitFn>
+PT_HD void ri_pass2_full_px(const RiBuffers& b, const RiScene& sc, const RiParamsFull& p, uint32_t px, uint32_t py, TraceFn&& trace, EmitFn&& emit)
+{
+    const uint32_t i = py * b.w + px;
+    const RiRecord rec = ri_load_record(b.rec, b.rec_t, i);
+    if (!is_finite(rec.r3.z)) return;
+    const RiSurface s = ri_surface(rec, p.cam_pos);
+    const RiReservoir centre = ri_load_reservoir(b.res, i);
+    const RiReservoir r = kPairwise ? ri_spatial_pairwise(b, sc, p, s, centre, px, py) : ri_spatial<kReuse>(b, sc, p, s, centre, px, py, trace);
+    float4 d, sp;
+    if (kReuse ? ri_final_reuse(sc, p.sh, s, r, trace, emit, d, sp) : ri_final(sc, s, r, trace, emit, d, sp)) { b.out_diffuse[i] = d; b.out_specular[i] = sp; }
+}
+
 #if defined(__HIPCC__)
 struct SceneView;
 struct PixelMap;
@@ -735,6 +988,11 @@ struct RiExtra {
 // launch 1 with p.brdf_samples > 0 and / or p.boiling_filter (both off: launch_restir_pass)
 hipError_t launch_restir_pass1_ex(const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParamsEx& p, uint32_t mode, const LrView& lr,
                                   const RiExtra& x, uint32_t grid, hipStream_t stream);
+// the launches of pt_restir_di_full (row N22, pt_restir_full.hip).  pass 0: launch 1 writing the visibility word, temporal resampling
+// pairwise where p.temporal_bias is 2; pass 1: launch 2 with the spatial pass pairwise where p.spatial_bias is 2 and final shading
+// through the word where p.sh.reuse.  The caller sends a call that needs neither to the launches above.
+hipError_t launch_restir_full(int pass, const SceneView& sv, const PixelMap& pm, const RiBuffers& b, const RiParamsFull& p, uint32_t mode, const LrView& lr,
+                              const RiExtra& x, uint32_t grid, hipStream_t stream);
 #endif
 
 }  // namespace pt

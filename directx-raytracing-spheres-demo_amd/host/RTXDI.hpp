@@ -4,7 +4,8 @@
 // (Source/MyAppData.h:190-250) the stand-in reads; resources are DEVICE pointers of RenderSize texels (the layouts of
 // PtRestirDiTextures) instead of D3D12 textures.  With a local-light sampling mode other than Uniform the passes run through
 // pt_restir_di_sampled (row N16, spec S22: Power_RIS tiles and the ReGIR grid, MyAppData.h:194-218); with BRDF candidates or the boiling
-// filter through pt_restir_di_ex (row N17, spec S23: MyAppData.h:220-221, 229-235).
+// filter through pt_restir_di_ex (row N17, spec S23: MyAppData.h:220-221, 229-235).  After the SetConstants overload that takes
+// ShadingSettings the passes run through pt_restir_di_full (row N22, spec S26), which accepts Pairwise and reuses final visibility.
 #pragma once
 
 #include <array>
@@ -47,6 +48,14 @@ struct ReSTIRDISettings {  // MyAppData.h:190-250 (IsEnabled = true is the refer
     }
 };
 
+// ReSTIRDI_ShadingParameters' final-visibility reuse, which the reference leaves at the SDK's defaults (Source/RTXDI.ixx:134; on, 4
+// frames and 16 pixels as recollected); this mirror's reuse stays off so that a host keeps the frames it had
+struct ShadingSettings {
+    bool ReuseFinalVisibility = false;
+    uint32_t MaxAge = 4;
+    float MaxDistance = 16;
+};
+
 class RTXDI {
 public:
     // the G-buffer textures RAB_GetGBufferSurface reads and the two textures DIFinalShading writes
@@ -84,6 +93,18 @@ public:
         m_candidates.BrdfSamples = settings.InitialSampling.BRDFSamples;
         m_candidates.EnableBoilingFilter = settings.TemporalResampling.BoilingFilter.IsEnabled ? 1u : 0u;
         m_candidates.BoilingFilterStrength = settings.TemporalResampling.BoilingFilter.Strength;
+        m_full = false;
+    }
+
+    // ... with the shading parameters: Render() then goes through pt_restir_di_full, where BiasCorrectionMode may be Pairwise
+    void SetConstants(const ReSTIRDISettings& settings, const ShadingSettings& shading, bool resetHistory, std::array<uint32_t, 2> renderSize, uint32_t frameIndex)
+    {
+        SetConstants(settings, resetHistory, renderSize, frameIndex);
+        m_shading = PtRestirDiShading{};
+        m_shading.ReuseFinalVisibility = shading.ReuseFinalVisibility ? 1u : 0u;
+        m_shading.FinalVisibilityMaxAge = shading.MaxAge;
+        m_shading.FinalVisibilityMaxDistance = shading.MaxDistance;
+        m_full = true;
     }
 
     // RTXDI::Render: the DI passes of the frame the next render call renders, asynchronous
@@ -92,7 +113,8 @@ public:
         const PtRestirDiTextures t{ GPUBuffers.Position, GPUBuffers.GeometricNormal, GPUBuffers.LinearDepth, GPUBuffers.MotionVector,
                                     GPUBuffers.BaseColorMetalness, GPUBuffers.NormalRoughness, GPUBuffers.IOR, GPUBuffers.Transmission,
                                     GPUBuffers.Diffuse, GPUBuffers.Specular };
-        if (m_candidates.BrdfSamples || m_candidates.EnableBoilingFilter)
+        if (m_full) ThrowIfFailed(pt_restir_di_full(m_ctx, &m_settings, &m_sampling, &m_candidates, &m_shading, &t), m_ctx, "pt_restir_di_full");
+        else if (m_candidates.BrdfSamples || m_candidates.EnableBoilingFilter)
             ThrowIfFailed(pt_restir_di_ex(m_ctx, &m_settings, &m_sampling, &m_candidates, &t), m_ctx, "pt_restir_di_ex");
         else if (m_sampling.Mode == PT_LIGHT_SAMPLING_UNIFORM) ThrowIfFailed(pt_restir_di(m_ctx, &m_settings, &t), m_ctx, "pt_restir_di");
         else ThrowIfFailed(pt_restir_di_sampled(m_ctx, &m_settings, &m_sampling, &t), m_ctx, "pt_restir_di_sampled");
@@ -103,6 +125,8 @@ private:
     PtRestirDiSettings m_settings{};
     PtLightSamplingSettings m_sampling{};
     PtRestirDiCandidates m_candidates{};
+    PtRestirDiShading m_shading{};
+    bool m_full = false;
 };
 
 }  // namespace dxrs

@@ -25,6 +25,7 @@
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_restir_di_sampled     the same with Power_RIS / ReGIR_RIS local-light presampling (spec S22)                 Source/RTXDI.ixx:209-226
  *   pt_restir_di_ex          ... and with BRDF candidates and the boiling filter (spec S23)                         Source/App.cpp:1092-1101
+ *   pt_restir_di_full        ... and with pairwise bias correction and final-visibility reuse (spec S26)            Source/RTXDI.ixx:134
  *   pt_render_sharc          Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings) (a stand-in for SHARC, spec S20)   Source/Raytracing.ixx:114-148
  *   pt_render_sharc_ex       ... with IsDIEnabled and a denoiser, the reference's default frame (spec S24)   Source/App.cpp:1255-1268,
  *                            Shaders/Raytracing.hlsl:150-163, 302-318, 376-414
@@ -378,12 +379,13 @@ PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, co
  * first use and freed by pt_destroy.  The history restarts on the first call, with ResetHistory, when RenderSize changes and after
  * pt_set_scene (emitter indices change); spheres moved by pt_update_spheres keep it.
  * The candidates are uniform over the emitter list; pt_restir_di_sampled below draws them from presampled structures (row N16).
- * BRDF candidates and the boiling filter: pt_restir_di_ex below (row N17).
+ * BRDF candidates and the boiling filter: pt_restir_di_ex below (row N17).  Pairwise bias correction and final-visibility reuse:
+ * pt_restir_di_full below (row N22).
  * Not built (spec S16): environment candidates (the reference's bridge stubs them to 0), checkerboard rendering,
- * visibility reuse, pairwise MIS, the DLSS-RR SpecularHitDistance write.
+ * the DLSS-RR SpecularHitDistance write.
  * PT_ERR_INVALID_ARG: a null argument; a missing buffer; a float4 buffer not 16-byte aligned, GeometricNormal not 8-byte, another not
  * 4-byte; an output overlapping an input or the other output; a value outside the ranges of PtRestirDiSettings.  PT_ERR_UNSUPPORTED:
- * bias correction mode 2 (Pairwise).  PT_ERR_STATE: as pt_render (the pass casts rays). */
+ * bias correction mode 2 (Pairwise), which only pt_restir_di_full accepts.  PT_ERR_STATE: as pt_render (the pass casts rays). */
 typedef struct PtRestirDiTextures {     /* DEVICE pointers; inputs are what RAB_GetGBufferSurface reads, as pt_render_gbuffer writes them */
     const void *Position;               /* float4 (P, PositionOffset) */
     const void *GeometricNormal;        /* float2 */
@@ -424,9 +426,29 @@ PtStatus pt_restir_di_sampled(PtContext *ctx, const PtRestirDiSettings *settings
 PtStatus pt_restir_di_ex(PtContext *ctx, const PtRestirDiSettings *settings, const PtLightSamplingSettings *sampling, const PtRestirDiCandidates *candidates,
                          const PtRestirDiTextures *textures);
 
-/* Test hook: a slot of the history pt_restir_di / pt_restir_di_sampled / pt_restir_di_ex keep, after waiting for the last call: which = 0 the slot the
+/* Row N22 -- pt_restir_di_ex with the two remaining values of the reference's ReSTIRDI settings block (DESIGN.md spec S26):
+ *   bias correction mode 2 (Pairwise) in TemporalBiasCorrection and / or SpatialBiasCorrection: pairwise MIS between the centre reservoir
+ *     and each accepted neighbour, targets without visibility (among occluders biased the way Basic is; Raytraced stays the unbiased mode);
+ *   final-visibility reuse (`shading`): a reservoir's eighth word records that the visibility ray of the surface that drew the sample
+ *     reached its emitter, and the pixel offset the sample has travelled since; a sample at most FinalVisibilityMaxAge frames old and
+ *     FinalVisibilityMaxDistance pixels away, on an emitter that is not alpha-tested, casts no final ray.  Reuse never changes a reservoir:
+ *     a pixel written without it holds the same bits with it; the extra pixels it writes are those an out-of-date visibility lets through.
+ *     With both limits 0 the output equals reuse off bit for bit.
+ * `shading` NULL or ReuseFinalVisibility 0, and no bias mode equal to 2: the call IS pt_restir_di_ex -- the same launches, history slots,
+ * restart rules and bits; calls of the four entry points may alternate on one context (the other three write the word as 0: nothing known).
+ * Errors, lane, ordering, buffer rotation, profiling slots: as pt_restir_di_ex.  The arithmetic is this library's own, written from the
+ * reference's shaders and from recollection of RTXDI (the SDK is not vendored): no parity with the SDK is claimed.
+ * Not built: writing the final ray's result back into the history, discardInvisibleSamples, a ray-traced pairwise variant, checkerboard
+ * rendering, environment candidates, ReGIR's onion mode and cell visualisation.
+ * PT_ERR_INVALID_ARG also: ReuseFinalVisibility above 1, FinalVisibilityMaxAge above 255, a FinalVisibilityMaxDistance that is not finite
+ * or is negative, a nonzero _pad. */
+PtStatus pt_restir_di_full(PtContext *ctx, const PtRestirDiSettings *settings, const PtLightSamplingSettings *sampling, const PtRestirDiCandidates *candidates,
+                           const PtRestirDiShading *shading, const PtRestirDiTextures *textures);
+
+/* Test hook: a slot of the history pt_restir_di / pt_restir_di_sampled / pt_restir_di_ex / pt_restir_di_full keep, after waiting for the last call: which = 0 the slot the
  * last call wrote, 1 the slot the call before it wrote.  planes: six planes of RenderSize float4 (the surface record's four, then the
- * reservoir's two: {emitter bits, u1, u2, W}, {M, p_hat, age bits, 0}); transmission: RenderSize floats.  A pixel without a surface
+ * reservoir's two: {emitter bits, u1, u2, W}, {M, p_hat, age bits, visibility word: 0 = nothing known, all that the first three entry
+ * points write; spec S26}); transmission: RenderSize floats.  A pixel without a surface
  * holds only plane 3 (its depth is +inf); its other words are whatever the slot held before.  PT_ERR_STATE: no call has left a history. */
 PtStatus pt_restir_di_history(PtContext *ctx, uint32_t which, void *planes, void *transmission);
 

@@ -16,6 +16,7 @@
  *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
  *   PtLightSamplingSettings (row N16) the local-light sampling mode and the ReGIR settings (Source/MyAppData.h:194-218), 32 B
  *   PtRestirDiCandidates  (row N17) InitialSampling.BRDFSamples and TemporalResampling.BoilingFilter (Source/MyAppData.h:220-235), 16 B
+ *   PtRestirDiShading     (row N22) ReSTIRDI_ShadingParameters' final-visibility reuse (the SDK's defaults apply in the reference), 16 B
  *   PtRestirDiSettings    (row N10) the parts of ReSTIRDI_Parameters (Source/MyAppData.h:190-250) the RTXDI stand-in reads, 48 B
  *
  * PtSphere replaces the reference's per-instance ObjectToWorld of the unit
@@ -188,7 +189,7 @@ typedef struct PtRestirDiSettings {
     uint32_t ResetHistory;           /* 12: nonzero = ignore the history (m_resetHistory) */
     uint32_t InitialSamples;         /* 16: 0 -> 8, at most 32 (InitialSampling.LocalLight.Samples) */
     uint32_t EnableTemporal;         /* 20: 0 / 1 */
-    uint32_t TemporalBiasCorrection; /* 24: 0 Off, 1 Basic, 3 Raytraced; 2 (Pairwise) -> PT_ERR_UNSUPPORTED */
+    uint32_t TemporalBiasCorrection; /* 24: 0 Off, 1 Basic, 3 Raytraced; 2 (Pairwise): pt_restir_di_full only, elsewhere PT_ERR_UNSUPPORTED */
     uint32_t MaxHistoryLength;       /* 28: 0 -> 20; a history reservoir's M is capped at this many times the current M */
     uint32_t EnableSpatial;          /* 32: 0 / 1 */
     uint32_t SpatialBiasCorrection;  /* 36: as the temporal field */
@@ -219,6 +220,16 @@ typedef struct PtRestirDiCandidates {
     float    BoilingFilterStrength; /*  8: finite, 0 .. 1; the reference's default is 0.2; read only when the filter is enabled */
     uint32_t _pad;                  /* 12: must be 0 */
 } PtRestirDiCandidates;
+
+/* Row N22 (pt_restir_di_full, DESIGN.md spec S26): final shading's reuse of a sample's visibility (DIFinalShading.hlsl:32-56,
+ * reuseFinalVisibility; the reference leaves the SDK's shading parameters at their defaults, Source/RTXDI.ixx:134 -- on, 4 and 16 as
+ * recollected).  The two limits are literal: 0 does not stand for a default.  All zero = off. */
+typedef struct PtRestirDiShading {
+    uint32_t ReuseFinalVisibility;       /*  0: 0 / 1 */
+    uint32_t FinalVisibilityMaxAge;      /*  4: frames, at most 255; 0 = only a sample drawn by this call */
+    float    FinalVisibilityMaxDistance; /*  8: pixels, finite and >= 0; 0 = only the pixel that drew the sample */
+    uint32_t _pad;                       /* 12: must be 0 */
+} PtRestirDiShading;
 
 /* Row N11 (pt_upscale, the XeSS / DLSS-SR stand-in of DESIGN.md spec S17): XeSSSettings as App::ProcessXeSSSuperResolution fills it
  * (Source/App.cpp:1685-1690; InputSize, Jitter, Reset), the output size XeSS is created with, and the stand-in's history cap. */
@@ -312,6 +323,8 @@ static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingS
               && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
               && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
 static_assert(sizeof(PtRestirDiCandidates) == 16 && offsetof(PtRestirDiCandidates, BoilingFilterStrength) == 8, "PtRestirDiCandidates layout");
+static_assert(sizeof(PtRestirDiShading) == 16 && offsetof(PtRestirDiShading, FinalVisibilityMaxAge) == 4 && offsetof(PtRestirDiShading, FinalVisibilityMaxDistance) == 8
+              && offsetof(PtRestirDiShading, _pad) == 12, "PtRestirDiShading layout");
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
@@ -341,6 +354,8 @@ _Static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSampling
                && offsetof(PtLightSamplingSettings, ReGIRBuildSamples) == 20 && offsetof(PtLightSamplingSettings, ReGIRCellSize) == 24
                && offsetof(PtLightSamplingSettings, _pad) == 28, "PtLightSamplingSettings layout");
 _Static_assert(sizeof(PtRestirDiCandidates) == 16 && offsetof(PtRestirDiCandidates, BoilingFilterStrength) == 8, "PtRestirDiCandidates layout");
+_Static_assert(sizeof(PtRestirDiShading) == 16 && offsetof(PtRestirDiShading, FinalVisibilityMaxAge) == 4 && offsetof(PtRestirDiShading, FinalVisibilityMaxDistance) == 8
+               && offsetof(PtRestirDiShading, _pad) == 12, "PtRestirDiShading layout");
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");

@@ -11,6 +11,11 @@ Per size, the median (and the 10-90 % spread) of --frames one-call-at-a-time mea
   * row N17 (pt_restir_di_ex): in each local-light sampling mode (the library's default sizes), the pass with {1 BRDF candidate}, {the
     boiling filter at 0.2}, {both}, and the same call with the extras off, per launch and per call as above (keys restir_ex_<mode>_<config>_...;
     the presampling launches are under ms_tail and not in these figures);
+  * row N22 (pt_restir_di_full; keys restir_full_<camera>_<config>_...): on the resting camera and on a travelling one (0.02 units per
+    frame along x with the jitter sequence running; its G-buffer is rendered before each call, outside the timing), per launch and
+    per call as above: final-visibility reuse off, at (MaxAge 0, MaxDistance 0) and at (4, 16) -- launch 2 with and without the final
+    rays, launch 1 without and with the visibility word -- and Basic, Pairwise and Raytraced bias correction in both reuse passes;
+    plus the share of the frame's pixels the pass wrote under each reuse setting;
 Also the share of pixels that have a surface for the pass (finite depth, roughness >= 0.05) and the bytes the two launches must move
 (launch 1: 20 B read per pixel (depth, NormalRoughness), without a surface 16 B written, with one 56 B more read, 100 B of record and
 reservoir written and 100 B of history read; launch 2: 16 B read per pixel, with a surface 84 B more and 100 B for a neighbour, 32 B
@@ -100,6 +105,40 @@ def main():
                     summary(res, f"restir_ex_{mode}_{config}_{size}_launch1", l1)
                     summary(res, f"restir_ex_{mode}_{config}_{size}_launch2", l2)
                     summary(res, f"restir_ex_{mode}_{config}_{size}_wall", wall)
+            # row N22: final-visibility reuse and pairwise MIS, on a resting and on a travelling camera
+            reuse = (("reuse_off", dict(shading={})), ("reuse_0_0", dict(shading=dict(reuse=True, max_age=0, max_distance=0.0))),
+                     ("reuse_4_16", dict(shading=dict(reuse=True, max_age=4, max_distance=16.0))))
+            bias = tuple((name, dict(shading={}, temporal_bias=mode, spatial_bias=mode)) for name, mode in
+                         (("basic", t.RESTIR_BIAS_BASIC), ("pairwise", t.RESTIR_BIAS_PAIRWISE), ("raytraced", t.RESTIR_BIAS_RAYTRACED)))
+            for camera in ("resting", "travelling"):
+                for config, kw in reuse + bias:
+                    l1, l2, wall, prev = [], [], [], None
+                    for k in range(args.warmup + args.frames):
+                        if camera == "travelling":
+                            prev = host.camera_matrices(w, h, position=(0.02 * k, 0.0, -15.0), jitter_index=k, previous=prev)
+                            r.set_camera(prev)
+                            r.render_gbuffer_device(gptrs)
+                            r.synchronize()
+                        if config.startswith("reuse") and k == args.warmup + args.frames - 1:
+                            dd.zero_(); ds.zero_()
+                            torch.cuda.synchronize(dev)
+                        r.profile(reset=True)
+                        t0 = time.perf_counter()
+                        r.restir_di_device(w, h, bufs, frame_index=k, reset_history=k == 0, **kw)
+                        r.synchronize()
+                        t1 = time.perf_counter()
+                        p = r.profile(reset=True)
+                        if k >= args.warmup:
+                            l1.append(p.ms_traverse); l2.append(p.ms_shade); wall.append((t1 - t0) * 1e3)
+                    summary(res, f"restir_full_{camera}_{config}_{size}_launch1", l1)
+                    summary(res, f"restir_full_{camera}_{config}_{size}_launch2", l2)
+                    summary(res, f"restir_full_{camera}_{config}_{size}_wall", wall)
+                    if config.startswith("reuse"):
+                        res[f"restir_full_{camera}_{config}_{size}_written_share"] = round(float((dd[..., :3].sum(-1) + ds[..., :3].sum(-1) > 0).float().mean()), 6)
+            r.set_camera(host.camera_matrices(w, h, jitter=False))
+            r.render_gbuffer_device(gptrs)
+            r.restir_di_device(w, h, bufs, frame_index=0, reset_history=True)
+            r.synchronize()
             r.set_profiling(False)
             res[f"lit_share_{size}"] = round(float((dd[..., :3].sum(-1) + ds[..., :3].sum(-1) > 0).float().mean()), 4)
             # the chain against pt_render with and without row N4's DI

@@ -12,7 +12,7 @@ pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --heig
 reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] [--bias-correction pairwise] [--reuse-visibility [4 16]] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
                                         [--ray-reconstruction [performance]]"""
 import argparse
 import os
@@ -83,6 +83,12 @@ def main():
                     help="with --restir-di: N BSDF-sampled candidates mixed into initial sampling (row N17, pt_restir_di_ex; 0 .. 8, the reference's default is 1)")
     ap.add_argument("--boiling-filter", type=float, default=None, metavar="STRENGTH",
                     help="with --restir-di: the boiling filter over the temporal result at this strength in [0, 1] (row N17; the reference's default is 0.2)")
+    ap.add_argument("--bias-correction", default=None, choices=["off", "basic", "pairwise", "raytraced"],
+                    help="with --restir-di: the bias correction of both reuse passes (the library's default is basic); pairwise runs through "
+                         "pt_restir_di_full (row N22)")
+    ap.add_argument("--reuse-visibility", nargs="*", type=float, default=None, metavar="AGE DIST",
+                    help="with --restir-di: final shading reuses a sample's visibility (row N22, pt_restir_di_full) where the sample is at most "
+                         "AGE frames old and DIST pixels from where it was drawn; without values 4 16, the RTXDI SDK's defaults as recollected")
     ap.add_argument("--upscale", default=None, metavar="MODE", choices=list(dxrs_amd.types.UPSCALE_MODES),
                     help="--frames frames of a resting camera rendered at the mode's input size (pt_upscale_input_size) with Halton jitter (row "
                          "N11): pt_render_gbuffer (LinearDepth, MotionVector) -> pt_render -> pt_upscale to --width x --height [-> pt_bloom with "
@@ -124,11 +130,25 @@ def main():
         ap.error("--light-sampling applies to --restir-di")
     if (args.brdf_samples or args.boiling_filter is not None) and not args.restir_di:
         ap.error("--brdf-samples and --boiling-filter apply to --restir-di")
+    if (args.bias_correction or args.reuse_visibility is not None) and not args.restir_di:
+        ap.error("--bias-correction and --reuse-visibility apply to --restir-di")
+    if args.reuse_visibility is not None and len(args.reuse_visibility) not in (0, 2):
+        ap.error("--reuse-visibility takes no value or AGE DIST")
     if args.nis is not None and not default_frame and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
     from PIL import Image
 
     t = dxrs_amd.types
+    # row N22: the arguments that send the reservoir pass through pt_restir_di_full
+    full = {}
+    if args.bias_correction:
+        mode = dict(off=t.RESTIR_BIAS_OFF, basic=t.RESTIR_BIAS_BASIC, pairwise=t.RESTIR_BIAS_PAIRWISE, raytraced=t.RESTIR_BIAS_RAYTRACED)[args.bias_correction]
+        full.update(temporal_bias=mode, spatial_bias=mode)
+    if args.reuse_visibility is not None:
+        age, dist = args.reuse_visibility or (4, 16)
+        full["shading"] = dict(reuse=True, max_age=int(age), max_distance=float(dist))
+    elif args.bias_correction == "pairwise":
+        full["shading"] = {}
     host = dxrs_amd.load_host()
     spheres, materials, sd = host.scene(dxrs_amd.host.SCENE_DEMO, seed=0)
     if args.time:
@@ -223,7 +243,8 @@ def main():
             ptrs = dict({name: v.data_ptr() for name, v in gbuf.items()}, LinearDepth=b["Depth"].data_ptr(), MotionVector=b["MotionVector"].data_ptr(),
                         NormalRoughness=b["NormalRoughness"].data_ptr())
             r.render_gbuffer_device(dict(ptrs, DiffuseAlbedo=b["DiffuseAlbedo"].data_ptr(), SpecularAlbedo=b["SpecularAlbedo"].data_ptr()))
-            r.restir_di_device(iw, ih, dict(ptrs, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), frame_index=k, reset_history=k == 0, light_sampling=ls, candidates=cd)
+            r.restir_di_device(iw, ih, dict(ptrs, Diffuse=dd.data_ptr(), Specular=ds.data_ptr()), frame_index=k, reset_history=k == 0, light_sampling=ls, candidates=cd,
+                               **full)
             rays = r.render_sharc_ex_device(b["Color"].data_ptr(), dd.data_ptr(), ds.data_ptr(), None, t.DENOISER_DLSS_RR,
                                             dict(SpecularHitDistance=b["SpecularHitDistance"].data_ptr()), want_stats=True, roughness_threshold=0.4, reset_history=k == 0,
                                             anti_firefly=args.sharc_anti_firefly).rays
@@ -334,7 +355,7 @@ def main():
         for k in range(args.frames):
             gs.FrameIndex = k
             r.set_constants(gs)
-            dd, ds, _ = r.restir_di(fill=0.0, reset_history=k == 0, light_sampling=ls, candidates=cd)  # (cleared outputs: a pixel without DI keeps 0)
+            dd, ds, _ = r.restir_di(fill=0.0, reset_history=k == 0, light_sampling=ls, candidates=cd, **full)  # (cleared outputs: a pixel without DI keeps 0)
             r.render_with_di_device(frame.data_ptr(), dd.data_ptr(), ds.data_ptr())
             r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
             r.synchronize()
@@ -342,7 +363,7 @@ def main():
         r.tonemap(accum.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
         r.synchronize()
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
-        entry = "pt_restir_di_ex, " + args.light_sampling if cd else ("pt_restir_di" if ls is None else "pt_restir_di_sampled, " + args.light_sampling)
+        entry = "pt_restir_di_full, " + args.light_sampling if "shading" in full else "pt_restir_di_ex, " + args.light_sampling if cd else ("pt_restir_di" if ls is None else "pt_restir_di_sampled, " + args.light_sampling)
         print(f"ReSTIR DI ({entry}, {args.frames} frames) {w}x{h} -> {args.out}")
         r.close()
         return
