@@ -194,6 +194,30 @@ class PtNisTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NIS_TEXTURES]
 
 
+# Row N23 (pt_physics_*, the PhysX stand-in, spec S27): a body record, the settings, an attractor and a step's report
+PHYSICS_SPRING, PHYSICS_LARGE, PHYSICS_DISABLED = 1, 2, 4
+PHYSICS_INVERSE_SQUARE, PHYSICS_CONSTANT = 0, 1
+PHYSICS_ALL_BODIES = 0xFFFFFFFF
+PHYSICS_MAX_ATTRACTORS, PHYSICS_MAX_LARGE = 4, 64
+PHYSICS_BODY_DTYPE = np.dtype([("InvMass", np.float32), ("Flags", np.uint32), ("SpringY0", np.float32), ("SpringOmega2", np.float32)])
+PHYSICS_ATTRACTOR_DTYPE = np.dtype([("Body", np.uint32), ("Kind", np.uint32), ("Strength", np.float32), ("Target", np.uint32)])
+
+
+class PtPhysicsSettings(C.Structure):
+    _fields_ = [("Iterations", C.c_uint32), ("RebuildInterval", C.c_uint32), ("Restitution", C.c_float), ("Friction", C.c_float), ("Baumgarte", C.c_float),
+                ("Slop", C.c_float), ("BounceThreshold", C.c_float), ("_pad", C.c_uint32)]
+
+
+class PtPhysicsReport(C.Structure):
+    _fields_ = [("Contacts", C.c_uint32), ("Clamped", C.c_uint32), ("Frozen", C.c_uint32), ("Steps", C.c_uint32)]
+
+
+def physics_settings(iterations=4, rebuild_interval=0, restitution=0.6, friction=0.5, baumgarte=0.2, slop=0.005, bounce_threshold=2.0):
+    """PtPhysicsSettings with S27's defaults"""
+    return PtPhysicsSettings(Iterations=iterations, RebuildInterval=rebuild_interval, Restitution=restitution, Friction=friction, Baumgarte=baumgarte, Slop=slop,
+                             BounceThreshold=bounce_threshold)
+
+
 # Row N13 (pt_frame_gen, the DLSS-G stand-in): the sizes, the packing of the tone-mapped colour and the reset flag, and the tagged buffers
 FRAME_GEN_TEXTURES = ("Color", "Depth", "MotionVector", "Output")
 FRAME_GEN_RGBA8, FRAME_GEN_RGB10A2 = 0, 1

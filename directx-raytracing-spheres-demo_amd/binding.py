@@ -11,7 +11,7 @@ from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GB
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
-                        ray_reconstruction_settings)
+                        ray_reconstruction_settings, PHYSICS_ATTRACTOR_DTYPE, PHYSICS_BODY_DTYPE, PtPhysicsReport, PtPhysicsSettings, physics_settings)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -23,6 +23,7 @@ API_SYMBOLS = [
     "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
+    "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
 ]
 
 
@@ -158,6 +159,16 @@ class HipLib:
         lib.pt_get_refl_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
         lib.pt_get_queue_sizes.restype = C.c_int
         lib.pt_get_queue_sizes.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        lib.pt_physics_create.restype = C.c_int
+        lib.pt_physics_create.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(PtPhysicsSettings)]
+        lib.pt_physics_set_attractors.restype = C.c_int
+        lib.pt_physics_set_attractors.argtypes = [vp, vp, u32]
+        lib.pt_physics_step.restype = C.c_int
+        lib.pt_physics_step.argtypes = [vp, C.c_float, u32, C.POINTER(PtPhysicsReport)]
+        lib.pt_physics_download.restype = C.c_int
+        lib.pt_physics_download.argtypes = [vp, vp, vp, vp, vp]
+        lib.pt_physics_destroy.restype = None
+        lib.pt_physics_destroy.argtypes = [vp]
         lib.pt_synchronize.restype = C.c_int
         lib.pt_synchronize.argtypes = [vp]
         lib.pt_comm_unique_id.restype = C.c_int
@@ -315,6 +326,41 @@ class Renderer:
         n = C.c_uint32(0)
         self._check(self._lib.pt_get_queue_sizes(self._ctx, buf.ctypes.data, len(buf), C.byref(n)))
         return [int(x) for x in buf[: n.value]]
+
+    # ---- pt_physics_* (row N23, spec S27): the rigid-sphere state the context owns
+    def physics_create(self, spheres, bodies, lin_vel=None, ang_vel=None, rotations=None, settings=None):
+        """spheres: (n, 4) float32 or the PtSphere dtype; bodies: PHYSICS_BODY_DTYPE; velocities (n, 3), rotations (n, 4) or None (zero,
+        identity); settings: PtPhysicsSettings or None (S27's defaults).  Replaces any earlier state; builds the tree (synchronous)."""
+        spheres = np.ascontiguousarray(spheres)
+        assert spheres.dtype.itemsize * (spheres.shape[-1] if spheres.ndim > 1 else 1) == 16
+        bodies = np.ascontiguousarray(bodies, dtype=PHYSICS_BODY_DTYPE)
+        n = len(spheres)
+        assert len(bodies) == n
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(n, k) for a, k in ((lin_vel, 3), (ang_vel, 3), (rotations, 4))]
+        self._check(self._lib.pt_physics_create(self._ctx, spheres.ctypes.data if n else None, bodies.ctypes.data if n else None,
+                                                *[None if a is None or n == 0 else a.ctypes.data for a in opt], n, C.byref(settings) if settings is not None else None))
+        self._physics_n = n
+
+    def physics_set_attractors(self, attractors):
+        """attractors: PHYSICS_ATTRACTOR_DTYPE records, or (Body, Kind, Strength, Target) tuples; at most 4"""
+        a = np.array([tuple(x) for x in attractors], dtype=PHYSICS_ATTRACTOR_DTYPE)
+        self._check(self._lib.pt_physics_set_attractors(self._ctx, a.ctypes.data if len(a) else None, len(a)))
+
+    def physics_step(self, dt, substeps=1, report=True):
+        """`substeps` steps of dt / substeps on the context's stream -> PtPhysicsReport (waits), or None with report=False (asynchronous)"""
+        r = PtPhysicsReport() if report else None
+        self._check(self._lib.pt_physics_step(self._ctx, dt, substeps, C.byref(r) if report else None))
+        return r
+
+    def physics_download(self, spheres=True, rotations=True, lin_vel=True, ang_vel=True):
+        """-> (spheres (n, 4), rotations (n, 4), lin_vel (n, 3), ang_vel (n, 3)); None for what was not asked for.  Waits for the stream."""
+        n = self._physics_n
+        out = [np.zeros((n, k), np.float32) if want else None for want, k in ((spheres, 4), (rotations, 4), (lin_vel, 3), (ang_vel, 3))]
+        self._check(self._lib.pt_physics_download(self._ctx, *[None if a is None else a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def physics_destroy(self):
+        self._lib.pt_physics_destroy(self._ctx)
 
     def synchronize(self):
         self._check(self._lib.pt_synchronize(self._ctx))

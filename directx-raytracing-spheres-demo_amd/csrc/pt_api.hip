@@ -1256,6 +1256,7 @@ void pt_destroy(PtContext* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
+    pt_physics_destroy(c);
     if (c->comm && rccl().handle) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
     free_textures(c);
     for (auto& L : c->lanes) {

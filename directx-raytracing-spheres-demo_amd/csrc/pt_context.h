@@ -33,6 +33,8 @@ struct Knobs {
         ray_replacement = -1, dyn_blocks_per_cu = -1, debug_counts = -1, sah = -1, sah_max_spheres = -1, beams = -1, wide = -1, descent = -1, roctx = -1, lane_priority = -1, fused_refit = -1, beam_reach = -1, beam_max_slack_pct = -1, beam_max_margin = -1, beam_share_wgs = -1, refl_beams = -1, coop_walk = -1, tile_order = -1, sky_fast = -1, tile_table = -1;
 };
 
+struct PtPhysicsState;
+
 // Per-frame-in-flight state (see PtContext::lanes).
 struct Lane {
     hipStream_t stream = nullptr;  // == PtContext::stream when there is a single lane
@@ -269,6 +271,9 @@ struct PtContext {
     // multi-GPU exchange (pt_comm_init / pt_gather): the RCCL communicator of this rank
     ncclComm_t comm = nullptr;
     uint32_t comm_rank = 0, comm_world = 1;
+
+    // pt_physics_* (row N23): the rigid-sphere state and its tree (pt_api_physics.hip), used on `stream` only; null until pt_physics_create
+    struct PtPhysicsState* physics = nullptr;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool profiling = false;

@@ -171,6 +171,13 @@ struct MySceneDesc : SceneDesc {
 //     -A w sin(-x) (MyScene.ixx:174-178,228) -> y(t) = PositionY + A cos(w t - x), w = 2 pi / Period (PhysX.h:30-34)
 //   * Moon: circular orbit of period 10 s around the Earth in the xz-plane (MyScene.ixx:240-248,270-277)
 //   * Earth / Star gravity on the other bodies is off by default (userData = false), their spin only matters with textures.
+struct MyScene;
+// What MyScene::TickPhysics drives: the reference's PhysX->Tick (MyScene.ixx:395).  dxrs::Physics (Physics.hpp) implements it over pt_physics_*.
+struct PhysicsBackend {
+    virtual ~PhysicsBackend() = default;
+    virtual void Tick(MyScene& scene, float elapsedSeconds) = 0;
+};
+
 struct MyScene : Scene {
     explicit MyScene(unsigned seed = 0, bool textured = false, bool environmentMap = false)
     {
@@ -188,6 +195,26 @@ struct MyScene : Scene {
         if (IsStatic()) return;
         m_time += elapsedSeconds;
         SetTime(m_time);
+    }
+
+    // The reference's G and H keys (Earth's inverse-square pull on every body, not just the Moon; the Star's constant 10 m/s^2 pull:
+    // MyScene.ixx:378-392, the actors' userData)
+    void SetEarthGravity(bool enabled) { m_isEarthGravityEnabled = enabled; }
+    void SetStarGravity(bool enabled) { m_isStarGravityEnabled = enabled; }
+    bool IsEarthGravityEnabled() const { return m_isEarthGravityEnabled; }
+    bool IsStarGravityEnabled() const { return m_isStarGravityEnabled; }
+    void SetPhysics(PhysicsBackend* physics) { m_physics = physics; }
+    const std::vector<RenderObjectDesc>& GetInitialRenderObjects() const { return m_initial; }
+
+    // MyScene::Tick with collisions (row N23): the forces and PhysX->Tick(min(1/60, elapsed)) of MyScene.ixx:351-396 through the attached
+    // backend, which writes the new poses into Desc.RenderObjects and refreshes.  Tick / SetTime remain the collision-free closed form.
+    void TickPhysics(double elapsedSeconds)
+    {
+        if (IsStatic() || !m_physics) return;
+        const double dt = elapsedSeconds < 1.0 / 60 ? elapsedSeconds : 1.0 / 60;
+        if (!(dt > 0)) return;
+        m_physics->Tick(*this, static_cast<float>(dt));
+        m_time += dt;
     }
 
     void SetTime(double time)
@@ -216,6 +243,8 @@ struct MyScene : Scene {
 private:
     std::vector<RenderObjectDesc> m_initial;
     bool m_isPhysXRunning = true;
+    bool m_isEarthGravityEnabled = false, m_isStarGravityEnabled = false;
+    PhysicsBackend* m_physics = nullptr;
     double m_time = 0;
 };
 

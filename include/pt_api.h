@@ -706,6 +706,28 @@ PtStatus pt_comm_init(PtContext *ctx, const void *id, uint32_t rank, uint32_t wo
 PtStatus pt_comm_destroy(PtContext *ctx);
 PtStatus pt_gather(PtContext *ctx, const void *send_device, void *recv_device, uint64_t bytes, uint32_t root);
 
+/* Row N23 -- pt_physics_*: a rigid-sphere dynamics step (a stand-in for PhysX as MyScene::Tick drives it, Source/MyScene.ixx:351-396:
+ * spring, inverse-square and constant pulls, then PhysX->Tick; DESIGN.md spec S27, whose arithmetic is this project's own -- no parity
+ * with PhysX is claimed).  The context owns the state on the device: centre + radius, linear and angular velocity, an orientation
+ * quaternion (x, y, z, w) and a PtPhysicsBody record per body, and a tree of its own over the spheres.  The pass reads and writes nothing
+ * of the scene, the lanes or the frames: the caller downloads and hands the result to pt_update_spheres / pt_update_rotations.
+ *   pt_physics_create   replaces any earlier state (validation first: an error keeps it).  lin_vel, ang_vel (n * 3 floats) and rotations
+ *                       (n * 4) may be NULL (zero, identity); settings NULL = the defaults of S27; n == 0 is valid.  Builds the tree:
+ *                       synchronous.  The first PT_PHYSICS_MAX_LARGE bodies flagged PT_PHYSICS_LARGE do not walk the tree (S27.4).
+ *   pt_physics_set_attractors  up to PT_PHYSICS_MAX_ATTRACTORS; pt_physics_create leaves none.
+ *   pt_physics_step     `substeps` steps of dt / substeps on the context's stream: asynchronous when report is NULL, except that a step
+ *                       which rebuilds the tree (Settings.RebuildInterval) waits for the stream, as the device builder reads the tree's
+ *                       depth back.  dt finite and > 0, substeps in [1, 1024]; an error leaves the state untouched.
+ *   pt_physics_download waits for the stream; any pointer may be NULL.  spheres: the layout pt_update_spheres takes, rotations: the one
+ *                       pt_update_rotations takes; never a NaN (a body whose step is not finite is frozen, S27.7).
+ *   pt_physics_destroy  frees the state; pt_destroy calls it. */
+PtStatus pt_physics_create(PtContext *ctx, const PtSphere *spheres, const PtPhysicsBody *bodies, const float *lin_vel, const float *ang_vel,
+                           const float *rotations, uint32_t n, const PtPhysicsSettings *settings);
+PtStatus pt_physics_set_attractors(PtContext *ctx, const PtPhysicsAttractor *attractors, uint32_t n_attractors);
+PtStatus pt_physics_step(PtContext *ctx, float dt, uint32_t substeps, PtPhysicsReport *report);
+PtStatus pt_physics_download(PtContext *ctx, PtSphere *spheres, float *rotations, float *lin_vel, float *ang_vel);
+void pt_physics_destroy(PtContext *ctx);
+
 PtStatus pt_synchronize(PtContext *ctx);
 
 const char *pt_last_error(PtContext *ctx);

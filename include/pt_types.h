@@ -294,6 +294,46 @@ typedef struct PtSharcSettings {
 
 enum { PT_SHARC_UPDATE = 1, PT_SHARC_RESOLVE = 2, PT_SHARC_QUERY = 4 };
 
+/* Row N23 -- pt_physics_* (a rigid-sphere dynamics stand-in for PhysX, DESIGN.md spec S27). */
+typedef struct PtPhysicsBody {
+    float InvMass;       /*  0: 1 / mass; 0 = immovable (moves with its velocity only, takes no force and no impulse) */
+    uint32_t Flags;      /*  4: PT_PHYSICS_SPRING | PT_PHYSICS_LARGE | PT_PHYSICS_DISABLED */
+    float SpringY0;      /*  8: SPRING: the rest height ... */
+    float SpringOmega2;  /* 12: ... and 4 pi^2 / T^2 */
+} PtPhysicsBody;
+
+enum { PT_PHYSICS_SPRING = 1, PT_PHYSICS_LARGE = 2, PT_PHYSICS_DISABLED = 4 };
+
+typedef struct PtPhysicsSettings {
+    uint32_t Iterations;       /*  0: Jacobi velocity iterations; 0 -> 4; at most 64 */
+    uint32_t RebuildInterval;  /*  4: the tree is rebuilt every so many steps (which waits for the stream); 0 = never (refit only) */
+    float Restitution;         /*  8: e, 0 .. 1 (the reference's material: 0.6) */
+    float Friction;            /* 12: mu >= 0 (0.5) */
+    float Baumgarte;           /* 16: beta, 0 .. 1 (0.2) */
+    float Slop;                /* 20: penetration left uncorrected, >= 0 (0.005) */
+    float BounceThreshold;     /* 24: approach speed above which a contact bounces, >= 0 (2: PhysX's default, 0.2 x its speed scale of 10) */
+    uint32_t _pad;             /* 28: must be 0 */
+} PtPhysicsSettings;
+
+typedef struct PtPhysicsAttractor {
+    uint32_t Body;      /*  0: the body that attracts */
+    uint32_t Kind;      /*  4: PT_PHYSICS_INVERSE_SQUARE (Strength = GM, acceleration GM / d^2) or PT_PHYSICS_CONSTANT (Strength = acceleration) */
+    float Strength;     /*  8: finite */
+    uint32_t Target;    /* 12: PT_PHYSICS_ALL_BODIES (all but Body itself) or the one body attracted */
+} PtPhysicsAttractor;
+
+enum { PT_PHYSICS_INVERSE_SQUARE = 0, PT_PHYSICS_CONSTANT = 1 };
+#define PT_PHYSICS_ALL_BODIES 0xFFFFFFFFu
+#define PT_PHYSICS_MAX_ATTRACTORS 4
+#define PT_PHYSICS_MAX_LARGE 64
+
+typedef struct PtPhysicsReport {
+    uint32_t Contacts;  /*  0: pairs in contact, summed over the call's substeps */
+    uint32_t Clamped;   /*  4: nonzero = some contribution to an accumulator was clamped (sticky over the substeps) */
+    uint32_t Frozen;    /*  8: bodies frozen by a non-finite result in this call */
+    uint32_t Steps;     /* 12: substeps made since pt_physics_create, this call's included */
+} PtPhysicsReport;
+
 /* Pixel rectangle in render-target coordinates. */
 typedef struct PtRect {
     uint32_t x, y, w, h;
@@ -305,6 +345,7 @@ typedef struct PtRect {
 
 #ifdef __cplusplus
 static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
+static_assert(sizeof(PtPhysicsBody) == 16 && sizeof(PtPhysicsSettings) == 32 && sizeof(PtPhysicsAttractor) == 16 && sizeof(PtPhysicsReport) == 16, "pt_physics layouts");
 static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
 static_assert(sizeof(PtCamera) == 608, "PtCamera layout");
 static_assert(sizeof(PtSceneData) == 80, "PtSceneData layout");
@@ -338,6 +379,7 @@ static_assert(sizeof(PtRayReconstructionSettings) == 240 && offsetof(PtRayRecons
               && offsetof(PtRayReconstructionSettings, PreviousWorldToProjection) == 176, "PtRayReconstructionSettings layout");
 #else
 _Static_assert(sizeof(PtSphere) == 16, "PtSphere layout");
+_Static_assert(sizeof(PtPhysicsBody) == 16 && sizeof(PtPhysicsSettings) == 32 && sizeof(PtPhysicsAttractor) == 16 && sizeof(PtPhysicsReport) == 16, "pt_physics layouts");
 _Static_assert(sizeof(PtMaterial) == 64, "PtMaterial layout");
 _Static_assert(sizeof(PtCamera) == 608, "PtCamera layout");
 _Static_assert(sizeof(PtSceneData) == 80, "PtSceneData layout");

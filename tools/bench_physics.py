@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Time pt_physics_step (row N23, the PhysX stand-in, DESIGN.md spec S27) and print one JSON line.
+
+Per scene -- C2 (the demo scene's bodies) and C5 (2^20 procedural spheres and the Star) -- with the Star's constant pull on, after
+--settle steps of 1/60 s so that bodies are in contact:
+  step_ms         one step of 1/60 s: the mean over --calls steps queued without a report, between two device events
+  contacts        the pairs in contact in one step after the timed ones
+  host_step_ms    the same step through the host-compiled header (tests/hostshim/physics_host.cpp), one thread, pairs by sort-and-sweep
+                  (C2 always; C5 with --host-big: minutes)
+  refit_ms        pt_update_spheres + pt_refit_accel of the same spheres alone
+  render_ms       the pt_render frame of the scene (1920x1080, 1 spp, 8 bounces), for scale
+Per kernel: run this under `rocprofv3 --kernel-trace --stats -- python tools/bench_physics.py` (physics_*_kernel, the refit's kernels).
+
+    python tools/bench_physics.py [--calls 100 --settle 120 --big 1048576 --host-big]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402  (events only)
+import dxrs_amd_loader  # noqa: E402,F401
+import dxrs_amd  # noqa: E402
+import __graft_entry__ as graft  # noqa: E402
+
+
+def bodies_for(t, spheres):
+    """density 1, the last sphere (the Star) immovable and LARGE"""
+    b = np.zeros(len(spheres), t.PHYSICS_BODY_DTYPE)
+    b["InvMass"] = (1.0 / (4.0 / 3.0 * np.pi * spheres["r"].astype(np.float64) ** 3)).astype(np.float32)
+    b["InvMass"][-1] = 0
+    b["Flags"][-1] = t.PHYSICS_LARGE
+    return b
+
+
+def host_step_ms(lib, t, spheres, vel, ang, rot, bodies, settings, att, steps):
+    vp = C.c_void_p
+    lib.ph_host_create.restype = vp
+    lib.ph_host_create.argtypes = [vp] * 5 + [C.c_uint32]
+    lib.ph_host_step.argtypes = [vp, C.POINTER(t.PtPhysicsSettings), vp, C.c_uint32, C.c_float, C.c_uint32, vp]
+    lib.ph_host_destroy.argtypes = [vp]
+    h = lib.ph_host_create(spheres.ctypes.data, bodies.ctypes.data, vel.ctypes.data, ang.ctypes.data, rot.ctypes.data, len(spheres))
+    rep = np.zeros(4, np.uint32)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        lib.ph_host_step(h, C.byref(settings), att.ctypes.data, len(att), 1 / 60, 1, rep.ctypes.data)
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    lib.ph_host_destroy(h)
+    return ms, int(rep[0])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--settle", type=int, default=120)
+    ap.add_argument("--big", type=int, default=1 << 20)
+    ap.add_argument("--host-big", action="store_true")
+    args = ap.parse_args()
+    torch.cuda.init()
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    t = dxrs_amd.types
+    host = dxrs_amd.load_host()
+    shim = C.CDLL(graft.build_physics_shim())
+    res = {"metric": "pt_physics_step", "calls": args.calls, "settle_steps": args.settle, "dt": 1 / 60, "scenes": {}}
+    for name, kind, count in (("C2", dxrs_amd.host.SCENE_DEMO, 0), ("C5", dxrs_amd.host.SCENE_PROCEDURAL, args.big)):
+        spheres, materials, sd = host.scene(kind, seed=0, count=count) if count else host.scene(kind, seed=0)
+        n = len(spheres)
+        r = dxrs_amd.Renderer(stream=stream.cuda_stream)
+        r.set_scene(spheres, materials, sd)
+        settings = t.physics_settings()
+        bodies = bodies_for(t, spheres)
+        att = np.array([(n - 1, t.PHYSICS_CONSTANT, 10.0, t.PHYSICS_ALL_BODIES)], t.PHYSICS_ATTRACTOR_DTYPE)
+        r.physics_create(spheres, bodies, settings=settings)
+        r.physics_set_attractors(att)
+        for _ in range(args.settle):
+            r.physics_step(1 / 60, 1, report=False)
+        sph, rot, vel, ang = r.physics_download()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(args.calls):
+            r.physics_step(1 / 60, 1, report=False)
+        b.record(stream)
+        b.synchronize()
+        step_ms = a.elapsed_time(b) / args.calls
+        contacts = r.physics_step(1 / 60, 1).Contacts
+        entry = {"bodies": n, "step_ms": round(step_ms, 4), "contacts": int(contacts)}
+        if name == "C2" or args.host_big:
+            ms, hc = host_step_ms(shim, t, sph, vel, ang, rot, bodies, settings, att, 20 if name == "C2" else 2)
+            entry.update(host_step_ms=round(ms, 3), host_threads=1, host_contacts=hc)
+        moved = spheres.copy()
+        for i, k in enumerate(("cx", "cy", "cz")):
+            moved[k] = sph[:, i]
+        r.update_spheres(moved)
+        r.synchronize()
+        a.record(stream)
+        for _ in range(20):
+            r.update_spheres(moved)
+        b.record(stream)
+        b.synchronize()
+        entry["refit_ms"] = round(a.elapsed_time(b) / 20, 4)
+        W, H = 1920, 1080
+        out = torch.zeros((H * W, 4), dtype=torch.float32, device="cuda")
+        r.set_camera(host.camera(W, H))
+        r.set_constants(t.graphics_settings(W, H, bounces=8, spp=1))
+        for _ in range(5):
+            r.render_device(out.data_ptr())
+        r.synchronize()
+        a.record(stream)
+        for _ in range(20):
+            r.render_device(out.data_ptr())
+        b.record(stream)
+        b.synchronize()
+        entry["render_ms"] = round(a.elapsed_time(b) / 20, 4)
+        res["scenes"][name] = entry
+        r.close()
+        del out
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--frames", type=int, default=16, help="jittered frames accumulated by pt_accumulate")
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--time", type=float, default=0.0, help="simulation time of the closed-form motion")
+    ap.add_argument("--physics", action="store_true", help="row N23: reach --time with pt_physics_step (steps of 1/60 s, collisions included) instead of the closed form")
+    ap.add_argument("--star-gravity", action="store_true", help="--physics: the Star's constant 10 m/s^2 pull on every body (the reference's H key)")
+    ap.add_argument("--earth-gravity", action="store_true", help="--physics: the Earth's inverse-square pull on every body, not just the Moon (the G key)")
     ap.add_argument("--textures", action="store_true", help="textured Alien-Metal / Moon / Earth (procedural stand-ins)")
     ap.add_argument("--env-map", action="store_true", help="lat-long HDR environment light (MyScene.ixx:94-95; procedural stand-in) instead of the sky")
     ap.add_argument("--texture-dir", default=None, help="directory of decoded images (<stem>.ptex, e.g. tests/golden/textures = the reference's Assets/Textures): use them instead of the stand-ins")
@@ -151,7 +154,7 @@ def main():
         full["shading"] = {}
     host = dxrs_amd.load_host()
     spheres, materials, sd = host.scene(dxrs_amd.host.SCENE_DEMO, seed=0)
-    if args.time:
+    if args.time and not args.physics:
         spheres = host.scene_at_time(0, args.time)
     torch.cuda.init()
     stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
@@ -165,6 +168,37 @@ def main():
     r.set_scene(spheres, materials, sd)
     if textured or args.env_map:
         r.set_textures(ts)
+    if args.physics:
+        # the bodies, initial velocities and forces of MyScene.ixx (heroes, the grid of oscillators, Moon, Earth, Star: host/Physics.hpp)
+        nb = len(spheres)
+        moon, earth, star = nb - 3, nb - 2, nb - 1
+        bodies = np.zeros(nb, t.PHYSICS_BODY_DTYPE)
+        bodies["InvMass"] = (1.0 / (4.0 / 3.0 * np.pi * spheres["r"].astype(np.float64) ** 3)).astype(np.float32)
+        bodies["Flags"][spheres["r"] > 4 * np.median(spheres["r"])] = t.PHYSICS_LARGE
+        omega = 2 * np.pi / 3.0
+        bodies["Flags"][4:moon] |= t.PHYSICS_SPRING
+        bodies["SpringY0"], bodies["SpringOmega2"] = 0.5, omega * omega
+        lin, ang = np.zeros((nb, 3), np.float32), np.zeros((nb, 3), np.float32)
+        lin[4:moon, 1] = -0.5 * omega * np.sin(-spheres["cx"][4:moon])
+        gm = 4 * np.pi ** 2 * 4.0 ** 3 / 100.0
+        bodies["InvMass"][earth], bodies["InvMass"][star] = 6.6743e-11 / gm, 0
+        lin[moon, 2], ang[moon, 1], ang[earth, 1] = -np.sqrt(gm / 4.0), -np.sqrt(gm / 4.0) / 4.0, -2 * np.pi / 15.0
+        r.physics_create(spheres, bodies, lin, ang, ts.rotations if textured else None)
+        att = [(earth, t.PHYSICS_INVERSE_SQUARE, gm, t.PHYSICS_ALL_BODIES if args.earth_gravity else moon)]
+        if args.star_gravity:
+            att.append((star, t.PHYSICS_CONSTANT, 10.0, t.PHYSICS_ALL_BODIES))
+        r.physics_set_attractors(att)
+        steps, contacts = int(round(args.time * 60)), 0
+        for _ in range(steps):
+            contacts = r.physics_step(1 / 60, 1).Contacts
+        sph, rot, _, _ = r.physics_download()
+        spheres = spheres.copy()
+        for i, k in enumerate(("cx", "cy", "cz")):
+            spheres[k] = sph[:, i]
+        r.update_spheres(spheres)
+        if textured:
+            r.update_rotations(rot)
+        print(f"physics (pt_physics_step): {steps} steps of 1/60 s, {contacts} contacts in the last")
     w, h, n = args.width, args.height, args.width * args.height
     gs = t.graphics_settings(w, h, bounces=args.bounces, spp=args.spp)
     if args.gbuffer:
