@@ -24,6 +24,7 @@ API_SYMBOLS = [
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
     "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
+    "pt_physics_publish", "pt_render_gbuffer_published",
 ]
 
 
@@ -169,6 +170,10 @@ class HipLib:
         lib.pt_physics_download.argtypes = [vp, vp, vp, vp, vp]
         lib.pt_physics_destroy.restype = None
         lib.pt_physics_destroy.argtypes = [vp]
+        lib.pt_physics_publish.restype = C.c_int
+        lib.pt_physics_publish.argtypes = [vp]
+        lib.pt_render_gbuffer_published.restype = C.c_int
+        lib.pt_render_gbuffer_published.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBuffer)]
         lib.pt_synchronize.restype = C.c_int
         lib.pt_synchronize.argtypes = [vp]
         lib.pt_comm_unique_id.restype = C.c_int
@@ -362,6 +367,12 @@ class Renderer:
     def physics_destroy(self):
         self._lib.pt_physics_destroy(self._ctx)
 
+    def physics_publish(self):
+        """Row N24 (spec S28): the simulation's current pose becomes the pose of every frame from the next render call on -- what
+        physics_download + update_spheres (+ update_rotations with textures) do, on the device: asynchronous on the context's stream,
+        no refit call needed."""
+        self._check(self._lib.pt_physics_publish(self._ctx))
+
     def synchronize(self):
         self._check(self._lib.pt_synchronize(self._ctx))
 
@@ -438,22 +449,30 @@ class Renderer:
         asynchronous on the context's stream"""
         self._check(self._lib.pt_bloom(self._ctx, C.c_void_p(hdr_ptr), C.c_void_p(out_ptr), width, height, strength))
 
-    def render_gbuffer_device(self, buffers, rect=None, previous_spheres=None, previous_rotations=None):
+    def render_gbuffer_device(self, buffers, rect=None, previous_spheres=None, previous_rotations=None, previous=None):
         """G-buffer (row N6) of the frame the next render call renders.  buffers: {channel name: device pointer} (names of
         GBUFFER_CHANNELS; the others are not requested).  Asynchronous, ordered like the frame the next render call renders (with frames
         in flight: rotate over one set of buffers per lane); what is queued on the context's stream later sees the result.  previous_spheres (SPHERE_DTYPE[n]) / previous_rotations (float32[n, 4]): the previous
-        pose the motion vectors are measured from, None = the current one."""
+        pose the motion vectors are measured from, None = the current one.  previous="published": the pose published before the newest
+        one (physics_publish), taken on the device (pt_render_gbuffer_published)."""
+        if previous not in (None, "published"):
+            raise ValueError(f"previous must be None or 'published', not {previous!r}")
+        if previous == "published" and (previous_spheres is not None or previous_rotations is not None):
+            raise ValueError("previous='published' takes no host pose")
         unknown = set(buffers) - {name for name, _ in GBUFFER_CHANNELS}
         if unknown:
             raise ValueError(f"unknown G-buffer channels {sorted(unknown)}")
         gb = PtGBuffer(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
         r = PtRect(*rect) if rect is not None else None
+        if previous == "published":
+            self._check(self._lib.pt_render_gbuffer_published(self._ctx, C.byref(r) if r is not None else None, C.byref(gb)))
+            return
         ps = np.ascontiguousarray(previous_spheres) if previous_spheres is not None else None
         pr = np.ascontiguousarray(previous_rotations, dtype=np.float32) if previous_rotations is not None else None
         self._check(self._lib.pt_render_gbuffer(self._ctx, C.byref(r) if r is not None else None, C.byref(gb),
                                                 ps.ctypes.data if ps is not None else None, pr.ctypes.data if pr is not None else None))
 
-    def render_gbuffer(self, channels="all", rect=None, previous_spheres=None, previous_rotations=None, fill=float("nan"), device=None):
+    def render_gbuffer(self, channels="all", rect=None, previous_spheres=None, previous_rotations=None, fill=float("nan"), device=None, previous=None):
         """render_gbuffer_device into torch buffers filled with `fill` (what a pixel the pass does not write keeps) -> {channel:
         numpy float32 (h, w, width)} for the requested channels ("all" or names).  Synchronous."""
         import torch
@@ -465,7 +484,7 @@ class Renderer:
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         bufs = {name: torch.full((h, w, width[name]), fill, dtype=torch.float32, device=dev) for name in names}
         torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
-        self.render_gbuffer_device({name: b.data_ptr() for name, b in bufs.items()}, rect, previous_spheres, previous_rotations)
+        self.render_gbuffer_device({name: b.data_ptr() for name, b in bufs.items()}, rect, previous_spheres, previous_rotations, previous)
         self.synchronize()
         return {name: b.cpu().numpy() for name, b in bufs.items()}
 

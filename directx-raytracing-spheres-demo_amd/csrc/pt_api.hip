@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "pt_context.h"
+#include "pt_publish.h"
 #include "pt_beam_cache.h"
 #include "pt_restir.h"
 
@@ -561,7 +562,7 @@ PtStatus beam_cache_lookup(PtContext* c, const PixelMap& pm, uint32_t max_job_bl
 // Moving spheres (row N2).  Every lane owns a copy of what moves (spheres, Morton-ordered spheres, node boxes) and a pinned staging
 // buffer.  stage_spheres_on_lane puts new spheres into L's staging buffer and gets them onto the device -- for small scenes by leaving
 // them there for refit_lane's single kernel (upload_pending), else with a copy on the lane's stream; refit_lane recomputes L's boxes.
-static PtStatus stage_spheres_on_lane(PtContext* c, Lane& L, const PtSphere* spheres)
+static PtStatus lane_scene_reserve(PtContext* c, Lane& L)
 {
     const uint32_t n = c->n;
     if (L.scene_n != n) {
@@ -577,6 +578,13 @@ static PtStatus stage_spheres_on_lane(PtContext* c, Lane& L, const PtSphere* sph
         if (!L.ev_upload) PT_HIP(c, hipEventCreateWithFlags(&L.ev_upload, hipEventDisableTiming));
         L.scene_n = n;
     }
+    return PT_OK;
+}
+
+static PtStatus stage_spheres_on_lane(PtContext* c, Lane& L, const PtSphere* spheres)
+{
+    const uint32_t n = c->n;
+    if (const PtStatus st = lane_scene_reserve(c, L); st != PT_OK) return st;
     if (!L.scene_private) {
         // first update on this lane: start from the master tree (topology + boxes), ordered after its build
         PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -639,11 +647,87 @@ static bool lanes_idle_for_next_frame(PtContext* c)
     return idle;
 }
 
-// the lane's copies of what moves: rotations, spheres, and the boxes of spheres updated without pt_refit_accel (the frame refits by itself)
+// A published pose (pt_physics_publish, spec S28) reaches a lane like moved spheres do: the lane that is behind TAKES the newest generation
+// from the context's ring on its own stream -- behind the slot's marker, in front of its reader marker (pt_publish_order.h) -- and refits
+// its own boxes: small scenes in the take's own launch, else with lbvh_gpu_refit.  No host wait but for the one-off allocations.
+// sph, rot, prev: the parts the lane lacks (spheres + tree, rotations, the previous pose for pt_render_gbuffer_published).
+static PtStatus lane_take_published(PtContext* c, Lane& L, bool sph, bool rot, bool prev)
+{
+    const uint32_t n = c->n;
+    auto& P = c->pub;
+    const TakePlan tp = publish_take(P.order, (uint32_t)(&L - c->lanes), sph || rot, prev);
+    const bool own_stream = L.stream != c->stream;
+    if (own_stream && !L.ev_pub_read) PT_HIP(c, hipEventCreateWithFlags(&L.ev_pub_read, hipEventDisableTiming));
+    if (own_stream) PT_HIP(c, hipStreamWaitEvent(L.stream, P.ev_slot[tp.slot], 0));  // (the marker of generation g - 1 is an earlier one on the same stream)
+    const size_t slot_size = 2u * (size_t)P.cap_n;
+    PublishTake t{};
+    t.n = n;
+    t.cur = P.ring + tp.slot * slot_size;
+    if (sph) {
+        if (const PtStatus st = lane_scene_reserve(c, L); st != PT_OK) return st;
+        if (!L.scene_private) {
+            // first private scene on this lane: start from the master tree (topology + boxes); its build precedes the publish on the caller's stream
+            if (c->n_nodes) PT_HIP(c, hipMemcpyAsync(L.d_nodes, c->d_nodes, (size_t)c->n_nodes * sizeof(PtBvhNode), hipMemcpyDeviceToDevice, L.stream));
+            L.scene_private = true;
+        }
+        t.sph = L.d_sph;
+        L.upload_pending = false;  // (spheres staged by an earlier pt_update_spheres and not refitted yet are superseded)
+        L.needs_refit = false;
+        L.sph_gen = c->sph_gen;
+        L.slab_tiny = std::numeric_limits<float>::quiet_NaN();  // the host never sees a published pose: the conservative value (slab_rcp)
+    }
+    if (rot) {
+        if (L.rot_n != n) {
+            PT_HIP(c, hipStreamSynchronize(L.stream));
+            free_dev(L.d_rot);
+            if (L.h_rot_stage) { (void)hipHostFree(L.h_rot_stage); L.h_rot_stage = nullptr; }
+            L.rot_n = 0;
+            PT_HIP(c, hipMalloc(&L.d_rot, (size_t)n * sizeof(float4)));
+            PT_HIP(c, hipHostMalloc(&L.h_rot_stage, (size_t)n * sizeof(float4)));
+            if (!L.ev_rot) PT_HIP(c, hipEventCreateWithFlags(&L.ev_rot, hipEventDisableTiming));
+            L.rot_n = n;
+        }
+        t.rot = L.d_rot;
+        L.rot_gen = c->rot_gen;
+    }
+    if (prev) {
+        if (const PtStatus st = lane_prev_pose_reserve(c, L, n); st != PT_OK) return st;
+        if (tp.prev_slot >= 0) {
+            t.prev = P.ring + (size_t)tp.prev_slot * slot_size;
+            t.prev_pose = L.d_prev_pose;
+            t.prev_rot = c->has_textures ? 1u : 0u;
+        }
+        L.pub_prev_gen = tp.gen;
+        L.pub_prev_valid = tp.prev_slot >= 0;
+    }
+    if (sph && lbvh_gpu_refit_fused_possible(n) && knob_or(c->knobs.fused_refit, 1u) != 0) {
+        PT_HIP(c, launch_lane_take_small(t, reinterpret_cast<PtBvhNode*>(L.d_nodes), L.d_sph_sorted, c->d_sorted_id, L.d_refit_hdr, L.stream));
+        if (own_stream) PT_HIP(c, hipEventRecord(L.ev_pub_read, L.stream));
+        return PT_OK;
+    }
+    if (t.sph || t.rot || t.prev_pose) PT_HIP(c, launch_lane_take(t, L.stream));
+    if (own_stream) PT_HIP(c, hipEventRecord(L.ev_pub_read, L.stream));
+    if (sph) PT_HIP(c, lbvh_gpu_refit(c->gpu_builder, L.d_sph, n, reinterpret_cast<PtBvhNode*>(L.d_nodes), L.d_sph_sorted, c->d_sorted_id, L.d_refit_flags,
+                                      L.d_refit_hdr, c->depth, L.stream));
+    return PT_OK;
+}
+
+// the lane's copies of what moves: rotations, spheres, and the boxes of spheres updated without pt_refit_accel (the frame refits by itself);
+// each quantity from where its newest value is: the caller's arrays (pt_update_*) or the published ring
 PtStatus lane_catch_up(PtContext* c, Lane& L)
 {
-    if (const PtStatus st = sync_lane_rotations(c, L); st != PT_OK) return st;
-    if (const PtStatus st = sync_lane_spheres(c, L); st != PT_OK) return st;
+    const PublishOrder& o = c->pub.order;
+    if (o.sph_live || o.rot_live) {
+        const bool sph = o.sph_live && L.sph_gen != c->sph_gen;
+        const bool rot = o.rot_live && c->has_textures && c->rot_gen != c->rot_master_gen && !(L.rot_gen == c->rot_gen && L.rot_n == c->n);
+        const bool prev = o.sph_live && c->pub.want_prev && L.pub_prev_gen != o.gen;
+        if (sph || rot || prev)
+            if (const PtStatus st = lane_take_published(c, L, sph, rot, prev); st != PT_OK) return st;
+    }
+    if (!o.rot_live)
+        if (const PtStatus st = sync_lane_rotations(c, L); st != PT_OK) return st;
+    if (!o.sph_live)
+        if (const PtStatus st = sync_lane_spheres(c, L); st != PT_OK) return st;
     return L.needs_refit ? refit_lane(c, L) : PT_OK;
 }
 
@@ -1087,6 +1171,22 @@ PtStatus check_tree_lds(PtContext* c)
     return PT_OK;
 }
 
+// room for n previous spheres and n previous rotations on the lane (pt_render_gbuffer's upload, a published take's copy): one set per
+// lane, since a call on another lane may still be reading its own
+PtStatus lane_prev_pose_reserve(PtContext* c, Lane& L, uint32_t n)
+{
+    if (L.prev_cap >= n) return PT_OK;
+    PT_HIP(c, hipStreamSynchronize(L.stream));
+    free_dev(L.d_prev_pose);
+    if (L.h_prev_stage) { (void)hipHostFree(L.h_prev_stage); L.h_prev_stage = nullptr; }
+    L.prev_cap = 0;
+    PT_HIP(c, hipMalloc(&L.d_prev_pose, 2u * (size_t)n * sizeof(float4)));
+    PT_HIP(c, hipHostMalloc(&L.h_prev_stage, 2u * (size_t)n * sizeof(float4)));
+    if (!L.ev_prev) PT_HIP(c, hipEventCreateWithFlags(&L.ev_prev, hipEventDisableTiming));
+    L.prev_cap = n;
+    return PT_OK;
+}
+
 // a side pass starts: the idle test made for the frame it belongs to (render_common must not mistake the pass for a frame in flight;
 // a second pass for the same frame finds its own lane busy with the first one), then the lane brought up to date and ordered
 PtStatus side_pass_begin(PtContext* c, Lane& L, bool shared)
@@ -1218,6 +1318,7 @@ PtStatus pt_create(const PtConfig* config, PtContext** out_ctx)
         ) { pt_destroy(c); return PT_ERR_HIP; }
     for (uint32_t i = 0; i < kMaxLanes; i++) c->ledgers[i] = &c->lanes[i].ledger;
     c->n_lanes = config->frames_in_flight > 1 ? std::min(config->frames_in_flight, kMaxLanes) : ((config->flags & PT_FLAG_TWO_FRAMES_IN_FLIGHT) ? 2u : 1u);
+    c->pub.order.n_lanes = c->n_lanes;
     for (uint32_t i = 0; i < c->n_lanes; i++)
         if (hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming) != hipSuccess) { pt_destroy(c); return PT_ERR_HIP; }
     for (uint32_t i = 0; i < c->n_lanes; i++) {
@@ -1269,6 +1370,7 @@ void pt_destroy(PtContext* c)
         if (L.h_prev_stage) (void)hipHostFree(L.h_prev_stage);
         if (L.ev_prev) (void)hipEventDestroy(L.ev_prev);
         if (L.ev_gb_in) (void)hipEventDestroy(L.ev_gb_in);
+        if (L.ev_pub_read) (void)hipEventDestroy(L.ev_pub_read);
         if (L.ev_upload) (void)hipEventDestroy(L.ev_upload);
         for (auto& e : L.ev_poll) if (e) (void)hipEventDestroy(e);
         free_dev(L.d_counts); free_dev(L.d_totals); free_dev(L.d_seg_counts);
@@ -1285,6 +1387,8 @@ void pt_destroy(PtContext* c)
     }
     if (c->beam.ev_last_use) (void)hipEventDestroy(c->beam.ev_last_use);
     if (c->beam.stream) (void)hipStreamDestroy(c->beam.stream);
+    free_dev(c->pub.ring);
+    for (auto& e : c->pub.ev_slot) if (e) (void)hipEventDestroy(e);
     free_dev(c->d_out);
     free_dev(c->d_bloom);
     for (History* H : { &c->dn, &c->up, &c->fg, &c->rr }) free_dev(H->mem);
@@ -1396,6 +1500,9 @@ PtStatus pt_set_scene(PtContext* c, const PtSphere* spheres, const PtMaterial* m
     for (auto& L : c->lanes) { L.scene_private = false; L.upload_pending = false; L.needs_refit = false; L.sph_gen = 0; }  // every lane renders the new master scene (with the master slab_tiny: make_scene_view)
     c->sph_gen = 0;
     c->latest_lane = -1;
+    // ... and nothing published (pt_physics_publish): no read of the ring is outstanding after sync_all
+    publish_forget(c->pub.order);
+    for (uint32_t i = 0; i < kMaxLanes; i++) { publish_reader_done(c->pub.order, i); c->lanes[i].pub_prev_gen = 0; }
     return PT_OK;
 }
 
@@ -1521,6 +1628,7 @@ PtStatus pt_update_spheres(PtContext* c, const PtSphere* spheres, uint32_t n)
     L.slab_tiny = slab_tiny_for(smax);
     L.sph_gen = ++c->sph_gen;
     c->latest_lane = (int)c->next_lane;
+    publish_host_spheres(c->pub.order);  // (newer than anything published)
     return PT_OK;
 }
 
@@ -1529,6 +1637,11 @@ PtStatus pt_refit_accel(PtContext* c)
     if (!c) return PT_ERR_INVALID_ARG;
     if (c->empty_scene && c->accel_valid) return PT_OK;  // no boxes
     Lane& L = c->lanes[c->next_lane];
+    if (c->accel_valid && c->pub.order.sph_live) {
+        // the newest spheres are a published pose (pt_physics_publish): the lane takes it and refits, as its next frame would
+        PT_HIP(c, hipSetDevice(c->device));
+        return lane_catch_up(c, L);
+    }
     if (!c->accel_valid || !L.scene_private) return fail(c, PT_ERR_STATE, "pt_refit_accel: call pt_update_spheres first");
     const RoctxRange range(c, "pt_refit_accel");
     PT_HIP(c, hipSetDevice(c->device));
@@ -1810,6 +1923,7 @@ PtStatus pt_update_rotations(PtContext* c, const float* rotations, uint32_t n)
     for (uint32_t i = 0; i < n; i++)
         c->h_rot[i] = rotations ? make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]) : make_float4(0.f, 0.f, 0.f, 1.f);
     c->rot_gen++;
+    publish_host_rotations(c->pub.order);  // (newer than anything published)
     return PT_OK;
 }
 

@@ -1,6 +1,6 @@
 // pt_api_physics.hip -- the C-ABI of row N23 (pt_physics_*, DESIGN.md spec S27): the state the context owns (PtContext::physics), its tree
 // (an LbvhGpu of its own over its own spheres) and the launches of a step on the context's stream.  It reads and writes nothing of the
-// scene, the lanes or the frames.
+// scene, the lanes or the frames -- but for pt_physics_publish (row N24, spec S28), which hands the pose to the frames through the context's ring.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -10,6 +10,7 @@
 #include "pt_device.h"
 #include "pt_trace.h"
 #include "pt_physics.h"
+#include "pt_publish.h"
 
 struct PtPhysicsState {
     PhDevice d{};
@@ -115,6 +116,9 @@ PtStatus pt_physics_create(PtContext* c, const PtSphere* spheres, const PtPhysic
         return fail(c, PT_ERR_INVALID_ARG, "pt_physics_create: a velocity or rotation is not finite");
     PT_HIP(c, hipSetDevice(c->device));
     pt_physics_destroy(c);
+    // a new simulation: its first published pose has no predecessor (pt_render_gbuffer_published: no object motion)
+    publish_restart(c->pub.order);
+    for (auto& L : c->lanes) L.pub_prev_gen = 0;
 
     PtPhysicsState* p = new PtPhysicsState;
     p->s = s;
@@ -254,6 +258,54 @@ PtStatus pt_physics_download(PtContext* c, PtSphere* spheres, float* rotations, 
         PT_HIP(c, hipMemcpy(tmp.data(), p->d.ang, v4, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; i++) { ang_vel[3 * i] = tmp[i].x; ang_vel[3 * i + 1] = tmp[i].y; ang_vel[3 * i + 2] = tmp[i].z; }
     }
+    return PT_OK;
+}
+
+// Row N24 (DESIGN.md spec S28): the simulation's current pose becomes the pose of every frame from the next render call on -- what
+// pt_physics_download + pt_update_spheres (+ pt_update_rotations with textures) would do, without the host: one copy kernel into the
+// next slot of the context's ring, behind the steps queued so far; the lanes take it from there when they next render (lane_catch_up).
+PtStatus pt_physics_publish(PtContext* c)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    PtPhysicsState* p = c->physics;
+    if (!p) return fail(c, PT_ERR_STATE, "pt_physics_publish: pt_physics_create has not been called");
+    if (!c->scene_set || !c->accel_valid) return fail(c, PT_ERR_STATE, "pt_physics_publish: pt_set_scene + pt_build_accel first");
+    const uint32_t n = p->d.n;
+    if (c->empty_scene && n == 0) return PT_OK;  // nothing to move
+    if (c->empty_scene || n != c->n) return fail(c, PT_ERR_INVALID_ARG, "pt_physics_publish: the body count differs from the scene's sphere count");
+    if (!c->gpu_builder) return fail(c, PT_ERR_UNSUPPORTED, "pt_physics_publish needs the device LBVH builder (no PT_FLAG_HOST_LBVH)");
+    PT_HIP(c, hipSetDevice(c->device));
+    auto& P = c->pub;
+    const uint32_t ring = publish_ring_size(c->n_lanes);
+    if (P.cap_n != n) {
+        // one-off: the ring for this body count, with nothing in flight (a ring of another count holds nothing a frame could still want:
+        // the count changes with pt_set_scene only, which forgets what was published)
+        for (uint32_t i = 0; i < c->n_lanes; i++) PT_HIP(c, hipStreamSynchronize(c->lanes[i].stream));
+        PT_HIP(c, hipStreamSynchronize(c->stream));
+        free_dev(P.ring);
+        P.cap_n = 0;
+        PT_HIP(c, hipMalloc(&P.ring, (size_t)ring * 2u * n * sizeof(float4)));
+        for (uint32_t s = 0; s < ring; s++)
+            if (!P.ev_slot[s]) PT_HIP(c, hipEventCreateWithFlags(&P.ev_slot[s], hipEventDisableTiming));
+        P.cap_n = n;
+        publish_restart(P.order);
+        for (uint32_t s = 0; s < kPubMaxSlots; s++) { P.order.slot_gen[s] = 0; P.order.readers[s] = 0; }
+    }
+    const PublishPlan plan = publish_begin(P.order, c->has_textures);
+    // the slot's outstanding readers: the caller's stream waits for their markers (a stream wait; none is needed where the marker has passed)
+    for (uint32_t i = 0; i < c->n_lanes; i++) {
+        Lane& L = c->lanes[i];
+        if (!(plan.wait_lanes >> i & 1u) || L.stream == c->stream || !L.ev_pub_read) continue;
+        if (hipEventQuery(L.ev_pub_read) == hipSuccess) { publish_reader_done(P.order, i); continue; }
+        (void)hipGetLastError();  // hipErrorNotReady is not an error here
+        PT_HIP(c, hipStreamWaitEvent(c->stream, L.ev_pub_read, 0));
+    }
+    PT_HIP(c, launch_physics_publish(reinterpret_cast<const float4*>(p->d.sph), reinterpret_cast<const float4*>(p->d.rot), n, P.ring + (size_t)plan.slot * 2u * n, c->stream));
+    if (c->n_lanes > 1) PT_HIP(c, hipEventRecord(P.ev_slot[plan.slot], c->stream));
+    // as pt_update_spheres / pt_update_rotations: beam lists are dropped, every lane is behind
+    c->scene_gen++;
+    ++c->sph_gen;
+    if (c->has_textures) ++c->rot_gen;
     return PT_OK;
 }
 

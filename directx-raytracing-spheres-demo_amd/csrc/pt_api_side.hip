@@ -10,10 +10,10 @@
 #include "pt_lightris.h"
 #include "pt_sharc.h"
 
-extern "C" {
-
-// Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12)
-PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations)
+// Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12).
+// published (pt_render_gbuffer_published, spec S28): the previous pose is the generation published before the newest one, copied on the
+// device by the lane's take (lane_catch_up); the two pointers are null.
+static PtStatus gbuffer_pass(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations, bool published)
 {
     if (!c) return PT_ERR_INVALID_ARG;
     if (!gb) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: null PtGBuffer");
@@ -45,11 +45,16 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
     }
     for (uint32_t i = 0; use_prev_rot && i < 4u * n; i++)
         if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous rotation " + std::to_string(i / 4) + " is not finite");
+    if (published && n > 0 && !c->pub.order.sph_live)
+        return fail(c, PT_ERR_STATE, "pt_render_gbuffer_published: the scene's newest spheres are not a published pose (pt_physics_publish first)");
     PT_HIP(c, hipSetDevice(c->device));
 
     Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
     // (shared: a buffer is one that another lane's G-buffer call or frame holds within the window, or no frame has been rendered yet)
-    if ((st = side_pass_begin(c, L, ledger_gbuffer({ c->ledgers, c->n_lanes, c->next_lane }, c->calls == 0, ptrs))) != PT_OK) return st;
+    c->pub.want_prev = published && !c->sd.IsStatic && n > 0;
+    st = side_pass_begin(c, L, ledger_gbuffer({ c->ledgers, c->n_lanes, c->next_lane }, c->calls == 0, ptrs));
+    c->pub.want_prev = false;
+    if (st != PT_OK) return st;
     const SceneView sv = make_scene_view(c, &L);
     GBufferScene sc{};
     sc.sph = sv.sph; sc.mats = sv.mats; sc.tex = sv.tex; sc.tex_maps = sv.tex_maps; sc.rot = sv.rot;
@@ -57,20 +62,16 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
     sc.env_tex = sv.env_tex; sc.env_cube = sv.env_cube;
     for (int k = 0; k < 4; k++) sc.env[k] = sv.env[k];
     for (int k = 0; k < 9; k++) sc.env_xf[k] = sv.env_xf[k];
-    if (use_prev_sph || use_prev_rot) {
-        // one set per lane: a call on another lane may still be reading its own
-        if (L.prev_cap < n) {
-            PT_HIP(c, hipStreamSynchronize(L.stream));
-            free_dev(L.d_prev_pose);
-            if (L.h_prev_stage) { (void)hipHostFree(L.h_prev_stage); L.h_prev_stage = nullptr; }
-            L.prev_cap = 0;
-            PT_HIP(c, hipMalloc(&L.d_prev_pose, 2u * (size_t)n * sizeof(float4)));
-            PT_HIP(c, hipHostMalloc(&L.h_prev_stage, 2u * (size_t)n * sizeof(float4)));
-            if (!L.ev_prev) PT_HIP(c, hipEventCreateWithFlags(&L.ev_prev, hipEventDisableTiming));
-            L.prev_cap = n;
-        } else {
-            PT_HIP(c, hipEventSynchronize(L.ev_prev));  // the previous upload from the staging buffer has been consumed
-        }
+    if (published) {
+        // (the lane's take has put generation g - 1 into d_prev_pose; a first generation has no predecessor: previous = current)
+        const bool have = !c->sd.IsStatic && n > 0 && L.pub_prev_gen == c->pub.order.gen && L.pub_prev_valid;
+        sc.prev_sph = have ? L.d_prev_pose : nullptr;
+        sc.prev_rot = have && c->has_textures ? L.d_prev_pose + n : nullptr;
+    } else if (use_prev_sph || use_prev_rot) {
+        const bool fresh = L.prev_cap < n;
+        if ((st = lane_prev_pose_reserve(c, L, n)) != PT_OK) return st;
+        if (!fresh) PT_HIP(c, hipEventSynchronize(L.ev_prev));  // the previous upload from the staging buffer has been consumed
+        L.pub_prev_gen = 0;  // (d_prev_pose no longer holds a published generation's predecessor)
         if (use_prev_sph) std::memcpy(L.h_prev_stage, previous_spheres, (size_t)n * sizeof(float4));
         if (use_prev_rot) std::memcpy(L.h_prev_stage + n, previous_rotations, (size_t)n * sizeof(float4));
         PT_HIP(c, hipMemcpyAsync(L.d_prev_pose, L.h_prev_stage, 2u * (size_t)n * sizeof(float4), hipMemcpyHostToDevice, L.stream));
@@ -93,6 +94,19 @@ PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb
     if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
         st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: launch: ") + hipGetErrorString(e));
     return publish_lane_to_caller(c, L, "pt_render_gbuffer", st);
+}
+
+extern "C" {
+
+PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations)
+{
+    return gbuffer_pass(c, rect, gb, previous_spheres, previous_rotations, false);
+}
+
+// Row N24 -- pt_render_gbuffer with the previous pose taken from the published ring (DESIGN.md spec S28)
+PtStatus pt_render_gbuffer_published(PtContext* c, const PtRect* rect, const PtGBuffer* gb)
+{
+    return gbuffer_pass(c, rect, gb, nullptr, nullptr, true);
 }
 
 // Row N10 -- the reservoir pass (DESIGN.md spec S16): two launches on the lane of the next render call, ordered like pt_render_gbuffer;

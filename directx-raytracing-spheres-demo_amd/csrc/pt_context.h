@@ -17,6 +17,7 @@
 #include "pt_lane_order.h"
 #include "pt_lbvh.h"
 #include "pt_lbvh_gpu.h"
+#include "pt_publish_order.h"
 
 using namespace pt;  // (an internal header: the units it serves are written in pt's names throughout)
 
@@ -90,6 +91,11 @@ struct Lane {
     hipEvent_t ev_prev = nullptr;     // the last upload from h_prev_stage has been consumed
     uint32_t prev_cap = 0;            // spheres the two buffers hold room for
     hipEvent_t ev_gb_in = nullptr;
+    // pt_physics_publish (row N24): the lane's reader marker (pt_publish_order.h), and the generation whose previous pose d_prev_pose holds
+    // (0 = none) with whether that generation had one (else previous = current)
+    hipEvent_t ev_pub_read = nullptr;
+    uint64_t pub_prev_gen = 0;
+    bool pub_prev_valid = false;
 };
 constexpr uint32_t kMaxLanes = 8;
 
@@ -274,6 +280,16 @@ struct PtContext {
 
     // pt_physics_* (row N23): the rigid-sphere state and its tree (pt_api_physics.hip), used on `stream` only; null until pt_physics_create
     struct PtPhysicsState* physics = nullptr;
+    // pt_physics_publish (row N24, spec S28): the ring of published poses -- publish_ring_size(n_lanes) slots of 2 * cap_n float4 (spheres,
+    // then rotations) -- with a marker per slot on `stream`, and the bookkeeping of pt_publish_order.h.  want_prev: the take that the
+    // call being made starts copies the previous pose too (pt_render_gbuffer_published).
+    struct Published {
+        PublishOrder order;
+        float4* ring = nullptr;
+        uint32_t cap_n = 0;
+        hipEvent_t ev_slot[kPubMaxSlots] = {};
+        bool want_prev = false;
+    } pub;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool profiling = false;
@@ -318,6 +334,7 @@ PtStatus denoise_out(PtContext* c, const PtDenoiserOutputs* outputs, const char*
 SceneView make_scene_view(const PtContext* c, const Lane* L = nullptr);
 uint32_t side_pass_grid(const PtContext* c, uint32_t n_slots);
 PtStatus side_pass_begin(PtContext* c, Lane& L, bool shared);
+PtStatus lane_prev_pose_reserve(PtContext* c, Lane& L, uint32_t n);
 PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus st);
 EventPair* next_events(PtContext* c, int kind);
 PtStatus staged_out_begin(PtContext* c, void* out, bool staged, size_t out_px, float4*& dev_out), staged_out_finish(PtContext* c, void* out, bool staged, size_t out_px);

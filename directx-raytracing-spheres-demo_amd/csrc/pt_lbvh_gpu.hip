@@ -4,6 +4,7 @@
 // Replaces Scene::CreateAccelerationStructures (Source/Scene.ixx:225-284), which the reference re-runs every frame while
 // the physics is live (Source/App.cpp:605-608).
 #include "pt_lbvh_gpu.h"
+#include "pt_refit_device.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -13,24 +14,6 @@
 namespace pt {
 
 namespace {
-
-// order-preserving float <-> uint mapping for atomicMin / atomicMax
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ __forceinline__ float ord2f(uint32_t o)
-{
-    const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __uint_as_float(u);
-#else
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    return f;
-#endif
-}
 
 // header[0..2] centroid min, [3..5] centroid max, [6..8] bounds min, [9..11] bounds max (ordered uints), [12] depth
 constexpr int kHdrWords = 16;
@@ -176,46 +159,6 @@ __global__ void hierarchy_kernel(const unsigned long long* __restrict__ keys, in
 //   so a racing same-pass write is never consumed.  Passes needed = tree depth.
 // This replaces one-thread-per-leaf climbing with atomic arrival counters: the agent-scope release / acquire fences that
 // scheme needs write back and invalidate the per-XCD L2 on this GPU -- 7.2 ms at 2^20 spheres, 35 us at 441.
-__device__ __forceinline__ void leaf_box(const float4 s, float pad, float lo[3], float hi[3])
-{
-    lo[0] = s.x - s.w - pad; lo[1] = s.y - s.w - pad; lo[2] = s.z - s.w - pad;
-    hi[0] = s.x + s.w + pad; hi[1] = s.y + s.w + pad; hi[2] = s.z + s.w + pad;
-}
-
-__device__ __forceinline__ void child_box(const float4* __restrict__ sorted, const PtBvhNode* nodes, int c, float pad, float lo[3], float hi[3])
-{
-    if (c < 0) {
-        leaf_box(sorted[~c], pad, lo, hi);
-    } else {
-        const PtBvhNode* nd = &nodes[c];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { lo[a] = fminf(nd->lo0[a], nd->lo1[a]); hi[a] = fmaxf(nd->hi0[a], nd->hi1[a]); }
-    }
-}
-
-__device__ __forceinline__ float refit_padding(const uint32_t* __restrict__ hdr_ro)
-{
-    // padding = 2^-17 * max |coordinate| of the scene bounds (lbvh_padding in pt_lbvh.cpp)
-    float smax = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) smax = fmaxf(smax, fmaxf(fabsf(ord2f(hdr_ro[6 + a])), fabsf(ord2f(hdr_ro[9 + a]))));
-    return smax * 7.62939453125e-06f;
-}
-
-__device__ __forceinline__ void write_node_boxes(const float4* __restrict__ sorted, PtBvhNode* nodes, int i, int c0, int c1, float pad)
-{
-    float lo[3], hi[3];
-    PtBvhNode* nd = &nodes[i];
-    child_box(sorted, nodes, c0, pad, lo, hi);
-#pragma unroll
-    for (int a = 0; a < 3; a++) { nd->lo0[a] = lo[a]; nd->hi0[a] = hi[a]; }
-    child_box(sorted, nodes, c1, pad, lo, hi);
-#pragma unroll
-    for (int a = 0; a < 3; a++) { nd->lo1[a] = lo[a]; nd->hi1[a] = hi[a]; }
-}
-
-constexpr int kRefitSmall = 1024;  // up to this many spheres one workgroup does every pass (barriers instead of launches)
-
 __global__ __launch_bounds__(kRefitSmall) void refit_small_kernel(const float4* __restrict__ sorted, int n, PtBvhNode* nodes,
                                                                   uint32_t* __restrict__ hdr)
 {

@@ -63,6 +63,14 @@ struct GBufferGeneration {
         const PtGBuffer o = Outputs();
         return pt_render_gbuffer(context, nullptr, &o, previousSpheres, previousRotations);
     }
+
+    // Render with PreviousObjectToWorld taken from the device: the pose published before the newest one (Physics in publishing mode;
+    // pt_render_gbuffer_published, row N24)
+    PtStatus RenderPublished(PtContext* context) const
+    {
+        const PtGBuffer o = Outputs();
+        return pt_render_gbuffer_published(context, nullptr, &o);
+    }
 };
 
 }  // namespace dxrs

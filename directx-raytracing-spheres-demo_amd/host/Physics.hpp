@@ -3,7 +3,9 @@
 // N23, DESIGN.md spec S27), a stand-in for the PhysX SDK, which the reference does not vendor.  No parity with PhysX is claimed.
 // The stand-in runs in render space (the layouts of pt_update_spheres / pt_update_rotations: PhysX z negated, Scene::Refresh), so polar
 // vectors have z negated and axial vectors x and y.  Tick downloads the poses into the scene; the caller hands them to the renderer
-// (Raytracing::UpdateSpheres / UpdateRotations) -- there is no device-to-device hand-over.
+// (pt_update_spheres / Raytracing::UpdateRotations).  In publishing mode (SetPublishing, row N24, spec S28) Tick hands them to the frames
+// on the device instead (pt_physics_publish): no download and no wait inside the frame loop; Download(scene) brings the poses into the
+// scene for callers that want them on the host.
 #pragma once
 
 #include <algorithm>
@@ -76,11 +78,27 @@ public:
     Physics(const Physics&) = delete;
     Physics& operator=(const Physics&) = delete;
 
-    // PhysX->Tick after the forces of MyScene::Tick: one step, then the poses back into the scene
+    // publishing: Tick publishes the poses on the device (the context needs the scene the physics was made from) and leaves the scene's
+    // host copy and GetReport() as they are
+    void SetPublishing(bool publishing) { m_publishing = publishing; }
+    bool IsPublishing() const { return m_publishing; }
+
+    // PhysX->Tick after the forces of MyScene::Tick: one step, then the poses back into the scene -- or, publishing, on to the frames
     void Tick(MyScene& scene, float elapsedSeconds) override
     {
         SetAttractors(scene);
+        if (m_publishing) {
+            ThrowIfFailed(pt_physics_step(m_ctx, elapsedSeconds, 1, nullptr), m_ctx, "pt_physics_step");
+            ThrowIfFailed(pt_physics_publish(m_ctx), m_ctx, "pt_physics_publish");
+            return;
+        }
         ThrowIfFailed(pt_physics_step(m_ctx, elapsedSeconds, 1, &m_report), m_ctx, "pt_physics_step");
+        Download(scene);
+    }
+
+    // the simulation's current poses into the scene (waits for the context's stream)
+    void Download(MyScene& scene)
+    {
         auto& objects = scene.Desc.RenderObjects;
         m_spheres.resize(objects.size());
         m_rotations.resize(4 * objects.size());
@@ -118,7 +136,7 @@ private:
     PtContext* m_ctx;
     int m_moon = -1, m_earth = -1, m_star = -1;
     float m_earthGM = 0.0f;
-    bool m_attractorsSet = false;
+    bool m_attractorsSet = false, m_publishing = false;
     std::vector<PtPhysicsBody> m_bodies;
     std::vector<float> m_linearVelocities, m_angularVelocities, m_rotations;
     std::vector<PtSphere> m_spheres;

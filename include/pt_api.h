@@ -709,8 +709,9 @@ PtStatus pt_gather(PtContext *ctx, const void *send_device, void *recv_device, u
 /* Row N23 -- pt_physics_*: a rigid-sphere dynamics step (a stand-in for PhysX as MyScene::Tick drives it, Source/MyScene.ixx:351-396:
  * spring, inverse-square and constant pulls, then PhysX->Tick; DESIGN.md spec S27, whose arithmetic is this project's own -- no parity
  * with PhysX is claimed).  The context owns the state on the device: centre + radius, linear and angular velocity, an orientation
- * quaternion (x, y, z, w) and a PtPhysicsBody record per body, and a tree of its own over the spheres.  The pass reads and writes nothing
- * of the scene, the lanes or the frames: the caller downloads and hands the result to pt_update_spheres / pt_update_rotations.
+ * quaternion (x, y, z, w) and a PtPhysicsBody record per body, and a tree of its own over the spheres.  A step reads and writes nothing
+ * of the scene, the lanes or the frames: the pose reaches the frames on the device through pt_physics_publish (row N24, below), or through
+ * the host: pt_physics_download, then pt_update_spheres / pt_update_rotations.
  *   pt_physics_create   replaces any earlier state (validation first: an error keeps it).  lin_vel, ang_vel (n * 3 floats) and rotations
  *                       (n * 4) may be NULL (zero, identity); settings NULL = the defaults of S27; n == 0 is valid.  Builds the tree:
  *                       synchronous.  The first PT_PHYSICS_MAX_LARGE bodies flagged PT_PHYSICS_LARGE do not walk the tree (S27.4).
@@ -727,6 +728,22 @@ PtStatus pt_physics_set_attractors(PtContext *ctx, const PtPhysicsAttractor *att
 PtStatus pt_physics_step(PtContext *ctx, float dt, uint32_t substeps, PtPhysicsReport *report);
 PtStatus pt_physics_download(PtContext *ctx, PtSphere *spheres, float *rotations, float *lin_vel, float *ang_vel);
 void pt_physics_destroy(PtContext *ctx);
+
+/* Row N24 -- the simulated pose handed to the frames on the device (DESIGN.md spec S28).
+ *   pt_physics_publish  makes the simulation's current pose the pose of every frame from the next render call on: the effect of
+ *                       pt_physics_download + pt_update_spheres (+ pt_update_rotations where the context has textures), as one copy
+ *                       kernel on the context's stream behind the steps queued so far -- no copy to the host and no host wait (but for
+ *                       one-off allocations on first use).  The lanes take the pose on their own streams when they next render or run a
+ *                       side pass and refit their trees there; pt_refit_accel is not needed.  May be mixed with pt_update_spheres /
+ *                       pt_update_rotations: the newest call wins, per quantity; pt_set_scene forgets what was published.  Images are
+ *                       those of the download path bit for bit.  PT_ERR_STATE without pt_physics_create or without scene + accel,
+ *                       PT_ERR_INVALID_ARG when the body count is not the scene's sphere count, PT_ERR_UNSUPPORTED with
+ *                       PT_FLAG_HOST_LBVH; an empty scene with 0 bodies: PT_OK, nothing done.  An error leaves everything untouched.
+ *   pt_render_gbuffer_published  pt_render_gbuffer with the previous pose taken from the device: the pose published before the newest one
+ *                       (rotations where the context has textures); after the first publish since pt_physics_create / pt_set_scene the
+ *                       current one (no object motion).  PT_ERR_STATE when the scene's newest spheres are not a published pose. */
+PtStatus pt_physics_publish(PtContext *ctx);
+PtStatus pt_render_gbuffer_published(PtContext *ctx, const PtRect *rect, const PtGBuffer *out);
 
 PtStatus pt_synchronize(PtContext *ctx);
 

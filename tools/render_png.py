@@ -55,6 +55,7 @@ def main():
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--time", type=float, default=0.0, help="simulation time of the closed-form motion")
     ap.add_argument("--physics", action="store_true", help="row N23: reach --time with pt_physics_step (steps of 1/60 s, collisions included) instead of the closed form")
+    ap.add_argument("--publish", action="store_true", help="--physics: hand the simulated pose to the frame on the device (pt_physics_publish, row N24) instead of download + pt_update_spheres")
     ap.add_argument("--star-gravity", action="store_true", help="--physics: the Star's constant 10 m/s^2 pull on every body (the reference's H key)")
     ap.add_argument("--earth-gravity", action="store_true", help="--physics: the Earth's inverse-square pull on every body, not just the Moon (the G key)")
     ap.add_argument("--textures", action="store_true", help="textured Alien-Metal / Moon / Earth (procedural stand-ins)")
@@ -191,14 +192,17 @@ def main():
         steps, contacts = int(round(args.time * 60)), 0
         for _ in range(steps):
             contacts = r.physics_step(1 / 60, 1).Contacts
-        sph, rot, _, _ = r.physics_download()
-        spheres = spheres.copy()
-        for i, k in enumerate(("cx", "cy", "cz")):
-            spheres[k] = sph[:, i]
-        r.update_spheres(spheres)
-        if textured:
-            r.update_rotations(rot)
-        print(f"physics (pt_physics_step): {steps} steps of 1/60 s, {contacts} contacts in the last")
+        if args.publish:
+            r.physics_publish()
+        else:
+            sph, rot, _, _ = r.physics_download()
+            spheres = spheres.copy()
+            for i, k in enumerate(("cx", "cy", "cz")):
+                spheres[k] = sph[:, i]
+            r.update_spheres(spheres)
+            if textured:
+                r.update_rotations(rot)
+        print(f"physics (pt_physics_step): {steps} steps of 1/60 s, {contacts} contacts in the last" + (", pose published on the device" if args.publish else ""))
     w, h, n = args.width, args.height, args.width * args.height
     gs = t.graphics_settings(w, h, bounces=args.bounces, spp=args.spp)
     if args.gbuffer:
