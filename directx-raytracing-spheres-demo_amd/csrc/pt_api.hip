@@ -285,7 +285,7 @@ Knobs read_knobs()
     k.loop_use_tail = std::getenv("PT_LOOP_USE_TAIL") ? 1 : -1; k.fuse_loop = env_knob("PT_FUSE_LOOP"); k.beam_reach = env_knob("PT_BEAM_REACH"); k.beam_max_slack_pct = env_knob("PT_BEAM_MAX_SLACK_PCT"); k.beam_max_margin = env_knob("PT_BEAM_MAX_MARGIN"); k.beam_share_wgs = env_knob("PT_BEAM_SHARE_WGS"); k.lane_priority = env_knob("PT_LANE_PRIORITY"); k.fused_refit = env_knob("PT_FUSED_REFIT"); k.ray_replacement = env_knob("PT_RAY_REPLACEMENT");
     k.dyn_blocks_per_cu = env_knob("PT_DYN_BLOCKS_PER_CU"); k.debug_counts = std::getenv("PT_DEBUG_COUNTS") ? 1 : -1; k.sah = env_knob("PT_SAH");
     k.sah_max_spheres = env_knob("PT_SAH_MAX_SPHERES"); k.beams = env_knob("PT_BEAMS"); k.refl_beams = env_knob("PT_REFL_BEAMS"); k.coop_walk = env_knob("PT_COOP_WALK"); k.wide = env_knob("PT_WIDE"); k.descent = env_knob("PT_DESCENT"); k.roctx = env_knob("PT_ROCTX");
-    k.tile_order = env_knob("PT_TILE_ORDER"); k.sky_fast = env_knob("PT_SKY_FAST"); k.tile_table = env_knob("PT_TILE_TABLE");
+    k.tile_order = env_knob("PT_TILE_ORDER"); k.sky_fast = env_knob("PT_SKY_FAST"); k.tile_table = env_knob("PT_TILE_TABLE"); k.tile_interleave = env_knob("PT_TILE_INTERLEAVE");
     return k;
 }
 
@@ -868,9 +868,10 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
     fc.coop_walk = knob_or(c->knobs.coop_walk, 1u) != 0 ? 1u : 0u;  // PT_COOP_WALK=0: the per-lane walk everywhere (A/B runs, tests)
     // The primary pass over a view with beam lists: every workgroup draws its tiles with a non-empty list first (PT_TILE_ORDER=0: raster order;
     // PT_TILE_TABLE caps the order table below kTileTable, for tests of the fallback), and a tile with an empty list takes the short path
-    // (PT_SKY_FAST=0: the general one)
+    // (PT_SKY_FAST=0: the general one).  Behind the segmented hand-over a 1-spp workgroup's draw w is tile b + grid * w: it samples the whole frame
+    // evenly, where the batch map (PT_TILE_INTERLEAVE=0) gave it eight runs of eight consecutive tiles and the workgroups on the spheres twice the mean
     fc.tile_opts = (knob_or(c->knobs.tile_order, 1u) != 0 ? std::min(knob_or(c->knobs.tile_table, kTileTable), kTileTable) : 0u)
-                   | (knob_or(c->knobs.sky_fast, 1u) != 0 ? 1u << 16 : 0u);
+                   | (knob_or(c->knobs.sky_fast, 1u) != 0 ? kTileOptSky : 0u) | (knob_or(c->knobs.tile_interleave, 1u) != 0 ? kTileOptInterleave : 0u);
     uint32_t* counts = fc.counts;
 
     // Launch grids: a kernel's queue size lives on the device; the host sizes the grid from the queue sizes an

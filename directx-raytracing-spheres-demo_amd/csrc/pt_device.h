@@ -199,9 +199,12 @@ struct FrameCounters {
     uint32_t fuse_loop;     // 1: the primary pass finishes its own segment itself (no separate looping pass is launched)
     uint32_t coop_walk;     // 1: the 1-spp looping pass (and the fused form's tail) splits each tree walk over the wave's idle lanes (closest_hit_coop)
     // The primary pass over a view with beam lists (bounce_kernel).  Bits 0-15: how many tiles a workgroup's order table may hold (0: slot
-    // order; at most kTileTable); bit 16: a tile with an empty list takes the short path
+    // order; at most kTileTable); bit 16 (kTileOptSky): a tile with an empty list takes the short path; bit 17 (kTileOptInterleave): draw w of
+    // workgroup b is tile b + gridDim.x * w (0: the batch map, eight consecutive tiles per batch of blockDim.x slots)
     uint32_t tile_opts;
 };
+
+constexpr uint32_t kTileOptSky = 1u << 16, kTileOptInterleave = 1u << 17;
 
 constexpr uint32_t kTileTable = 256;  // entries of the tile order table: a workgroup's tiles of a 4K 1-spp frame (32 batches of 8 waves)
 

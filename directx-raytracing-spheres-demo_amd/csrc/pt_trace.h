@@ -1258,31 +1258,49 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
     const bool tile_builder = n_tiles != 0u && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1u;
     constexpr uint32_t kTileChunks = kTileTable / 64u;
     constexpr uint32_t kNoTile = ~0u;  // (a draw past the end of the table: the tiles of the workgroup are all taken)
-    uint32_t tile_class[kTileChunks];
+    // Which tiles a workgroup visits.  The batch map -- draw w is wave slot w % waves of batch b + (w / waves) * gridDim.x -- is what the dense
+    // hand-over needs, whose barriers keep a whole workgroup on one batch of blockDim.x slots; it gives a workgroup runs of eight consecutive
+    // tiles, 17 block rows apart at 1080p, so the workgroups whose runs fall on the spheres (tiles without a region record, whose bounce-1 rays
+    // walk the tree) got up to 23 such tiles against a mean of 8 (tools/tile_balance.py).  The segmented hand-over has no barrier in the tile loop: there draw w of a 1-spp
+    // workgroup is tile b + gridDim.x * w, every gridDim.x-th tile of the whole frame (kTileOptInterleave; PT_TILE_INTERLEAVE=0: the batch map).
+    // Both maps rise with w, so the tiles past the end of the frame are a workgroup's largest w in either.
+    // Three classes where the view has region records: tiles with a list and no region first (the tree walks), then the region-served, then the
+    // empty ones -- the same ballots and prefix counts, one more word loaded per tile.
+    uint32_t tile_class[kTileChunks], tile_region[kTileChunks];
     if (tile_builder) {
         const uint32_t waves = blockDim.x >> 6;
+        const bool interleave = (fc.tile_opts & kTileOptInterleave) != 0u;
 #pragma unroll
         for (uint32_t k = 0; k < kTileChunks; k++) {
             const uint32_t w = k * 64u + lane_id();
-            const uint32_t i0 = (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x + (w % waves) * 64u;
-            tile_class[k] = (w < n_tiles && i0 < count) ? fp.beam_lists[(size_t)(i0 >> 6) * kBeamRecord] : 0u;
+            const uint32_t i0 = interleave ? (blockIdx.x + gridDim.x * w) << 6 : (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x + (w % waves) * 64u;
+            const bool inside = w < n_tiles && i0 < count;
+            tile_class[k] = inside ? fp.beam_lists[(size_t)(i0 >> 6) * kBeamRecord] : 0u;
+            tile_region[k] = (inside && fp.refl_lists != nullptr) ? fp.refl_lists[(size_t)(i0 >> 6) * kReflRecord] : 0u;
         }
     }
     auto build_tile_order = [&]() {
-        unsigned long long heavy[kTileChunks];
-        uint32_t n_heavy = 0;
+        unsigned long long heavy[kTileChunks], served[kTileChunks];
+        uint32_t n_heavy = 0, n_served = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < kTileChunks; k++) { heavy[k] = __ballot(tile_class[k] != 0u); n_heavy += __popcll(heavy[k]); }
+        for (uint32_t k = 0; k < kTileChunks; k++) {
+            heavy[k] = __ballot(tile_class[k] != 0u && tile_region[k] == 0u);
+            served[k] = __ballot(tile_class[k] != 0u && tile_region[k] != 0u);
+            n_heavy += __popcll(heavy[k]);
+            n_served += __popcll(served[k]);
+        }
         const unsigned long long below = (1ull << lane_id()) - 1ull;
-        uint32_t at_heavy = 0, at_light = n_heavy;
+        uint32_t at_heavy = 0, at_served = n_heavy, at_light = n_heavy + n_served;
 #pragma unroll
         for (uint32_t k = 0; k < kTileChunks; k++) {
             const uint32_t w = k * 64u + lane_id();
-            const bool h = tile_class[k] != 0u;
-            const uint32_t pos = h ? at_heavy + __popcll(heavy[k] & below) : at_light + __popcll(~heavy[k] & below);
+            const bool h = tile_class[k] != 0u && tile_region[k] == 0u, s = tile_class[k] != 0u && tile_region[k] != 0u;
+            const unsigned long long light = ~(heavy[k] | served[k]);
+            const uint32_t pos = h ? at_heavy + __popcll(heavy[k] & below) : s ? at_served + __popcll(served[k] & below) : at_light + __popcll(light & below);
             if (w < n_tiles) s_tile_order[pos] = (uint16_t)w;
             at_heavy += __popcll(heavy[k]);
-            at_light += 64u - __popcll(heavy[k]);
+            at_served += __popcll(served[k]);
+            at_light += __popcll(light);
         }
     };
     if (kTileOrder && seg_out && threadIdx.x == 0) s_tile_n = n_tiles;
@@ -1349,8 +1367,8 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             if (b >= count) break;
             i = b + lane;
         } else if (seg_out) {
-            // the workgroup's batches are the same strided set as below, but its waves take the 64-slot tiles of them from a
-            // counter in LDS: a wave that drew sky tiles moves on instead of idling behind its neighbours
+            // the workgroup's waves take its 64-slot tiles (every gridDim.x-th tile of the frame; with the batch map those of the same strided
+            // set of batches as below) from a counter in LDS: a wave that drew sky tiles moves on instead of idling behind its neighbours
             uint32_t w = 0;
             if (lane == 0) {
                 w = atomicAdd(&s_seg_next, 1u);
@@ -1361,10 +1379,17 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
             }
             w = __builtin_amdgcn_readfirstlane(w);
             if (w == kNoTile) break;
-            const uint32_t waves = blockDim.x >> 6;
-            const uint32_t b = (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x;
-            if (b >= count) break;
-            i = b + (w % waves) * 64u + lane;
+            // (the map's switch is read where it is used, like the short path's below: one scalar load per draw, nothing carried through the body)
+            if (kTileOrder && (cold_arg<uint32_t>(offsetof(BounceArgs, fc) + offsetof(FrameCounters, tile_opts)) & kTileOptInterleave) != 0u) {
+                const uint32_t b = (blockIdx.x + gridDim.x * w) << 6;
+                if (b >= count) break;
+                i = b + lane;
+            } else {
+                const uint32_t waves = blockDim.x >> 6;
+                const uint32_t b = (blockIdx.x + (w / waves) * gridDim.x) * blockDim.x;
+                if (b >= count) break;
+                i = b + (w % waves) * 64u + lane;
+            }
         } else {
             if (base >= count) break;
             i = base + threadIdx.x;
@@ -1405,7 +1430,7 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         constexpr bool kSky = kPrimary && !kLoop && !kMulti && !kTex;
         // (wave-uniform, and used up before the trace: the knob's word is read from the kernarg segment only behind an empty list, and nothing of
         // this is carried through the loop's body, where the scalar registers are short)
-        const bool sky = kSky && beam_count == 0u && (cold_arg<uint32_t>(offsetof(BounceArgs, fc) + offsetof(FrameCounters, tile_opts)) >> 16) != 0u;
+        const bool sky = kSky && beam_count == 0u && (cold_arg<uint32_t>(offsetof(BounceArgs, fc) + offsetof(FrameCounters, tile_opts)) & kTileOptSky) != 0u;
         if (i < count) {
             bool live = true;
             float tmin = 0.0f, tmax = kInf;
