@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
     "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
@@ -124,6 +124,8 @@ class HipLib:
         lib.pt_sharc_download.argtypes = [vp, vp, vp, u32]
         lib.pt_sharc_upload.restype = C.c_int
         lib.pt_sharc_upload.argtypes = [vp, vp, vp, u32]
+        lib.pt_render_lens.restype = C.c_int
+        lib.pt_render_lens.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtStats)]
         lib.pt_upscale.restype = C.c_int
         lib.pt_upscale.argtypes = [vp, C.POINTER(PtUpscaleSettings), C.POINTER(PtUpscaleTextures)]
         lib.pt_upscale_input_size.restype = C.c_int
@@ -717,6 +719,27 @@ class Renderer:
         out = np.empty((r.h, r.w, 4), dtype=np.float32) if query else None
         stats = PtStats()
         self._check(self._lib.pt_render_sharc(self._ctx, C.byref(r), out.ctypes.data if query else None, 0, C.byref(s), C.byref(stats) if want_stats else None))
+        if not want_stats:
+            self.synchronize()
+        return out, stats
+
+    def render_lens_device(self, out_ptr, rect=None, want_stats=False):
+        """The pure path-traced frame through the thin-lens camera (row N26, DESIGN.md spec S29; pt_render_lens) into device memory: the
+        aperture is the camera's ApertureRadius (set_camera), the plane in focus lies at view depth |ForwardDirection|; aperture 0 is
+        render_device's frame bit for bit.  Runs on the lane of the next render call; asynchronous unless want_stats."""
+        r = PtRect(*rect) if rect is not None else None
+        stats = PtStats()
+        self._check(self._lib.pt_render_lens(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr or 0), 1, C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_lens(self, rect=None, want_stats=True):
+        """render_lens_device to a host numpy array (h, w, 4) float32 -> (image, stats).  Synchronous."""
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        r = PtRect(*rect)
+        out = np.empty((r.h, r.w, 4), dtype=np.float32)
+        stats = PtStats()
+        self._check(self._lib.pt_render_lens(self._ctx, C.byref(r), out.ctypes.data, 0, C.byref(stats) if want_stats else None))
         if not want_stats:
             self.synchronize()
         return out, stats

@@ -1399,6 +1399,7 @@ void pt_destroy(PtContext* c)
     if (c->ev_ri) (void)hipEventDestroy(c->ev_ri);
     free_dev(c->d_sh);
     if (c->ev_sh) (void)hipEventDestroy(c->ev_sh);
+    free_dev(c->d_lens_counters);
     for (auto& e : c->ev_in) if (e) (void)hipEventDestroy(e);
     if (c->gpu_builder) lbvh_gpu_destroy(c->gpu_builder);
     for (auto& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }

@@ -1,6 +1,6 @@
 // pt_api_side.hip -- the entry points of the C-ABI (include/pt_api.h) that are side passes of a frame: work for the frame the NEXT render call renders,
 // queued on the lane that frame will take and ordered against the caller's stream like the frame itself (pt_lane_order.h, side_pass_begin): the G-buffer pass,
-// the reservoir pass and the frame through the radiance cache, with their downloads.  The frames and the shared helpers (end of pt_context.h) are in pt_api.hip.
+// the reservoir pass, the frame through the radiance cache and the frame through the thin-lens camera, with their downloads.  The frames and the shared helpers (end of pt_context.h) are in pt_api.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "pt_restir.h"
 #include "pt_lightris.h"
 #include "pt_sharc.h"
+#include "pt_lens.h"
 
 // Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12).
 // published (pt_render_gbuffer_published, spec S28): the previous pose is the generation published before the newest one, copied on the
@@ -360,6 +361,24 @@ PtStatus pt_light_ris_download(PtContext* c, float* pyramid, uint32_t* n_pyramid
     return PT_OK;
 }
 
+// The stats of a frame-like side pass (pt_render_sharc*, pt_render_lens) that recorded PtContext::ev0 on the lane before its launches: the time
+// between the two markers and the rays its kernels counted at d_rays.  Waits for the lane.
+static PtStatus side_frame_stats(PtContext* c, Lane& L, const unsigned long long* d_rays, PtStats* stats, uint64_t pixels, uint64_t paths)
+{
+    unsigned long long rays = 0;
+    PT_HIP(c, hipEventRecord(c->ev1, L.stream));
+    PT_HIP(c, hipMemcpyAsync(&rays, d_rays, sizeof rays, hipMemcpyDeviceToHost, L.stream));
+    PT_HIP(c, hipStreamSynchronize(L.stream));
+    std::memset(stats, 0, sizeof *stats);
+    float ms = 0;
+    PT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    stats->ms_total = ms;
+    stats->rays = rays;
+    stats->pixels = pixels;
+    stats->paths = paths;
+    return PT_OK;
+}
+
 // Row N14 -- the frame through the radiance cache (DESIGN.md spec S20): up to three stages on the lane of the next render call, ordered
 // like pt_restir_di; the cache (keys, two voxel arrays that swap at every resolve, two counters) lives in the context.
 static PtStatus sharc_allocate(PtContext* c, uint32_t capacity)
@@ -508,19 +527,9 @@ static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_
     }
     const hipError_t e0 = hipEventRecord(c->ev_sh, L.stream);
     if (st == PT_OK && e0 != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": cache event: " + hipGetErrorString(e0));
-    if (st == PT_OK && timed) {
-        unsigned long long counters[2] = { 0, 0 };
-        PT_HIP(c, hipEventRecord(c->ev1, L.stream));
-        PT_HIP(c, hipMemcpyAsync(counters, c->d_sh_counters, sizeof counters, hipMemcpyDeviceToHost, L.stream));
-        PT_HIP(c, hipStreamSynchronize(L.stream));
-        std::memset(stats, 0, sizeof *stats);
-        float ms = 0;
-        PT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        stats->ms_total = ms;
-        stats->rays = counters[0];
-        stats->pixels = query ? out_px : 0;
-        stats->paths = (query ? out_px * c->gs.SamplesPerPixel : 0) + ((stages & PT_SHARC_UPDATE) ? (uint64_t)gw * gh : 0);
-    }
+    if (st == PT_OK && timed)
+        if (const PtStatus e = side_frame_stats(c, L, c->d_sh_counters, stats, query ? out_px : 0,
+                                                (query ? out_px * c->gs.SamplesPerPixel : 0) + ((stages & PT_SHARC_UPDATE) ? (uint64_t)gw * gh : 0)); e != PT_OK) return e;
     st = publish_lane_to_caller(c, L, who.c_str(), st);
     if (st != PT_OK) return st;
     c->sh_valid = true;
@@ -531,6 +540,51 @@ static PtStatus sharc_call(PtContext* c, const PtRect* rect, void* out, int out_
 PtStatus pt_render_sharc(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, PtStats* stats) { return sharc_call(c, rect, out, out_is_device, s, nullptr, nullptr, stats, false, "pt_render_sharc"); }
 
 PtStatus pt_render_sharc_ex(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtSharcSettings* s, const PtDirectLighting* di, const PtDenoiserOutputs* outputs, PtStats* stats) { return sharc_call(c, rect, out, out_is_device, s, di, outputs, stats, true, "pt_render_sharc_ex"); }
+
+// Row N26 -- the pure path-traced frame through the thin-lens camera (DESIGN.md spec S29): one launch on the lane of the next render call,
+// ordered like pt_render_sharc's query (the cache family of pt_lane_order.h with QUERY, no DI and no denoiser outputs).  The only entry
+// point that reads PtCamera::ApertureRadius.
+PtStatus pt_render_lens(PtContext* c, const PtRect* rect, void* out, int out_is_device, PtStats* stats)
+{
+    const char* who = "pt_render_lens";
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!out) return fail(c, PT_ERR_INVALID_ARG, "pt_render_lens: null output");
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    if (c->gs.IsDIEnabled || c->gs.Denoiser) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_lens: IsDIEnabled and Denoiser must be 0 (DI and denoiser outputs behind the lens are not built)");
+    const float aperture = c->cam.ApertureRadius;
+    if (!(aperture >= 0.0f) || !std::isfinite(aperture)) return fail(c, PT_ERR_INVALID_ARG, "pt_render_lens: ApertureRadius must be finite and not negative");
+    PtRect r;
+    PixelMap pm{};
+    if ((st = rect_pixel_map(c, rect, who, r, pm)) != PT_OK) return st;
+    if ((st = check_environment(c)) != PT_OK) return st;
+    if ((st = check_tree_lds(c)) != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    float4* dev_out = nullptr;
+    const size_t out_px = (size_t)r.w * r.h;
+    if ((st = staged_out_begin(c, out, !out_is_device, out_px, dev_out)) != PT_OK) return st;
+    if (reinterpret_cast<uintptr_t>(dev_out) & 15u) return fail(c, PT_ERR_INVALID_ARG, "pt_render_lens: the output must be 16-byte aligned");
+    if (!c->d_lens_counters) PT_HIP(c, hipMalloc(&c->d_lens_counters, kMaxLanes * sizeof(unsigned long long)));  // (every call clears its lane's counter on the lane's stream)
+
+    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
+    const bool shared = ledger_cache({ c->ledgers, c->n_lanes, c->next_lane }, c->calls == 0, true, dev_out, false, nullptr, nullptr, nullptr, false, nullptr, nullptr);
+    if ((st = side_pass_begin(c, L, shared)) != PT_OK) return st;
+    unsigned long long* counter = c->d_lens_counters + c->next_lane;
+    const bool timed = stats != nullptr;
+    if (timed) PT_HIP(c, hipEventRecord(c->ev0, L.stream));
+    PT_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), L.stream));
+    const SceneView sv = make_scene_view(c, &L);
+    const LensFrame fr = lens_frame(c->cam, c->gs.RenderSize[0], c->gs.RenderSize[1], c->gs.FrameIndex, c->gs.Bounces, c->gs.SamplesPerPixel,
+                                    c->gs.IsRussianRouletteEnabled != 0, c->gs.ThroughputThreshold);
+    // pt_get_profile: the frame under ms_shade, like the cache's query
+    const hipError_t e = profiled_launch(c, L.stream, 2, [&] { return launch_lens(sv, pm, fr, dev_out, counter, side_pass_grid(c, pm.n_slots), L.stream); });
+    st = e == hipSuccess ? PT_OK : fail(c, PT_ERR_HIP, std::string("pt_render_lens: launch: ") + hipGetErrorString(e));
+    if (st == PT_OK && timed)
+        if (const PtStatus e2 = side_frame_stats(c, L, counter, stats, out_px, out_px * c->gs.SamplesPerPixel); e2 != PT_OK) return e2;
+    st = publish_lane_to_caller(c, L, who, st);
+    if (st != PT_OK) return st;
+    return staged_out_finish(c, out, !out_is_device, out_px);
+}
 
 PtStatus pt_sharc_download(PtContext* c, void* keys, void* voxels, uint32_t capacity)
 {

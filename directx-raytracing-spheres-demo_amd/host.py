@@ -22,6 +22,9 @@ class HostLib:
         self.lib.pth_scene.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(PtSceneData)]
         self.lib.pth_camera.restype = None
         self.lib.pth_camera.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PtCamera)]
+        self.lib.pth_camera_lens.restype = None
+        self.lib.pth_camera_lens.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                             C.POINTER(PtCamera)]
         self.lib.pth_scene_at_time.restype = C.c_int
         self.lib.pth_scene_at_time.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         self.lib.pth_halton.restype = C.c_float
@@ -109,6 +112,19 @@ class HostLib:
         pos = (C.c_float * 3)(*position)
         la = (C.c_float * 3)(*look_at) if look_at is not None else None
         self.lib.pth_camera(pos, la, hfov, width, height, 1 if jitter else 0, jitter_index, jitter_count, C.byref(cam))
+        return cam
+
+    def camera_lens(self, width, height, aperture, focus_distance=None, position=(0.0, 0.0, -15.0), look_at=None, hfov=math.pi / 2, jitter=True, jitter_index=0,
+                    jitter_count=8):
+        """camera() for pt_render_lens (row N26): CameraController::SetFocusDistance(focus_distance) (None: as camera() leaves it, 1; else
+        positive), then ApertureRadius = aperture."""
+        if focus_distance is not None and not focus_distance > 0.0:
+            raise ValueError("focus_distance must be positive")
+        cam = PtCamera()
+        pos = (C.c_float * 3)(*position)
+        la = (C.c_float * 3)(*look_at) if look_at is not None else None
+        self.lib.pth_camera_lens(pos, la, hfov, width, height, 1 if jitter else 0, jitter_index, jitter_count, aperture, 0.0 if focus_distance is None else focus_distance,
+                                 C.byref(cam))
         return cam
 
     def camera_matrices(self, width, height, position=(0.0, 0.0, -15.0), look_at=None, hfov=math.pi / 2, jitter=True, jitter_index=0, jitter_count=8,

@@ -250,6 +250,19 @@ struct Raytracing {
         return stats;
     }
 
+    // The pure path-traced frame through Camera::GenerateThinLensRay (Camera.hlsli:43-54, which the reference declares and never calls;
+    // row N26, spec S29, pt_render_lens): the aperture is the ApertureRadius of the camera last given to pt_set_camera (the reference's
+    // controller has no setter: callers write Camera::ApertureRadius), the plane in focus what CameraController::SetFocusDistance set.
+    // ApertureRadius == 0 is Render(radiance), bit for bit.
+    PtStats RenderThinLens(std::vector<Float4>& radiance)
+    {
+        ThrowIfFailed(pt_set_constants(m_ctx, &m_graphicsSettings), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtStats stats{};
+        ThrowIfFailed(pt_render_lens(m_ctx, nullptr, radiance.data(), 0, &stats), m_ctx, "pt_render_lens");
+        return stats;
+    }
+
 private:
     PtContext* m_ctx;
     PtGraphicsSettings m_graphicsSettings{};

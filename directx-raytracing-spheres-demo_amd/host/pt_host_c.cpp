@@ -79,15 +79,16 @@ int pth_demo_textures(uint32_t seed, double time, uint32_t* n_textures, uint32_t
     return pth_demo_textures_ex(seed, time, 1u, n_textures, n_objects, pixel_bytes, image_info, pixels, object_textures, rotations, nullptr);
 }
 
-// CameraController at `position` with identity rotation (or looking at `look_at` when non-null), SetLens(hfov, w/h),
-// jitter = Halton2D(jitter_index + 1) - 0.5 when jitter_enabled (Source/App.cpp:542-551), jitter_index cycling mod jitter_count.
-void pth_camera(const float position[3], const float* look_at, float hfov, uint32_t width, uint32_t height, int jitter_enabled,
-                uint32_t jitter_index, uint32_t jitter_count, PtCamera* out)
+// the demo camera of pth_camera / pth_camera_lens: focus_distance > 0 goes through the controller's SetFocusDistance; ApertureRadius is written
+// by the caller, as the reference's controller has no setter for it
+static void camera_of(const float position[3], const float* look_at, float hfov, uint32_t width, uint32_t height, int jitter_enabled, uint32_t jitter_index,
+                      uint32_t jitter_count, float aperture_radius, float focus_distance, PtCamera* out)
 {
     CameraController controller;
     controller.SetPosition({ position[0], position[1], position[2] });
     if (look_at) controller.LookAt({ look_at[0], look_at[1], look_at[2] }, { 0, 1, 0 }, false);
     controller.SetLens(hfov, static_cast<float>(width) / static_cast<float>(height));
+    if (focus_distance > 0.0f) controller.SetFocusDistance(focus_distance);
     Float2 jitter{};
     if (jitter_enabled) {
         const auto h = HaltonSampler::Get2D(jitter_index % (jitter_count ? jitter_count : 1) + 1);
@@ -96,7 +97,23 @@ void pth_camera(const float position[3], const float* look_at, float hfov, uint3
     Camera camera;
     controller.Fill(camera, jitter);
     camera.PreviousPosition = camera.Position;
+    camera.ApertureRadius = aperture_radius;
     *out = ToPt(camera);
+}
+
+// CameraController at `position` with identity rotation (or looking at `look_at` when non-null), SetLens(hfov, w/h),
+// jitter = Halton2D(jitter_index + 1) - 0.5 when jitter_enabled (Source/App.cpp:542-551), jitter_index cycling mod jitter_count.
+void pth_camera(const float position[3], const float* look_at, float hfov, uint32_t width, uint32_t height, int jitter_enabled,
+                uint32_t jitter_index, uint32_t jitter_count, PtCamera* out)
+{
+    camera_of(position, look_at, hfov, width, height, jitter_enabled, jitter_index, jitter_count, 0.0f, 0.0f, out);
+}
+
+// pth_camera through the thin lens of row N26 (pt_render_lens): SetFocusDistance(focus_distance) (<= 0: left as it is) and ApertureRadius
+void pth_camera_lens(const float position[3], const float* look_at, float hfov, uint32_t width, uint32_t height, int jitter_enabled,
+                     uint32_t jitter_index, uint32_t jitter_count, float aperture_radius, float focus_distance, PtCamera* out)
+{
+    camera_of(position, look_at, hfov, width, height, jitter_enabled, jitter_index, jitter_count, aperture_radius, focus_distance, out);
 }
 
 // pth_camera with the lens depths and the eight matrices (CameraController::FillMatrices) for the G-buffer pass: SetLens(hfov, w/h,

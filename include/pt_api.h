@@ -29,6 +29,8 @@
  *   pt_render_sharc          Raytracing::Render(commandList, tlas, SHARC&, SHARCSettings) (a stand-in for SHARC, spec S20)   Source/Raytracing.ixx:114-148
  *   pt_render_sharc_ex       ... with IsDIEnabled and a denoiser, the reference's default frame (spec S24)   Source/App.cpp:1255-1268,
  *                            Shaders/Raytracing.hlsl:150-163, 302-318, 376-414
+ *   pt_render_lens           Camera::GenerateThinLensRay in front of the bounce loop (declared, never called by the reference; spec S29)
+ *                            Shaders/Camera.hlsli:43-54
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
@@ -511,6 +513,20 @@ PtStatus pt_render_sharc(PtContext *ctx, const PtRect *rect, void *out, int out_
  * a partial rect.  On any error nothing is written. */
 PtStatus pt_render_sharc_ex(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtSharcSettings *settings,
                             const PtDirectLighting *di, const PtDenoiserOutputs *outputs, PtStats *stats);
+
+/* Row N26 -- the pure path-traced frame through the thin-lens camera (Camera::GenerateThinLensRay, Shaders/Camera.hlsli:43-54, which the
+ * reference declares and never calls; DESIGN.md spec S29): pt_render's DEFAULT loop with every sample's primary ray leaving its own point
+ * of a lens of radius PtCamera.ApertureRadius towards the pixel's point at view depth |ForwardDirection| (the plane in focus: what
+ * CameraController::SetFocusDistance sets).  The lens point is ImportanceSampling::Uniform::GetRay(u).xy of two numbers from a stream of
+ * the pixel's own; the bounce loop's random numbers are pt_render's.  ApertureRadius == 0: the frame is pt_render's, bit for bit.  The only
+ * entry point that reads ApertureRadius.
+ * Camera and aperture come from pt_set_camera, the frame settings (RenderSize, FrameIndex, Bounces, SamplesPerPixel, Russian roulette,
+ * ThroughputThreshold) from pt_set_constants.  rect / out / out_is_device / stats: as pt_render_sharc; stats->rays counts every ray
+ * traced, each sample's primary ray included.  Runs and is ordered like pt_render_sharc: on the lane of the next render call; the lanes
+ * are not advanced and pt_get_totals does not count the call.
+ * PT_ERR_INVALID_ARG: a null context or `out`; a rect outside RenderSize; an ApertureRadius that is negative, NaN or infinite.
+ * PT_ERR_UNSUPPORTED: IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as pt_render. */
+PtStatus pt_render_lens(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, PtStats *stats);
 
 /* Test hooks of row N14: the cache as the last pt_render_sharc call left it -- `capacity` keys (uint64, 0 = empty) and resolved voxels
  * (4 x uint32: fixed-point RGB sums, samples | frames << 16 | stale << 24) to HOST memory -- and the reverse, which installs a cache made

@@ -74,7 +74,8 @@ typedef struct PtCamera {
     float UpDirection[3];               /*  48 */
     float _pad2;                        /*  60 */
     float ForwardDirection[3];          /*  64 */
-    float ApertureRadius;               /*  76 */
+    float ApertureRadius;               /*  76: read by pt_render_lens only (the thin-lens camera, Camera.hlsli:43-54);
+                                                pt_set_camera accepts anything, every other entry point ignores it */
     float NearDepth;                    /*  80 */
     float FarDepth;                     /*  84 */
     float Jitter[2];                    /*  88 */

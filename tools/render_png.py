@@ -9,7 +9,8 @@ upscaler when there is one and before bloom; --frame-gen MID.png: the frames at 
 pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting camera through pt_render_sharc, row N14, the last one tone
 mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendered at the mode's input size through pt_render_gbuffer ->
 pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height; --sharc --restir-di --ray-reconstruction together: the
-reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction; --aperture R [--focus-distance F]: the accumulated frames through the thin-lens camera,
+pt_render_lens, row N26).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
                                         --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] [--bias-correction pairwise] [--reuse-visibility [4 16]] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
@@ -115,6 +116,10 @@ def main():
                          "mode's input size (pt_upscale_input_size; native without a mode) with Halton jitter: pt_render_gbuffer -> "
                          "pt_render_denoiser mode 1 -> pt_ray_reconstruction to --width x --height [-> pt_nis_sharpen with --nis] [-> pt_bloom "
                          "with --bloom] -> the tone map; the last frame")
+    ap.add_argument("--aperture", type=float, default=None, metavar="R",
+                    help="the plain path-traced frame through the thin-lens camera (row N26): pt_render_lens with ApertureRadius R, accumulated like pt_render's frames")
+    ap.add_argument("--focus-distance", type=float, default=None, metavar="F",
+                    help="--aperture: the view depth in focus, through CameraController::SetFocusDistance (default 15: the demo's spheres)")
     ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
@@ -128,6 +133,14 @@ def main():
         ap.error("--sharc applies to the plain path-traced frame")
     if not default_frame and args.ray_reconstruction and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale):
         ap.error("--ray-reconstruction is a path of its own: it takes --nis and --bloom only")
+    if args.aperture is not None and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale
+                                      or args.ray_reconstruction):
+        ap.error("--aperture applies to the plain path-traced frame")
+    if args.focus_distance is not None and args.aperture is None:
+        ap.error("--focus-distance applies to --aperture")
+    if args.focus_distance is not None and not args.focus_distance > 0.0:
+        ap.error("--focus-distance must be positive")
+    focus_distance = 15.0 if args.focus_distance is None else args.focus_distance
     if args.sharc_anti_firefly and not args.sharc:
         ap.error("--sharc-anti-firefly applies to --sharc")
     if args.light_sampling != "uniform" and not args.restir_di:
@@ -437,9 +450,15 @@ def main():
         return
     for k in range(args.frames):
         gs.FrameIndex = k
-        r.set_camera(host.camera(w, h, jitter_index=k, jitter_count=max(args.frames, 8)))
+        if args.aperture is not None:
+            r.set_camera(host.camera_lens(w, h, args.aperture, focus_distance, jitter_index=k, jitter_count=max(args.frames, 8)))
+        else:
+            r.set_camera(host.camera(w, h, jitter_index=k, jitter_count=max(args.frames, 8)))
         r.set_constants(gs)
-        r.render_device(frame.data_ptr())
+        if args.aperture is not None:
+            r.render_lens_device(frame.data_ptr())
+        else:
+            r.render_device(frame.data_ptr())
         r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
     op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
     hdr = accum
@@ -453,8 +472,11 @@ def main():
     r.synchronize()
     rgba = ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)
     Image.fromarray(rgba[..., :3]).save(args.out)
-    tot = r.totals()
-    print(f"{args.frames} frames x {args.spp} spp, {tot.rays} rays -> {args.out}")
+    if args.aperture is not None:  # (pt_get_totals does not count pt_render_lens)
+        print(f"thin lens (pt_render_lens, aperture {args.aperture}, in focus at {focus_distance}), {args.frames} frames x {args.spp} spp -> {args.out}")
+    else:
+        tot = r.totals()
+        print(f"{args.frames} frames x {args.spp} spp, {tot.rays} rays -> {args.out}")
     r.close()
 
 
