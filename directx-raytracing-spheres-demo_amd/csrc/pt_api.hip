@@ -984,7 +984,7 @@ PtStatus render_common(PtContext* c, const PixelMap& pm, uint64_t valid_pixels, 
                 const uint32_t items = primary ? pm.n_slots : estimate(k);
                 const uint32_t cap = loop ? tail_cap : trav_cap;
                 if (loop && c->knobs.loop_use_tail >= 0) {
-                    PT_HIP(c, launch_tail(sv, pm, fp, qin, scr, out, counts + k, fc.tail_rays, fc.totals, grid_for(items, kTailThreads, tail_cap), L.stream));
+                    PT_HIP(c, profiled_launch(c, L.stream, 3, [&] { return launch_tail(sv, pm, fp, qin, scr, out, counts + k, fc.tail_rays, fc.totals, grid_for(items, kTailThreads, tail_cap), L.stream); }));
                     break;
                 }
                 PT_HIP(c, profiled_launch(c, L.stream, loop ? 3 : (primary ? 0 : 1), [&] {

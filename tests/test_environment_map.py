@@ -232,7 +232,7 @@ def test_oracle_cube_map_consistency(dxrs, host, oracle):
 def test_gpu_environment_map_matches_oracle(dxrs, host, oracle, renderer, seed):
     from dxrs_amd import textures as T
     rng = np.random.default_rng(9100 + seed)
-    n = int(rng.choice([3, 8, 20, 500]))  # 500: BVH in global memory
+    n = int(rng.choice([3, 8, 20, 500]))  # (500 is still staged in LDS, like the rest: a tree in global memory is test_gpu_schedule_matrix.py's)
     spheres, materials, ts = make_textured_scene(dxrs, rng, n, seed % 2)
     if seed % 3 == 0:  # the environment map alone: no sphere has maps
         ts = T.TextureSet(n)

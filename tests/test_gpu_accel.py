@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from test_abi import check_lbvh
-from util import assert_hits_match_oracle
+from util import assert_hits_match_oracle, context_under
 from wide_reference import check_wide
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +62,48 @@ def test_bvh_equals_brute_force(dxrs, host, oracle, name, count, flags):
             assert (id_bvh != 0xFFFFFFFF).mean() > 0.3
         # CPU oracle on a subset: same closest hit, bit-exact t
         sub = slice(0, 2000 if len(spheres) < 50000 else 300)
+        t_bvh, id_bvh = r.trace_rays(o[sub], d[sub], tmin=0.0, use_bvh=True)
+        assert_hits_match_oracle(oracle.lib, spheres, o[sub], d[sub], t_bvh, id_bvh)
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("wide", [True, False], ids=["wide", "binary"])
+@pytest.mark.parametrize("n", [32766, 32767, 32768, 32769])
+def test_stack_width_boundary(dxrs, host, oracle, n, wide):
+    """with_tree_walk takes 16-bit stack entries while the tree has fewer than 32767 nodes, and stack_encode packs a leaf as 0x8000 | k:
+    n = 32766 spheres (32765 nodes, the largest leaf code and node index of the 16-bit form), 32767 (one node short of the switch) and the
+    first two trees of the 32-bit form.  Besides the mix of make_rays, 2000 rays aim at the 64 spheres with the highest Morton-sorted
+    index, so that the largest leaf codes are pushed and popped.  wide: the 4-wide walk; else the binary one (PT_WIDE=0)."""
+    spheres, materials, sd = host.scene(dxrs.host.SCENE_PROCEDURAL, seed=1, count=n - 1)  # (count small spheres and the ground)
+    assert len(spheres) == n
+    r = context_under(dxrs, {} if wide else {"PT_WIDE": "0"})
+    try:
+        info = r.set_scene(spheres, materials, sd)
+        assert info.leaf_count == n and info.node_count == n - 1 and info.lds_resident == 0
+        assert (r.download_wide() is not None) == wide
+        last = r.download_accel()[1][-64:]
+        rng = np.random.default_rng(n)
+        n_aimed = 2000
+        pick = last[rng.integers(0, len(last), n_aimed)]
+        c = np.stack([spheres["cx"], spheres["cy"], spheres["cz"]], 1).astype(np.float64)[pick]
+        rad = spheres["r"].astype(np.float64)[pick]
+        u = rng.normal(size=(n_aimed, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
+        o_aim = c + u * (rad + rng.uniform(1.0, 5.0, n_aimed))[:, None]  # (from outside, farther away than either tmin)
+        d_aim = c + rng.normal(size=(n_aimed, 3)) * rad[:, None] * 0.3 - o_aim
+        d_aim /= np.linalg.norm(d_aim, axis=1, keepdims=True)
+        d_aim = d_aim.astype(np.float32)
+        d_aim /= np.linalg.norm(d_aim.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
+        o_mix, d_mix = make_rays(spheres, 20000, seed=n)
+        o, d = np.concatenate([o_aim.astype(np.float32), o_mix]), np.concatenate([d_aim, d_mix])
+        for tmin in (0.0, 0.3):
+            t_bvh, id_bvh = r.trace_rays(o, d, tmin=tmin, use_bvh=True)
+            t_bf, id_bf = r.trace_rays(o, d, tmin=tmin, use_bvh=False)
+            assert np.array_equal(id_bvh, id_bf)
+            assert np.array_equal(t_bvh.view(np.uint32), t_bf.view(np.uint32))
+            assert (id_bvh[:n_aimed] != 0xFFFFFFFF).mean() > 0.9
+            assert np.isin(id_bvh[:n_aimed], last).mean() > 0.5  # (and most of them the sphere aimed at, not one in front of it)
+        sub = np.concatenate([np.arange(150), n_aimed + np.arange(150)])  # CPU oracle: aimed and mixed rays
         t_bvh, id_bvh = r.trace_rays(o[sub], d[sub], tmin=0.0, use_bvh=True)
         assert_hits_match_oracle(oracle.lib, spheres, o[sub], d[sub], t_bvh, id_bvh)
     finally:

@@ -7,27 +7,13 @@ import os
 import numpy as np
 import pytest
 
-from util import count_mismatch
+from util import context_under as _context, count_mismatch
 
 gpu = pytest.mark.gpu
 
 SIZES = [(64, 40), (136, 72)]
 FRAMES = (0, 1, 2)
 BOUNCES = 8
-
-
-def _context(dxrs, env, **kw):
-    """A context created under `env` (the knobs are read once, at pt_create)."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return dxrs.Renderer(device=0, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.fixture(scope="module")

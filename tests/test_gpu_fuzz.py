@@ -71,7 +71,8 @@ def test_random_scene_matches_oracle(dxrs, host, oracle, renderer, seed):
     assert np.isfinite(img).all()
 
 
-# scenes too large for the LDS-resident path: global-memory BVH, split traverse/shade schedule
+# 1000 and 4000 spheres are too many for the LDS-resident path: global-memory BVH, split traverse/shade schedule.  450 are not: pt_build_accel
+# stages a tree in LDS up to about 780 spheres (test_scene_sizes_around_the_lds_limits, tests/test_gpu_side_pass_lds.py)
 @pytest.mark.parametrize("seed", range(int(os.environ.get("PT_FUZZ_LARGE_SEEDS", "12"))))
 def test_random_large_scene_matches_oracle(dxrs, host, oracle, renderer, seed):
     rng = np.random.default_rng(5000 + seed)
@@ -83,7 +84,9 @@ def test_random_large_scene_matches_oracle(dxrs, host, oracle, renderer, seed):
     pos = (float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)), -12.0) if seed % 4 else (0.1, 0.2, 0.3)
     cam = host.camera(w, h, position=pos, look_at=(0.0, 0.0, 0.0) if seed % 2 else None, jitter_index=seed)
     gs = dxrs.types.graphics_settings(w, h, frame_index=seed * 104729, bounces=bounces, spp=spp, rr=bool(seed % 3))
-    renderer.set_scene(spheres, materials, sd)
+    info = renderer.set_scene(spheres, materials, sd)
+    if n >= 1000:
+        assert info.lds_resident == 0  # (a larger LDS budget must not quietly take these scenes off the global-memory path)
     renderer.set_camera(cam)
     renderer.set_constants(gs)
     img, st = renderer.render()

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from util import bits, count_mismatch
+from util import bits, context_under as _context, count_mismatch
 
 pytestmark = pytest.mark.gpu
 
@@ -23,20 +23,6 @@ FUSED, SEPARATE = {"PT_FUSE_LOOP": "1"}, {"PT_FUSE_LOOP": "0"}
 BOUNCES = 8
 DLSS_RR = 1  # abi_types.DENOISER_DLSS_RR
 KNOBS = ("PT_TILE_INTERLEAVE", "PT_TILE_ORDER", "PT_TILE_TABLE", "PT_SKY_FAST", "PT_BEAMS", "PT_REFL_BEAMS", "PT_FUSE_LOOP", "PT_SEG")
-
-
-def _context(dxrs, env, **kw):
-    """A context created under `env` (the knobs are read once, at pt_create)."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return dxrs.Renderer(device=0, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.fixture(scope="module")

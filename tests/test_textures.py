@@ -219,7 +219,7 @@ def test_oracle_identity_textures_change_nothing(dxrs, host, oracle):
 @pytest.mark.parametrize("seed", range(int(os.environ.get("PT_FUZZ_TEX_SEEDS", "12"))))
 def test_gpu_textured_scene_matches_oracle(dxrs, host, oracle, renderer, seed):
     rng = np.random.default_rng(7000 + seed)
-    n = int(rng.choice([3, 8, 20, 500]))  # 500: BVH in global memory
+    n = int(rng.choice([3, 8, 20, 500]))  # (500 is still staged in LDS, like the rest: a tree in global memory is test_gpu_schedule_matrix.py's)
     spheres, materials, ts = make_textured_scene(dxrs, rng, n, seed % 2)
     sd = host.scene(dxrs.host.SCENE_SMALL)[2]
     w, h = int(rng.choice([64, 97])), int(rng.choice([48, 61]))

@@ -1,6 +1,21 @@
 import ctypes as C
+import os
 
 import numpy as np
+
+
+def context_under(dxrs, env, **kw):
+    """A context created under the environment `env` (the knobs are read once, at pt_create); the environment is restored."""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return dxrs.Renderer(device=0, **kw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def rel_l2(a, b):
