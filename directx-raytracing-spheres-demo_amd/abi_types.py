@@ -61,6 +61,25 @@ class PtGBuffer(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in GBUFFER_CHANNELS]
 
 
+# Row N27 (pt_render_gbuffer_packed, pt_render_from_gbuffer; DESIGN.md spec S30): each channel's packed texel as (numpy dtype of its raw
+# words, words per pixel) -- the reference's texture formats (Source/App.cpp:431-447), 79 bytes per pixel against float32's 128 -- and the
+# eight channels a frame from the G-buffer reads (Shaders/Raytracing.hlsl:118-148), in PtGBufferInput's field order
+GBUFFER_PACKED = (("Position", np.float32, 4), ("FlatNormal", np.uint16, 2), ("GeometricNormal", np.uint16, 2), ("LinearDepth", np.float32, 1),
+                  ("NormalizedDepth", np.float32, 1), ("MotionVector", np.uint16, 4), ("BaseColorMetalness", np.uint8, 4), ("DiffuseAlbedo", np.uint16, 4),
+                  ("SpecularAlbedo", np.uint16, 4), ("NormalRoughness", np.uint16, 4), ("IOR", np.uint16, 1), ("Transmission", np.uint8, 1), ("Radiance", np.uint16, 4))
+GBUFFER_PACKED_DTYPE = {name: (dtype, width) for name, dtype, width in GBUFFER_PACKED}
+GBUFFER_FRAME_INPUTS = ("Position", "FlatNormal", "GeometricNormal", "BaseColorMetalness", "NormalRoughness", "IOR", "Transmission", "Radiance")
+GBUFFER_FORMAT_FLOAT32, GBUFFER_FORMAT_PACKED = 0, 1
+
+
+class PtGBufferPacked(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in GBUFFER_CHANNELS]
+
+
+class PtGBufferInput(C.Structure):
+    _fields_ = [("Format", C.c_uint32), ("_pad", C.c_uint32)] + [(name, C.c_void_p) for name in GBUFFER_FRAME_INPUTS]
+
+
 # Row N7 (pt_render_denoiser): GraphicsSettings.Denoiser values (Source/Denoiser.ixx) and the outputs of each mode, with their float32
 # counts per pixel
 DENOISER_NONE, DENOISER_DLSS_RR, DENOISER_NRD_REBLUR, DENOISER_NRD_RELAX = 0, 1, 2, 3

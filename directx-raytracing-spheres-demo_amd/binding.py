@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
+from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, GBUFFER_FRAME_INPUTS, GBUFFER_PACKED_DTYPE, PtGBufferInput, PtGBufferPacked, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_render_gbuffer_packed", "pt_render_from_gbuffer", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
     "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
@@ -126,6 +126,10 @@ class HipLib:
         lib.pt_sharc_upload.argtypes = [vp, vp, vp, u32]
         lib.pt_render_lens.restype = C.c_int
         lib.pt_render_lens.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtStats)]
+        lib.pt_render_gbuffer_packed.restype = C.c_int
+        lib.pt_render_gbuffer_packed.argtypes = [vp, C.POINTER(PtRect), C.POINTER(PtGBufferPacked), vp, vp]
+        lib.pt_render_from_gbuffer.restype = C.c_int
+        lib.pt_render_from_gbuffer.argtypes = [vp, C.POINTER(PtRect), vp, C.c_int, C.POINTER(PtGBufferInput), C.POINTER(PtDirectLighting), C.POINTER(PtStats)]
         lib.pt_upscale.restype = C.c_int
         lib.pt_upscale.argtypes = [vp, C.POINTER(PtUpscaleSettings), C.POINTER(PtUpscaleTextures)]
         lib.pt_upscale_input_size.restype = C.c_int
@@ -743,6 +747,72 @@ class Renderer:
         if not want_stats:
             self.synchronize()
         return out, stats
+
+    def render_gbuffer_packed_device(self, buffers, rect=None, previous_spheres=None, previous_rotations=None):
+        """render_gbuffer_device into the reference's texel formats (row N27, DESIGN.md spec S30; pt_render_gbuffer_packed): buffers =
+        {channel name: device pointer}, each rect.w * rect.h texels of abi_types.GBUFFER_PACKED, aligned to its texel.  Asynchronous, ordered
+        like render_gbuffer_device."""
+        unknown = set(buffers) - {name for name, _ in GBUFFER_CHANNELS}
+        if unknown:
+            raise ValueError(f"unknown G-buffer channels {sorted(unknown)}")
+        gb = PtGBufferPacked(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        r = PtRect(*rect) if rect is not None else None
+        ps = np.ascontiguousarray(previous_spheres) if previous_spheres is not None else None
+        pr = np.ascontiguousarray(previous_rotations, dtype=np.float32) if previous_rotations is not None else None
+        self._check(self._lib.pt_render_gbuffer_packed(self._ctx, C.byref(r) if r is not None else None, C.byref(gb),
+                                                       ps.ctypes.data if ps is not None else None, pr.ctypes.data if pr is not None else None))
+
+    def render_gbuffer_packed(self, channels="all", rect=None, previous_spheres=None, previous_rotations=None, fill=0xAB, device=None):
+        """render_gbuffer_packed_device into torch buffers whose every byte is `fill` (what a texel the pass does not write keeps) ->
+        {channel: numpy array (h, w, words) of the texel's raw words (abi_types.GBUFFER_PACKED)}.  Synchronous."""
+        import torch
+        names = [name for name, _ in GBUFFER_CHANNELS] if channels == "all" else list(channels)
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        shapes = {name: (GBUFFER_PACKED_DTYPE[name][0], GBUFFER_PACKED_DTYPE[name][1]) for name in names}
+        bufs = {name: torch.full((h * w * width * np.dtype(dtype).itemsize,), fill, dtype=torch.uint8, device=dev) for name, (dtype, width) in shapes.items()}
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        self.render_gbuffer_packed_device({name: b.data_ptr() for name, b in bufs.items()}, rect, previous_spheres, previous_rotations)
+        self.synchronize()
+        return {name: b.cpu().numpy().view(shapes[name][0]).reshape(h, w, shapes[name][1]) for name, b in bufs.items()}
+
+    def render_from_gbuffer_device(self, out_ptr, inputs, fmt=0, rect=None, diffuse_ptr=None, specular_ptr=None, want_stats=False):
+        """The pure path-traced frame whose first vertex is the G-buffer's texel instead of a traced ray (row N27, DESIGN.md spec S30;
+        pt_render_from_gbuffer) into device memory.  inputs = {name: device pointer} for the eight channels of abi_types.GBUFFER_FRAME_INPUTS,
+        rect-sized, in the float32 layouts of render_gbuffer_device (fmt 0) or the packed ones of render_gbuffer_packed_device (fmt 1);
+        diffuse_ptr / specular_ptr: the DI as for render_with_di_device (None: no DI).  Runs on the lane of the next render call, after a
+        G-buffer call queued there just before without a wait; asynchronous unless want_stats."""
+        r = PtRect(*rect) if rect is not None else None
+        unknown = set(inputs) - set(GBUFFER_FRAME_INPUTS)
+        if unknown:
+            raise ValueError(f"unknown G-buffer frame inputs {sorted(unknown)}")
+        gi = PtGBufferInput(Format=fmt, **{name: C.c_void_p(int(ptr)) for name, ptr in inputs.items() if ptr})
+        di = PtDirectLighting(Diffuse=C.c_void_p(int(diffuse_ptr or 0)), Specular=C.c_void_p(int(specular_ptr or 0))) if diffuse_ptr or specular_ptr else None
+        stats = PtStats()
+        self._check(self._lib.pt_render_from_gbuffer(self._ctx, C.byref(r) if r is not None else None, C.c_void_p(out_ptr or 0), 1, C.byref(gi),
+                                                     C.byref(di) if di is not None else None, C.byref(stats) if want_stats else None))
+        return stats
+
+    def render_from_gbuffer(self, inputs, fmt=0, rect=None, di=None, device=None):
+        """render_from_gbuffer_device with the inputs given as numpy arrays {name: array} (float32 for fmt 0, the raw words render_gbuffer_packed
+        returns for fmt 1) and di = None or (diffuse, specular) float32 (h, w, 4) -> (image (h, w, 4) float32, stats).  Synchronous."""
+        import torch
+        if rect is None:
+            rect = (0, 0, self._gs.RenderSize[0], self._gs.RenderSize[1])
+        w, h = rect[2], rect[3]
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+
+        def on_device(a):
+            return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(dev)
+        bufs = {name: on_device(a) for name, a in inputs.items()}
+        dd, ds = (on_device(np.asarray(a, dtype=np.float32)) for a in di) if di is not None else (None, None)
+        out = torch.zeros((h, w, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)  # (filled on torch's stream, which the context's stream knows nothing of)
+        stats = self.render_from_gbuffer_device(out.data_ptr(), {name: b.data_ptr() for name, b in bufs.items()}, fmt, rect,
+                                                dd.data_ptr() if dd is not None else None, ds.data_ptr() if ds is not None else None, want_stats=True)
+        return out.cpu().numpy(), stats
 
     def render_sharc_ex_device(self, out_ptr, diffuse_ptr=None, specular_ptr=None, rect=None, mode=0, buffers=None, want_stats=False, **settings):
         """render_sharc_device with the frame's direct illumination and denoiser outputs (row N18, DESIGN.md spec S24; pt_render_sharc_ex).

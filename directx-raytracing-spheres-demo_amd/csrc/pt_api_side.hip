@@ -1,6 +1,6 @@
 // pt_api_side.hip -- the entry points of the C-ABI (include/pt_api.h) that are side passes of a frame: work for the frame the NEXT render call renders,
 // queued on the lane that frame will take and ordered against the caller's stream like the frame itself (pt_lane_order.h, side_pass_begin): the G-buffer pass,
-// the reservoir pass, the frame through the radiance cache and the frame through the thin-lens camera, with their downloads.  The frames and the shared helpers (end of pt_context.h) are in pt_api.hip.
+// the reservoir pass, the frame through the radiance cache, the frame through the thin-lens camera and the frame from G-buffer texels, with their downloads.  The frames and the shared helpers (end of pt_context.h) are in pt_api.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,30 +10,34 @@
 #include "pt_lightris.h"
 #include "pt_sharc.h"
 #include "pt_lens.h"
+#include "pt_gbframe.h"
 
 // Row N6 -- the G-buffer pass of the frame the next pt_render renders, on the lane that frame will use (DESIGN.md spec S12).
 // published (pt_render_gbuffer_published, spec S28): the previous pose is the generation published before the newest one, copied on the
 // device by the lane's take (lane_catch_up); the two pointers are null.
-static PtStatus gbuffer_pass(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations, bool published)
+static PtStatus gbuffer_pass(PtContext* c, const PtRect* rect, void* const* gb13, const PtSphere* previous_spheres, const float* previous_rotations, bool published,
+                             bool packed = false)
 {
     if (!c) return PT_ERR_INVALID_ARG;
-    if (!gb) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: null PtGBuffer");
-    // the requested channels; every buffer must be aligned to its channel's vector width (float4: 16 B, float2: 8 B, else 4 B)
-    void* const ptrs[13] = { gb->Position, gb->FlatNormal, gb->GeometricNormal, gb->LinearDepth, gb->NormalizedDepth, gb->MotionVector,
-                             gb->BaseColorMetalness, gb->DiffuseAlbedo, gb->SpecularAlbedo, gb->NormalRoughness, gb->IOR, gb->Transmission, gb->Radiance };
-    const uint32_t align[13] = { 16, 8, 8, 4, 4, 4, 16, 4, 4, 16, 4, 4, 4 };
+    // packed (pt_render_gbuffer_packed, row N27, spec S30): the same pass stored in the reference's texel formats
+    const std::string who = packed ? "pt_render_gbuffer_packed" : "pt_render_gbuffer";
+    if (!gb13) return fail(c, PT_ERR_INVALID_ARG, who + (packed ? ": null PtGBufferPacked" : ": null PtGBuffer"));
+    // the requested channels; every buffer must be aligned to its channel's vector width (float4: 16 B, float2: 8 B, else 4 B), a packed one to its texel
+    void* const* ptrs = gb13;
+    const uint32_t align_f32[13] = { 16, 8, 8, 4, 4, 4, 16, 4, 4, 16, 4, 4, 4 };
+    const uint32_t* align = packed ? kGbPackedTexelBytes : align_f32;
     uint32_t want = 0;
     for (uint32_t k = 0; k < 13; k++) {
         if (!ptrs[k]) continue;
-        if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: a buffer is not aligned to its channel's width");
+        if (reinterpret_cast<uintptr_t>(ptrs[k]) % align[k]) return fail(c, PT_ERR_INVALID_ARG, who + ": a buffer is not aligned to its channel's width");
         want |= 1u << k;
     }
-    if (!want) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: no output requested (all 13 pointers are NULL)");
+    if (!want) return fail(c, PT_ERR_INVALID_ARG, who + ": no output requested (all 13 pointers are NULL)");
     PtStatus st = validate_frame(c);
     if (st != PT_OK) return st;
     PtRect r;
     PixelMap pm{};
-    if ((st = rect_pixel_map(c, rect, "pt_render_gbuffer", r, pm)) != PT_OK) return st;
+    if ((st = rect_pixel_map(c, rect, who.c_str(), r, pm)) != PT_OK) return st;
     if ((st = check_environment(c)) != PT_OK) return st;
     if ((st = check_tree_lds(c)) != PT_OK) return st;
     // previous poses (PreviousObjectToWorld): only while the scene is not static; the empty scene has none
@@ -42,10 +46,10 @@ static PtStatus gbuffer_pass(PtContext* c, const PtRect* rect, const PtGBuffer* 
     for (uint32_t i = 0; use_prev_sph && i < n; i++) {
         const PtSphere& p = previous_spheres[i];
         if (!std::isfinite(p.cx) || !std::isfinite(p.cy) || !std::isfinite(p.cz) || !std::isfinite(p.r) || !(p.r > 0.0f))
-            return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous sphere " + std::to_string(i) + " is not finite or has radius <= 0");
+            return fail(c, PT_ERR_INVALID_ARG, who + ": previous sphere " + std::to_string(i) + " is not finite or has radius <= 0");
     }
     for (uint32_t i = 0; use_prev_rot && i < 4u * n; i++)
-        if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, "pt_render_gbuffer: previous rotation " + std::to_string(i / 4) + " is not finite");
+        if (!std::isfinite(previous_rotations[i])) return fail(c, PT_ERR_INVALID_ARG, who + ": previous rotation " + std::to_string(i / 4) + " is not finite");
     if (published && n > 0 && !c->pub.order.sph_live)
         return fail(c, PT_ERR_STATE, "pt_render_gbuffer_published: the scene's newest spheres are not a published pose (pt_physics_publish first)");
     PT_HIP(c, hipSetDevice(c->device));
@@ -88,26 +92,56 @@ static PtStatus gbuffer_pass(PtContext* c, const PtRect* rect, const PtGBuffer* 
     std::memcpy(fr.world_to_projection, c->cam.Matrices[5], sizeof fr.world_to_projection);
     std::memcpy(fr.prev_world_to_projection, c->cam.Matrices[2], sizeof fr.prev_world_to_projection);
     std::memcpy(fr.prev_world_to_view, c->cam.Matrices[0], sizeof fr.prev_world_to_view);
-    const GBufferOut out{ static_cast<float4*>(ptrs[0]), static_cast<float2*>(ptrs[1]), static_cast<float2*>(ptrs[2]), static_cast<float*>(ptrs[3]), static_cast<float*>(ptrs[4]),
-                          static_cast<f3*>(ptrs[5]), static_cast<float4*>(ptrs[6]), static_cast<f3*>(ptrs[7]), static_cast<f3*>(ptrs[8]), static_cast<float4*>(ptrs[9]),
-                          static_cast<float*>(ptrs[10]), static_cast<float*>(ptrs[11]), static_cast<f3*>(ptrs[12]) };  // (GBufferOut's members in the order of ptrs)
     st = PT_OK;
-    if (const hipError_t e = launch_gbuffer(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream); e != hipSuccess)
-        st = fail(c, PT_ERR_HIP, std::string("pt_render_gbuffer: launch: ") + hipGetErrorString(e));
-    return publish_lane_to_caller(c, L, "pt_render_gbuffer", st);
+    hipError_t e;
+    if (packed) {
+        const GBufferPackedOut out{ static_cast<float4*>(ptrs[0]), static_cast<uint32_t*>(ptrs[1]), static_cast<uint32_t*>(ptrs[2]), static_cast<float*>(ptrs[3]),
+                                    static_cast<float*>(ptrs[4]), static_cast<uint64_t*>(ptrs[5]), static_cast<uint32_t*>(ptrs[6]), static_cast<uint64_t*>(ptrs[7]),
+                                    static_cast<uint64_t*>(ptrs[8]), static_cast<uint64_t*>(ptrs[9]), static_cast<uint16_t*>(ptrs[10]), static_cast<uint8_t*>(ptrs[11]),
+                                    static_cast<uint64_t*>(ptrs[12]) };  // (GBufferPackedOut's members in the order of ptrs)
+        e = launch_gbuffer_packed(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream);
+    } else {
+        const GBufferOut out{ static_cast<float4*>(ptrs[0]), static_cast<float2*>(ptrs[1]), static_cast<float2*>(ptrs[2]), static_cast<float*>(ptrs[3]), static_cast<float*>(ptrs[4]),
+                              static_cast<f3*>(ptrs[5]), static_cast<float4*>(ptrs[6]), static_cast<f3*>(ptrs[7]), static_cast<f3*>(ptrs[8]), static_cast<float4*>(ptrs[9]),
+                              static_cast<float*>(ptrs[10]), static_cast<float*>(ptrs[11]), static_cast<f3*>(ptrs[12]) };  // (GBufferOut's members in the order of ptrs)
+        e = launch_gbuffer(sv, pm, fr, sc, out, want, side_pass_grid(c, pm.n_slots), L.stream);
+    }
+    if (e != hipSuccess) st = fail(c, PT_ERR_HIP, who + ": launch: " + hipGetErrorString(e));
+    return publish_lane_to_caller(c, L, who.c_str(), st);
+}
+
+// the 13 pointers of a PtGBuffer / PtGBufferPacked in field order
+template <typename G>
+static void gbuffer_pointers(const G* gb, void* out[13])
+{
+    void* const p[13] = { gb->Position, gb->FlatNormal, gb->GeometricNormal, gb->LinearDepth, gb->NormalizedDepth, gb->MotionVector,
+                          gb->BaseColorMetalness, gb->DiffuseAlbedo, gb->SpecularAlbedo, gb->NormalRoughness, gb->IOR, gb->Transmission, gb->Radiance };
+    std::copy(p, p + 13, out);
 }
 
 extern "C" {
 
 PtStatus pt_render_gbuffer(PtContext* c, const PtRect* rect, const PtGBuffer* gb, const PtSphere* previous_spheres, const float* previous_rotations)
 {
-    return gbuffer_pass(c, rect, gb, previous_spheres, previous_rotations, false);
+    void* p[13];
+    if (gb) gbuffer_pointers(gb, p);
+    return gbuffer_pass(c, rect, gb ? p : nullptr, previous_spheres, previous_rotations, false);
+}
+
+// Row N27 -- pt_render_gbuffer into the reference's texel formats (DESIGN.md spec S30)
+PtStatus pt_render_gbuffer_packed(PtContext* c, const PtRect* rect, const PtGBufferPacked* gb, const PtSphere* previous_spheres, const float* previous_rotations)
+{
+    void* p[13];
+    if (gb) gbuffer_pointers(gb, p);
+    return gbuffer_pass(c, rect, gb ? p : nullptr, previous_spheres, previous_rotations, false, true);
 }
 
 // Row N24 -- pt_render_gbuffer with the previous pose taken from the published ring (DESIGN.md spec S28)
 PtStatus pt_render_gbuffer_published(PtContext* c, const PtRect* rect, const PtGBuffer* gb)
 {
-    return gbuffer_pass(c, rect, gb, nullptr, nullptr, true);
+    void* p[13];
+    if (gb) gbuffer_pointers(gb, p);
+    return gbuffer_pass(c, rect, gb ? p : nullptr, nullptr, nullptr, true);
 }
 
 // Row N10 -- the reservoir pass (DESIGN.md spec S16): two launches on the lane of the next render call, ordered like pt_render_gbuffer;
@@ -579,6 +613,76 @@ PtStatus pt_render_lens(PtContext* c, const PtRect* rect, void* out, int out_is_
     // pt_get_profile: the frame under ms_shade, like the cache's query
     const hipError_t e = profiled_launch(c, L.stream, 2, [&] { return launch_lens(sv, pm, fr, dev_out, counter, side_pass_grid(c, pm.n_slots), L.stream); });
     st = e == hipSuccess ? PT_OK : fail(c, PT_ERR_HIP, std::string("pt_render_lens: launch: ") + hipGetErrorString(e));
+    if (st == PT_OK && timed)
+        if (const PtStatus e2 = side_frame_stats(c, L, counter, stats, out_px, out_px * c->gs.SamplesPerPixel); e2 != PT_OK) return e2;
+    st = publish_lane_to_caller(c, L, who, st);
+    if (st != PT_OK) return st;
+    return staged_out_finish(c, out, !out_is_device, out_px);
+}
+
+// Row N27 -- the frame whose first vertex is the G-buffer's texel (DESIGN.md spec S30): one launch on the lane of the next render call, on
+// pt_render_lens's lane and ledger (the cache family's query) with the eight input channels and the optional DI as inputs (ledger_gbframe).
+PtStatus pt_render_from_gbuffer(PtContext* c, const PtRect* rect, void* out, int out_is_device, const PtGBufferInput* in, const PtDirectLighting* di, PtStats* stats)
+{
+    const char* who = "pt_render_from_gbuffer";
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!out) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: null output");
+    if (!in) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: null PtGBufferInput");
+    if (in->Format > kGbFormatPacked) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: Format must be 0 (the float32 layouts of PtGBuffer) or 1 (those of PtGBufferPacked)");
+    if (in->_pad != 0) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: PtGBufferInput._pad must be 0");
+    PtStatus st = validate_frame(c);
+    if (st != PT_OK) return st;
+    // the reference's Denoiser::None frame; its IsDIEnabled is `di` (as pt_render_with_di: whatever the constants say once a DI is supplied)
+    if (c->gs.Denoiser) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: Denoiser must be 0 (denoiser outputs through this entry point are not built)");
+    if (c->gs.IsDIEnabled && !di) return fail(c, PT_ERR_INVALID_ARG, "pt_render_from_gbuffer: IsDIEnabled is set and no direct lighting is supplied (this frame makes no estimate of its own)");
+    PtRect r;
+    PixelMap pm{};
+    if ((st = rect_pixel_map(c, rect, who, r, pm)) != PT_OK) return st;
+    if ((st = check_environment(c)) != PT_OK) return st;
+    if ((st = check_tree_lds(c)) != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    float4* dev_out = nullptr;
+    const size_t out_px = (size_t)r.w * r.h;
+    if ((st = staged_out_begin(c, out, !out_is_device, out_px, dev_out)) != PT_OK) return st;
+    {
+        // the buffer rule of pt_args.h: every channel present and aligned to its texel, `out` sharing no byte with an input
+        const bool packed = in->Format == kGbFormatPacked;
+        const uint64_t px = out_px;
+        auto texel = [&](uint32_t channel, uint32_t f32_bytes) { return packed ? kGbPackedTexelBytes[channel] : f32_bytes; };
+        auto align = [&](uint32_t channel, uint32_t f32_align) { return packed ? kGbPackedTexelBytes[channel] : f32_align; };
+        const BufferUse use[11] = { { dev_out, px * 16u, 16u, true, true, "out" },
+                                    { in->Position, px * 16u, 16u, false, true, "Position" },
+                                    { in->FlatNormal, px * texel(1, 8), align(1, 8), false, true, "FlatNormal" },
+                                    { in->GeometricNormal, px * texel(2, 8), align(2, 8), false, true, "GeometricNormal" },
+                                    { in->BaseColorMetalness, px * texel(6, 16), align(6, 16), false, true, "BaseColorMetalness" },
+                                    { in->NormalRoughness, px * texel(9, 16), align(9, 16), false, true, "NormalRoughness" },
+                                    { in->IOR, px * texel(10, 4), align(10, 4), false, true, "IOR" },
+                                    { in->Transmission, px * texel(11, 4), align(11, 4), false, true, "Transmission" },
+                                    { in->Radiance, px * texel(12, 12), align(12, 4), false, true, "Radiance" },
+                                    { di ? di->Diffuse : nullptr, px * 16u, 16u, false, di != nullptr, "di->Diffuse" },
+                                    { di ? di->Specular : nullptr, px * 16u, 16u, false, di != nullptr, "di->Specular" } };
+        const std::string msg = check_buffers(who, use, 11);
+        if (!msg.empty()) return fail(c, PT_ERR_INVALID_ARG, msg);
+    }
+    if (!c->d_lens_counters) PT_HIP(c, hipMalloc(&c->d_lens_counters, kMaxLanes * sizeof(unsigned long long)));  // (every call clears its lane's counter on the lane's stream)
+
+    Lane& L = c->lanes[c->next_lane];  // the lane of the next frame
+    const void* const in13[13] = { in->Position, in->FlatNormal, in->GeometricNormal, nullptr, nullptr, nullptr, in->BaseColorMetalness, nullptr, nullptr,
+                                   in->NormalRoughness, in->IOR, in->Transmission, in->Radiance };
+    const bool shared = ledger_gbframe({ c->ledgers, c->n_lanes, c->next_lane }, c->calls == 0, dev_out, in13, di != nullptr, di ? di->Diffuse : nullptr, di ? di->Specular : nullptr);
+    if ((st = side_pass_begin(c, L, shared)) != PT_OK) return st;
+    unsigned long long* counter = c->d_lens_counters + c->next_lane;
+    const bool timed = stats != nullptr;
+    if (timed) PT_HIP(c, hipEventRecord(c->ev0, L.stream));
+    PT_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), L.stream));
+    const SceneView sv = make_scene_view(c, &L);
+    const GbFrame fr = gb_frame(c->cam, c->gs.RenderSize[0], c->gs.RenderSize[1], c->gs.FrameIndex, c->gs.Bounces, c->gs.SamplesPerPixel,
+                                c->gs.IsRussianRouletteEnabled != 0, c->gs.ThroughputThreshold);
+    const GbInput gi{ in->Format, static_cast<const float4*>(in->Position), in->FlatNormal, in->GeometricNormal, in->BaseColorMetalness, in->NormalRoughness, in->IOR,
+                      in->Transmission, in->Radiance, di ? static_cast<const float4*>(di->Diffuse) : nullptr, di ? static_cast<const float4*>(di->Specular) : nullptr };
+    // pt_get_profile: the frame under ms_shade, like pt_render_lens
+    const hipError_t e = profiled_launch(c, L.stream, 2, [&] { return launch_gbframe(sv, pm, fr, gi, dev_out, counter, side_pass_grid(c, pm.n_slots), L.stream); });
+    st = e == hipSuccess ? PT_OK : fail(c, PT_ERR_HIP, std::string("pt_render_from_gbuffer: launch: ") + hipGetErrorString(e));
     if (st == PT_OK && timed)
         if (const PtStatus e2 = side_frame_stats(c, L, counter, stats, out_px, out_px * c->gs.SamplesPerPixel); e2 != PT_OK) return e2;
     st = publish_lane_to_caller(c, L, who, st);

@@ -226,7 +226,8 @@ struct PtContext {
     uint64_t sh_scene = 0;
     bool sh_valid = false;
     hipEvent_t ev_sh = nullptr;
-    // pt_render_lens (row N26): one ray counter per lane (calls on one lane are ordered by its stream), made by the first call
+    // pt_render_lens (row N26): one ray counter per lane (calls on one lane are ordered by its stream), made by the first call;
+    // pt_render_from_gbuffer (row N27) counts its rays there too
     unsigned long long* d_lens_counters = nullptr;
     uint64_t tot_pixels = 0, tot_paths = 0, tot_fixed_bytes = 0, tot_sec_coeff = 96;  // host-known parts of the totals
     uint32_t tot_beam_frames = 0;  // frames since the last reset whose primary pass used the primary-beam lists

@@ -15,6 +15,11 @@
 //   cache (pt_render_sharc*)      asks, with QUERY only, out, SpecularHitDistance, Diffuse, Specular; looks at all five groups; forced by first_call
 //                                 and by a supplied DI; records only with a DI or denoiser outputs: dn = SpecularHitDistance, Diffuse, Specular
 //                                 (nulls without QUERY), di = the DI's buffers or nulls
+//   G-buffer frame                asks out and its 8 input channels; looks at all five groups; forced by first_call, by a supplied DI and by an
+//   (pt_render_from_gbuffer)      input that is not in its OWN lane's gb (made elsewhere: on the caller's stream; written by pt_render_gbuffer*
+//                                 on the same lane just before, it is ordered by the lane's stream); records di = the DI's buffers or nulls
+//                                 with a DI, and, where an input was made elsewhere, gb = the inputs at their channels (nulls between them): a
+//                                 G-buffer, reservoir or cache call of another lane that would write one of them inside the window then waits
 // first_call: no render call has recorded a marker yet (PtContext::calls == 0).  A supplied DI is an input that may have been written on the
 // caller's stream right before the call, after the window marker.  Three asymmetries are kept as they are (removing one would add waits):
 // frames and the G-buffer pass do not look at `ri` (a caller that hands them a DI output of another lane inside the window relies on the
@@ -89,6 +94,18 @@ static inline bool ledger_cache(Ledgers v, bool first_call, bool query, const vo
         me.dn[0] = query ? hit_dist : nullptr; me.dn[1] = query ? diffuse : nullptr; me.dn[2] = query ? specular : nullptr;
         me.di[0] = has_di ? di_d : nullptr; me.di[1] = has_di ? di_s : nullptr;
     }
+    return shared;
+}
+
+// in13: the 8 input channels at their places among PtGBuffer's 13, nulls elsewhere
+static inline bool ledger_gbframe(Ledgers v, bool first_call, const void* out, const void* const in13[13], bool has_di, const void* di_d, const void* di_s)
+{
+    LaneLedger& me = *v.of[v.own];
+    bool elsewhere = false, shared = false;
+    for (int k = 0; k < 13; k++) elsewhere = elsewhere || (in13[k] && std::find(me.gb, me.gb + 13, in13[k]) == me.gb + 13);
+    for (int k = 0; k < 13; k++) shared = shared || other_lane_holds(v, in13[k], kLedgerAll);
+    shared = ledger_cache(v, first_call, true, out, false, nullptr, nullptr, nullptr, has_di, di_d, di_s) || shared || elsewhere;
+    if (elsewhere) std::copy(in13, in13 + 13, me.gb);
     return shared;
 }
 

@@ -64,6 +64,22 @@ struct GBufferGeneration {
         return pt_render_gbuffer(context, nullptr, &o, previousSpheres, previousRotations);
     }
 
+    // The reference's texture formats (Source/App.cpp:431-447; row N27, spec S30): a texel's size, and the Textures read as such textures
+    static constexpr uint32_t PackedTexelBytes[13] = { 16, 4, 4, 4, 4, 8, 4, 8, 8, 8, 2, 1, 8 };  // in Textures' order: 79 bytes per pixel
+    struct PackedTextures : Textures {};  // the same 13 names; each buffer RenderSize texels of PackedTexelBytes, aligned to its texel
+
+    // Render into textures of the reference's formats (pt_render_gbuffer_packed); RenderFlags select as for Render
+    PtStatus Render(PtContext* context, const PackedTextures& textures, const PtSphere* previousSpheres = nullptr, const float* previousRotations = nullptr) const
+    {
+        GBufferGeneration bound;
+        bound.GPUBuffers = textures;
+        bound.RenderFlags = RenderFlags;
+        const PtGBuffer o = bound.Outputs();
+        const PtGBufferPacked q{ o.Position, o.FlatNormal, o.GeometricNormal, o.LinearDepth, o.NormalizedDepth, o.MotionVector, o.BaseColorMetalness,
+                                 o.DiffuseAlbedo, o.SpecularAlbedo, o.NormalRoughness, o.IOR, o.Transmission, o.Radiance };
+        return pt_render_gbuffer_packed(context, nullptr, &q, previousSpheres, previousRotations);
+    }
+
     // Render with PreviousObjectToWorld taken from the device: the pose published before the newest one (Physics in publishing mode;
     // pt_render_gbuffer_published, row N24)
     PtStatus RenderPublished(PtContext* context) const

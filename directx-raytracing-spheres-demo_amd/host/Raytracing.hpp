@@ -263,6 +263,36 @@ struct Raytracing {
         return stats;
     }
 
+    // The G-buffer textures Raytracing.hlsl:118-148 loads as the primary surface of every sample (App.cpp:1235-1268 binds them; row N27,
+    // spec S30): DEVICE buffers of W*H texels in the float32 layouts of GBufferGeneration::Textures (Packed = false) or in the
+    // reference's formats (GBufferGeneration::PackedTextures).
+    struct GBufferTextures {
+        bool Packed = false;
+        const void *Position = nullptr, *FlatNormal = nullptr, *GeometricNormal = nullptr, *BaseColorMetalness = nullptr, *NormalRoughness = nullptr, *IOR = nullptr,
+                   *Transmission = nullptr, *Radiance = nullptr;
+    };
+
+    // Raytracing::Render as the reference's raygen shader runs it, Denoiser::None: no primary ray, the first vertex of every sample is the
+    // G-buffer's texel (pt_render_from_gbuffer).  di: IsDIEnabled with its two textures, nullptr = off.
+    PtStats Render(std::vector<Float4>& radiance, const GBufferTextures& gbuffer, const DirectLighting* di = nullptr)
+    {
+        PtGraphicsSettings constants = m_graphicsSettings;
+        constants.Denoiser = 0;
+        constants.IsDIEnabled = di ? 1 : 0;
+        ThrowIfFailed(pt_set_constants(m_ctx, &constants), m_ctx, "pt_set_constants");
+        radiance.resize(static_cast<size_t>(m_graphicsSettings.RenderSize[0]) * m_graphicsSettings.RenderSize[1]);
+        PtGBufferInput in{};
+        in.Format = gbuffer.Packed ? 1u : 0u;
+        in.Position = gbuffer.Position; in.FlatNormal = gbuffer.FlatNormal; in.GeometricNormal = gbuffer.GeometricNormal;
+        in.BaseColorMetalness = gbuffer.BaseColorMetalness; in.NormalRoughness = gbuffer.NormalRoughness; in.IOR = gbuffer.IOR;
+        in.Transmission = gbuffer.Transmission; in.Radiance = gbuffer.Radiance;
+        PtDirectLighting lighting{};
+        if (di) { lighting.Diffuse = di->Diffuse; lighting.Specular = di->Specular; }
+        PtStats stats{};
+        ThrowIfFailed(pt_render_from_gbuffer(m_ctx, nullptr, radiance.data(), 0, &in, di ? &lighting : nullptr, &stats), m_ctx, "pt_render_from_gbuffer");
+        return stats;
+    }
+
 private:
     PtContext* m_ctx;
     PtGraphicsSettings m_graphicsSettings{};

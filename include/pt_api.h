@@ -31,6 +31,10 @@
  *                            Shaders/Raytracing.hlsl:150-163, 302-318, 376-414
  *   pt_render_lens           Camera::GenerateThinLensRay in front of the bounce loop (declared, never called by the reference; spec S29)
  *                            Shaders/Camera.hlsli:43-54
+ *   pt_render_gbuffer_packed GBufferGeneration::Render into the texture formats App::CreateWindowSizeDependentResources gives them (spec S30)
+ *                            Source/App.cpp:431-447
+ *   pt_render_from_gbuffer   Raytracing::Render's raygen shader as it runs: the primary surface loaded from those textures, not traced
+ *                            (spec S30)   Shaders/Raytracing.hlsl:103-386, Source/App.cpp:1235-1268
  *   pt_upscale               XeSS::SetConstants / Tag / Execute (a stand-in for XeSS / DLSS-SR, spec S17)   Source/XeSS.ixx:46-73,
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
@@ -527,6 +531,56 @@ PtStatus pt_render_sharc_ex(PtContext *ctx, const PtRect *rect, void *out, int o
  * PT_ERR_INVALID_ARG: a null context or `out`; a rect outside RenderSize; an ApertureRadius that is negative, NaN or infinite.
  * PT_ERR_UNSUPPORTED: IsDIEnabled or Denoiser set in the constants.  PT_ERR_STATE: as pt_render. */
 PtStatus pt_render_lens(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, PtStats *stats);
+
+/* Row N27 -- the G-buffer round trip of the reference's frame (DESIGN.md spec S30).
+ *
+ * pt_render_gbuffer_packed: pt_render_gbuffer with the 13 buffers in the formats the reference's textures have (Source/App.cpp:431-447),
+ * 79 bytes per pixel instead of 128:
+ *   Position R32G32B32A32_FLOAT 16 B | FlatNormal, GeometricNormal R16G16_SNORM 4 B | LinearDepth, NormalizedDepth R32_FLOAT 4 B |
+ *   MotionVector R16G16B16A16_FLOAT 8 B (w = 0) | BaseColorMetalness R8G8B8A8_UNORM 4 B | DiffuseAlbedo, SpecularAlbedo R16G16B16A16_FLOAT
+ *   8 B (w = 0) | NormalRoughness R16G16B16A16_SNORM 8 B | IOR R16_FLOAT 2 B | Transmission R8_UNORM 1 B | Radiance R16G16B16A16_FLOAT 8 B
+ *   (w = 1).
+ * Components in memory order x, y, z, w, little-endian; the conversions are spec S30's (this library's own: D3D's rules are pinned by
+ * nothing in the reference tree, no parity with a D3D device is claimed).  In every other respect the contract is pt_render_gbuffer's: the
+ * lane and ordering, the miss rule, Transmission only where Metallic < 1, untouched texels left untouched (texel by texel, the 1- and
+ * 2-byte ones included), the previous poses, the errors.  Each buffer is aligned to its texel size. */
+typedef struct PtGBufferPacked {    /* DEVICE pointers, NULL = not requested; each aligned to its texel: 16 / 8 / 4 / 2 / 1 bytes */
+    void *Position, *FlatNormal, *GeometricNormal, *LinearDepth, *NormalizedDepth, *MotionVector,
+         *BaseColorMetalness, *DiffuseAlbedo, *SpecularAlbedo, *NormalRoughness, *IOR, *Transmission, *Radiance;
+} PtGBufferPacked;
+PtStatus pt_render_gbuffer_packed(PtContext *ctx, const PtRect *rect, const PtGBufferPacked *out,
+                                  const PtSphere *previous_spheres, const float *previous_rotations);
+
+/* pt_render_from_gbuffer: the pure path-traced frame (the DEFAULT permutation, Denoiser::None) as Shaders/Raytracing.hlsl:103-386 runs
+ * it: no primary ray is traced; the first vertex of EVERY sample is the pixel's texel of the eight channels below (:118-148).
+ *   Position.w not finite (a miss): out = (Radiance, 1); nothing else is read, no ray is traced.
+ *   Otherwise P = Position.xyz with spawn offset Position.w along the decoded FlatNormal; front face = dot(decoded GeometricNormal,
+ *   primary direction) < 0; shading normal = NormalRoughness.xyz as stored; material = BaseColor, Metalness, NormalRoughness.w, IOR and
+ *   Metalness < 1 ? Transmission : 0 (Transmission is read only there); emission = Radiance.  From the first bounce on the loop, its
+ *   random numbers and its result (mean of the samples, 0 where not finite, alpha 1) are pt_render's.
+ * Format 0: the float32 layouts of PtGBuffer; with Bounces = 0 and one sample the frame is pt_render's bit for bit, beyond that its
+ * first vertex differs from pt_render's by the octahedral round trip of the normals.  Format 1: the layouts of PtGBufferPacked; the
+ * picture the reference's arithmetic makes from quantised surfaces (biased against pt_render by design).
+ * di (may be NULL): the frame's direct illumination as pt_render_with_di takes it, DI = Diffuse.rgb + Specular.rgb, valid where any
+ * component is positive on a hit pixel; where valid the emission at the second vertex is dropped unless the first left through the
+ * transmission lobe, and out.rgb += DI after the mean.
+ * Buffers are rect.w * rect.h texels, row-major inside the rect.  rect / out / out_is_device / stats: as pt_render_lens; stats->rays
+ * counts the rays of the bounce loop (there is no primary ray).  Runs and is ordered like pt_render_lens, on the lane of the next render
+ * call; the inputs are held to the rule pt_render_with_di states for its DI buffers: written by pt_render_gbuffer* on the same lane just
+ * before (no render call between), they are ordered without a host wait; from anywhere else the frame waits for everything queued on the
+ * context's stream before it.  "Written on the same lane" is read from the lane's record of its latest pt_render_gbuffer* call, as
+ * pt_restir_di reads it: a pointer that call wrote and that the caller has since overwritten on its own stream is not noticed, so callers
+ * keep to the rotation rule (one set of G-buffer buffers per lane, written by this library's pass or made before the window).
+ * PT_ERR_INVALID_ARG: a null context, out or input; an unknown Format or a non-zero _pad; a null or misaligned channel or DI buffer; out
+ * overlapping an input; a bad rect; IsDIEnabled set without di (with di the constants' flag is not read, as for pt_render_with_di; a
+ * Denoiser in the constants is refused by pt_set_constants already).  PT_ERR_STATE: as pt_render. */
+typedef struct PtGBufferInput {     /* DEVICE pointers, all required; aligned as PtGBuffer's (Format 0) or PtGBufferPacked's (Format 1) */
+    uint32_t Format;                /* 0 float32 layouts, 1 packed layouts */
+    uint32_t _pad;                  /* 0 */
+    const void *Position, *FlatNormal, *GeometricNormal, *BaseColorMetalness, *NormalRoughness, *IOR, *Transmission, *Radiance;
+} PtGBufferInput;
+PtStatus pt_render_from_gbuffer(PtContext *ctx, const PtRect *rect, void *out, int out_is_device, const PtGBufferInput *in,
+                                const PtDirectLighting *di, PtStats *stats);
 
 /* Test hooks of row N14: the cache as the last pt_render_sharc call left it -- `capacity` keys (uint64, 0 = empty) and resolved voxels
  * (4 x uint32: fixed-point RGB sums, samples | frames << 16 | stale << 24) to HOST memory -- and the reverse, which installs a cache made

@@ -10,7 +10,8 @@ pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting
 mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendered at the mode's input size through pt_render_gbuffer ->
 pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height; --sharc --restir-di --ray-reconstruction together: the
 reference's default frame, pt_render_gbuffer -> pt_restir_di_ex -> pt_render_sharc_ex (row N18) -> pt_ray_reconstruction; --aperture R [--focus-distance F]: the accumulated frames through the thin-lens camera,
-pt_render_lens, row N26).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
+pt_render_lens, row N26; --from-gbuffer {float,packed}: the accumulated frames with the G-buffer's texel as every sample's primary surface,
+pt_render_gbuffer[_packed] -> pt_render_from_gbuffer, row N27).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
                                         --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] [--bias-correction pairwise] [--reuse-visibility [4 16]] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
@@ -120,6 +121,9 @@ def main():
                     help="the plain path-traced frame through the thin-lens camera (row N26): pt_render_lens with ApertureRadius R, accumulated like pt_render's frames")
     ap.add_argument("--focus-distance", type=float, default=None, metavar="F",
                     help="--aperture: the view depth in focus, through CameraController::SetFocusDistance (default 15: the demo's spheres)")
+    ap.add_argument("--from-gbuffer", default=None, choices=["float", "packed"],
+                    help="the plain path-traced frame the way the reference runs it (row N27): each frame's G-buffer pass (float: pt_render_gbuffer, packed: "
+                         "pt_render_gbuffer_packed, the reference's texture formats), then pt_render_from_gbuffer, which loads it as the primary surface of every sample")
     ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
@@ -136,6 +140,9 @@ def main():
     if args.aperture is not None and (args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale
                                       or args.ray_reconstruction):
         ap.error("--aperture applies to the plain path-traced frame")
+    if args.from_gbuffer and (args.aperture is not None or args.frame_gen or args.sharc or args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di
+                              or args.upscale or args.ray_reconstruction):
+        ap.error("--from-gbuffer applies to the plain path-traced frame")
     if args.focus_distance is not None and args.aperture is None:
         ap.error("--focus-distance applies to --aperture")
     if args.focus_distance is not None and not args.focus_distance > 0.0:
@@ -448,6 +455,13 @@ def main():
         print(f"NRD {args.nrd} (identity denoiser) {w}x{h} -> {args.out}")
         r.close()
         return
+    gb = None
+    if args.from_gbuffer:
+        inputs = t.GBUFFER_FRAME_INPUTS
+        size = {name: 4 * width for name, width in t.GBUFFER_CHANNELS} if args.from_gbuffer == "float" else \
+            {name: np.dtype(dtype).itemsize * width for name, dtype, width in t.GBUFFER_PACKED}
+        gb = {name: torch.zeros(n * size[name], dtype=torch.uint8, device="cuda") for name in inputs}
+        torch.cuda.synchronize()
     for k in range(args.frames):
         gs.FrameIndex = k
         if args.aperture is not None:
@@ -457,6 +471,10 @@ def main():
         r.set_constants(gs)
         if args.aperture is not None:
             r.render_lens_device(frame.data_ptr())
+        elif gb is not None:  # (the pass and the frame that reads it are queued on one lane: no wait between them)
+            ptrs = {name: b.data_ptr() for name, b in gb.items()}
+            (r.render_gbuffer_device if args.from_gbuffer == "float" else r.render_gbuffer_packed_device)(ptrs)
+            r.render_from_gbuffer_device(frame.data_ptr(), ptrs, 0 if args.from_gbuffer == "float" else 1)
         else:
             r.render_device(frame.data_ptr())
         r.accumulate(accum.data_ptr(), frame.data_ptr(), n, k)
@@ -474,6 +492,8 @@ def main():
     Image.fromarray(rgba[..., :3]).save(args.out)
     if args.aperture is not None:  # (pt_get_totals does not count pt_render_lens)
         print(f"thin lens (pt_render_lens, aperture {args.aperture}, in focus at {focus_distance}), {args.frames} frames x {args.spp} spp -> {args.out}")
+    elif gb is not None:  # (nor pt_render_from_gbuffer)
+        print(f"from the {args.from_gbuffer} G-buffer (pt_render_from_gbuffer, {sum(b.numel() for b in gb.values()) // n} bytes per pixel read), {args.frames} frames x {args.spp} spp -> {args.out}")
     else:
         tot = r.totals()
         print(f"{args.frames} frames x {args.spp} spp, {tot.rays} rays -> {args.out}")
