@@ -60,6 +60,16 @@ PT_HD Surf surf_init(bool front, f3 Ng, f3 Ns)
     return s;
 }
 
+// surf_init for a shading normal that normalize() produced (hit_material's Ns): see get_basis_unit
+PT_HD Surf surf_init_unit(bool front, f3 Ng, f3 Ns)
+{
+    Surf s;
+    s.FrontNg = front ? Ng : -Ng;
+    s.Ns = Ns;
+    s.basis = get_basis_unit(Ns);
+    return s;
+}
+
 // EstimateDiffuseProbability (BxDF.hlsli:21-34)
 PT_HD float estimate_diffuse_probability(f3 albedo, f3 f0, float roughness, float nov)
 {

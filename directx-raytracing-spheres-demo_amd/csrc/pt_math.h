@@ -41,10 +41,71 @@ PT_HD float as_float(uint32_t u) { return __builtin_bit_cast(float, u); }
 // normal, v_sqrt_f32 + the neighbour fix-up without the rescaling is exact from 2^-96 up (all 2^32 operands checked on the GPU,
 // tools/experiments/exact_math.hip) -- but the branch to the full expansion that the remaining operands need costs more scalar
 // instructions and scheduling freedom than the vector instructions it saves: C2 0.081 -> 0.083 ms, C3 3.12 -> 3.17 (tools/experiments/README.md).
+// So these three stay the expansions, and the short forms below serve only the call sites whose operands are provably in range.
 PT_HD float pt_sqrt(float x) { return __builtin_sqrtf(x); }
 PT_HD float pt_rcp(float x) { return 1.0f / x; }
 PT_HD float pt_half_rcp(float x) { return 0.5f / x; }
 PT_HD f3 normalize(f3 a) { float inv = pt_rcp(pt_sqrt(dot(a, a))); return a * inv; }
+
+// The short forms, WITHOUT any run-time test of the operand: for call sites where the operand's range is a theorem of the site (the proof is a
+// comment there).  Same bits as pt_sqrt / pt_rcp / pt_half_rcp for every operand inside the contract and for +-0, +-inf and NaN (which return
+// what the hardware estimate returns: the IEEE answer); 9, 5 and 6 instructions.  On the host they are the plain operators.
+//   pt_sqrt_ranged(x):     |x| >= 2^-96, or x special                (below 2^-96 the residuals of the fix-up leave the normal range)
+//   pt_rcp_ranged(x):      2^-126 <= |x| <= 2^126, or x special      (outside, x or 1 / x is subnormal and v_rcp_f32 flushes it)
+//   pt_half_rcp_ranged(x): 2^-126 <= |x| <= 2^125, or x special      (the reciprocal of x + x, which is exact)
+// tests/test_short_math.py sweeps all 2^32 operands of each against the expansion; tests/test_short_math_ranges.py records, on a host build
+// with PT_RANGED defined, the magnitudes that reach each site below.
+enum RangedSite : int {
+    kRsBasisRcp = 0, kRsCosineSin, kRsVndfDisk, kRsVndfNh, kRsVndfPdfRoot, kRsVndfPdfHalf, kRsGeomRootL, kRsGeomRootV,
+    kRsFresnelCos, kRsRefractRoot, kRsCount
+};
+#ifndef PT_RANGED
+#define PT_RANGED(site, x) (x)
+#endif
+
+PT_HD float pt_sqrt_ranged(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    // v_sqrt_f32 is within 1 ulp; the residuals x - s_dn * s and x - s_up * s (one fma each, exact in sign) say which neighbour, if any, is the
+    // correctly rounded root.  +-0, +inf and NaN fail both comparisons and keep the estimate; x < 0 gives the estimate's NaN.
+    float s = __builtin_amdgcn_sqrtf(x);
+    const float s_dn = as_float(as_uint(s) - 1u), s_up = as_float(as_uint(s) + 1u);
+    const float r_dn = pt_fma(-s_dn, s, x), r_up = pt_fma(-s_up, s, x);
+    s = r_dn <= 0.0f ? s_dn : s;
+    s = r_up > 0.0f ? s_up : s;
+    return s;
+#else
+    return __builtin_sqrtf(x);
+#endif
+}
+PT_HD float pt_rcp_ranged(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = __builtin_amdgcn_rcpf(x);
+    const float n = pt_fma(r, pt_fma(-x, r, 1.0f), r);  // one Newton step: r + r * (1 - x * r)
+    return __builtin_amdgcn_classf(x, 0x267) ? r : n;    // +-0, +-inf, NaN (v_cmp_class_f32): the step would make NaN of inf * 0
+#else
+    return 1.0f / x;
+#endif
+}
+PT_HD float pt_half_rcp_ranged(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return pt_rcp_ranged(x + x);
+#else
+    return 0.5f / x;
+#endif
+}
+// Two lemmas the range proofs at the call sites use (fl = rounding to nearest float, which is monotone):
+//   L1  for any float X, fl(1 - X) is NaN, <= 0, or >= 2^-24: X < 1 means X <= 1 - 2^-24, the largest float below 1, and 2^-24 is a float.  So
+//       saturate(1 - X) is 0 or in [2^-24, 1].
+//   L2  for floats a, b and c >= 2^-36, q = fma(-a, b, c) is NaN, +-inf, <= 0, or >= 2^-85.  If a b <= c / 2 (or a b < 0) the exact value is >= c / 2.
+//       Otherwise a b > 2^(ec - 1) with ec = exponent(c) >= -36, so exponent(a) + exponent(b) >= ec - 2 and a b is a multiple of
+//       2^(exponent(a) + exponent(b) - 46) >= 2^(ec - 48) (a subnormal factor only enlarges the other one's exponent and with it the quantum); c is a
+//       multiple of 2^(ec - 23).  The exact c - a b is then a multiple of 2^(ec - 48) >= 2^-84: zero, negative or >= 2^-84, and so is its rounding.
+//   M   Roughness = max(kMinRoughness, r) is >= fl(2e-3) or NaN, so m = Roughness^2 >= 3.99e-6 > 2^-18 and m2 = m * m >= 2^-36, or they are inf / NaN.
+// normalize() for a vector whose squared length d = dot(a, a) is zero, special or >= 2^-96: the root is then in [2^-48, 2^64], inside pt_rcp_ranged's range.
+PT_HD f3 normalize_ranged(f3 a, int site) { float inv = pt_rcp_ranged(pt_sqrt_ranged(PT_RANGED(site, dot(a, a)))); return a * inv; }
 PT_HD float pt_abs(float x) { return __builtin_fabsf(x); }
 PT_HD float pt_max(float a, float b) { return a > b ? a : b; }
 PT_HD float pt_min(float a, float b) { return a < b ? a : b; }
@@ -144,10 +205,8 @@ struct Basis {
 };
 
 // Geometry::GetBasis (SurfaceVectors.hlsli:14)
-PT_HD Basis get_basis(f3 N)
+PT_HD Basis basis_from(f3 N, float sz, float a)  // a = 1 / (sz + N.z)
 {
-    float sz = sign(N.z);
-    float a = pt_rcp(sz + N.z);
     float ya = N.y * a;
     float b = N.x * ya;
     float c = N.x * sz;
@@ -157,6 +216,13 @@ PT_HD Basis get_basis(f3 N)
     m.N = N;
     return m;
 }
+PT_HD Basis get_basis(f3 N) { float sz = sign(N.z); return basis_from(N, sz, pt_rcp(sz + N.z)); }
+// get_basis for an N that normalize() produced (a hit frame's normal, +-, or perturb_normal's result) -- not for a normal a caller hands in.
+// Range proof: sz has the sign of N.z, so |sz + N.z| = fl(1 + |N.z|) >= 1.  A finite component of a * inv, inv = 1 / sqrt(d), d = dot(a, a), is below
+// 2^12: inv finite means d >= 2^-149, so inv <= 2^74.5; if |a.z| >= 2^-63 then d >= fl(a.z^2) >= a.z^2 (1 - 2^-24) (the other two terms of the dot
+// are >= 0 and rounding is monotone), so |a.z| inv <= 1 + 2^-21; otherwise |a.z| inv < 2^-63 * 2^74.5.  Hence |sz + N.z| is in [1, 2^12 + 1], or N.z is
+// inf / NaN.
+PT_HD Basis get_basis_unit(f3 N) { float sz = sign(N.z); return basis_from(N, sz, pt_rcp_ranged(PT_RANGED(kRsBasisRcp, sz + N.z))); }
 PT_HD f3 rotate_vector(const Basis& m, f3 v) { return make_f3(dot(m.T, v), dot(m.B, v), dot(m.N, v)); }
 PT_HD f3 rotate_vector_inverse(const Basis& m, f3 v)
 {
@@ -170,7 +236,7 @@ PT_HD f3 refract(f3 i, f3 n, float eta)
     float c = dot(n, i);
     float k = 1.0f - eta * eta * (1.0f - c * c);
     if (k < 0.0f) return make_f3(0.0f, 0.0f, 0.0f);
-    float a = pt_fma(eta, c, pt_sqrt(k));
+    float a = pt_fma(eta, c, pt_sqrt_ranged(PT_RANGED(kRsRefractRoot, k)));  // k = fl(1 - X) is not < 0 here: NaN, 0 or >= 2^-24 (L1)
     return make_f3(pt_fma(-a, n.x, eta * i.x), pt_fma(-a, n.y, eta * i.y), pt_fma(-a, n.z, eta * i.z));
 }
 
@@ -179,21 +245,27 @@ PT_HD f3 cosine_ray(float u0, float u1)
 {
     float s, c;
     sincos_2pi(u0, s, c);
+    // The first root stays on the expansion: the bounce loop's u1 is rng_float()'s, a multiple of 2^-23, but the function takes any float (the
+    // leaf tests pass it subnormals).  The second radicand is saturate(1 - X): 0 or >= 2^-24 (L1).
     float cos_t = sqrt01(u1);
-    float sin_t = sqrt01(1.0f - cos_t * cos_t);
+    float sin_t = pt_sqrt_ranged(PT_RANGED(kRsCosineSin, saturate(1.0f - cos_t * cos_t)));
     return make_f3(sin_t * c, sin_t * s, cos_t);
 }
 
 PT_HD f3 vndf_ray(float u0, float u1, float roughness, f3 Vl)
 {
     float m = roughness * roughness;
+    // This normalisation stays on the expansion: its squared length is >= 2^-96 only if some |component of Vl| >= 2^-30, which holds for a unit V in
+    // an orthonormal frame but not for the shading normals a caller may hand to the G-buffer passes (Ns = (0, 0, 1e-20) gives Vl.z = 1e-20).
     f3 Vh = normalize(make_f3(m * Vl.x, m * Vl.y, Vl.z));
     float s, c;
     sincos_2pi(u0, s, c);
     float z = pt_fma(1.0f - u1, 1.0f + Vh.z, -Vh.z);
-    float sr = sqrt01(1.0f - z * z);
+    float sr = pt_sqrt_ranged(PT_RANGED(kRsVndfDisk, saturate(1.0f - z * z)));  // 0 or >= 2^-24 (L1)
     f3 Nh = make_f3(pt_fma(sr, c, Vh.x), pt_fma(sr, s, Vh.y), z + Vh.z);
-    return normalize(make_f3(m * Nh.x, m * Nh.y, pt_max(Nh.z, 1e-7f)));
+    // The z component is >= 1e-7 whatever Nh.z is (pt_max returns 1e-7 for NaN), and the dot's other two terms are >= 0: the squared length is
+    // >= fl(1e-14) > 2^-96, or inf / NaN.
+    return normalize_ranged(make_f3(m * Nh.x, m * Nh.y, pt_max(Nh.z, 1e-7f)), kRsVndfNh);
 }
 
 PT_HD float distribution_term(float roughness, float noh)
@@ -212,15 +284,21 @@ PT_HD float vndf_pdf(f3 Vl, float noh, float roughness)
     float m2 = m * m;
     float nov = pt_abs(Vl.z);
     float d = distribution_term(roughness, noh);
-    return d * pt_half_rcp(nov + pt_sqrt(pt_fma(1.0f - m2, nov * nov, m2)));  // D G1 / (4 NoV), one division (0.5 / x)
+    // The radicand q = fma(-(m2 - 1), nov^2, m2) with m2 >= 2^-36 (M) is NaN, inf, <= 0 or >= 2^-85 (L2).  The sum x = nov + sqrt(q), nov >= 0: for
+    // m2 <= 1, q >= m2 and x >= 2^-18; for m2 > 1, q >= m2 / 2 > 1/2 unless (m2 - 1) nov^2 > m2 / 2, which needs nov > 0.7: x >= 0.7.  And
+    // x <= 2^64 + 2^64 when finite, because nov > 2^64 makes nov^2, q and x infinite (or NaN).  So x is in [2^-18, 2^65], or special.
+    const float root = pt_sqrt_ranged(PT_RANGED(kRsVndfPdfRoot, pt_fma(1.0f - m2, nov * nov, m2)));
+    return d * pt_half_rcp_ranged(PT_RANGED(kRsVndfPdfHalf, nov + root));  // D G1 / (4 NoV), one division (0.5 / x)
 }
 
 PT_HD float geometry_term_mod(float roughness, float nol, float nov)
 {
     float m = roughness * roughness;
     float m2 = m * m;
-    float a = nov * sqrt01(pt_fma(pt_fma(-m2, nol, nol), nol, m2));
-    float b = nol * sqrt01(pt_fma(pt_fma(-m2, nov, nov), nov, m2));
+    // Each radicand is fma(t, x, m2) with m2 >= 2^-36 (M): NaN, inf, <= 0 or >= 2^-85 (L2 with a = -t, b = x), and saturate() maps it to 0 or
+    // [2^-85, 1].  The sum a + b has no lower bound (NoL and NoV may both be tiny): its reciprocal stays on the expansion.
+    float a = nov * pt_sqrt_ranged(PT_RANGED(kRsGeomRootL, saturate(pt_fma(pt_fma(-m2, nol, nol), nol, m2))));
+    float b = nol * pt_sqrt_ranged(PT_RANGED(kRsGeomRootV, saturate(pt_fma(pt_fma(-m2, nov, nov), nov, m2))));
     return pt_half_rcp(a + b);  // 0.5 / (a + b)
 }
 
@@ -235,7 +313,7 @@ PT_HD f3 fresnel_schlick(f3 f0, float voh)
 PT_HD float fresnel_dielectric(float eta, float von)
 {
     float sa2 = eta * eta * (1.0f - von * von);
-    float ca = sqrt01(1.0f - sa2);
+    float ca = pt_sqrt_ranged(PT_RANGED(kRsFresnelCos, saturate(1.0f - sa2)));  // 0 or >= 2^-24 (L1)
     float rs = (eta * von - ca) / (eta * von + ca);
     float rp = (eta * ca - von) / (eta * ca + von);
     return 0.5f * (rs * rs + rp * rp);

@@ -947,7 +947,9 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
             end_sample = true;  // the sample drawn on the final iteration is never used and no later sample reads the RNG
             return;
         }
-        const Surf surf = surf_init(hf.front, hf.N, Ns);
+        // Ns is hit_material's: +-hit_frame's normal or perturb_normal's result, both outputs of normalize() (the regenerated hit reads back the
+        // normal that this code stored), which is what get_basis_unit's range proof needs
+        const Surf surf = surf_init_unit(hf.front, hf.N, Ns);
         const f3 V = -ps.d;
         float w[3];
         if (kCacheMode == 2 && regen) {
