@@ -213,6 +213,22 @@ class PtNisTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NIS_TEXTURES]
 
 
+# Row N29 (pt_chromatic_aberration, spec S31): the size, the focus and the per-channel offsets, and the two buffers.  The default offsets
+# are a recollection of upstream's later revision, not read from the reference tree at hand (csrc/pt_chromab.h: kCabDefaultOffsets).
+CHROMATIC_ABERRATION_TEXTURES = ("Color", "Output")
+CHROMATIC_ABERRATION_FOCUS_UV = (0.5, 0.5)
+CHROMATIC_ABERRATION_OFFSETS = (0.003, 0.003, -0.003)
+CHROMATIC_ABERRATION_MAX_OFFSET = 0.0625
+
+
+class PtChromaticAberrationSettings(C.Structure):
+    _fields_ = [("Size", C.c_uint32 * 2), ("FocusUV", C.c_float * 2), ("Offsets", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class PtChromaticAberrationTextures(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in CHROMATIC_ABERRATION_TEXTURES]
+
+
 # Row N23 (pt_physics_*, the PhysX stand-in, spec S27): a body record, the settings, an attractor and a step's report
 PHYSICS_SPRING, PHYSICS_LARGE, PHYSICS_DISABLED = 1, 2, 4
 PHYSICS_INVERSE_SQUARE, PHYSICS_CONSTANT = 0, 1

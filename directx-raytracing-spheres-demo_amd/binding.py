@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, GBUFFER_FRAME_INPUTS, GBUFFER_PACKED_DTYPE, PtGBufferInput, PtGBufferPacked, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
-                        PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtNrdCompositionConstants, PtNrdCompositionTextures,
+                        PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtChromaticAberrationSettings, PtChromaticAberrationTextures, CHROMATIC_ABERRATION_TEXTURES, CHROMATIC_ABERRATION_FOCUS_UV, CHROMATIC_ABERRATION_OFFSETS, PtNrdCompositionConstants, PtNrdCompositionTextures,
                         PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
                         ray_reconstruction_settings, PHYSICS_ATTRACTOR_DTYPE, PHYSICS_BODY_DTYPE, PtPhysicsReport, PtPhysicsSettings, physics_settings)
@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_render_gbuffer_packed", "pt_render_from_gbuffer", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_render_gbuffer_packed", "pt_render_from_gbuffer", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_chromatic_aberration", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
     "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
@@ -136,6 +136,8 @@ class HipLib:
         lib.pt_upscale_input_size.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
         lib.pt_nis_sharpen.restype = C.c_int
         lib.pt_nis_sharpen.argtypes = [vp, C.POINTER(PtNisSettings), C.POINTER(PtNisTextures)]
+        lib.pt_chromatic_aberration.restype = C.c_int
+        lib.pt_chromatic_aberration.argtypes = [vp, C.POINTER(PtChromaticAberrationSettings), C.POINTER(PtChromaticAberrationTextures)]
         lib.pt_frame_gen.restype = C.c_int
         lib.pt_frame_gen.argtypes = [vp, C.POINTER(PtFrameGenSettings), C.POINTER(PtFrameGenTextures), C.POINTER(u32)]
         lib.pt_ray_reconstruction.restype = C.c_int
@@ -889,6 +891,18 @@ class Renderer:
         s = PtNisSettings(Size=(C.c_uint32 * 2)(*size), Sharpness=sharpness, HdrMode=hdr_mode)
         t = PtNisTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
         self._check(self._lib.pt_nis_sharpen(self._ctx, C.byref(s), C.byref(t)))
+
+    def chromatic_aberration_device(self, size, buffers, focus_uv=CHROMATIC_ABERRATION_FOCUS_UV, offsets=CHROMATIC_ABERRATION_OFFSETS):
+        """Chromatic aberration (row N29, DESIGN.md spec S31): Color -> Output, both float4 at size = (w, h); between nis_sharpen_device and
+        bloom in the post chain.  buffers: {CHROMATIC_ABERRATION_TEXTURES name: device pointer}; Output must not overlap Color.  focus_uv
+        in [0, 1]^2; offsets: the factor of r, g, b, each within +-1/16 (channel c is magnified by 1 + offsets[c] about the focus).
+        Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(CHROMATIC_ABERRATION_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown chromatic aberration buffers {sorted(unknown)}")
+        s = PtChromaticAberrationSettings(Size=(C.c_uint32 * 2)(*size), FocusUV=(C.c_float * 2)(*focus_uv), Offsets=(C.c_float * 3)(*offsets))
+        t = PtChromaticAberrationTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_chromatic_aberration(self._ctx, C.byref(s), C.byref(t)))
 
     def frame_gen_device(self, render_size, output_size, buffers, fmt=0, reset=False):
         """The frame-interpolation stand-in (row N13, DESIGN.md spec S19): the frame half way between the previous call's frame and this

@@ -1,6 +1,6 @@
 // pt_api_post.hip -- the entry points of the C-ABI (include/pt_api.h) that touch nothing but the context's stream and their own state:
-// tone mapping, accumulation, bloom, the NRD composition and stand-in, super-resolution, sharpening, frame interpolation and ray
-// reconstruction.
+// tone mapping, accumulation, bloom, the NRD composition and stand-in, super-resolution, sharpening, chromatic aberration, frame
+// interpolation and ray reconstruction.
 // Everything that knows lanes, the scene, the tree or the beam cache is in pt_api.hip and pt_api_side.hip (the side passes of a frame).
 #include <algorithm>
 #include <string>
@@ -11,6 +11,7 @@
 #include "pt_denoise.h"
 #include "pt_upscale.h"
 #include "pt_nis.h"
+#include "pt_chromab.h"
 #include "pt_framegen.h"
 #include "pt_rr.h"
 
@@ -269,6 +270,28 @@ PtStatus pt_nis_sharpen(PtContext* c, const PtNisSettings* s, const PtNisTexture
     PT_HIP(c, hipSetDevice(c->device));
     const NisConfig k = nis_config(s->Sharpness, s->HdrMode);
     PT_HIP(c, launch_nis(static_cast<const float4*>(t->Color), static_cast<float4*>(t->Output), w, h, k, s->HdrMode, c->stream));
+    return PT_OK;
+}
+
+// Row N29 -- chromatic aberration (DESIGN.md spec S31): one launch on the context's stream, no state
+PtStatus pt_chromatic_aberration(PtContext* c, const PtChromaticAberrationSettings* s, const PtChromaticAberrationTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_chromatic_aberration: null pointer");
+    const uint32_t w = s->Size[0], h = s->Size[1];
+    if (w == 0 || h == 0 || w > kCabMaxSize || h > kCabMaxSize) return fail(c, PT_ERR_INVALID_ARG, "pt_chromatic_aberration: Size must be in [1, 16384]");
+    for (const float f : s->FocusUV)
+        if (!is_finite(f) || !(f >= 0.0f && f <= 1.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_chromatic_aberration: FocusUV must be finite and in [0, 1]");
+    for (const float k : s->Offsets)
+        if (!is_finite(k) || !(pt_abs(k) <= kCabMaxOffset)) return fail(c, PT_ERR_INVALID_ARG, "pt_chromatic_aberration: Offsets must be finite and within [-1/16, 1/16]");
+    if (s->_pad) return fail(c, PT_ERR_INVALID_ARG, "pt_chromatic_aberration: padding must be 0");
+    // the output must not share a byte with the input (a lane reads other lanes' texels): no in-place call
+    const uint64_t bytes = (uint64_t)w * h * sizeof(float4);
+    const BufferUse use[2] = { {t->Color, bytes, 16, false, true, "Color"}, {t->Output, bytes, 16, true, true, "Output"} };
+    if (const PtStatus st = buffers_ok(c, "pt_chromatic_aberration", use, 2); st != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    const CabConfig k = cab_config(w, h, s->FocusUV, s->Offsets);
+    PT_HIP(c, launch_chromab(static_cast<const float4*>(t->Color), static_cast<float4*>(t->Output), w, h, k, c->stream));
     return PT_OK;
 }
 

@@ -39,6 +39,8 @@
  *                            Source/App.cpp:1682-1708; pt_upscale_input_size: XeSS::GetInputResolution + the Auto rule, App.cpp:1374-1450
  *   pt_nis_sharpen           Streamline::SetConstants(NISOptions) / Tag / Evaluate(kFeatureNIS) (a stand-in for NIS, spec S18)
  *                            Source/App.cpp:1710-1721, Source/Streamline.ixx:73-74
+ *   pt_chromatic_aberration  the Post-Processing setting "Chromatic Aberration" (README.md:59, between NVIDIA Image Scaling and Bloom); the
+ *                            reference tree holds no source for it, so the arithmetic is this project's own (spec S31)
  *   pt_frame_gen             App::ProcessDLSSFrameGeneration's tags + Streamline's DLSS-G plugin (a stand-in, spec S19)
  *                            Source/App.cpp:1673-1680, 1460-1525
  *   pt_ray_reconstruction    Streamline::SetConstants(DLSSDOptions) / Tag / Evaluate(kFeatureDLSS_RR) (a stand-in for DLSS-RR, spec S21)
@@ -636,6 +638,24 @@ typedef struct PtNisTextures {          /* DEVICE pointers, float4 per texel, Si
     void *Output;                       /* kBufferTypeScalingOutputColor (what pt_bloom and pt_tonemap take) */
 } PtNisTextures;
 PtStatus pt_nis_sharpen(PtContext *ctx, const PtNisSettings *settings, const PtNisTextures *textures);
+
+/* Row N29 -- chromatic aberration (the reference's README lists it among the Post-Processing settings, README.md:59, after NVIDIA Image
+ * Scaling and before Bloom; the reference tree holds no source for it, so DESIGN.md spec S31 is this project's own and claims no
+ * parity): per-channel radial fringing.  Channel c of output texel (x, y) is the bilinear sample, with clamp addressing, of channel c
+ * of the sanitised Color (NaN -> 0, else clamped to [0, 65504]) at x + ((x + 0.5) - FocusUV.x W) Offsets[c], and likewise in y: the
+ * channel is magnified by 1 + Offsets[c] about the focus.  An offset of 0, or a texel whose centre is the focus, returns the sanitised
+ * texel bit for bit; alpha passes through bit for bit.  It sits between pt_nis_sharpen and pt_bloom in the post chain.
+ * On the context's stream (asynchronous), ordered like pt_nis_sharpen: after what is already queued there, before whatever the caller
+ * queues next.  Stateless: no context state, nothing added to pt_get_totals, the render lanes are never touched.
+ * Not built: tile and multi-GPU entry points, a multi-tap spectral variant, barrel distortion, an in-place call, the packed image.
+ * PT_ERR_INVALID_ARG: a null argument or buffer; a size of 0 or above 16384; a FocusUV component that is not finite or outside [0, 1];
+ * an Offsets component that is not finite or above 1/16 in magnitude; a nonzero _pad; a buffer not 16-byte aligned; Output overlapping
+ * Color, Output == Color included (the pass gathers, so it cannot run in place). */
+typedef struct PtChromaticAberrationTextures {   /* DEVICE pointers, float4 per texel, Size[0] x Size[1] texels, row-major */
+    const void *Color;                  /* pt_nis_sharpen's Output, or the radiance at output size */
+    void *Output;                       /* what pt_bloom and pt_tonemap take */
+} PtChromaticAberrationTextures;
+PtStatus pt_chromatic_aberration(PtContext *ctx, const PtChromaticAberrationSettings *settings, const PtChromaticAberrationTextures *textures);
 
 /* Row N13 -- the frame-interpolation stand-in (DLSS frame generation as App::ProcessDLSSFrameGeneration feeds it, Source/App.cpp:1673-1680;
  * DESIGN.md spec S19): after the tone map the reference tags the G-buffer depth, the motion vectors and the tone-mapped HUD-less colour,

@@ -10,6 +10,7 @@
  *   PtNrdCompositionConstants == NRDComposition::Constants   Source/NRDComposition.ixx:23-28 (== Shaders/NRDComposition.hlsl:3-9), 32 B
  *   PtUpscaleSettings     (row N11) the XeSSSettings App::ProcessXeSSSuperResolution fills, plus the output size and the history cap, 32 B
  *   PtNisSettings         (row N12) the sl::NISOptions App::ProcessNIS fills (sharpness, hdrMode; mode is always eSharpen), plus the size, 16 B
+ *   PtChromaticAberrationSettings (row N29) the size, FocusUV and Offsets of the README's Chromatic Aberration entry (no source in the reference tree), 32 B
  *   PtRayReconstructionSettings (row N15) the sizes, jitter and reset of sl::DLSSDOptions / sl::Constants plus the camera fields the stand-in reads, 240 B
  *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
@@ -250,6 +251,15 @@ typedef struct PtNisSettings {
     uint32_t HdrMode;             /* 12: sl::NISHDR: 0 None (what the reference passes), 1 Linear; 2 PQ is PT_ERR_UNSUPPORTED */
 } PtNisSettings;
 
+/* Row N29 (pt_chromatic_aberration, DESIGN.md spec S31): the reference's README lists Chromatic Aberration among its post-processing
+ * settings, between NVIDIA Image Scaling and Bloom; the reference tree holds no source for it, so the fields are this project's own. */
+typedef struct PtChromaticAberrationSettings {
+    uint32_t Size[2];             /*  0: texels of Color and Output, 1..16384 each */
+    float FocusUV[2];             /*  8: the point the fringes radiate from, each in [0, 1]; (0.5, 0.5) is the image centre */
+    float Offsets[3];             /* 16: the signed factor k of r, g, b: a channel is magnified by 1 + k about the focus; |k| <= 1/16 */
+    uint32_t _pad;                /* 28: must be 0 */
+} PtChromaticAberrationSettings;
+
 /* Row N13 (pt_frame_gen, the DLSS-G stand-in of DESIGN.md spec S19): App::ProcessDLSSFrameGeneration (Source/App.cpp:1673-1680) only
  * tags resources; their sizes, the packing of the tone-mapped colour and m_resetHistory travel here. */
 typedef struct PtFrameGenSettings {
@@ -370,6 +380,8 @@ static_assert(sizeof(PtRestirDiShading) == 16 && offsetof(PtRestirDiShading, Fin
 static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
               && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
+static_assert(sizeof(PtChromaticAberrationSettings) == 32 && offsetof(PtChromaticAberrationSettings, FocusUV) == 8 && offsetof(PtChromaticAberrationSettings, Offsets) == 16
+              && offsetof(PtChromaticAberrationSettings, _pad) == 28, "PtChromaticAberrationSettings layout");
 static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
               && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16
@@ -402,6 +414,8 @@ _Static_assert(sizeof(PtRestirDiShading) == 16 && offsetof(PtRestirDiShading, Fi
 _Static_assert(sizeof(PtUpscaleSettings) == 32 && offsetof(PtUpscaleSettings, OutputSize) == 8 && offsetof(PtUpscaleSettings, Jitter) == 16
                && offsetof(PtUpscaleSettings, Reset) == 24 && offsetof(PtUpscaleSettings, MaxHistoryWeight) == 28, "PtUpscaleSettings layout");
 _Static_assert(sizeof(PtNisSettings) == 16 && offsetof(PtNisSettings, Sharpness) == 8 && offsetof(PtNisSettings, HdrMode) == 12, "PtNisSettings layout");
+_Static_assert(sizeof(PtChromaticAberrationSettings) == 32 && offsetof(PtChromaticAberrationSettings, FocusUV) == 8 && offsetof(PtChromaticAberrationSettings, Offsets) == 16
+               && offsetof(PtChromaticAberrationSettings, _pad) == 28, "PtChromaticAberrationSettings layout");
 _Static_assert(sizeof(PtFrameGenSettings) == 32 && offsetof(PtFrameGenSettings, OutputSize) == 8 && offsetof(PtFrameGenSettings, Format) == 16
                && offsetof(PtFrameGenSettings, Reset) == 20 && offsetof(PtFrameGenSettings, _pad) == 24, "PtFrameGenSettings layout");
 _Static_assert(sizeof(PtSharcSettings) == 48 && offsetof(PtSharcSettings, SceneScale) == 8 && offsetof(PtSharcSettings, AccumulationFrames) == 16

@@ -5,7 +5,8 @@ R8G8B8A8 (--nrd: one frame through the NRD path instead, row N8; --nrd-denoise: 
 NRD stand-in, row N9; --restir-di: --frames frames of a resting camera through pt_render_gbuffer -> pt_restir_di -> pt_render_with_di,
 row N10, accumulated; --upscale MODE: --frames frames of a resting camera rendered at the mode's input size with Halton jitter and
 upscaled to --width x --height by pt_upscale, row N11; --nis SHARPNESS: pt_nis_sharpen, row N12, on the frame at output size, after the
-upscaler when there is one and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
+upscaler when there is one and before bloom; --chromatic-aberration R G B: pt_chromatic_aberration, row N29, with the three channels'
+offsets, after --nis and before bloom; --frame-gen MID.png: the frames at --time minus --dt and at --time, and the frame
 pt_frame_gen, row N13, makes between them; --sharc: --frames frames of a resting camera through pt_render_sharc, row N14, the last one tone
 mapped; --ray-reconstruction [MODE]: --frames frames of a resting camera rendered at the mode's input size through pt_render_gbuffer ->
 pt_render_denoiser mode 1 -> pt_ray_reconstruction, row N15, to --width x --height; --sharc --restir-di --ray-reconstruction together: the
@@ -14,7 +15,7 @@ pt_render_lens, row N26; --from-gbuffer {float,packed}: the accumulated frames w
 pt_render_gbuffer[_packed] -> pt_render_from_gbuffer, row N27).  Viewer convenience; the measured output of the hot path is the fp32 HDR radiance buffer.
 
     python tools/render_png.py out.png [--width 1280 --height 720 --spp 8 --frames 16 --bounces 8 --time 0.0 --textures
-                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] [--bias-correction pairwise] [--reuse-visibility [4 16]] | --upscale performance] [--nis 0.5] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
+                                        --texture-dir /path/to/Assets/Textures --bloom 0.05 --gbuffer NormalRoughness | --denoiser-output Diffuse | --nrd ReBLUR | --nrd-denoise ReLAX | --restir-di [--light-sampling regir] [--brdf-samples 1] [--boiling-filter 0.2] [--bias-correction pairwise] [--reuse-visibility [4 16]] | --upscale performance] [--nis 0.5] [--chromatic-aberration 0.003 0.003 -0.003] [--frame-gen mid.png --dt 0.1] [--sharc [--sharc-anti-firefly]] | --sharc --sharc-anti-firefly --restir-di --brdf-samples 1 --boiling-filter 0.2 --ray-reconstruction quality
                                         [--ray-reconstruction [performance]]"""
 import argparse
 import os
@@ -102,6 +103,9 @@ def main():
     ap.add_argument("--nis", type=float, default=None, metavar="SHARPNESS",
                     help="pt_nis_sharpen (row N12; the reference's default sharpness is 0.5) at output size: after pt_upscale with --upscale, "
                          "else on the accumulated radiance; before pt_bloom")
+    ap.add_argument("--chromatic-aberration", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="pt_chromatic_aberration (row N29) about the image centre with these offsets (each within +-1/16; 0.003 0.003 -0.003 are "
+                         "the defaults): wherever --nis applies, after it and before pt_bloom")
     ap.add_argument("--frame-gen", default=None, metavar="MID.png",
                     help="render the scene at --time minus --dt and at --time (one frame each: pt_render_gbuffer with the earlier pose as the "
                          "previous one -> pt_render [-> pt_bloom] -> pt_tonemap) and write the frame pt_frame_gen (row N13) makes between the "
@@ -160,6 +164,11 @@ def main():
         ap.error("--reuse-visibility takes no value or AGE DIST")
     if args.nis is not None and not default_frame and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di):
         ap.error("--nis applies to the path-traced frame, with or without --upscale; not to --gbuffer, --denoiser-output, --nrd, --nrd-denoise or --restir-di")
+    if args.chromatic_aberration is not None:
+        if args.frame_gen or (args.sharc and not default_frame) or (not default_frame and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di)):
+            ap.error("--chromatic-aberration applies where --nis does: the path-traced frame, --upscale, --ray-reconstruction and the default frame")
+        if not all(abs(k) <= dxrs_amd.types.CHROMATIC_ABERRATION_MAX_OFFSET for k in args.chromatic_aberration):
+            ap.error("--chromatic-aberration: each offset must be within +-1/16")
     from PIL import Image
 
     t = dxrs_amd.types
@@ -315,6 +324,9 @@ def main():
         if args.nis is not None:
             r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
             hdr = frame
+        if args.chromatic_aberration is not None:
+            src, hdr = hdr, torch.empty_like(frame)
+            r.chromatic_aberration_device((w, h), dict(Color=src.data_ptr(), Output=hdr.data_ptr()), offsets=args.chromatic_aberration)
         if args.bloom is not None:
             r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
         op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
@@ -367,6 +379,9 @@ def main():
         if args.nis is not None:
             r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
             hdr = frame
+        if args.chromatic_aberration is not None:
+            src, hdr = hdr, torch.empty_like(frame)
+            r.chromatic_aberration_device((w, h), dict(Color=src.data_ptr(), Output=hdr.data_ptr()), offsets=args.chromatic_aberration)
         if args.bloom is not None:
             r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
         op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
@@ -397,6 +412,9 @@ def main():
         if args.nis is not None:
             r.nis_sharpen_device((w, h), dict(Color=hdr.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
             hdr = frame
+        if args.chromatic_aberration is not None:
+            src, hdr = hdr, torch.empty_like(frame)
+            r.chromatic_aberration_device((w, h), dict(Color=src.data_ptr(), Output=hdr.data_ptr()), offsets=args.chromatic_aberration)
         if args.bloom is not None:
             r.bloom(hdr.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
         op = {"saturate": t.TONE_SATURATE, "reinhard": t.TONE_REINHARD, "aces": t.TONE_ACES_FILMIC}[args.operator]
@@ -483,6 +501,9 @@ def main():
     if args.nis is not None:
         r.nis_sharpen_device((w, h), dict(Color=accum.data_ptr(), Output=frame.data_ptr()), sharpness=args.nis)
         hdr = frame
+    if args.chromatic_aberration is not None:
+        src, hdr = hdr, torch.empty_like(accum)
+        r.chromatic_aberration_device((w, h), dict(Color=src.data_ptr(), Output=hdr.data_ptr()), offsets=args.chromatic_aberration)
     if args.bloom is not None:
         src, hdr = hdr, torch.empty_like(accum)  # the running mean stays as it is
         r.bloom(src.data_ptr(), hdr.data_ptr(), w, h, args.bloom)
