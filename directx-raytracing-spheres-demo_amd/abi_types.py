@@ -121,6 +121,22 @@ class PtNrdDenoiseTextures(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in NRD_DENOISE_TEXTURES]
 
 
+# Row N30 (pt_nrd_reblur, the ReBLUR stand-in): its settings; the buffers are PtNrdDenoiseTextures
+class PtNrdReblurSettings(C.Structure):
+    _fields_ = [("RenderSize", C.c_uint32 * 2), ("AccumulationMode", C.c_uint32), ("FrameIndex", C.c_uint32), ("MaxAccumulatedFrames", C.c_uint32),
+                ("MaxFastAccumulatedFrames", C.c_uint32), ("HistoryFixFrames", C.c_uint32), ("MinBlurRadius", C.c_float), ("MaxBlurRadius", C.c_float),
+                ("_pad", C.c_uint32 * 3)]
+
+
+def nrd_reblur_settings(width, height, accumulation_mode=0, frame_index=0, max_accumulated_frames=0, max_fast_accumulated_frames=0, history_fix_frames=0,
+                        min_blur_radius=0.0, max_blur_radius=0.0):
+    """PtNrdReblurSettings from keywords; 0 = nrd::ReblurSettings' defaults as recollected: 30 frames, 6 fast frames, 3 history-fix frames,
+    radii 1 and 30 pixels"""
+    return PtNrdReblurSettings(RenderSize=(C.c_uint32 * 2)(width, height), AccumulationMode=accumulation_mode, FrameIndex=frame_index,
+                               MaxAccumulatedFrames=max_accumulated_frames, MaxFastAccumulatedFrames=max_fast_accumulated_frames,
+                               HistoryFixFrames=history_fix_frames, MinBlurRadius=float(min_blur_radius), MaxBlurRadius=float(max_blur_radius))
+
+
 # Row N10 (pt_restir_di, the RTXDI stand-in): the settings and the buffers it reads (G-buffer channels) and writes
 RESTIR_DI_INPUTS = ("Position", "GeometricNormal", "LinearDepth", "MotionVector", "BaseColorMetalness", "NormalRoughness", "IOR", "Transmission")
 RESTIR_DI_TEXTURES = RESTIR_DI_INPUTS + ("Diffuse", "Specular")

@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi_types import (BVH_NODE_DTYPE, DENOISER_OUTPUTS, FRAME_GEN_TEXTURES, GBUFFER_CHANNELS, GBUFFER_FRAME_INPUTS, GBUFFER_PACKED_DTYPE, PtGBufferInput, PtGBufferPacked, NIS_TEXTURES, NRD_DENOISE_TEXTURES, NRD_REBLUR_HIT_DISTANCE, NRD_TEXTURES, PtAccelInfo,
                         PtCamera, PtConfig, PtDenoiserOutputs, PtDirectLighting, PtFrameGenSettings, PtFrameGenTextures, PtGBuffer, PtGraphicsSettings, PtNisSettings, PtNisTextures, PtChromaticAberrationSettings, PtChromaticAberrationTextures, CHROMATIC_ABERRATION_TEXTURES, CHROMATIC_ABERRATION_FOCUS_UV, CHROMATIC_ABERRATION_OFFSETS, PtNrdCompositionConstants, PtNrdCompositionTextures,
-                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
+                        PtNrdDenoiseSettings, PtNrdDenoiseTextures, PtNrdReblurSettings, nrd_reblur_settings, PtRect, PtLightSamplingSettings, LIGHT_RIS_ENTRY_DTYPE, light_sampling_settings, PtRestirDiCandidates, restir_di_candidates, PtRestirDiShading, restir_di_shading, PtRestirDiSettings, PtSharcSettings, PtRestirDiTextures, PtSceneData, PtStats, PtUpscaleSettings, PtUpscaleTextures,
                         PtRayReconstructionSettings, PtRayReconstructionTextures, RAY_RECONSTRUCTION_TEXTURES, RESTIR_DI_TEXTURES, UPSCALE_TEXTURES,
                         ray_reconstruction_settings, PHYSICS_ATTRACTOR_DTYPE, PHYSICS_BODY_DTYPE, PtPhysicsReport, PtPhysicsSettings, physics_settings)
 
@@ -20,7 +20,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERR_INVALID_ARG", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR
 # every symbol include/pt_api.h declares
 API_SYMBOLS = [
     "pt_create", "pt_destroy", "pt_set_scene", "pt_build_accel", "pt_update_spheres", "pt_refit_accel", "pt_set_camera", "pt_set_constants", "pt_render",
-    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_render_gbuffer_packed", "pt_render_from_gbuffer", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_chromatic_aberration", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
+    "pt_set_partition", "pt_tiles_count", "pt_render_tiles", "pt_unpack_tiles", "pt_set_partition_ex", "pt_tiles_count_ex", "pt_unpack_tiles_ex", "pt_tonemap", "pt_accumulate", "pt_bloom", "pt_render_gbuffer", "pt_render_denoiser", "pt_render_with_di", "pt_nrd_composition", "pt_nrd_denoise", "pt_nrd_reblur", "pt_nrd_reblur_history", "pt_restir_di", "pt_restir_di_sampled", "pt_restir_di_ex", "pt_restir_di_full", "pt_restir_di_history", "pt_light_ris_download", "pt_render_sharc", "pt_render_sharc_ex", "pt_sharc_download", "pt_sharc_upload", "pt_render_lens", "pt_render_gbuffer_packed", "pt_render_from_gbuffer", "pt_upscale", "pt_upscale_input_size", "pt_nis_sharpen", "pt_chromatic_aberration", "pt_frame_gen", "pt_ray_reconstruction", "pt_ray_reconstruction_history", "pt_set_textures", "pt_update_rotations", "pt_pack_rgb", "pt_unpack_tiles_rgb", "pt_trace_rays", "pt_trace_rays_stats", "pt_accel_download",
     "pt_accel_download_order", "pt_accel_download_wide", "pt_lbvh_build_host", "pt_sah_build_host", "pt_set_profiling", "pt_get_profile", "pt_get_totals", "pt_get_queue_sizes", "pt_get_refl_stats", "pt_synchronize", "pt_last_error", "pt_version",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_device_alloc", "pt_device_free", "pt_download",
     "pt_physics_create", "pt_physics_set_attractors", "pt_physics_step", "pt_physics_download", "pt_physics_destroy",
@@ -102,6 +102,10 @@ class HipLib:
         lib.pt_nrd_composition.argtypes = [vp, C.POINTER(PtNrdCompositionConstants), C.POINTER(PtNrdCompositionTextures)]
         lib.pt_nrd_denoise.restype = C.c_int
         lib.pt_nrd_denoise.argtypes = [vp, C.POINTER(PtNrdDenoiseSettings), C.POINTER(PtNrdDenoiseTextures)]
+        lib.pt_nrd_reblur.restype = C.c_int
+        lib.pt_nrd_reblur.argtypes = [vp, C.POINTER(PtNrdReblurSettings), C.POINTER(PtNrdDenoiseTextures)]
+        lib.pt_nrd_reblur_history.restype = C.c_int
+        lib.pt_nrd_reblur_history.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.pt_restir_di.restype = C.c_int
         lib.pt_restir_di.argtypes = [vp, C.POINTER(PtRestirDiSettings), C.POINTER(PtRestirDiTextures)]
         lib.pt_restir_di_sampled.restype = C.c_int
@@ -623,6 +627,24 @@ class Renderer:
         t = PtNrdDenoiseTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
         self._check(self._lib.pt_nrd_denoise(self._ctx, C.byref(s), C.byref(t)))
 
+    def nrd_reblur_device(self, width, height, buffers, **settings):
+        """The ReBLUR stand-in (row N30, DESIGN.md spec S32) over width x height pixels: the In buffers pt_nrd_composition packed with
+        DENOISER_NRD_REBLUR -> the Out buffers its compose reads, with a history of its own in the context (apart from nrd_denoise_device's).
+        buffers: {NRD_DENOISE_TEXTURES name: device pointer} (BaseColorMetalness may be left out).  settings: abi_types.nrd_reblur_settings'
+        keywords.  Asynchronous on the context's stream."""
+        unknown = set(buffers) - set(NRD_DENOISE_TEXTURES)
+        if unknown:
+            raise ValueError(f"unknown NRD denoise buffers {sorted(unknown)}")
+        s = nrd_reblur_settings(width, height, **settings)
+        t = PtNrdDenoiseTextures(**{name: C.c_void_p(int(ptr)) for name, ptr in buffers.items() if ptr})
+        self._check(self._lib.pt_nrd_reblur(self._ctx, C.byref(s), C.byref(t)))
+
+    def nrd_reblur_history(self, width, height):
+        """pt_nrd_reblur_history -> dict slow_d, slow_s, fast_d, fast_s, guide: the slot the last nrd_reblur_device call wrote, (h, w, 4) each"""
+        out = {k: np.zeros((height, width, 4), np.float32) for k in ("slow_d", "slow_s", "fast_d", "fast_s", "guide")}
+        self._check(self._lib.pt_nrd_reblur_history(self._ctx, *[a.ctypes.data for a in out.values()]))
+        return out
+
     def restir_di_device(self, width, height, buffers, frame_index=0, reset_history=False, initial_samples=0, temporal=True, temporal_bias=1,
                          max_history=0, spatial=True, spatial_bias=1, spatial_samples=0, spatial_radius=0.0, light_sampling=None,
                          candidates=None, shading=None):
@@ -953,6 +975,11 @@ class Renderer:
         settings: nrd_denoise_device's keywords.  `previous_pose` = (previous_spheres, previous_rotations) for the next G-buffer."""
         return NrdDenoiser(self, mode, rect, device, settings)
 
+    def nrd_reblur_denoiser(self, rect=None, device=None, **settings):
+        """nrd_denoiser's counterpart backed by pt_nrd_reblur (row N30): a `denoise(diffuse, specular)` for nrd_chain(DENOISER_NRD_REBLUR).
+        settings: nrd_reblur_device's keywords; `frame_index` advances by one per call from the value given (default 0)."""
+        return NrdDenoiser(self, 2, rect, device, settings, reblur=True)
+
     def pack_rgb(self, src_ptr, n_pixels, dst_ptr):
         """device float4[n] -> device 3 floats per pixel (the 12-byte exchange format)"""
         self._check(self._lib.pt_pack_rgb(self._ctx, C.c_void_p(src_ptr), n_pixels, C.c_void_p(dst_ptr)))
@@ -1011,11 +1038,12 @@ def sharc_settings(capacity=0, downscale_factor=0, scene_scale=0.0, roughness_th
 
 
 class NrdDenoiser:
-    """Renderer.nrd_denoiser: the `denoise` callable nrd_chain takes, backed by pt_nrd_denoise."""
+    """Renderer.nrd_denoiser / nrd_reblur_denoiser: the `denoise` callable nrd_chain takes, backed by pt_nrd_denoise or (reblur) pt_nrd_reblur."""
 
-    def __init__(self, renderer, mode, rect, device, settings):
+    def __init__(self, renderer, mode, rect, device, settings, reblur=False):
         import torch
-        self._r, self.mode, self.settings = renderer, mode, dict(settings)
+        self._r, self.mode, self.settings, self.reblur = renderer, mode, dict(settings), reblur
+        self.frame_index = self.settings.pop("frame_index", 0) if reblur else 0
         if rect is None:
             rect = (0, 0, renderer._gs.RenderSize[0], renderer._gs.RenderSize[1])
         self.w, self.h = rect[2], rect[3]
@@ -1036,11 +1064,14 @@ class NrdDenoiser:
         torch.cuda.synchronize(diffuse.device)
         mode = 2 if self._restart else self.settings.get("accumulation_mode", 0)
         settings = dict(self.settings, accumulation_mode=mode)
-        self._r.nrd_denoise_device(self.mode, self.w, self.h, dict(ViewZ=self.guides["LinearDepth"].data_ptr(),
-                                                                   MotionVector=self.gbuffer["MotionVector"].data_ptr(),
-                                                                   NormalRoughness=self.guides["NormalRoughness"].data_ptr(),
-                                                                   InDiffuse=diffuse.data_ptr(), InSpecular=specular.data_ptr(),
-                                                                   OutDiffuse=od.data_ptr(), OutSpecular=os_.data_ptr()), **settings)
+        buffers = dict(ViewZ=self.guides["LinearDepth"].data_ptr(), MotionVector=self.gbuffer["MotionVector"].data_ptr(),
+                       NormalRoughness=self.guides["NormalRoughness"].data_ptr(), InDiffuse=diffuse.data_ptr(), InSpecular=specular.data_ptr(),
+                       OutDiffuse=od.data_ptr(), OutSpecular=os_.data_ptr())
+        if self.reblur:
+            self._r.nrd_reblur_device(self.w, self.h, buffers, frame_index=self.frame_index, **settings)
+            self.frame_index += 1
+        else:
+            self._r.nrd_denoise_device(self.mode, self.w, self.h, buffers, **settings)
         self._r.synchronize()
         self._restart = False
         return od, os_

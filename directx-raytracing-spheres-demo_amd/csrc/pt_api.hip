@@ -1392,7 +1392,7 @@ void pt_destroy(PtContext* c)
     for (auto& e : c->pub.ev_slot) if (e) (void)hipEventDestroy(e);
     free_dev(c->d_out);
     free_dev(c->d_bloom);
-    for (History* H : { &c->dn, &c->up, &c->fg, &c->rr }) free_dev(H->mem);
+    for (History* H : { &c->dn, &c->up, &c->fg, &c->rr, &c->rb }) free_dev(H->mem);
     free_dev(c->d_ri);
     free_dev(c->d_lr_pyramid);
     free_dev(c->d_lr_ris);

@@ -9,6 +9,7 @@
 #include "pt_bloom.h"
 #include "pt_nrd.h"
 #include "pt_denoise.h"
+#include "pt_reblur.h"
 #include "pt_upscale.h"
 #include "pt_nis.h"
 #include "pt_chromab.h"
@@ -20,6 +21,9 @@ namespace {
 // Row N9's history and work buffers per pixel: two history slots of four float4 (accumulated diffuse / specular, moments, guide), two
 // hit distances, two a-trous ping-pong pairs of float4.
 constexpr uint64_t kDnBytesPerPixel = 2 * 4 * sizeof(float4) + 2 * sizeof(float) + 4 * sizeof(float4);
+// Row N30's history and work buffers per pixel: two history slots of five float4 (slow diffuse / specular, fast diffuse / specular,
+// guide) and two work float4.
+constexpr uint64_t kRbBytesPerPixel = 2 * 5 * sizeof(float4) + 2 * sizeof(float4);
 // Row N11's history per output pixel and slot: a float4 (t-space colour, accumulated weight) and a float (depth).
 constexpr uint64_t kUpSlotBytesPerPixel = sizeof(float4) + sizeof(float);
 // Row N15's history per output pixel and slot: two float4 (t-space colour + weight, normal + roughness) and a float (depth); its
@@ -198,6 +202,84 @@ PtStatus pt_nrd_denoise(PtContext* c, const PtNrdDenoiseSettings* s, const PtNrd
     const uint32_t iterations = s->AtrousIterations ? s->AtrousIterations : kDnDefaultIterations;
     PT_HIP(c, launch_nrd_denoise(b, s->Denoiser, P, iterations, c->stream));
     history_commit(c->dn, s->Denoiser);
+    return PT_OK;
+}
+
+// Row N30 -- the ReBLUR stand-in (DESIGN.md spec S32): passes (a) to (d) on the context's stream, the history in the context
+// (kRbBytesPerPixel), apart from pt_nrd_denoise's.
+PtStatus pt_nrd_reblur(PtContext* c, const PtNrdReblurSettings* s, const PtNrdDenoiseTextures* t)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!s || !t) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: null pointer");
+    if (s->AccumulationMode > 2) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: AccumulationMode must be 0, 1 or 2");
+    const uint32_t w = s->RenderSize[0], h = s->RenderSize[1];
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: RenderSize must be in [1, 16384]");
+    RbParams P{};
+    P.max_n = s->MaxAccumulatedFrames ? s->MaxAccumulatedFrames : kRbDefaultFrames;
+    P.max_fast = s->MaxFastAccumulatedFrames ? s->MaxFastAccumulatedFrames : kRbDefaultFastFrames;
+    P.fix_frames = s->HistoryFixFrames ? s->HistoryFixFrames : kRbDefaultFixFrames;
+    if (P.max_fast > P.max_n) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: MaxFastAccumulatedFrames must be at most MaxAccumulatedFrames");
+    for (const float r : { s->MinBlurRadius, s->MaxBlurRadius })
+        if (!is_finite(r) || !(r >= 0.0f)) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: MinBlurRadius and MaxBlurRadius must be finite and not negative");
+    P.rmin = s->MinBlurRadius != 0.0f ? s->MinBlurRadius : kRbDefaultMinRadius;
+    P.rmax = s->MaxBlurRadius != 0.0f ? s->MaxBlurRadius : kRbDefaultMaxRadius;
+    if (P.rmax > kRbMaxRadius) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: MaxBlurRadius must be at most 64");
+    if (P.rmin > P.rmax) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: MinBlurRadius must be at most MaxBlurRadius");
+    if (s->_pad[0] || s->_pad[1] || s->_pad[2]) return fail(c, PT_ERR_INVALID_ARG, "pt_nrd_reblur: padding must be 0");
+    const uint64_t n = (uint64_t)w * h;
+    // an output must not share a byte with any input or the other output (the passes read their neighbours' inputs)
+    const BufferUse use[8] = {
+        {t->ViewZ, n * 4, 4, false, true, "ViewZ"}, {t->MotionVector, n * 12, 4, false, true, "MotionVector"},
+        {t->NormalRoughness, n * 16, 16, false, true, "NormalRoughness"}, {t->BaseColorMetalness, n * 16, 16, false, false, "BaseColorMetalness"},
+        {t->InDiffuse, n * 16, 16, false, true, "InDiffuse"}, {t->InSpecular, n * 16, 16, false, true, "InSpecular"},
+        {t->OutDiffuse, n * 16, 16, true, true, "OutDiffuse"}, {t->OutSpecular, n * 16, 16, true, true, "OutSpecular"},
+    };
+    if (const PtStatus st = buffers_ok(c, "pt_nrd_reblur", use, 8); st != PT_OK) return st;
+    PT_HIP(c, hipSetDevice(c->device));
+    bool restart = s->AccumulationMode != 0 || !c->rb.valid;  // (a change of RenderSize makes a new allocation, which restarts)
+    if (const PtStatus st = history_begin(c, c->rb, {w, h}, n * kRbBytesPerPixel, restart); st != PT_OK) return st;
+    // the allocation: per slot slow[2], fast[2], guide; then the work buffers x[2]
+    float4* const f4 = static_cast<float4*>(c->rb.mem);
+    const uint32_t cur = c->rb.slot ^ 1u, prev = c->rb.slot;
+    RbBuffers b{};
+    b.w = w;
+    b.h = h;
+    b.viewz = static_cast<const float*>(t->ViewZ);
+    b.mv = static_cast<const float*>(t->MotionVector);
+    b.nr = static_cast<const float4*>(t->NormalRoughness);
+    b.in_d = static_cast<const float4*>(t->InDiffuse);
+    b.in_s = static_cast<const float4*>(t->InSpecular);
+    b.out_d = static_cast<float4*>(t->OutDiffuse);
+    b.out_s = static_cast<float4*>(t->OutSpecular);
+    for (int l = 0; l < 2; l++) {
+        b.prev_slow[l] = f4 + (uint64_t)(5 * prev + l) * n;
+        b.prev_fast[l] = f4 + (uint64_t)(5 * prev + 2 + l) * n;
+        b.slow[l] = f4 + (uint64_t)(5 * cur + l) * n;
+        b.fast[l] = f4 + (uint64_t)(5 * cur + 2 + l) * n;
+        b.x[l] = f4 + (uint64_t)(10 + l) * n;
+    }
+    b.prev_guide = f4 + (uint64_t)(5 * prev + 4) * n;
+    b.guide = f4 + (uint64_t)(5 * cur + 4) * n;
+    P.restart = restart ? 1u : 0u;
+    P.frame = s->FrameIndex;
+    PT_HIP(c, launch_nrd_reblur(b, P, c->stream));
+    history_commit(c->rb, 0);
+    return PT_OK;
+}
+
+// the slot the last pt_nrd_reblur call wrote, for tests: slow diffuse, slow specular, fast diffuse, fast specular, guide (float4 per
+// pixel each; a null pointer skips one).  Waits for the stream.
+PtStatus pt_nrd_reblur_history(PtContext* c, void* slow_d, void* slow_s, void* fast_d, void* fast_s, void* guide)
+{
+    if (!c) return PT_ERR_INVALID_ARG;
+    if (!c->rb.valid || !c->rb.mem) return fail(c, PT_ERR_STATE, "pt_nrd_reblur_history: no pt_nrd_reblur call has been made");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t n = (uint64_t)c->rb.dims[0] * c->rb.dims[1];
+    const float4* const f4 = static_cast<const float4*>(c->rb.mem) + (uint64_t)5 * c->rb.slot * n;
+    void* const dst[5] = { slow_d, slow_s, fast_d, fast_s, guide };
+    for (int k = 0; k < 5; k++)
+        if (dst[k]) PT_HIP(c, hipMemcpy(dst[k], f4 + (uint64_t)k * n, n * sizeof(float4), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

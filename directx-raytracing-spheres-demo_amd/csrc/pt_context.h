@@ -198,6 +198,8 @@ struct PtContext {
     //       Depth (4 B per render pixel); dims = RenderSize, OutputSize, tag = the Format
     //   rr  pt_ray_reconstruction (row N15): per slot and output pixel two float4 and a float, then the prepare pass's three float4
     //       records per render pixel; dims = OutputSize, RenderSize, no tag
+    //   rb  pt_nrd_reblur (row N30): history and work buffers, kRbBytesPerPixel per pixel; dims = RenderSize, no tag (last: the members
+    //       before it keep their places)
     History dn, up, fg, rr;
     // pt_restir_di's history (row N10): two alternating slots of kRiBytesPerPixel / 2 bytes per pixel (surface record + reservoir),
     // allocated on first use and again when RenderSize changes; `ri_slot` = the slot the last call wrote, `ri_scene` = the
@@ -298,6 +300,7 @@ struct PtContext {
     bool profiling = false;
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;
+    History rb;
 };
 
 inline PtStatus fail(PtContext* ctx, PtStatus st, const std::string& msg)

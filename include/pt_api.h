@@ -21,6 +21,8 @@
  *   pt_render_with_di        Raytracing::Render with IsDIEnabled = isReSTIRDIEnabled   Source/App.cpp:1262, Shaders/Raytracing.hlsl:150-163
  *   pt_nrd_denoise           NRD::NewFrame / Tag / SetConstants / Denoise (a stand-in for NRD, spec S15)   Source/NRD.ixx:88-140,
  *                            Source/App.cpp:1584-1638
+ *   pt_nrd_reblur            the same with nrd::Denoiser::REBLUR_DIFFUSE_SPECULAR's own arithmetic (a recurrent-blur stand-in, spec S32)
+ *                            Source/Denoiser.ixx:8, Source/App.cpp:1618-1637
  *   pt_restir_di             RTXDI::SetConstants / Render: the DI passes (a stand-in for RTXDI, spec S16)   Source/App.cpp:1187-1227,
  *                            Shaders/DIInitialSampling.hlsl ... DIFinalShading.hlsl over Shaders/RTXDIAppBridge.hlsli
  *   pt_restir_di_sampled     the same with Power_RIS / ReGIR_RIS local-light presampling (spec S22)                 Source/RTXDI.ixx:209-226
@@ -370,6 +372,26 @@ typedef struct PtNrdDenoiseTextures {   /* DEVICE pointers; the reference's nrd:
     void *OutDiffuse, *OutSpecular;     /* OUT_DIFF / OUT_SPEC_RADIANCE_HITDIST: float4, what compose reads */
 } PtNrdDenoiseTextures;
 PtStatus pt_nrd_denoise(PtContext *ctx, const PtNrdDenoiseSettings *settings, const PtNrdDenoiseTextures *textures);
+
+/* Row N30 -- the ReBLUR stand-in (the ReBLUR branch of App::ProcessNRD, Source/App.cpp:1618-1637; DESIGN.md spec S32): a recurrent-blur
+ * denoiser of ReBLUR's family -- temporal accumulation into a slow and a fast history (a resting mirror accumulates too), a history fix
+ * and a clamp of the slow history to the fast one, then a blur and a post-blur over a rotated 8-point disc whose radius shrinks with the
+ * history length and grows with the normalised hit distance; the post-blur's result is Out and the next call's history.  No variance,
+ * no luminance edge-stopping.  It takes PtNrdDenoiseTextures unchanged; In and Out are always in ReBLUR's encoding (YCoCg + normalised
+ * hit distance: what pt_nrd_composition packs and composes with Denoiser = 2); Out.w is the reconstructed hit distance.  pt_nrd_denoise
+ * is unchanged, and the two may alternate on one context: each owns its history (this one: allocated on first use, freed by pt_destroy).
+ * On the context's stream (asynchronous), ordered like pt_nrd_denoise; it adds nothing to pt_get_totals.  A pixel whose ViewZ is not
+ * finite (a miss) is never written.  The first call, a non-zero AccumulationMode and a change of RenderSize restart the history.
+ * The arithmetic is this project's own.  Out of scope: NRD's exact ReBLUR, its pre-pass, temporal stabilisation, virtual-motion specular
+ * reprojection, OUT_VALIDATION, and the checkerboard and half-resolution modes.
+ * PT_ERR_INVALID_ARG: a null argument; AccumulationMode above 2; a RenderSize of 0 or > 16384; MaxFastAccumulatedFrames above
+ * MaxAccumulatedFrames (after the defaults); a radius that is not finite or negative, MinBlurRadius above MaxBlurRadius or MaxBlurRadius
+ * above 64 (after the defaults); non-zero padding; and pt_nrd_denoise's buffer rules. */
+PtStatus pt_nrd_reblur(PtContext *ctx, const PtNrdReblurSettings *settings, const PtNrdDenoiseTextures *textures);
+/* Test / tooling hook: the history slot the last pt_nrd_reblur call wrote, to HOST arrays of RenderSize float4 texels (any may be
+ * NULL): the slow history per lobe (the blurred signal, its hit distance: Out itself), the fast history per lobe (the signal, the
+ * history length) and the guide (ViewZ, normal).  Waits for the context's stream.  PT_ERR_STATE: no call has been made yet. */
+PtStatus pt_nrd_reblur_history(PtContext *ctx, void *slow_diffuse, void *slow_specular, void *fast_diffuse, void *fast_specular, void *guide);
 
 /* Row N10 -- the reservoir pass that makes the DI pt_render_with_di takes (RTXDI::Render, Source/App.cpp:1187-1227; DESIGN.md spec S16): a
  * ReSTIR-DI stand-in for the RTXDI SDK, which the reference does not vendor -- RIS over InitialSamples uniform (emitter, cone) candidates

@@ -14,6 +14,7 @@
  *   PtRayReconstructionSettings (row N15) the sizes, jitter and reset of sl::DLSSDOptions / sl::Constants plus the camera fields the stand-in reads, 240 B
  *   PtFrameGenSettings    (row N13) the sizes, the packing and the reset flag of the frame-interpolation stand-in (the reference hands DLSS-G only tags), 32 B
  *   PtNrdDenoiseSettings  (row N9) the parts of nrd::CommonSettings / ReblurSettings / RelaxSettings the NRD stand-in reads, 32 B
+ *   PtNrdReblurSettings   (row N30) the parts of nrd::CommonSettings / ReblurSettings the ReBLUR stand-in reads, 48 B
  *   PtSharcSettings       (row N14) SHARCSettings (Source/MyAppData.h:256-265) plus the cache's accumulation constants, 48 B
  *   PtLightSamplingSettings (row N16) the local-light sampling mode and the ReGIR settings (Source/MyAppData.h:194-218), 32 B
  *   PtRestirDiCandidates  (row N17) InitialSampling.BRDFSamples and TemporalResampling.BoilingFilter (Source/MyAppData.h:220-235), 16 B
@@ -182,6 +183,22 @@ typedef struct PtNrdDenoiseSettings {
     uint32_t MaxSpecularFrames;   /* 24: 0 -> 30 */
     uint32_t AtrousIterations;    /* 28: 0 -> 5, at most 8 */
 } PtNrdDenoiseSettings;
+
+/* Row N30 (pt_nrd_reblur, the ReBLUR stand-in of DESIGN.md spec S32): what App::ProcessNRD hands NRD through nrd::CommonSettings
+ * (rectSize, frameIndex, accumulationMode) and the history lengths and blur radii of nrd::ReblurSettings.  0 = the default; the defaults
+ * are nrd::ReblurSettings' (maxAccumulatedFrameNum 30, maxFastAccumulatedFrameNum 6, historyFixFrameNum 3, minBlurRadius 1, maxBlurRadius
+ * 30) as recollected: the reference does not vendor the NRD SDK. */
+typedef struct PtNrdReblurSettings {
+    uint32_t RenderSize[2];            /*  0: 1..16384 each */
+    uint32_t AccumulationMode;         /*  8: nrd::AccumulationMode: 0 CONTINUE, 1 RESTART, 2 CLEAR_AND_RESTART */
+    uint32_t FrameIndex;               /* 12: read: it turns the blur's tap pattern */
+    uint32_t MaxAccumulatedFrames;     /* 16: 0 -> 30 */
+    uint32_t MaxFastAccumulatedFrames; /* 20: 0 -> 6; at most MaxAccumulatedFrames */
+    uint32_t HistoryFixFrames;         /* 24: 0 -> 3 */
+    float MinBlurRadius;               /* 28: pixels; 0 -> 1; finite, >= 0, at most MaxBlurRadius */
+    float MaxBlurRadius;               /* 32: pixels; 0 -> 30; finite, >= 0, at most 64 */
+    uint32_t _pad[3];                  /* 36: must be 0 */
+} PtNrdReblurSettings;
 
 /* Row N10 (pt_restir_di, the RTXDI stand-in of DESIGN.md spec S16): what RTXDI::SetConstants hands the DI passes (Source/App.cpp:1187-1227;
  * defaults of Source/MyAppData.h:190-250). */
@@ -368,6 +385,10 @@ static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdCompositi
               "NRDComposition::Constants layout");
 static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
               && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
+static_assert(sizeof(PtNrdReblurSettings) == 48 && offsetof(PtNrdReblurSettings, AccumulationMode) == 8 && offsetof(PtNrdReblurSettings, FrameIndex) == 12
+              && offsetof(PtNrdReblurSettings, MaxAccumulatedFrames) == 16 && offsetof(PtNrdReblurSettings, MaxFastAccumulatedFrames) == 20
+              && offsetof(PtNrdReblurSettings, HistoryFixFrames) == 24 && offsetof(PtNrdReblurSettings, MinBlurRadius) == 28
+              && offsetof(PtNrdReblurSettings, MaxBlurRadius) == 32 && offsetof(PtNrdReblurSettings, _pad) == 36, "PtNrdReblurSettings layout");
 static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
               && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingSettings, TileSize) == 4 && offsetof(PtLightSamplingSettings, TileCount) == 8
@@ -402,6 +423,10 @@ _Static_assert(sizeof(PtNrdCompositionConstants) == 32 && offsetof(PtNrdComposit
                "NRDComposition::Constants layout");
 _Static_assert(sizeof(PtNrdDenoiseSettings) == 32 && offsetof(PtNrdDenoiseSettings, Denoiser) == 8 && offsetof(PtNrdDenoiseSettings, AccumulationMode) == 12
                && offsetof(PtNrdDenoiseSettings, MaxDiffuseFrames) == 20 && offsetof(PtNrdDenoiseSettings, AtrousIterations) == 28, "PtNrdDenoiseSettings layout");
+_Static_assert(sizeof(PtNrdReblurSettings) == 48 && offsetof(PtNrdReblurSettings, AccumulationMode) == 8 && offsetof(PtNrdReblurSettings, FrameIndex) == 12
+               && offsetof(PtNrdReblurSettings, MaxAccumulatedFrames) == 16 && offsetof(PtNrdReblurSettings, MaxFastAccumulatedFrames) == 20
+               && offsetof(PtNrdReblurSettings, HistoryFixFrames) == 24 && offsetof(PtNrdReblurSettings, MinBlurRadius) == 28
+               && offsetof(PtNrdReblurSettings, MaxBlurRadius) == 32 && offsetof(PtNrdReblurSettings, _pad) == 36, "PtNrdReblurSettings layout");
 _Static_assert(sizeof(PtRestirDiSettings) == 48 && offsetof(PtRestirDiSettings, ResetHistory) == 12 && offsetof(PtRestirDiSettings, TemporalBiasCorrection) == 24
                && offsetof(PtRestirDiSettings, EnableSpatial) == 32 && offsetof(PtRestirDiSettings, SpatialRadius) == 44, "PtRestirDiSettings layout");
 _Static_assert(sizeof(PtLightSamplingSettings) == 32 && offsetof(PtLightSamplingSettings, TileSize) == 4 && offsetof(PtLightSamplingSettings, TileCount) == 8

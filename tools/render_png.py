@@ -79,6 +79,9 @@ def main():
     ap.add_argument("--nrd-denoise", default=None, choices=["ReBLUR", "ReLAX"],
                     help="--frames frames of a resting camera through the NRD path with pt_nrd_denoise for NRD (row N9): pt_render_gbuffer "
                          "-> pt_render_denoiser -> pack -> denoise -> compose; the last frame, tone mapped")
+    ap.add_argument("--nrd-reblur", action="store_true",
+                    help="the chain of --nrd-denoise ReBLUR with pt_nrd_reblur for NRD (row N30: the recurrent-blur stand-in for ReBLUR itself); "
+                         "what applies to --nrd-denoise applies to it")
     ap.add_argument("--restir-di", action="store_true",
                     help="--frames frames of a resting camera whose direct illumination the reservoir pass makes (row N10): pt_render_gbuffer "
                          "-> pt_restir_di (the history running) -> pt_render_with_di, accumulated, tone mapped")
@@ -130,6 +133,10 @@ def main():
                          "pt_render_gbuffer_packed, the reference's texture formats), then pt_render_from_gbuffer, which loads it as the primary surface of every sample")
     ap.add_argument("--dt", type=float, default=0.1, help="--frame-gen: seconds between the two rendered frames")
     args = ap.parse_args()
+    if args.nrd_reblur:
+        if args.nrd_denoise:
+            ap.error("--nrd-reblur and --nrd-denoise are two stand-ins for the same pass: give one")
+        args.nrd_denoise = "ReBLUR"
     if args.frame_gen and (args.gbuffer or args.denoiser_output or args.nrd or args.nrd_denoise or args.restir_di or args.upscale or args.nis is not None):
         ap.error("--frame-gen applies to the plain path-traced frame")
     default_frame = bool(args.sharc and args.restir_di and args.ray_reconstruction)  # the reference's default frame, rows N6 / N17 / N18 / N15
@@ -446,7 +453,7 @@ def main():
     if args.nrd_denoise:
         mode = t.DENOISER_NRD_REBLUR if args.nrd_denoise == "ReBLUR" else t.DENOISER_NRD_RELAX
         r.set_camera(host.camera(w, h, jitter=False))
-        den = r.nrd_denoiser(mode)
+        den = r.nrd_reblur_denoiser() if args.nrd_reblur else r.nrd_denoiser(mode)
         for k in range(args.frames):
             gs.FrameIndex = k
             r.set_constants(gs)
@@ -457,7 +464,7 @@ def main():
         r.tonemap(composed.data_ptr(), n, t.tonemap_params(op, t.TRANSFER_SRGB, args.exposure), ldr.data_ptr())
         r.synchronize()
         Image.fromarray(ldr.cpu().numpy().view(np.uint8).reshape(h, w, 4)[..., :3]).save(args.out)
-        print(f"NRD {args.nrd_denoise} (pt_nrd_denoise, {args.frames} frames) {w}x{h} -> {args.out}")
+        print(f"NRD {args.nrd_denoise} ({'pt_nrd_reblur' if args.nrd_reblur else 'pt_nrd_denoise'}, {args.frames} frames) {w}x{h} -> {args.out}")
         r.close()
         return
     if args.nrd:
