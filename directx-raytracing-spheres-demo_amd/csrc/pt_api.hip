@@ -1214,14 +1214,8 @@ PtStatus publish_lane_to_caller(PtContext* c, Lane& L, const char* who, PtStatus
 static uint64_t rect_slots(const PtRect& r) { return (uint64_t)((r.w + 7) / 8) * ((r.h + 7) / 8) * 64ull; }
 PixelMap make_pixel_map(uint32_t img_w, uint32_t img_h, const PtRect& r)
 {
-    PixelMap pm{};
-    pm.mode = 0;
-    pm.img_w = img_w; pm.img_h = img_h;
-    pm.rx = r.x; pm.ry = r.y; pm.rw = r.w; pm.rh = r.h;
-    pm.blocks_x = (r.w + 7) / 8;
-    pm.inv_blocks_x = 1.0f / (float)pm.blocks_x;
+    PixelMap pm = pixel_map_rect(img_w, img_h, r.x, r.y, r.w, r.h);
     const uint64_t slots = rect_slots(r);
-    pm.exact_div = (slots >> 6) >= (1ull << 22) ? 1u : 0u;  // quotient estimate error stays below one
     pm.n_slots = (uint32_t)slots;
     return pm;
 }
@@ -1764,16 +1758,7 @@ PtStatus pt_render_tiles(PtContext* c, void* out_device_packed, PtStats* stats)
     if (st != PT_OK) return st;
     PT_HIP(c, hipSetDevice(c->device));
     const uint32_t ts = c->tile_size, w = c->gs.RenderSize[0], h = c->gs.RenderSize[1];
-    PixelMap pm{};
-    pm.mode = 1;
-    pm.img_w = w; pm.img_h = h;
-    pm.ts = ts;
-    pm.ts_shift = (uint32_t)__builtin_ctz(ts);
-    pm.tiles_x = (w + ts - 1) / ts;
-    pm.inv_tiles_x = 1.0f / (float)pm.tiles_x;
-    pm.tiles_total = pm.tiles_x * ((h + ts - 1) / ts);
-    pm.first = c->part_first; pm.run = c->part_run; pm.stride = c->part_stride;
-    pm.inv_run = pm.run ? 1.0f / (float)pm.run : 0.0f;
+    PixelMap pm = pixel_map_tiles(w, h, ts, c->part_first, c->part_run, c->part_stride);
     const uint64_t slots = (uint64_t)count_tiles(pm.tiles_total, pm.first, pm.run, pm.stride) * ts * ts;
     if (slots == 0) {  // this rank owns no tile of the frame
         if (stats) std::memset(stats, 0, sizeof *stats);
@@ -1781,7 +1766,6 @@ PtStatus pt_render_tiles(PtContext* c, void* out_device_packed, PtStats* stats)
     }
     if (slots > 0xFFFFFFFFull) return fail(c, PT_ERR_INVALID_ARG, "pt_render_tiles: too many pixels");
     pm.n_slots = (uint32_t)slots;
-    pm.exact_div = (slots >> (2u * pm.ts_shift)) >= (1ull << 22) ? 1u : 0u;
     return render_common(c, pm, count_tile_pixels(w, h, ts, pm.first, pm.run, pm.stride), static_cast<float4*>(out_device_packed), stats);
 }
 

@@ -264,19 +264,31 @@ PT_HD CameraParams camera_params(const PtCamera& c, uint32_t w, uint32_t h)
     return p;
 }
 
-PT_HD void primary_ray(const CameraParams& cam, uint32_t px, uint32_t py, f3& o, f3& d, float& tmin, float& tmax)
+// the direction part of the primary ray: everything up to normalize (a sky tile of the primary pass needs nothing else)
+PT_HD f3 primary_dir(const CameraParams& cam, uint32_t px, uint32_t py)
 {
     float u = ((float)px + 0.5f + cam.JitterX) * cam.InvW;
     float v = ((float)py + 0.5f + cam.JitterY) * cam.InvH;
     float nx = pt_fma(u, 2.0f, -1.0f);
     float ny = pt_fma(v, -2.0f, 1.0f);
     f3 dir = mad(ny, cam.Up, cam.Right * nx) + cam.Forward;
-    dir = normalize(dir);
+    return normalize(dir);
+}
+
+// the range part: [Near, Far] along the view axis, as distances along dir (one division and two multiplies)
+PT_HD void primary_range(const CameraParams& cam, f3 dir, float& tmin, float& tmax)
+{
     float inv_cos = pt_rcp(dot(cam.ForwardN, dir));
-    o = cam.Position;
-    d = dir;
     tmin = cam.Near * inv_cos;
     tmax = cam.Far * inv_cos;
+}
+
+PT_HD void primary_ray(const CameraParams& cam, uint32_t px, uint32_t py, f3& o, f3& d, float& tmin, float& tmax)
+{
+    const f3 dir = primary_dir(cam, px, py);
+    o = cam.Position;
+    d = dir;
+    primary_range(cam, dir, tmin, tmax);
 }
 
 }  // namespace pt

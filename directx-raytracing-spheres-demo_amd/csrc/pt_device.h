@@ -9,6 +9,7 @@
 #include "pt_texture.h"
 #include "pt_surface.h"
 #include "pt_light.h"
+#include "pt_pixel_map.h"
 
 namespace pt {
 
@@ -77,75 +78,7 @@ struct SceneView {
 };
 
 // ---- slot -> pixel mapping ---------------------------------------------------------------------------
-// A slot is 64-aligned to an 8x8 pixel block so that one wave64 = one 8x8 block of pixels.
-//   mode 0 (rect):  block b = slot / 64 over ceil(w/8) x ceil(h/8) blocks of the rect
-//   mode 1 (tiles): tile k = slot / ts^2 is this rank's k-th tile = global tile (rank + k * world)
-struct PixelMap {
-    uint32_t mode;
-    uint32_t img_w, img_h;        // RenderSize
-    uint32_t rx, ry, rw, rh;      // rect (mode 0)
-    uint32_t blocks_x;            // ceil(rw / 8) (mode 0)
-    uint32_t ts, tiles_x, tiles_total;  // mode 1 (ts = 1 << ts_shift)
-    // mode 1 ownership: the tiles t with first <= t % stride < first + run, in increasing t (pt_set_partition_ex);
-    // the plain rank/world interleave is (first, run, stride) = (rank, 1, world)
-    uint32_t first, run, stride;
-    uint32_t ts_shift;
-    uint32_t n_slots;
-    float inv_blocks_x, inv_tiles_x, inv_run;  // reciprocals for fast_div
-    uint32_t exact_div;               // 1: slot counts too large for the float-reciprocal division
-};
-
-struct PixelRef {
-    uint32_t px, py;     // global pixel
-    uint32_t out_index;  // index into the output float4 buffer
-    bool valid;
-};
-
-// n / d for a launch-invariant divisor: float reciprocal + one exact correction step.  Valid while n < 2^22 (the float
-// conversion is exact and the quotient estimate is off by at most one); PixelMap::exact_div selects the plain division
-// for larger slot counts.  A 32-bit integer division costs ~25 VALU instructions on gfx950, this ~8.
-__device__ __forceinline__ uint32_t fast_div(uint32_t n, uint32_t d, float inv_d, bool exact_div)
-{
-    if (exact_div) return n / d;
-    uint32_t q = (uint32_t)((float)n * inv_d);
-    const int32_t r = (int32_t)(n - q * d);
-    if (r < 0) q--; else if ((uint32_t)r >= d) q++;
-    return q;
-}
-
-__device__ __forceinline__ PixelRef slot_to_pixel(const PixelMap& m, uint32_t slot)
-{
-    PixelRef r;
-    if (m.mode == 0) {
-        const uint32_t b = slot >> 6, l = slot & 63u;
-        const uint32_t by = fast_div(b, m.blocks_x, m.inv_blocks_x, m.exact_div != 0), bx = b - by * m.blocks_x;
-        const uint32_t x = bx * 8u + (l & 7u), y = by * 8u + (l >> 3);
-        r.valid = x < m.rw && y < m.rh;
-        r.px = m.rx + x;
-        r.py = m.ry + y;
-        r.out_index = y * m.rw + x;
-    } else {
-        // tile edge ts is a power of two >= 8 (ts_shift = log2 ts): shifts and masks only, except the tile -> (tx, ty) split
-        const uint32_t ts2_shift = 2u * m.ts_shift;
-        const uint32_t k = slot >> ts2_shift, w = slot & ((1u << ts2_shift) - 1u);
-        const uint32_t bpt_shift = m.ts_shift - 3u;  // 8x8 blocks per tile row = ts / 8
-        const uint32_t b = w >> 6, l = w & 63u;
-        const uint32_t lx = ((b & ((1u << bpt_shift) - 1u)) << 3) + (l & 7u), ly = ((b >> bpt_shift) << 3) + (l >> 3);
-        uint32_t gt;
-        if (m.run == 1u) {
-            gt = m.first + k * m.stride;
-        } else {
-            const uint32_t q = fast_div(k, m.run, m.inv_run, m.exact_div != 0);
-            gt = m.first + q * m.stride + (k - q * m.run);
-        }
-        const uint32_t ty = fast_div(gt, m.tiles_x, m.inv_tiles_x, m.exact_div != 0), tx = gt - ty * m.tiles_x;
-        r.px = (tx << m.ts_shift) + lx;
-        r.py = (ty << m.ts_shift) + ly;
-        r.valid = gt < m.tiles_total && r.px < m.img_w && r.py < m.img_h;
-        r.out_index = (k << ts2_shift) + (ly << m.ts_shift) + lx;
-    }
-    return r;
-}
+// PixelMap, block_origin / block_pixel and the per-lane slot_to_pixel: pt_pixel_map.h (shared with the host side and the host-compiled tests)
 
 // a share of a primary-beam list build carried by a primary pass (bounce_kernel): blocks [first_block, first_block + n_blocks) of `lists`,
 // for a camera at `centre` (this frame's orientation) with Beam::slack `slack`; n_blocks = 0: none

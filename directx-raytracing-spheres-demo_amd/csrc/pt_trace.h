@@ -852,12 +852,18 @@ struct NoTrace {
 // flags (ps.dn_spec), its bounce-1 hit replaces hd; with kDI the estimate goes straight to scratch (split by lobe in the NRD modes).
 enum : int { kShadeDone = 0, kShadeRay = 1, kShadePending = 2 };
 
-template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kMerge = false, bool kDn = false, typename TraceFn = NoTrace>
+// kBlock (the 1-spp primary pass): the wave's slots are one 8x8 block and `bo` is its origin, made once per tile on the scalar unit
+// (block_origin): a pixel write forms its index from it in three instructions, and nothing here maps the slot again.
+template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kMerge = false, bool kDn = false, bool kBlock = false, typename TraceFn = NoTrace>
 __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const Scratch& scratch,
-                                             float4* __restrict__ out, PathState& ps, float t, uint32_t id, bool pending, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr)
+                                             float4* __restrict__ out, PathState& ps, float t, uint32_t id, bool pending, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr,
+                                             const BlockOrigin* bo = nullptr)
 {
     static_assert(!kMerge || (kMulti && !kDI), "the merged form is the looping pass of spp > 1 frames");
+    static_assert(!kBlock || !kMulti, "the block form is the 1-spp primary pass");
     const uint32_t slot = ps.slot;
+    auto pixel_of_slot = [&]() -> PixelRef { return kBlock ? block_pixel(*bo, slot & 63u) : slot_to_pixel(pm, slot); };
+    auto out_index_of_slot = [&]() -> uint32_t { return kBlock ? block_out_index(*bo, slot & 63u) : slot_to_pixel(pm, slot).out_index; };
     f3 di_val = make_f3(0.f, 0.f, 0.f);
     bool di_have = false;  // di_val is this pixel's estimate, made in this call
     bool regen = false;    // kCacheMode 2: the surface being shaded is a regenerated primary hit described by the pixel's cached record
@@ -876,7 +882,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
             env = sv.env_cube ? environment_cube(sv.tex + sv.env_tex, sv.env_xf, ps.d) : environment_texture(sv.tex[sv.env_tex], sv.env_xf, ps.d);
         else env = environment_color(sv.env[0], sv.env[1], sv.env[2], sv.env[3], ps.d);
         if (!kMerge && ps.bounce == 0) {  // primary miss: pixel = environment (GBufferGeneration.hlsl:223-227; Raytracing.hlsl:249-252); the looping pass only sees paths with a primary hit
-            out[slot_to_pixel(pm, slot).out_index] = make_float4(env.x, env.y, env.z, 1.0f);
+            out[out_index_of_slot()] = make_float4(env.x, env.y, env.z, 1.0f);
             return true;
         }
         if (ps.dirty) { const float4 s = scratch.sample_rad[slot]; srad = load3(s); }
@@ -920,7 +926,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
         // transmission lobe keeps its emission, because DI evaluates the reflective lobes only.
         if (fp.di_enabled && ps.bounce == 1 && !ps.via_t) emission = make_f3(0.f, 0.f, 0.f);
         if (kDI && fp.di_enabled && ps.bounce == 0 && (!kMulti || ps.sample == 0) && !di_have) {
-            const PixelRef dpr = slot_to_pixel(pm, slot);
+            const PixelRef dpr = pixel_of_slot();
             if (kDn) {  // stored at once (the finish reads it back): no estimate lives across the bounce in registers
                 f3 halves[2];
                 const f3 est = di_estimate<kTex, true>(sv, fp, dpr.px, dpr.py, id, ps.d, hm, trace, *di_rays, halves);
@@ -960,7 +966,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
                 float4* rec = scratch.primary_cache + (size_t)slot * 3u;
                 rec[0] = make_float4(hf.N.x, hf.N.y, hf.N.z, hf.offset);
                 rec[1] = make_float4(w[0], w[1], w[2], as_float(id));
-                rec[2] = make_float4(ps.d.x, ps.d.y, ps.d.z, as_float(slot_to_pixel(pm, slot).out_index));  // (where the pixel is written: the looping pass needs no slot -> pixel mapping)
+                rec[2] = make_float4(ps.d.x, ps.d.y, ps.d.z, as_float(out_index_of_slot()));  // (where the pixel is written: the looping pass needs no slot -> pixel mapping)
             }
         }
         float rnd[4];
@@ -1007,7 +1013,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
                 res = total * fp.inv_spp;
             }
             if (kDn) {  // spec S13, by mode (Raytracing.hlsl:377-414)
-                const uint32_t out_index = kCacheMode == 2 ? as_uint(scratch.primary_cache[(size_t)slot * 3u + 2u].w) : slot_to_pixel(pm, slot).out_index;
+                const uint32_t out_index = kCacheMode == 2 ? as_uint(scratch.primary_cache[(size_t)slot * 3u + 2u].w) : out_index_of_slot();
                 const float4 rec = scratch.dn.rec[slot];
                 const bool diffuse = !ps.dn_spec;
                 if (scratch.dn.mode == 1) {  // DLSS-RR: the radiance of pt_render, and the hit distance of a specular first bounce
@@ -1031,7 +1037,7 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
                 if (kDI && di_have) res = res + di_val;
                 else { const float4 di = scratch.di[slot]; res = res + load3(di); }
             }
-            const uint32_t out_index = kCacheMode == 2 ? as_uint(scratch.primary_cache[(size_t)slot * 3u + 2u].w) : slot_to_pixel(pm, slot).out_index;
+            const uint32_t out_index = kCacheMode == 2 ? as_uint(scratch.primary_cache[(size_t)slot * 3u + 2u].w) : out_index_of_slot();
             out[out_index] = make_float4(res.x, res.y, res.z, 1.0f);
             return true;
         }
@@ -1089,11 +1095,12 @@ __device__ __forceinline__ int shade_step_ex(const SceneView& sv, const PixelMap
 
 // One iteration of the bounce-loop body for a path whose ray (ps.o, ps.d) has been traced to (t, id), as the kernels outside the merged
 // looping pass use it: true = ps holds a new ray that must be traced, false = the pixel is finished.
-template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kDn = false, typename TraceFn = NoTrace>
+template <bool kMulti, bool kTex = false, bool kDI = false, int kCacheMode = 0, bool kDn = false, bool kBlock = false, typename TraceFn = NoTrace>
 __device__ __forceinline__ bool shade_step(const SceneView& sv, const PixelMap& pm, const FrameParams& fp, const Scratch& scratch,
-                                           float4* __restrict__ out, PathState& ps, float t, uint32_t id, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr)
+                                           float4* __restrict__ out, PathState& ps, float t, uint32_t id, TraceFn&& trace = NoTrace(), uint32_t* di_rays = nullptr,
+                                           const BlockOrigin* bo = nullptr)
 {
-    return shade_step_ex<kMulti, kTex, kDI, kCacheMode, false, kDn>(sv, pm, fp, scratch, out, ps, t, id, false, trace, di_rays) == kShadeRay;
+    return shade_step_ex<kMulti, kTex, kDI, kCacheMode, false, kDn, kBlock>(sv, pm, fp, scratch, out, ps, t, id, false, trace, di_rays, bo) == kShadeRay;
 }
 
 // kDn: the queue record also carries PathState::dn_spec (kFlagDnSpecular; denoiser frames)
@@ -1433,26 +1440,33 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
         // (wave-uniform, and used up before the trace: the knob's word is read from the kernarg segment only behind an empty list, and nothing of
         // this is carried through the loop's body, where the scalar registers are short)
         const bool sky = kSky && beam_count == 0u && (cold_arg<uint32_t>(offsetof(BounceArgs, fc) + offsetof(FrameCounters, tile_opts)) & kTileOptSky) != 0u;
+        // the slot -> pixel mapping, once per tile: the wave's 64 slots are one 8x8 block, so the block's origin is scalar arithmetic (two
+        // multiply-high quotients at most) and a lane adds its place in the block; the pixel writes of shade_step use the same origin
+        // (the primary instances that also loop keep the per-lane form: with the origin's scalars live they gained scratch)
+        constexpr bool kTileMap = kPrimary && !kLoop, kBlock = kTileMap && !kMulti;
+        BlockOrigin bo{};
+        if (kTileMap) bo = block_origin(cold_arg<PixelMap>(offsetof(BounceArgHead, pm)), (uint32_t)__builtin_amdgcn_readfirstlane(i >> 6));
         if (i < count) {
             bool live = true;
             float tmin = 0.0f, tmax = kInf;
             if (kPrimary) {
-                const PixelMap pm_c = cold_arg<PixelMap>(offsetof(BounceArgHead, pm));
-                const PixelRef pr = slot_to_pixel(pm_c, i);
+                const PixelRef pr = kTileMap ? block_pixel(bo, i & 63u) : slot_to_pixel(cold_arg<PixelMap>(offsetof(BounceArgHead, pm)), i);
                 live = pr.valid;
                 ps.slot = i; ps.bounce = 0; ps.sample = 0; ps.dirty = false; ps.via_t = false; ps.dn_spec = false; ps.rng = 0;
                 ps.T = make_f3(1.f, 1.f, 1.f);
                 ps.o = make_f3(0.f, 0.f, 0.f); ps.d = make_f3(0.f, 0.f, 1.f);
                 if (live) {
                     const CameraParams cam_c = cold_arg<CameraParams>(offsetof(BounceArgHead, fp) + offsetof(FrameParams, cam));
-                    primary_ray(cam_c, pr.px, pr.py, ps.o, ps.d, tmin, tmax);
+                    ps.o = cam_c.Position;
+                    ps.d = primary_dir(cam_c, pr.px, pr.py);
                     if (kSky && sky) {
                         const f3 env = environment_color(sv.env[0], sv.env[1], sv.env[2], sv.env[3], ps.d);
                         out[pr.out_index] = make_float4(env.x, env.y, env.z, 1.0f);
                     } else {
+                        primary_range(cam_c, ps.d, tmin, tmax);  // (the division is the traced tiles' alone: a sky tile reads no tmin / tmax)
                         ps.rng = rng_init(pr.px, pr.py, fp.frame_index);
                     }
-                } else if (pm_c.mode == 1) {
+                } else if (cold_arg<uint32_t>(offsetof(BounceArgHead, pm) + offsetof(PixelMap, mode)) == 1u) {
                     out[pr.out_index] = make_float4(0.f, 0.f, 0.f, 0.f);  // padding pixel of an edge tile
                 }
                 if (kSky && sky) live = false;
@@ -1510,11 +1524,11 @@ __global__ __launch_bounds__(kFusedThreads) __attribute__((amdgpu_waves_per_eu(4
                     // Scratch::primary_cache: the compacting primary pass of an spp > 1 frame writes the records, the looping pass restarts samples from them
                     constexpr int kCacheMode = (kMulti && !kTex) ? ((kPrimary && !kLoop) ? 1 : ((kLoop && !kPrimary) ? 2 : 0)) : 0;
                     if (kDI)  // row N4: the first shading of the primary surface also makes its direct-illumination estimate
-                        emit = shade_step<kMulti, kTex, true, kCacheMode, kDn>(sv, pm, fp, scratch, out, ps, t, id,
+                        emit = shade_step<kMulti, kTex, true, kCacheMode, kDn, kBlock>(sv, pm, fp, scratch, out, ps, t, id,
                                                               [&](f3 so, f3 sd, float& t2, uint32_t& id2) { closest_hit_any<kLds, StackT, kTex>(sv, nodes, sph, ids, so, sd, 0.0f, kInf, stack, blockDim.x, t2, id2); },
-                                                              &my_rays);
+                                                              &my_rays, kBlock ? &bo : nullptr);
                     else
-                        emit = shade_step<kMulti, kTex, false, kCacheMode, kDn>(sv, pm, fp, scratch, out, ps, t, id);
+                        emit = shade_step<kMulti, kTex, false, kCacheMode, kDn, kBlock>(sv, pm, fp, scratch, out, ps, t, id, NoTrace(), nullptr, kBlock ? &bo : nullptr);
                     if (!emit) break;
                     if (!kLoop && ++iter >= kIters) break;
                     my_rays++;  // a ray spawned and traced inside this kernel (queued rays are counted by counts[])
