@@ -141,6 +141,10 @@ float oracle_exp2(float y)
 }
 
 float oracle_pow(float x, float y) { return oracle_exp2(y * oracle_log2(x)); }
+void oracle_pow_batch(const float *x, float y, uint32_t n, float *out)
+{
+    for (uint32_t i = 0; i < n; i++) out[i] = oracle_pow(x[i], y);
+}
 
 /* Color::FromSrgb, one channel (c saturated) */
 float oracle_from_srgb(float c)
@@ -1375,15 +1379,24 @@ static const float k_rotation[3][9] = {
     { 0.822461969f, 0.1775380f, 0.0f, 0.033194199f, 0.966805801f, 0.0f, 0.017082631f, 0.0723974f, 0.910519969f },       /* 709 -> P3-D65 */
 };
 
+void oracle_rotate_primaries(const float c3[3], uint32_t rotation, float out[3])
+{
+    const float *m = k_rotation[rotation < 3 ? rotation : 0];
+    v3 c = V3(c3[0], c3[1], c3[2]);
+    out[0] = v_dot(V3(m[0], m[1], m[2]), c);
+    out[1] = v_dot(V3(m[3], m[4], m[5]), c);
+    out[2] = v_dot(V3(m[6], m[7], m[8]), c);
+}
+
 uint32_t oracle_tonemap_pixel(const float hdr[3], const PtToneMapParams *p)
 {
     if (p->TransferFunction == 2) {
-        const float *m = k_rotation[p->ColorRotation < 3 ? p->ColorRotation : 0];
-        v3 c = V3(hdr[0], hdr[1], hdr[2]);
+        float rot[3];
+        oracle_rotate_primaries(hdr, p->ColorRotation, rot);
         float k = p->PaperWhiteNits * (1.0f / 10000.0f);
-        float r = st2084(v_dot(V3(m[0], m[1], m[2]), c) * k);
-        float g = st2084(v_dot(V3(m[3], m[4], m[5]), c) * k);
-        float b = st2084(v_dot(V3(m[6], m[7], m[8]), c) * k);
+        float r = st2084(rot[0] * k);
+        float g = st2084(rot[1] * k);
+        float b = st2084(rot[2] * k);
         return to_unorm(r, 1023.0f) | (to_unorm(g, 1023.0f) << 10) | (to_unorm(b, 1023.0f) << 20) | (3u << 30);
     }
     float c[3];

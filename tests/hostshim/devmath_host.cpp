@@ -72,6 +72,20 @@ void dev_accumulate(float* accum, const float* rad, uint32_t n_pixels, uint32_t 
     const float inv = 1.0f / (float)(frames_accumulated + 1u);
     for (uint32_t i = 0; i < 4u * n_pixels; i++) accum[i] = accumulate_value(accum[i], rad[i], inv, frames_accumulated == 0);
 }
+// batch entries for the dense sweeps of tests/test_post_reference.py (dev_tonemap has oracle_tonemap's signature)
+void dev_tonemap(const float* hdr_rgba, uint32_t n_pixels, const PtToneMapParams* p, uint32_t* out)
+{
+    for (uint32_t i = 0; i < n_pixels; i++) out[i] = tonemap_pixel(make_f3(hdr_rgba[4u * i], hdr_rgba[4u * i + 1u], hdr_rgba[4u * i + 2u]), *p);
+}
+void dev_rotate_primaries(const float c[3], uint32_t rotation, float out[3])
+{
+    const f3 r = rotate_primaries(make_f3(c[0], c[1], c[2]), rotation);
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+void dev_pow_batch(const float* x, float y, uint32_t n, float* out)
+{
+    for (uint32_t i = 0; i < n; i++) out[i] = pow_spec(x[i], y);
+}
 
 // ---- row N4 leaf
 int dev_sample_sphere_cone(const float P[3], const float C[3], float r, float u1, float u2, float L[3], float* inv_pdf)
